@@ -8,20 +8,28 @@ transforms in a second fused kernel) over one batch of synthetic ciphertexts alr
 
 One process per GPU; ranks shard the batch (weak scaling: the per-GPU batch is fixed), no data-path collective.
 `--gpus N` with N > 1 and no torchrun environment re-executes this script under `python -m torch.distributed.run`
-with N ranks (RCCL); under torchrun the environment's WORLD_SIZE is what runs and what `n_gpus` reports.  After the
-timed region the optional final gather (north_star: "RCCL over xGMI only for the final gather") is timed on its own, so
-the JSON carries the rate without (`value`) and with it (`gather.value_with_gather`).
+with N ranks (RCCL); under torchrun the environment's WORLD_SIZE is what runs and what `n_gpus` reports.
 
-After the headline line's legs, rank 0 of a single-GPU run also measures the other BASELINE.json configurations
-(`other_configs`: cfg#3 / #4 / #5 key switch, rotation and rescale rates, N = 2^16 and 60-bit NTT rates, each case checked
-against the oracle on one ciphertext before it is timed -- tools/bench_configs.py); `--no-configs` skips that leg.
+A plain run sets up, warms up, times `--steps` steps and prints the line (headline rate, `ms_per_step`, and the roofline of
+the kernels inside the timed steps, which needs no run of its own).  `--dump-outputs DIR` also writes what the last timed
+step computed (rank 0's `out`, a fixed sample of it: dump_outputs) as .npy files; the inputs are seeded, so two builds
+compare output for output.
 
-A multi-rank run (--gpus N > 1) also carries `configs_multi`: the configurations BASELINE.json defines across the GPUs of a node --
-cfg#4 (4096 key switches sharded over the ranks, strong scaling) and cfg#5 (the ciphertext sets of the MNIST test set sharded over
-the ranks) -- each with per-rank rates, max/min imbalance, nranks_seen and the final gather timed on its own.  `--config cfg3|cfg4|cfg5`
-makes one of them THE line of the run instead of the BFV metric.
+`--full` adds every other leg, each a run of its own after the timed steps, and writes the full record (profiles/bench_full.json
+and stderr):
+  * the stand-alone NTT record (BASELINE.md #2'; `--no-ntt` skips it) and the CPU baseline (`--no-cpu`);
+  * on a single GPU the other BASELINE.json configurations (`other_configs`: cfg#3 / #4 / #5 key switch, rotation and rescale
+    rates, N = 2^16 and 60-bit NTT rates, each case checked against the oracle on one ciphertext before it is timed --
+    tools/bench_configs.py; `--no-configs` skips that leg);
+  * on several ranks the final gather (north_star: "RCCL over xGMI only for the final gather") timed on its own, so the JSON
+    carries the rate without (`value`) and with it (`gather.value_with_gather`; `--no-gather` skips it), and `configs_multi`:
+    the configurations BASELINE.json defines across the GPUs of a node -- cfg#4 (4096 key switches sharded over the ranks, strong
+    scaling) and cfg#5 (the ciphertext sets of the MNIST test set sharded over the ranks) -- each with per-rank rates, max/min
+    imbalance, nranks_seen and the final gather timed on its own (`--no-configs` skips it).
+`--config cfg3|cfg4|cfg5` makes one of them THE line of the run instead of the BFV metric.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config bfv|cfg3|cfg4|cfg5] [--no-cpu] [--no-ntt] [--no-gather] [--no-configs]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--config bfv|cfg3|cfg4|cfg5]
+                  [--full [--no-cpu] [--no-ntt] [--no-gather] [--no-configs]]
 """
 import argparse
 import hashlib
@@ -49,6 +57,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1024, help="ciphertext pairs per GPU per step")
     ap.add_argument("--chunk", type=int, default=0, help="ciphertexts per internal pipeline chunk (0 = default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a fixed sample, float64) to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (NTT record, CPU baseline, other configurations, gather) and write the full record")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-ntt", action="store_true", help="skip the stand-alone NTT record")
     ap.add_argument("--no-gather", action="store_true", help="skip the timed final gather (multi-rank runs)")
@@ -64,7 +76,10 @@ def parse():
     ap.add_argument("--total", type=int, default=0, help="--config cfg*: global units instead of the configuration's own (tests)")
     ap.add_argument("--backend", default=os.environ.get("TFHE_BENCH_BACKEND", "nccl"),
                     help="torch.distributed backend; 'gloo' + ranks sharing a GPU is a functional check only")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.config != "bfv":
+        ap.error("--dump-outputs writes the BFV line's outputs (--config bfv)")
+    return args
 
 
 def respawn(args):
@@ -237,18 +252,39 @@ def compact_line(result, limit=LINE_LIMIT):
     return line
 
 
-def emit(result):
-    """full record -> profiles/bench_full.json (+ gpurun_out/ when present) and stderr; compact line -> the LAST stdout line"""
-    full = json.dumps(result)
-    for path in (FULL_RECORD, os.path.join(ROOT, "gpurun_out", "bench_full.json")):
+def emit(result, full_record=True):
+    """compact line -> the LAST stdout line; with `full_record` (--full) the full record also goes to profiles/bench_full.json and stderr"""
+    line = compact_line(result)
+    if full_record:
+        full = json.dumps(result)
         try:
-            if os.path.isdir(os.path.dirname(path)):
-                with open(path, "w") as f:
-                    f.write(full + "\n")
+            with open(FULL_RECORD, "w") as f:
+                f.write(full + "\n")
         except OSError:
             pass
-    print(full, file=sys.stderr, flush=True)
-    print(json.dumps(compact_line(result)), flush=True)
+        print(full, file=sys.stderr, flush=True)
+    else:
+        line.pop("full_record", None)
+    print(json.dumps(line), flush=True)
+
+
+DUMP_ELEMS = 1 << 22     # --dump-outputs: float64 elements written (32 MiB), below the 64 MB a dump may take
+
+
+def dump_outputs(path, out):
+    """Write `out` -- (B, 2, L, N) residues below 2^50 from the last timed step -- to `path` as float64 (exact below 2^53):
+    every ciphertext, component and limb at the same seeded sample of coefficient positions (256 of 2^14 at B = 1024), so
+    a fault confined to some ciphertexts, limbs or chunks shows.  The positions go alongside as `<name>_coeff_index.npy`."""
+    import numpy as np
+    import torch
+    n = out.shape[-1]
+    k = max(1, min(n, DUMP_ELEMS // (out.numel() // n)))
+    idx = np.sort(np.random.default_rng(0xD0_5A3D).choice(n, size=k, replace=False))
+    sample = out.index_select(out.dim() - 1, torch.as_tensor(idx, device=out.device)).cpu().numpy()
+    assert sample.size * 8 <= 64_000_000, sample.shape
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "bfv_mul_relin_out.npy"), sample.astype(np.float64))
+    np.save(os.path.join(path, "bfv_mul_relin_out_coeff_index.npy"), idx.astype(np.float64))
 
 
 def main():
@@ -298,7 +334,7 @@ def main():
             else:                                                       # cfg#5 (the MNIST pass: ~30 kernels): no single launch to price
                 line["roofline"] = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
                                     "note": "a pass of ~500 launches; per-kernel counters: profiles/pmc_configs.json (MNIST case)"}
-            emit(line)
+            emit(line, full_record=args.full)
         if world > 1:
             torch.distributed.destroy_process_group()
         return
@@ -355,10 +391,12 @@ def main():
 
     total_units = B * world * args.steps
     value = total_units / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # ---- optional final gather (all ranks end up with every result), timed on its own -----------------------------
     gather = None
-    if world > 1 and not args.no_gather:
+    if world > 1 and args.full and not args.no_gather:
       try:                                                              # never let the optional leg cost the headline line
           import torch.distributed as dist
           flat = out.view(-1)
@@ -564,7 +602,7 @@ def main():
 
     # ---- multi-rank runs: the configurations BASELINE.json defines across the GPUs of a node (cfg#4 strong-scaled key switches,
     # cfg#5 the MNIST test set), every rank on its shard; a failure anywhere is a record with "error", never a lost line ------------
-    if world > 1 and not args.no_configs:
+    if world > 1 and args.full and not args.no_configs:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_configs
@@ -581,13 +619,13 @@ def main():
 
     for enabled, leg in ((rank == 0 and not args.no_ntt, ntt_record), (rank == 0 and world == 1 and not args.no_cpu, cpu_record),
                          (rank == 0 and world == 1 and not args.no_configs, configs_record)):
-        if enabled:
+        if enabled and args.full:
             try:                                                        # a failing side record must not cost the headline line
                 leg()
             except Exception as e:                                      # noqa: BLE001
                 result.setdefault("errors", []).append(f"{leg.__name__}: {type(e).__name__}: {e}")
     if rank == 0:
-        emit(result)
+        emit(result, full_record=args.full)
     if world > 1:
         torch.distributed.destroy_process_group()
 

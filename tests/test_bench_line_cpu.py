@@ -7,6 +7,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -117,3 +119,47 @@ def test_line_of_a_multi_rank_configuration_run():
     assert line["nranks_seen"] == 8 and line["roofline"]["bound"] == "hbm" and line["roofline"]["frac"] == 0.05
     assert line["gather"]["fallback"].startswith("RuntimeError: tfhe_comm_create") and len(line["gather"]["fallback"]) <= 120
     assert "per_rank" not in line
+
+
+def test_emit_of_a_plain_run_prints_the_line_only(tmp_path, monkeypatch):
+    """without --full: the compact line on stdout and nothing else -- no full record on disk or stderr, no key pointing at one"""
+    monkeypatch.setattr(bench, "FULL_RECORD", str(tmp_path / "bench_full.json"))
+    out, err = io.StringIO(), io.StringIO()
+    with contextlib.redirect_stdout(out), contextlib.redirect_stderr(err):
+        bench.emit(canned(), full_record=False)
+    lines = [l for l in out.getvalue().splitlines() if l.strip()]
+    assert len(lines) == 1 and err.getvalue() == "" and not os.path.exists(tmp_path / "bench_full.json")
+    back = json.loads(lines[0])
+    for k in CONTRACT:
+        assert k in back, k
+    assert "full_record" not in back
+
+
+def test_dump_outputs_writes_a_seeded_exact_float64_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_ELEMS", 3 * 2 * 2 * 16)          # 16 of 64 coefficient positions per polynomial
+    rng = np.random.default_rng(5)
+    out = torch.from_numpy(rng.integers(2**49, 2**50, size=(3, 2, 2, 64), dtype=np.int64))
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    got, idx = np.load(tmp_path / "a" / "bfv_mul_relin_out.npy"), np.load(tmp_path / "a" / "bfv_mul_relin_out_coeff_index.npy")
+    assert got.dtype == np.float64 and idx.dtype == np.float64 and got.shape == (3, 2, 2, 16)
+    pos = idx.astype(np.int64)
+    assert np.array_equal(pos, np.unique(pos)) and 0 <= pos[0] and pos[-1] < 64
+    assert np.array_equal(got.astype(np.int64), out.numpy()[..., pos])    # residues below 2^53 survive float64 exactly
+    assert np.array_equal(got, np.load(tmp_path / "b" / "bfv_mul_relin_out.npy"))
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "bfv_mul_relin_out_coeff_index.npy"))
+
+
+def test_bench_options(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--config", "cfg4", "--dump-outputs", "d"])
+    with contextlib.redirect_stderr(io.StringIO()), pytest.raises(SystemExit) as e:
+        bench.parse()
+    assert e.value.code == 2

@@ -50,12 +50,11 @@ def test_shard_partition():
     assert tdist.shard(4096, 3, 8) == (1536, 512)      # BASELINE.json configs[3]: 4096 over 8 GPUs
 
 
-def test_two_rank_gloo():
+def test_two_rank_gloo(tmp_path):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    script = os.path.join(ROOT, "gpurun_out", "_dist_worker.py")
-    os.makedirs(os.path.dirname(script), exist_ok=True)
+    script = str(tmp_path / "_dist_worker.py")
     open(script, "w").write(WORKER % {"root": ROOT})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), script]

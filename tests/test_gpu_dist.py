@@ -79,9 +79,8 @@ def free_port():
         return s.getsockname()[1]
 
 
-def test_two_ranks_run_the_engine_on_their_shards():
-    script = os.path.join(ROOT, "gpurun_out", "_dist_gpu_worker.py")
-    os.makedirs(os.path.dirname(script), exist_ok=True)
+def test_two_ranks_run_the_engine_on_their_shards(tmp_path):
+    script = str(tmp_path / "_dist_gpu_worker.py")
     open(script, "w").write(WORKER % {"root": ROOT})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), script]
@@ -132,7 +131,7 @@ def test_bench_spawns_the_ranks_it_is_asked_for():
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64",
-           "--no-cpu", "--no-ntt", "--backend", backend, "--total", "96"]
+           "--full", "--no-cpu", "--no-ntt", "--backend", backend, "--total", "96"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line, res = _line_and_record(out)
@@ -159,7 +158,7 @@ def test_bench_multi_rank_modes_of_the_other_configurations(cfg, total, units):
     import torch
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", cfg, "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", cfg, "--steps", "2", "--warmup", "1", "--full",
            "--total", str(total), "--backend", backend]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -190,7 +189,7 @@ def test_eight_rank_rehearsal(mode, extra, units):
     backend = "nccl" if torch.cuda.device_count() >= 8 else "gloo"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--backend", backend] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--full", "--backend", backend] + extra
     if mode != "bfv":
         cmd += ["--config", mode]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=2400, env=env)

@@ -96,9 +96,8 @@ print(json.dumps(out))
 '''
 
 
-def test_two_lanes_and_one_stream_give_the_same_words():
-    script = os.path.join(ROOT, "gpurun_out", "_lanes_worker.py")
-    os.makedirs(os.path.dirname(script), exist_ok=True)
+def test_two_lanes_and_one_stream_give_the_same_words(tmp_path):
+    script = str(tmp_path / "_lanes_worker.py")
     open(script, "w").write(WORKER % {"root": ROOT})
     res = {}
     for lanes in ("0", "1"):

@@ -15,7 +15,7 @@ cp gpurun_out/pmc_$TAG/${TAG}_pmc_bench_kernels.json gpurun_out/pmc_$TAG/${TAG}_
 bash tools/pmc_configs.sh $TAG > $E/pmc_configs.log 2>&1
 cp gpurun_out/pmcc_$TAG/${TAG}_pmc_configs.json profiles/pmc_configs.json
 cp gpurun_out/pmcc_$TAG/${TAG}_pmc_configs.json gpurun_out/pmcc_$TAG/${TAG}_pmc_configs.txt $E/
-cd $R && python bench.py 2> $E/bench.err | tail -1 > $E/${TAG}_bench.json
+cd $R && python bench.py --full 2> $E/bench.err | tail -1 > $E/${TAG}_bench.json
 cp profiles/bench_full.json $E/${TAG}_bench_full.json
 bash tools/prof_mnist_last_pass.sh ${TAG}_evidence > /dev/null 2>&1
 # keep the merge small: the raw traces stay on the box
