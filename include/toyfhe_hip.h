@@ -23,7 +23,9 @@
  *     of the fused key switch) that is recycled in stream order, so ONE host thread drives a given context at a time;
  *     different contexts / plans are independent and may be driven from different threads (no global mutable state
  *     besides the thread-local error text).  Share read-only inputs (evaluation keys, ciphertexts) freely.
- *     tfhe_free, tfhe_ctx_destroy, tfhe_bfv_plan_destroy and tfhe_comm_destroy may be called from ANY thread (a garbage
+ *     A tfhe_plain_plan runs on its context's stream and uses that context's workspace: it is driven by the thread that
+ *     drives its context.
+ *     tfhe_free, tfhe_ctx_destroy, tfhe_bfv_plan_destroy, tfhe_plain_plan_destroy and tfhe_comm_destroy may be called from ANY thread (a garbage
  *     collector's finalizer thread): tfhe_free takes the allocator's lock and parks the block behind events recorded on every
  *     live context's stream -- it never waits and never touches a context's scratch; the destroy calls synchronise the
  *     object's own stream first and must only not race with a call that is still USING that object.
@@ -55,6 +57,7 @@ typedef enum {
 typedef struct tfhe_ctx tfhe_ctx;       /* a ring: NegacyclicRing{CRTEncoded{L,...},N} */
 typedef struct tfhe_bfv_plan tfhe_bfv_plan; /* (ℛ, ℛbig, t) of a BFVParams */
 typedef struct tfhe_comm tfhe_comm;     /* the ranks of a multi-GPU job (one process per GPU) */
+typedef struct tfhe_plain_plan tfhe_plain_plan; /* (ring limbs, t) of a BFVParams / BGVParams: the plaintext codec */
 
 const char *tfhe_last_error(void);      /* thread-local text of the last failure */
 int tfhe_device_count(int *n);
@@ -249,6 +252,29 @@ int tfhe_bfv_mul_relin(tfhe_bfv_plan *plan, const uint64_t *evk, int n_digits, c
 int tfhe_bfv_plan_set_variant(tfhe_bfv_plan *plan, int variant);
 /* ciphertexts processed per internal chunk (workspace = chunk * (7 nb + 3 ns) * N * 8 bytes); 0 = default (256) */
 int tfhe_bfv_plan_set_chunk(tfhe_bfv_plan *plan, int chunk);
+
+/* ---- BFV / BGV plaintext codecs on the device (π⁻¹ / π, bfv.jl:21-29, bgv.jl:21-25; noise, bfv.jl:137-166) ---------
+ * plan = (ring = ctx limbs limb_idx, t).  t in [2, 2^62) and t < Q (Q = product of the selected moduli); limb_idx entries
+ * in range and distinct; else TFHE_E_BADARG (checked on the host before any device use).  Exact: bit-identical to the
+ * BigInt path of the reference.  Work runs on the ctx's stream; count == 0 does nothing.
+ *   scheme         : TFHE_PLAIN_BFV or TFHE_PLAIN_BGV.
+ *   encode         : m [count][N] plaintext words (any uint64; reduced mod t first: a negative plaintext arrives as its
+ *                    residue mod t) -> out [count][limbs][N] coefficient domain.
+ *                    BFV: (m mod t)(Δ mod q_l) mod q_l, Δ = Q ÷ t (bfv.jl:21-24).  BGV: (m mod t) mod q_l (bgv.jl:21-25).
+ *   decode         : in [count][limbs][N] coefficient domain -> out [count][N] in [0, t).
+ *                    BFV: mod(SignedMod(div(centred(x), Δ, RoundNearestTiesAway)), t) (bfv.jl:26-29).
+ *                    BGV: mod(centred(x), t) (bgv.jl:21-25).  centred(x) = x - Q if x > Q÷2 else x (signedmod.jl:12-19).
+ *   bfv_noise_max  : in [count][limbs][N] (the decryption b = c_1 + s c_2 + ...) -> out_words [count][delta_words], the exact
+ *                    max over the N coefficients of birem(x) = min(x mod Δ, Δ - x mod Δ) (r <= Δ÷2 keeps r; x unsigned),
+ *                    little-endian 64-bit words, delta_words = number of 64-bit words of Δ = Q ÷ t.  The host applies
+ *                    log2(Q) - log2(t) - 1 - log2(max) (bfv.jl:137-166).
+ * m / in / out / out_words are device memory; limb_idx is a host array (NULL = 0..limbs-1). */
+typedef enum { TFHE_PLAIN_BFV = 0, TFHE_PLAIN_BGV = 1 } tfhe_plain_scheme;
+int tfhe_plain_plan_create(tfhe_ctx *ctx, const int32_t *limb_idx, int limbs, uint64_t t, tfhe_plain_plan **out);
+int tfhe_plain_plan_destroy(tfhe_plain_plan *plan);
+int tfhe_plain_encode(tfhe_plain_plan *plan, int scheme, const uint64_t *m, uint64_t *out, int64_t count);
+int tfhe_plain_decode(tfhe_plain_plan *plan, int scheme, const uint64_t *in, uint64_t *out, int64_t count);
+int tfhe_bfv_noise_max(tfhe_plain_plan *plan, const uint64_t *in, uint64_t *out_words, int64_t count);
 
 /* ---- multi-GPU: the final gather (the reference is single-process) ---------------------------------------
  * A batch of independent ciphertexts shards by ciphertext over one process per GPU (contexts and keys replicated, tens of

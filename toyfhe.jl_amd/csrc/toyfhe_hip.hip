@@ -16,6 +16,7 @@
 
 #include "../../include/toyfhe_hip.h"
 #include "bfv_tables.h"
+#include "plain_tables.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "ckks_kernels.h"
@@ -2293,6 +2294,7 @@ int tfhe_event_elapsed_ms(void* a, void* b, float* ms) {
 
 #include "bfv_api.inc"
 #include "comm_api.inc"
+#include "plain_api.inc"
 
 #ifdef TFHE_KS_TRACE
 extern "C" int tfhe_debug_kstrace(unsigned long long* out, unsigned* n, int reset) {

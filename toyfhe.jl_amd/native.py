@@ -138,6 +138,11 @@ def lib():
         "tfhe_bfv_expand": [vp, vp, vp, i64],
         "tfhe_bfv_contract": [vp, vp, vp, i64],
         "tfhe_bfv_mul_relin": [vp, vp, i32, vp, vp, vp, i64],
+        "tfhe_plain_plan_create": [vp, i32p, i32, u64, C.POINTER(vp)],
+        "tfhe_plain_plan_destroy": [vp],
+        "tfhe_plain_encode": [vp, i32, vp, vp, i64],
+        "tfhe_plain_decode": [vp, i32, vp, vp, i64],
+        "tfhe_bfv_noise_max": [vp, vp, vp, i64],
         "tfhe_prof_enable": [vp, i32],
         "tfhe_prof_read": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double)],
         "tfhe_event_create": [C.POINTER(vp)],
@@ -159,7 +164,8 @@ EXPORTED_SYMBOLS = [
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
     "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
-    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_prof_enable", "tfhe_prof_read",
+    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
+    "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
 ]
 
@@ -429,6 +435,49 @@ class BfvPlan:
 
     def mul_relin(self, evk, n_digits, c1, c2, out, batch):
         check(lib().tfhe_bfv_mul_relin(self.h, evk, n_digits, c1, c2, out, batch))
+
+
+PLAIN_BFV, PLAIN_BGV = 0, 1   # tfhe_plain_scheme
+
+
+class PlainPlan:
+    """(ring limbs, t) of a BFVParams / BGVParams: the plaintext codecs π / π⁻¹ (bfv.jl:21-29, bgv.jl:21-25) and the BFV noise
+    maximum (bfv.jl:137-166) on the device (tfhe_plain_*).  Buffers are device pointers."""
+
+    def __init__(self, ctx: Context, t: int, idx=None):
+        self.ctx, self.t = ctx, int(t)
+        self.idx = list(range(ctx.L)) if idx is None else [int(i) for i in idx]
+        self.limbs = len(self.idx)
+        h = C.c_void_p()
+        check(lib().tfhe_plain_plan_create(ctx.h, _idx(self.idx), self.limbs, self.t, C.byref(h)))
+        self.h = h.value
+        Q = 1
+        for i in self.idx:
+            Q *= ctx.qs[i]
+        self.delta_words = ((Q // self.t).bit_length() + 63) // 64   # words of Δ = Q ÷ t (>= 1): tfhe_bfv_noise_max's row
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().tfhe_plain_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def encode(self, scheme, m, out, count):
+        """m [count][N] plaintext words -> out [count][limbs][N] (coefficient domain)"""
+        check(lib().tfhe_plain_encode(self.h, int(scheme), m, out, count))
+
+    def decode(self, scheme, src, out, count):
+        """src [count][limbs][N] (coefficient domain) -> out [count][N] in [0, t)"""
+        check(lib().tfhe_plain_decode(self.h, int(scheme), src, out, count))
+
+    def noise_max(self, src, out_words, count):
+        """src [count][limbs][N] -> out_words [count][delta_words]: max birem per element, little-endian words"""
+        check(lib().tfhe_bfv_noise_max(self.h, src, out_words, count))
 
 
 class Comm:

@@ -20,7 +20,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import native
-from .native import BfvPlan, DeviceBuffer, UsageError
+from .native import PLAIN_BFV, PLAIN_BGV, BfvPlan, DeviceBuffer, PlainPlan, UsageError
 from .ring import NegacyclicRing, RingElement, plaintext_space as _plaintext_space
 
 DOT_MAX = 64   # operands / rotations one device pass of tfhe_dot, tfhe_lincomb[_many], tfhe_matmul_diag takes (TFHE_DOT_MAX, csrc/kernels.h)
@@ -157,11 +157,37 @@ class BFVParams(SHESchemeParams):
         return _plaintext_space(self.ring, self.t)
 
     def encode(self, plain) -> RingElement:
-        """π⁻¹, bfv.jl:21-24: Δ * plaintext (a list of coefficients, or a list of such lists = a batch)."""
+        """π⁻¹, bfv.jl:21-24: Δ * plaintext (a list of coefficients, or a list of such lists = a batch).  On the device
+        (tfhe_plain_encode) whenever numpy holds the plaintext as int64 / uint64 without loss; Python big integers take the
+        host path."""
+        el = _device_encode(self, self.ring, PLAIN_BFV, plain)
+        if el is not None:
+            return el
         return self.ring(_map_plain(plain, lambda m: self.delta * (int(m) % self.t)))
+
+    def _device_ring(self, b: RingElement) -> bool:
+        # the device codec centres by the element's own Q; the reference centres by params.ring's (bfv.jl:26-29): the two agree
+        # exactly when the element lives on params.ring's moduli (not so for ModulusRaised(BFV), whose ciphertext ring drops
+        # the special prime -- that case stays on the host)
+        return b.ring.N == self.ring.N and b.ring.moduli == self.ring.moduli
+
+    def decode_array(self, b: RingElement) -> np.ndarray:
+        """π as a uint64 array [N] / [batch][N] (tfhe_plain_decode when the element's ring is params.ring)."""
+        if self._device_ring(b):
+            a = _device_decode(self, b, PLAIN_BFV)
+            if a is not None:
+                return a
+        return np.array(self._host_decode(b), dtype=np.uint64)
 
     def decode(self, b: RingElement):
         """π, bfv.jl:26-29: mod(SignedMod(divround(x, Δ)), t)."""
+        if self._device_ring(b):
+            a = _device_decode(self, b, PLAIN_BFV)
+            if a is not None:
+                return a.tolist()
+        return self._host_decode(b)
+
+    def _host_decode(self, b: RingElement):
         Q = self.ring.modulus()
 
         def one(x):
@@ -191,9 +217,22 @@ class BGVParams(SHESchemeParams):
         return _plaintext_space(self.ring, self.t)
 
     def encode(self, plain):
+        el = _device_encode(self, self.ring, PLAIN_BGV, plain)
+        if el is not None:
+            return el
         return self.ring(_map_plain(plain, lambda m: int(m) % self.t))
 
+    # BGV's π centres by the element's own modulus, so the device codec of the element's ring (a plan per ring, cached here)
+    # is exact for every ring with t < Q -- the ModulusRaised ciphertext ring included.
+    def decode_array(self, b) -> np.ndarray:
+        a = _device_decode(self, b, PLAIN_BGV)
+        return a if a is not None else np.array(self._host_decode(b), dtype=np.uint64)
+
     def decode(self, b):
+        a = _device_decode(self, b, PLAIN_BGV)
+        return a.tolist() if a is not None else self._host_decode(b)
+
+    def _host_decode(self, b):
         Q = b.ring.modulus()                 # the ciphertext's own level (a ModulusRaised / modswitched ring is a sub-basis)
         return _map_plain(b.to_ints(), lambda x: (x - Q if x > Q // 2 else x) % self.t)
 
@@ -242,6 +281,65 @@ class ModulusRaised(SHESchemeParams):
 
     def decode(self, b):
         return self.params.decode(b)
+
+    def decode_array(self, b):
+        return self.params.decode_array(b)
+
+
+def _plain_plan(params, ring: NegacyclicRing):
+    """the device codec of (ring, params.t), cached on the params object per ring; None when the device does not take it
+    (t outside [2, 2^62) or not below the ring's modulus)"""
+    cache = params.__dict__.setdefault("_plain_plans", {})
+    key = (id(ring.ctx), tuple(ring.idx))
+    if key not in cache:
+        ok = 2 <= params.t < min(2**62, ring.modulus())
+        cache[key] = PlainPlan(ring.ctx, params.t, ring.idx) if ok else None
+    return cache[key]
+
+
+def _device_decode(params, b: RingElement, scheme):
+    """π on the device: uint64 [N] / [batch][N], or None when the plan cannot take this ring"""
+    plan = _plain_plan(params, b.ring)
+    if plan is None:
+        return None
+    n, N = b.count, b.ring.N
+    out = DeviceBuffer(n * N)
+    plan.decode(scheme, b.coeffs_primal().ptr, out.ptr, n)
+    b.ring.ctx.sync()
+    a = out.to_numpy((n, N))
+    return a if b.batch is not None else a[0]
+
+
+def _plain_array(plain, t: int, N: int):
+    """the plaintext as uint64 [N] / [B][N] with negative values reduced mod t, or None when numpy cannot hold it as
+    int64 / uint64 without loss (Python big integers, floats, ragged rows): those take the host path"""
+    if isinstance(plain, np.ndarray):
+        a = plain
+    else:
+        try:
+            a = np.asarray(plain)
+        except (ValueError, OverflowError, TypeError):
+            return None
+    if a.dtype.kind not in "iu" or a.ndim not in (1, 2) or a.shape[-1] != N or a.size == 0:
+        return None
+    if a.dtype.kind == "i":
+        a = np.mod(a.astype(np.int64), np.int64(t))
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _device_encode(params, ring: NegacyclicRing, scheme, plain):
+    """π⁻¹ on the device (tfhe_plain_encode) into `ring`, or None (host path)"""
+    a = _plain_array(plain, params.t, ring.N)
+    if a is None:
+        return None
+    plan = _plain_plan(params, ring)
+    if plan is None:
+        return None
+    n = 1 if a.ndim == 1 else a.shape[0]
+    src = DeviceBuffer.from_numpy(a)
+    out = DeviceBuffer(n * ring.L * ring.N)
+    plan.encode(scheme, src.ptr, out.ptr, n)               # (src is parked by the allocator until the kernel has read it)
+    return RingElement(ring, out, None, None if a.ndim == 1 else n)
 
 
 def _map_plain(plain, f):
@@ -786,7 +884,7 @@ def encrypt(rng, key, plaintext, scale=None) -> CipherText:
     return c
 
 
-def decrypt(key, c: CipherText):
+def _decryption(key, c: CipherText):
     priv = key.priv if isinstance(key, KeyPair) else key
     secret = priv.secret
     while secret.ring.L != c[0].ring.L:  # rlwe_she.jl:202-204
@@ -798,29 +896,61 @@ def decrypt(key, c: CipherText):
         b = b + spow * c[i]
         if i + 1 < len(c):
             spow = spow * secret
+    return priv, b
+
+
+def decrypt(key, c: CipherText):
+    priv, b = _decryption(key, c)
     return priv.params.decode(b)
 
 
-def invariant_noise_budget(key, c: CipherText) -> float:
+def decrypt_array(key, c: CipherText) -> np.ndarray:
+    """decrypt(key, c) as a uint64 numpy array [N] (one ciphertext) or [batch][N] -- the same values; BFV / BGV only.  The
+    plaintext codec runs on the device (tfhe_plain_decode) where decrypt's does."""
+    priv, b = _decryption(key, c)
+    dec = getattr(priv.params, "decode_array", None)
+    if dec is None:
+        raise NotImplementedError("decrypt_array: BFV / BGV parameters")
+    return dec(b)
+
+
+def invariant_noise_budget(key, c: CipherText):
     """invariant_noise_budget(pk::PrivKey{BFVParams}, c), bfv.jl:137-166:
     log2(q) - log2(t) - 1 - max_i log2(birem(b_i)) with b = c_1 + s c_2 + s^2 c_3 ... and birem(x) = min(x mod Δ, Δ - x mod Δ).
-    A host-side diagnostic over the device ring ops (one ciphertext, not a batch)."""
+    One ciphertext -> a float; a batch -> a list of floats, one per ciphertext (the same formula).  The maximum of birem runs
+    on the device (tfhe_bfv_noise_max) when b lives on params.ring's moduli, else on the host."""
     priv = key.priv if isinstance(key, KeyPair) else key
     params = priv.params
-    if not isinstance(params, BFVParams) or c[0].batch is not None:
-        raise NotImplementedError("invariant_noise_budget: single BFV ciphertexts")
-    b, spow = c[0], priv.secret
+    if not isinstance(params, BFVParams):
+        raise NotImplementedError("invariant_noise_budget: BFV ciphertexts")
+    secret = priv.secret
+    if c[0].batch is not None:
+        secret = _broadcast(secret, c[0].batch)
+    b, spow = c[0], secret
     for i in range(1, len(c)):
         b = b + spow * c[i]
         if i + 1 < len(c):
-            spow = spow * priv.secret
+            spow = spow * secret
     delta = params.delta
+    plan = _plain_plan(params, b.ring) if params._device_ring(b) else None
+    if plan is not None:
+        n, nw = b.count, plan.delta_words
+        out = DeviceBuffer(n * nw)
+        plan.noise_max(b.coeffs_primal().ptr, out.ptr, n)
+        b.ring.ctx.sync()
+        words = out.to_numpy((n, nw))
+        worsts = [sum(int(w) << (64 * i) for i, w in enumerate(row)) for row in words]
+    else:
+        def birem(x):
+            r = x % delta
+            return delta - r if r > delta // 2 else r
+        ints = b.to_ints()
+        worsts = [max(birem(x) for x in row) for row in (ints if b.batch is not None else [ints])]
 
-    def birem(x):
-        r = x % delta
-        return delta - r if r > delta // 2 else r
-    worst = max(birem(x) for x in b.to_ints())
-    return math.log2(params.ring.modulus()) - math.log2(params.t) - 1 - (math.log2(worst) if worst else 0.0)
+    def budget(worst):
+        return math.log2(params.ring.modulus()) - math.log2(params.t) - 1 - (math.log2(worst) if worst else 0.0)
+    out_b = [budget(w) for w in worsts]
+    return out_b if c[0].batch is not None else out_b[0]
 
 
 def slot_encode(plain_ring: NegacyclicRing, slots) -> RingElement:
