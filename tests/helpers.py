@@ -48,3 +48,57 @@ def real_evk(seed, N, qs, special, sigma=3.2):
         evk[i, 0] = m_ntt
         evk[i, 1] = ctx.nntt(masked[None])[0]
     return secret, evk
+
+
+# ---------------------------------------------------------------------------------------------------
+# modulus size classes of the engine (each bound is read back out of the sources by tests/test_modulus_edges_cpu.py)
+# ---------------------------------------------------------------------------------------------------
+Q_LIMIT = 1 << 62                  # tfhe_ctx_create: every prime below 2^62
+FP_QMAX = (1 << 50) + (1 << 40)    # fp64arith.h TFHE_FP_QMAX: fp64 transforms, narrow BFV conversions below it
+FPS_QMAX = 1 << 42                 # fp64arith.h TFHE_FPS_QMAX: ArithFpS in k_ks_fused_sub when every working limb is below it
+FOLD_BITS = 52                     # kernels.h k_ks_inner: high-word fold for moduli wider than 52 bits (acc52 forms up to 52)
+KS_FOLD_LAZY_62 = 3                # kernels.h k_ks_inner: terms between two reductions at 62 bits (DCH up to 61 bits)
+MIXED_MIN_WORDS = 1 << 20          # toyfhe_hip.hip TFHE_MIXED_MIN_WORDS: words before a mixed ring is split per policy
+
+
+def sum_chunk(bits):
+    """kernels.h k_dot / k_lincomb / k_lincomb_many / k_matmul_acc / k_md_acc: products summed between two Barrett
+    reductions, 2^(62 - bits(q)) capped at 64 (chunk (q - 1)^2 < 2^(bits + 62), the Barrett window)"""
+    return 1 if bits >= 62 else min(64, 1 << (62 - bits))
+
+
+def conv_lazy(bits, k):
+    """bfv_tables.h lazy_of: exact-conversion products summed between two reductions"""
+    return max(1, min(k, 1 << 20 if 62 - bits >= 20 else 1 << max(0, 62 - bits)))
+
+
+def primes_below(bound, n, N):
+    """the n largest NTT-friendly primes (q = 1 mod 2N) below `bound`, largest first"""
+    q = (bound - 2) // (2 * N) * (2 * N) + 1
+    out = []
+    while len(out) < n:
+        assert q > 2 * N, (bound, n, N)
+        if spec.is_prime(q):
+            out.append(q)
+        q -= 2 * N
+    return out
+
+
+def primes_above(bound, n, N):
+    """the n smallest NTT-friendly primes above `bound`, smallest first"""
+    q = bound // (2 * N) * (2 * N) + 1
+    q += 2 * N if q <= bound else 0
+    out = []
+    while len(out) < n:
+        if spec.is_prime(q):
+            out.append(q)
+        q += 2 * N
+    return out
+
+
+def primes_above_ratio(k, bits, n, N):
+    """the n smallest NTT-friendly primes above 2^64 / k, all of `bits` bits: there 2^64 mod q = 2^64 - (k - 1) q is
+    close to q, the worst case of the high-word fold in k_ks_inner (z' = hi (2^64 mod q) + lo)"""
+    out = primes_above((1 << 64) // k, n, N)
+    assert all(q.bit_length() == bits for q in out), (k, bits, out)
+    return out

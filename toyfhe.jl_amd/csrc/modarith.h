@@ -157,19 +157,24 @@ struct mont26_t {
 };
 #define TFHE_MONT26_RBITS 78
 TFHE_HD u64 acc52_redc(acc52 a, const mont26_t& M) {
-    // rounds one and two take the multiplier unmasked (any m = -s p^-1 mod 2^26 clears the low 26 bits; a 32-bit m only makes
-    // the carries larger: s1 < 2^57.1, s2 < 2^56.1, both carries still fit 32 bits); the last round masks, so that r < 2 p
-    u32 m = (u32)a.s0 * M.pp;
+    // Every round masks its multiplier to 26 bits, so the lanes end up holding z + M p with M = m1 + m2 2^26 + m3 2^52 < 2^78,
+    // and r = (z + M p) 2^-78 < z 2^-78 + p.  Each of the at most 16 terms of z is a source operand below 2^51 (a residue, the
+    // alpha count or 1) times a constant reduced mod the target p, so z < 16 2^51 p = 2^55 p, z 2^-78 < 2^-23 p and r < 2 p for
+    // every p: one conditional subtraction makes it canonical.  Every lane stays below 2^57 (s0 < 2^56 + 2^52, s1 and s2 less),
+    // so every carry (lane >> 26) fits 31 bits.  (An unmasked 32-bit m in rounds one and two carried up to 2^32.3 out of s0 / s1
+    // -- truncated -- at primes whose low 26 bits are large, such as the top of the fp64 class, and left r up to 64 p at primes
+    // below 2^31.)
+    u32 m = ((u32)a.s0 * M.pp) & 0x3ffffffu;
     a.s0 += (u64)m * M.pl;  // low 26 bits are zero now
     a.s1 += (u64)m * M.ph;
     a.s1 += (u64)(u32)(a.s0 >> 26);
-    m = (u32)a.s1 * M.pp;
+    m = ((u32)a.s1 * M.pp) & 0x3ffffffu;
     a.s1 += (u64)m * M.pl;
     a.s2 += (u64)m * M.ph;
     a.s2 += (u64)(u32)(a.s1 >> 26);
     m = ((u32)a.s2 * M.pp) & 0x3ffffffu;
     a.s2 += (u64)m * M.pl;
-    const u64 r = (u64)m * M.ph + (u64)(u32)(a.s2 >> 26);  // < p + 2^31 < 2 p
+    const u64 r = (u64)m * M.ph + (u64)(u32)(a.s2 >> 26);  // < (1 + 2^-23) p
     const u64 p = ((u64)M.ph << 26) | M.pl;
     unsigned long long d;
     return __builtin_usubll_overflow(r, p, &d) ? r : (u64)d;  // the borrow of r - p selects
