@@ -37,6 +37,29 @@ def test_product_does_not_touch_oracle():
                 assert "libemul" not in src, f
 
 
+def test_kernels_are_launched_through_the_helper_only():
+    """csrc/launch.h is the one place that launches a kernel and raises a kernel's dynamic-LDS limit (once per device and
+    kernel, behind a mutex).  No other source launches by hand, sets the attribute itself, or keeps a function-local
+    `static bool` that remembers an attribute was set: those flags were unsynchronised and process-wide."""
+    csrc = os.path.join(ROOT, "toyfhe.jl_amd", "csrc")
+    helper = open(os.path.join(csrc, "launch.h")).read()
+    assert helper.count("hipLaunchKernelGGL(") == 1 and helper.count("hipFuncSetAttribute(") == 1
+    assert "std::mutex" in helper
+    seen = 0
+    for f in sorted(os.listdir(csrc)):
+        if f == "launch.h" or not f.endswith((".h", ".hip", ".inc", ".cpp")):
+            continue
+        seen += 1
+        src = open(os.path.join(csrc, f), errors="replace").read()
+        for banned in ("hipFuncSetAttribute", "hipLaunchKernelGGL", "hipLaunchKernel(", "hipModuleLaunchKernel", "<<<", "set_lds"):
+            assert banned not in src, f"{f}: {banned} outside csrc/launch.h"
+        # a mutable function-local or file-scope `static bool` is how the attribute flags were kept (`static const bool` switches
+        # read from the environment and `static bool f(...)` functions are something else)
+        flags = re.findall(r"^.*\bstatic\s+bool\s+\w+\s*(?:=|;).*$", src, flags=re.M)
+        assert not flags, f"{f}: {flags}"
+    assert seen >= 15
+
+
 @pytest.mark.skipif(native.device_count() > 0, reason="only meaningful without a GPU")
 def test_fails_loudly_without_device():
     with pytest.raises(tf.HipError):

@@ -83,19 +83,22 @@ int launch_fast(tfhe_bfv_plan* p, bool contract, const u64* src, u64* dst, int64
     const dim3 grid(gx * (unsigned)count);
     const bool lift3 = contract && lift_c2 && p->fast_narrow && count % 3 == 0;
     if (t_double && !(contract && p->fast_narrow)) return fail(TFHE_E_UNSUPPORTED, "internal: double-valued tensor rows need the narrow contraction");
+    tfhe_ctx* const c = p->big;   // the conversions run on the stream of the big ring's context
 #define X(S, P_)                                                                                                          \
     if (p->fast_ns == S && p->fast_np == P_) {                                                                            \
-        if (lift3 && t_double) hipLaunchKernelGGL((k_bfv_contract_fast<S, P_, true, true, true>), grid, dim3(256), 0, p->big->stream, src, dst, p->fast_dev, n, gx); \
-        else if (t_double) hipLaunchKernelGGL((k_bfv_contract_fast<S, P_, true, false, true>), grid, dim3(256), 0, p->big->stream, src, dst, p->fast_dev, n, gx); \
-        else if (lift3) hipLaunchKernelGGL((k_bfv_contract_fast<S, P_, true, true>), grid, dim3(256), 0, p->big->stream, src, dst, p->fast_dev, n, gx); \
-        else if (contract && p->fast_narrow) hipLaunchKernelGGL((k_bfv_contract_fast<S, P_, true>), grid, dim3(256), 0, p->big->stream, src, dst, p->fast_dev, n, gx); \
-        else if (contract) hipLaunchKernelGGL((k_bfv_contract_fast<S, P_, false>), grid, dim3(256), 0, p->big->stream, src, dst, p->fast_dev, n, gx); \
-        else if (p->fast_narrow) hipLaunchKernelGGL((k_bfv_expand_fast<S, P_, true>), grid, dim3(256), 0, p->big->stream, src, dst, p->fast_dev, n, gx, copy_shared ? 1 : 0); \
-        else hipLaunchKernelGGL((k_bfv_expand_fast<S, P_, false>), grid, dim3(256), 0, p->big->stream, src, dst, p->fast_dev, n, gx, copy_shared ? 1 : 0); \
+        if (!contract) {                                                                                                  \
+            auto ek = p->fast_narrow ? k_bfv_expand_fast<S, P_, true> : k_bfv_expand_fast<S, P_, false>;                  \
+            return launch(c, ek, grid, dim3(256), 0, src, dst, p->fast_dev, n, gx, copy_shared ? 1 : 0);                  \
+        }                                                                                                                 \
+        auto ck = lift3 && t_double ? k_bfv_contract_fast<S, P_, true, true, true>                                        \
+                  : t_double        ? k_bfv_contract_fast<S, P_, true, false, true>                                       \
+                  : lift3           ? k_bfv_contract_fast<S, P_, true, true>                                              \
+                  : p->fast_narrow  ? k_bfv_contract_fast<S, P_, true>                                                    \
+                                    : k_bfv_contract_fast<S, P_, false>;                                                  \
+        return launch(c, ck, grid, dim3(256), 0, src, dst, p->fast_dev, n, gx);                                           \
     }
     TFHE_FAST_PAIRS(X)
 #undef X
-    HIP_TRY(hipGetLastError());
     return TFHE_OK;
 }
 
@@ -104,12 +107,8 @@ int launch_expand(tfhe_bfv_plan* p, const u64* src, u64* dst, int64_t count) {
     if (p->fast_dev && p->use_fast) return launch_fast(p, false, src, dst, count);
     const u32 n = (u32)p->big->N;
     const unsigned gx = (n + BFV_BS - 1) / BFV_BS;
-    static bool attr = false;
-    if (!attr) { int rc = set_lds(k_bfv_expand, 3 * TFHE_MAX_LIMBS * BFV_BS * 8); if (rc) return rc; rc = set_lds(k_bfv_contract, 3 * TFHE_MAX_LIMBS * BFV_BS * 8); if (rc) return rc; attr = true; }
     const size_t lds = (size_t)std::max(p->tab.nb, p->tab.ns) * BFV_BS * 8;
-    hipLaunchKernelGGL(k_bfv_expand, dim3(gx * (unsigned)count), dim3(BFV_BS), lds, p->big->stream, src, dst, p->tab_dev, n, gx);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(p->big, k_bfv_expand, dim3(gx * (unsigned)count), dim3(BFV_BS), lds, src, dst, p->tab_dev, n, gx);
 }
 int launch_contract(tfhe_bfv_plan* p, const u64* src, u64* dst, int64_t count, bool lift_c2 = false, bool t_double = false) {
     if (count == 0) return TFHE_OK;
@@ -118,12 +117,8 @@ int launch_contract(tfhe_bfv_plan* p, const u64* src, u64* dst, int64_t count, b
     if (lift_c2) return fail(TFHE_E_UNSUPPORTED, "internal: lifted output needs the narrow fast path");
     const u32 n = (u32)p->big->N;
     const unsigned gx = (n + BFV_BS - 1) / BFV_BS;
-    static bool attr = false;
-    if (!attr) { int rc = set_lds(k_bfv_expand, 3 * TFHE_MAX_LIMBS * BFV_BS * 8); if (rc) return rc; rc = set_lds(k_bfv_contract, 3 * TFHE_MAX_LIMBS * BFV_BS * 8); if (rc) return rc; attr = true; }
     const size_t lds = (size_t)(2 * p->tab.nb + p->tab.ns) * BFV_BS * 8;
-    hipLaunchKernelGGL(k_bfv_contract, dim3(gx * (unsigned)count), dim3(BFV_BS), lds, p->big->stream, src, dst, p->tab_dev, n, gx);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(p->big, k_bfv_contract, dim3(gx * (unsigned)count), dim3(BFV_BS), lds, src, dst, p->tab_dev, n, gx);
 }
 
 // one chunk of c1*c2: c1,c2 [nct][2][ns][N] -> out3 [nct][3][ns][N]; E [nct][4][nb][N], T [nct][3][nb][N] scratch
@@ -137,8 +132,7 @@ int bfv_mul_chunk(tfhe_bfv_plan* p, const u64* c1, const u64* c2, u64* out3, int
     bool t_double = false;
     if (p->fast_dev && p->use_fast && bfv_core_fusable(p->big, p->sel_b)) {
         // the limbs ℛbig shares with ℛ are not copied by the expansion: the fused core reads them from the inputs
-        core_alt_t alt;
-        memset(&alt, 0, sizeof alt);
+        core_alt_t alt{};
         alt.a = c1; alt.b = c2; alt.ns = p->tab.ns;
         for (int w = 0; w < nb; w++) alt.idx[w] = -1;
         for (int i = 0; i < p->tab.ns; i++) alt.idx[p->tab.pos_s[i]] = (signed char)i;
@@ -160,8 +154,8 @@ int bfv_mul_chunk(tfhe_bfv_plan* p, const u64* c1, const u64* c2, u64* out3, int
     if (!fused) {
         rc = run_ntt(p->big, false, E, E, nct * 4 * nb, p->sel_b);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_tensor, row_grid((unsigned)(nct * nb), (size_t)N), dim3(256), 0, p->big->stream, E1, E2, T, p->big->limbs_dev, p->sel_b, (u32)N);  // rlwe_she.jl:255-258
-        HIP_TRY(hipGetLastError());
+        rc = launch(p->big, k_tensor, row_grid((unsigned)(nct * nb), (size_t)N), dim3(256), 0, E1, E2, T, p->big->limbs_dev, p->sel_b, (u32)N);  // rlwe_she.jl:255-258
+        if (rc) return rc;
         rc = run_ntt(p->big, true, T, T, nct * 3 * nb, p->sel_b);
         if (rc) return rc;
     }

@@ -207,9 +207,9 @@ int tfhe_plain_encode(tfhe_plain_plan* p, int scheme, const uint64_t* m, uint64_
     const unsigned gx = (n + PLAIN_BS - 1) / PLAIN_BS;
     for (int64_t b0 = 0; b0 < count; b0 += PLAIN_MAX_GRID_Y) {
         const int64_t nb = std::min<int64_t>(PLAIN_MAX_GRID_Y, count - b0);
-        hipLaunchKernelGGL(k_plain_encode, dim3(gx, (unsigned)nb), dim3(PLAIN_BS), 0, p->ctx->stream, m + (size_t)b0 * n,
-                           out + (size_t)b0 * L * n, p->tab_dev, scheme == TFHE_PLAIN_BGV ? 1 : 0, n);
-        HIP_TRY(hipGetLastError());
+        rc = launch(p->ctx, k_plain_encode, dim3(gx, (unsigned)nb), dim3(PLAIN_BS), 0, m + (size_t)b0 * n, out + (size_t)b0 * L * n, p->tab_dev,
+                    scheme == TFHE_PLAIN_BGV ? 1 : 0, n);
+        if (rc) return rc;
     }
     return TFHE_OK;
 }
@@ -225,12 +225,10 @@ int tfhe_plain_decode(tfhe_plain_plan* p, int scheme, const uint64_t* in, uint64
         const dim3 grid(gx, (unsigned)nb);
         const u64* src = in + (size_t)b0 * L * n;
         u64* dst = out + (size_t)b0 * n;
-#define X(KM)                                                                                                             \
-    if (scheme == TFHE_PLAIN_BGV) hipLaunchKernelGGL((k_plain_decode<KM, true>), grid, dim3(PLAIN_BS), 0, p->ctx->stream, src, dst, p->tab_dev, n); \
-    else hipLaunchKernelGGL((k_plain_decode<KM, false>), grid, dim3(PLAIN_BS), 0, p->ctx->stream, src, dst, p->tab_dev, n);
+#define X(KM) rc = launch(p->ctx, scheme == TFHE_PLAIN_BGV ? k_plain_decode<KM, true> : k_plain_decode<KM, false>, grid, dim3(PLAIN_BS), 0, src, dst, p->tab_dev, n)
         PLAIN_KM_DISPATCH(p->km, X)
 #undef X
-        HIP_TRY(hipGetLastError());
+        if (rc) return rc;
     }
     return TFHE_OK;
 }
@@ -252,12 +250,12 @@ int tfhe_bfv_noise_max(tfhe_plain_plan* p, const uint64_t* in, uint64_t* out_wor
         const int64_t nb = std::min(chunk, count - b0);
         const u64* src = in + (size_t)b0 * L * n;
         u64* dst = out_words + (size_t)b0 * nd;
-#define X(KM)                                                                                                                 \
-    hipLaunchKernelGGL((k_plain_noise_partial<KM>), dim3(gx, (unsigned)nb), dim3(PLAIN_BS), 0, p->ctx->stream, src, part, p->tab_dev, n); \
-    hipLaunchKernelGGL((k_plain_noise_reduce<KM>), dim3((unsigned)nb), dim3(PLAIN_BS), 0, p->ctx->stream, part, dst, nd, G);
+#define X(KM)                                                                                                             \
+    rc = launch(p->ctx, k_plain_noise_partial<KM>, dim3(gx, (unsigned)nb), dim3(PLAIN_BS), 0, src, part, p->tab_dev, n);   \
+    if (!rc) rc = launch(p->ctx, k_plain_noise_reduce<KM>, dim3((unsigned)nb), dim3(PLAIN_BS), 0, part, dst, nd, G)
         PLAIN_KM_DISPATCH(p->km, X)
 #undef X
-        HIP_TRY(hipGetLastError());
+        if (rc) return rc;
     }
     return TFHE_OK;
 }

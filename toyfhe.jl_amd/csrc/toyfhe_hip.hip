@@ -12,6 +12,7 @@
 #include <mutex>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/toyfhe_hip.h"
@@ -47,6 +48,22 @@ struct prof_pair {
     hipEvent_t a, b;
     int64_t limb_polys;
 };
+
+// The environment switches, each read once where it is used.  A switch that defaults to on is
+// turned off by a value starting with '0'; one that defaults to off is turned on by a value starting with '1'.
+bool env_flag(const char* name, bool dflt) {
+    const char* e = getenv(name);
+    return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+size_t env_gib(const char* name, long dflt) {   // a positive number of GiB, in bytes
+    const char* e = getenv(name);
+    const long g = e ? atol(e) : 0;
+    return (size_t)(g > 0 ? g : dflt) << 30;
+}
 
 }  // namespace
 
@@ -142,7 +159,7 @@ struct ws_borrow_t {
 };
 // workspaces above this size are per-call (pooled); TFHE_WS_KEEP_GIB overrides
 size_t ws_keep_bytes() {
-    static const size_t keep = [] { const char* e = getenv("TFHE_WS_KEEP_GIB"); const long g = e ? atol(e) : 0; return (size_t)(g > 0 ? g : 4) << 30; }();
+    static const size_t keep = env_gib("TFHE_WS_KEEP_GIB", 4);
     return keep;
 }
 
@@ -161,7 +178,7 @@ struct lanes_t {
     bool owner = false, on = false;
     hipStream_t entry = nullptr;
     explicit lanes_t(tfhe_ctx* ctx, bool want = true) : c(ctx) {
-        static const bool enabled = !(getenv("TFHE_LANES") && getenv("TFHE_LANES")[0] == '0');
+        static const bool enabled = env_flag("TFHE_LANES", true);
         entry = c->stream;
         if (!want || !enabled || c->lanes_broken) return;
         if (c->lane_depth > 0) { on = true; c->lane_depth++; return; }
@@ -214,25 +231,9 @@ int make_sel(const tfhe_ctx* c, int limbs, const int32_t* idx, limb_sel_t* sel) 
 }
 
 
-template <typename K>
-int set_lds(K kern, size_t bytes) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return TFHE_OK;
-}
-
-void prof_begin(tfhe_ctx* c, int64_t limb_polys) {
-    if (!c->prof) return;
-    prof_pair p;
-    hipEventCreate(&p.a);
-    hipEventCreate(&p.b);
-    p.limb_polys = limb_polys;
-    hipEventRecord(p.a, c->stream);
-    c->prof_pairs.push_back(p);
-}
-void prof_end(tfhe_ctx* c) {
-    if (!c->prof) return;
-    hipEventRecord(c->prof_pairs.back().b, c->stream);
-}
+}  // namespace
+#include "launch.h"
+namespace {
 
 bool sel_fp(const tfhe_ctx* c, const limb_sel_t& sel, int x) {
     (void)x;  // sub-blocks of N > 2^14 transforms use the same fp64 block kernels (top stages stay u64)
@@ -242,281 +243,44 @@ bool sel_fp(const tfhe_ctx* c, const limb_sel_t& sel, int x) {
     return true;
 }
 
-ntt_io_t io_plain() { ntt_io_t io; memset(&io, 0, sizeof io); return io; }
+// By-value kernel arguments are value-initialised (`T x{}`) throughout: the kernels read named members only, so the padding
+// bytes of these structs never matter and none of them needs a memset.
+ntt_io_t io_plain() { return ntt_io_t{}; }
 // a ring of mixed modulus sizes is split into one pass per arithmetic policy only when there is enough work to pay for the
 // second set of launches (a single ciphertext at N = 2^16 is 0.9 M words and stays on the u64 kernels)
 static long long mixed_min_words() {   // TFHE_MIXED_MIN_LOG2 overrides (measurements)
-    static const long long v = [] { const char* e = getenv("TFHE_MIXED_MIN_LOG2"); const int l = e ? atoi(e) : -1; return 1ll << ((l >= 0 && l < 40) ? l : 20); }();
+    static const long long v = [] { const int l = env_int("TFHE_MIXED_MIN_LOG2", -1); return 1ll << ((l >= 0 && l < 40) ? l : 20); }();
     return v;
 }
 #define TFHE_MIXED_MIN_WORDS mixed_min_words()
 
-template <class A, int LOGB, int IOMODE = 0>
-int launch_block_fwd(tfhe_ctx* c, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, int x, const ntt_io_t& io) {
-    if constexpr (IOMODE == 0) {
-        if (io.mode == 1) return launch_block_fwd<A, LOGB, 1>(c, src, dst, rows, sel, x, io);
-    }
-    constexpr int LOGT = logt_for(LOGB);
-    const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
-    if constexpr (IOMODE == 1) {
-        // digit lift, whole-transform blocks: read each source row once and produce all nw lifted transforms from it
-        if (x == 0 && c->variant != 3 && io.nw >= 2 && rows % io.nw == 0) {
-            auto lkern = k_ntt_fwd_lift<A, LOGB, LOGT>;
-            static bool lattr_set = false;
-            if (!lattr_set) { int rc = set_lds(lkern, lds); if (rc) return rc; lattr_set = true; }
-            const unsigned litems = (unsigned)(rows / io.nw);
-            const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)(160 * 1024) / lds, (size_t)2048 >> LOGT}));
-            const unsigned lgrid = std::min(litems, (unsigned)c->num_cus * per_cu);
-            prof_begin(c, rows);
-            hipLaunchKernelGGL(lkern, dim3(lgrid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, litems, io);
-            prof_end(c);
-            HIP_TRY(hipGetLastError());
-            return TFHE_OK;
-        }
-    }
-    if constexpr (std::is_same<A, ArithFp>::value && LOGB == 14 && IOMODE == 0) {
-        if (x == 0 && c->variant == 0 && io.limb_mask == 0) {  // next row prefetched into registers under the middle pass: +6 % stand-alone, neutral inside the BFV pipeline
-            auto pkern = k_ntt_fwd_pf<A, LOGB, LOGT>;
-            static bool pattr_set = false;
-            if (!pattr_set) { int rc = set_lds(pkern, lds); if (rc) return rc; pattr_set = true; }
-            const unsigned pgrid = std::min((unsigned)rows, (unsigned)c->num_cus);
-            prof_begin(c, rows);
-            hipLaunchKernelGGL(pkern, dim3(pgrid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, (u32)rows);
-            prof_end(c);
-            HIP_TRY(hipGetLastError());
-            return TFHE_OK;
-        }
-    }
-    auto kern = k_ntt_fwd_block<A, LOGB, LOGT, IOMODE>;
-    static bool attr_set = false;
-    if (!attr_set) { int rc = set_lds(kern, lds); if (rc) return rc; attr_set = true; }
-    // persistent workgroups: as many as are co-resident (LDS-limited), each loops over items
-    const unsigned items = (unsigned)(rows << x);
-    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)(160 * 1024) / lds, (size_t)2048 >> LOGT}));
-    const unsigned grid = std::min(items, (unsigned)c->num_cus * per_cu);
-    prof_begin(c, rows);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, x, items, io);
-    prof_end(c);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+// the first `level` moduli of the ring: a ciphertext's own limbs
+limb_sel_t first_limbs(int level) {
+    limb_sel_t s{};
+    s.n = level;
+    for (int j = 0; j < level; j++) s.idx[j] = j;
+    return s;
 }
-template <class A, int LOGB, int IOMODE = 0>
-int launch_block_inv(tfhe_ctx* c, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, int x, const ntt_io_t& io) {
-    if constexpr (IOMODE == 0) {
-        if (io.mode == 2) return launch_block_inv<A, LOGB, 2>(c, src, dst, rows, sel, x, io);
-    }
-    constexpr int LOGT = logt_for(LOGB);
-    const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
-    if constexpr (std::is_same<A, ArithFp>::value && LOGB == 14) {
-        // whole 2^14 rows in fp64: the staged kernel (next row copied HBM -> LDS under the last pass)
-        if (x == 0 && c->variant != 3 && io.limb_mask == 0) {
-            auto skern = k_ntt_inv_staged<A, LOGB, LOGT, IOMODE>;
-            static bool sattr_set = false;
-            if (!sattr_set) { int rc = set_lds(skern, lds); if (rc) return rc; sattr_set = true; }
-            const unsigned sgrid = std::min((unsigned)rows, (unsigned)c->num_cus);
-            prof_begin(c, rows);
-            hipLaunchKernelGGL(skern, dim3(sgrid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, (u32)rows, io);
-            prof_end(c);
-            HIP_TRY(hipGetLastError());
-            return TFHE_OK;
-        }
-    }
-    auto kern = k_ntt_inv_block<A, LOGB, LOGT, IOMODE>;
-    static bool attr_set = false;
-    if (!attr_set) { int rc = set_lds(kern, lds); if (rc) return rc; attr_set = true; }
-    // persistent workgroups: as many as are co-resident (LDS-limited), each loops over items
-    const unsigned items = (unsigned)(rows << x);
-    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)(160 * 1024) / lds, (size_t)2048 >> LOGT}));
-    const unsigned grid = std::min(items, (unsigned)c->num_cus * per_cu);
-    prof_begin(c, rows);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, x, items, io);
-    prof_end(c);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+// working limbs of a key switch: key limbs 0 .. level-1 (+ the special prime, the key's last limb: downswitch_keyelement,
+// modulusraising.jl:43-49)
+limb_sel_t working_limbs(int Lk, int level, int special) {
+    limb_sel_t w = first_limbs(level);
+    if (special) w.idx[w.n++] = Lk - 1;
+    return w;
+}
+ks_arg_t make_ks_arg(int Lk, int level, int special, int polys) {
+    ks_arg_t A{};
+    A.level = level; A.special = special; A.polys = polys;
+    A.w = working_limbs(Lk, level, special);
+    A.nw = A.w.n;
+    return A;
+}
+// P^-1 mod q_j for j < level, P the special prime (the key's last limb), as Shoup multipliers: the ModulusRaised contraction
+void special_inv_table(const tfhe_ctx* c, int Lk, int level, tw_t* out) {
+    const u64 P = c->q[Lk - 1];
+    for (int j = 0; j < level; j++) out[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
 }
 
-// sub-blocks of N >= 2^16 rows, two per workgroup (k_ntt_*_subpair); plain I/O, 16-byte aligned rows
-template <class A>
-int launch_subpair(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, int x, u32 mask) {
-    constexpr int LOGB = 14, LOGT = logt_for(LOGB);
-    const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
-    auto fk = k_ntt_fwd_subpair<A, LOGB, LOGT>;
-    auto ik = k_ntt_inv_subpair<A, LOGB, LOGT>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        int rc = set_lds(fk, lds);
-        if (!rc) rc = set_lds(ik, lds);
-        if (rc) return rc;
-        attr_set = true;
-    }
-    const unsigned items = (unsigned)(rows << (x - 1));
-    const unsigned grid = std::min(items, (unsigned)c->num_cus);
-    prof_begin(c, rows);
-    if (inverse) hipLaunchKernelGGL(ik, dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, x, items, mask);
-    else hipLaunchKernelGGL(fk, dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, x, items, mask);
-    prof_end(c);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
-}
-
-int launch_generic(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, const ntt_io_t& io) {
-    const size_t lds = (size_t)c->N * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        int rc = set_lds(k_ntt_fwd_generic, 128 * 1024);
-        if (rc) return rc;
-        rc = set_lds(k_ntt_inv_generic, 128 * 1024);
-        if (rc) return rc;
-        attr_set = true;
-    }
-    const int threads = (int)std::min<int64_t>(1024, std::max<int64_t>(64, c->N / 2));
-    prof_begin(c, rows);
-    if (inverse)
-        hipLaunchKernelGGL(k_ntt_inv_generic, dim3((unsigned)rows), dim3(threads), lds, c->stream, src, dst, c->limbs_dev, sel, c->logN, io);
-    else
-        hipLaunchKernelGGL(k_ntt_fwd_generic, dim3((unsigned)rows), dim3(threads), lds, c->stream, src, dst, c->limbs_dev, sel, c->logN, io);
-    prof_end(c);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
-}
-
-// N > 2^14 with one arithmetic policy (`fp`) for the block stage: x top stages on global memory + 2^14 blocks (needs an
-// out-of-place intermediate), or the one-kernel variants of the fp64 policy.  io.limb_mask restricts every kernel of the
-// call to those limbs (rings that mix modulus sizes: one call per policy).
-int run_ntt_large(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, const ntt_io_t& io,
-                  const ntt_io_t* iop, bool fp, bool wide_lift = false) {
-    const int n = c->logN, x = n - 14;
-    const bool pair15 = x == 1 && c->variant == 0 && fp;
-    if (iop && x == 1 && !(pair15 && !inverse && io.mode == 1))
-        return fail(TFHE_E_UNSUPPORTED, "fused NTT I/O transforms need N <= 2^14 (digit lift: N <= 2^16, fp64 policy)");
-    if (pair15) {
-        // N = 2^15, fp64 policy: top stage and both 2^14 sub-blocks in one kernel (one read + one write of the row)
-        constexpr int LOGT = logt_for(14);
-        const size_t lds = (size_t)lds_words<14, LOGT>() * 8;
-        static bool pattr_set = false;
-        if (!pattr_set) {
-            int rc2 = set_lds(k_ntt_fwd_pair<ArithFp, 14, LOGT>, lds);
-            if (!rc2) rc2 = set_lds(k_ntt_fwd_pair<ArithFp, 14, LOGT, true>, lds);
-            if (!rc2) rc2 = set_lds(k_ntt_fwd_pair<ArithFpWide, 14, LOGT, true>, lds);
-            if (!rc2) rc2 = set_lds(k_ntt_inv_pair<ArithFp, 14, LOGT>, lds);
-            if (rc2) return rc2;
-            pattr_set = true;
-        }
-        const unsigned grid = std::min((unsigned)rows, (unsigned)c->num_cus);
-        prof_begin(c, rows);
-        if (inverse) hipLaunchKernelGGL((k_ntt_inv_pair<ArithFp, 14, LOGT>), dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, (u32)rows, io.limb_mask);
-        else if (io.mode == 1 && wide_lift) hipLaunchKernelGGL((k_ntt_fwd_pair<ArithFpWide, 14, LOGT, true>), dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, (u32)rows, io);
-        else if (io.mode == 1) hipLaunchKernelGGL((k_ntt_fwd_pair<ArithFp, 14, LOGT, true>), dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, (u32)rows, io);
-        else hipLaunchKernelGGL((k_ntt_fwd_pair<ArithFp, 14, LOGT>), dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, (u32)rows, io);
-        prof_end(c);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
-    }
-    if (x > 3) return fail(TFHE_E_UNSUPPORTED, "N = 2^%d not supported (max 2^17)", n);
-    // fp64 policy: two sub-blocks per workgroup (16-byte pieces on the natural-order side)
-    const bool pairable = x >= 2 && c->variant == 0 && fp && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0;
-    if (iop && !(pairable && x == 2 && !inverse && io.mode == 1 && src != dst))
-        return fail(TFHE_E_UNSUPPORTED, "fused NTT I/O transforms need N <= 2^14 (digit lift: N <= 2^16, fp64 policy)");
-    if (!inverse && pairable && x == 2 && src != dst) {
-        // N = 2^16 forward in one kernel: top stages folded into the paired sub-block kernel (out of place only: the
-        // row's other workgroup reads the same source words)
-        constexpr int LOGT = logt_for(14);
-        const size_t lds = (size_t)lds_words<14, LOGT>() * 8;
-        auto qk = io.mode == 1 ? (wide_lift ? k_ntt_fwd_quad<ArithFpWide, 14, LOGT, true> : k_ntt_fwd_quad<ArithFp, 14, LOGT, true>)
-                               : k_ntt_fwd_quad<ArithFp, 14, LOGT, false>;
-        static bool qattr_set = false;
-        if (!qattr_set) {
-            int rc2 = set_lds(k_ntt_fwd_quad<ArithFp, 14, LOGT, true>, lds);
-            if (!rc2) rc2 = set_lds(k_ntt_fwd_quad<ArithFpWide, 14, LOGT, true>, lds);
-            if (!rc2) rc2 = set_lds(k_ntt_fwd_quad<ArithFp, 14, LOGT, false>, lds);
-            if (rc2) return rc2;
-            qattr_set = true;
-        }
-        const unsigned items = (unsigned)(rows << 1);
-        const unsigned grid = std::min(items, (unsigned)c->num_cus);
-        prof_begin(c, rows);
-        hipLaunchKernelGGL(qk, dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, items, io);
-        prof_end(c);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
-    }
-    // MEASURED (r03, same box, 512 polys x 7 limbs of 50 bits): 1.75 TB/s against 1.98 for the two-kernel path below (1.64 with
-    // device-scope atomic loads of the parked words instead of an L1-invalidating acquire fence; 1.14 with a release fence, which
-    // writes the L2 back) -- one 512-thread workgroup per CU runs its load, four sub-block transforms, parking, read-back, top
-    // stages and stores strictly one after the other, where the two-kernel path has two workgroups per row in flight and
-    // streaming kernels around them.  Off: the template is not instantiated unless -DTFHE_INV_QUAD=1.
-#ifndef TFHE_INV_QUAD
-#define TFHE_INV_QUAD 0
-#endif
-#if TFHE_INV_QUAD
-    if (inverse && pairable && x == 2 && !iop) {
-        // N = 2^16 inverse in one kernel (k_ntt_inv_quad): one row per workgroup pass, sub-block results parked in a
-        // per-workgroup scratch row, top stages on the thread's own columns
-        constexpr int LOGT = logt_for(14);
-        const size_t lds = (size_t)lds_words<14, LOGT>() * 8;
-        auto qk = k_ntt_inv_quad<ArithFp, 14, LOGT>;
-        static bool iqattr_set = false;
-        if (!iqattr_set) { int rc2 = set_lds(qk, lds); if (rc2) return rc2; iqattr_set = true; }
-        const unsigned grid = (unsigned)std::min<int64_t>(rows, (int64_t)c->num_cus);
-        void* scr = nullptr;
-        int rc2 = ensure_ws(c, (size_t)grid * c->N * 8, &scr);
-        if (rc2) return rc2;
-        prof_begin(c, rows);
-        hipLaunchKernelGGL(qk, dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, (u64*)scr, c->limbs_dev, sel, (u32)rows, io.limb_mask);
-        prof_end(c);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
-    }
-#endif
-    // N = 2^16 inverse, out of place, in ONE pass (k_ntt_inv_quad2: the two top stages first, r04): 2 N 8 bytes per row instead of
-    // the 4 N 8 of the sub-block kernel + k_ntt_inv_top<2> below; TFHE_INV_I2=0 keeps the two-kernel path (comparisons)
-    static const bool inv_i2 = !(getenv("TFHE_INV_I2") && getenv("TFHE_INV_I2")[0] == '0');
-    if (inverse && pairable && x == 2 && !iop && src != dst && inv_i2) {
-        constexpr int LOGT = logt_for(14);
-        const size_t lds = (size_t)lds_words<14, LOGT>() * 8;
-        auto qk = k_ntt_inv_quad2<ArithFp, 14, LOGT>;
-        static bool i2attr_set = false;
-        if (!i2attr_set) { int rc2 = set_lds(qk, lds); if (rc2) return rc2; i2attr_set = true; }
-        const unsigned items = (unsigned)(rows << 1);
-        const unsigned grid = std::min(items, (unsigned)c->num_cus);
-        prof_begin(c, rows);
-        hipLaunchKernelGGL(qk, dim3(grid), dim3(1 << LOGT), lds, c->stream, src, dst, c->limbs_dev, sel, items, io.limb_mask);
-        prof_end(c);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
-    }
-    void* tmp = nullptr;
-    int rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
-    if (rc) return rc;
-    u64* t = (u64*)tmp;
-    const dim3 tg((unsigned)((((c->N >> x) + 255) / 256) * rows));
-    if (!inverse) {
-        prof_begin(c, 0);
-        switch (x) {
-            case 1: hipLaunchKernelGGL(k_ntt_fwd_top<1>, tg, dim3(256), 0, c->stream, src, t, c->limbs_dev, sel, n, io.limb_mask); break;
-            case 2: hipLaunchKernelGGL(k_ntt_fwd_top<2>, tg, dim3(256), 0, c->stream, src, t, c->limbs_dev, sel, n, io.limb_mask); break;
-            default: hipLaunchKernelGGL(k_ntt_fwd_top<3>, tg, dim3(256), 0, c->stream, src, t, c->limbs_dev, sel, n, io.limb_mask); break;
-        }
-        prof_end(c);
-        HIP_TRY(hipGetLastError());
-        if (pairable) return launch_subpair<ArithFp>(c, false, t, dst, rows, sel, x, io.limb_mask);
-        return fp ? launch_block_fwd<ArithFp, 14>(c, t, dst, rows, sel, x, io) : launch_block_fwd<ArithInt, 14>(c, t, dst, rows, sel, x, io);
-    }
-    if (pairable) rc = launch_subpair<ArithFp>(c, true, src, t, rows, sel, x, io.limb_mask);
-    else rc = fp ? launch_block_inv<ArithFp, 14>(c, src, t, rows, sel, x, io) : launch_block_inv<ArithInt, 14>(c, src, t, rows, sel, x, io);
-    if (rc) return rc;
-    prof_begin(c, 0);
-    switch (x) {
-        case 1: hipLaunchKernelGGL(k_ntt_inv_top<1>, tg, dim3(256), 0, c->stream, t, dst, c->limbs_dev, sel, n, io.limb_mask); break;
-        case 2: hipLaunchKernelGGL(k_ntt_inv_top<2>, tg, dim3(256), 0, c->stream, t, dst, c->limbs_dev, sel, n, io.limb_mask); break;
-        default: hipLaunchKernelGGL(k_ntt_inv_top<3>, tg, dim3(256), 0, c->stream, t, dst, c->limbs_dev, sel, n, io.limb_mask); break;
-    }
-    prof_end(c);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
-}
-
-// forward / inverse transform of `rows` limb-polynomials; src == dst allowed
 // Per-limb routing masks are 32 bits wide (ntt_io_t::limb_mask, the key-switch kernels' limb_mask); TFHE_MAX_LIMBS is 40
 // and a special prime makes 41 working limbs, so rings with more than 32 selected limbs cannot be split by policy: they
 // run whole on the policy that takes every limb (all fp64-size / all narrow: the fast kernels unmasked; otherwise the
@@ -534,7 +298,148 @@ static inline u32 mask_of(int n, F pred) {  // bit j set where pred(j); for n > 
         if (pred(j)) m |= 1u << j;
     return m;
 }
+// how a selection splits between the arithmetic policies: the limbs with fp64 twiddle tables (moduli of fp64 size: the fp64
+// transforms), the limbs below 2^52 (the carry-free key sums), and all of them
+struct policy_split_t {
+    u32 fpmask, narrow, all;
+    bool mixed_fp() const { return fpmask != 0 && fpmask != all; }
+};
+policy_split_t policy_split(const tfhe_ctx* c, const limb_sel_t& sel) {
+    policy_split_t p;
+    p.fpmask = mask_of(sel.n, [&](int j) { return c->limbs_host[sel.idx[j]].Wd != nullptr; });
+    p.narrow = mask_of(sel.n, [&](int j) { return (c->limbs_host[sel.idx[j]].q >> 52) == 0; });
+    p.all = mask_all(sel.n);
+    return p;
+}
 
+template <class A, int LOGB, int IOMODE = 0>
+int launch_block_fwd(tfhe_ctx* c, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, int x, const ntt_io_t& io) {
+    if constexpr (IOMODE == 0) {
+        if (io.mode == 1) return launch_block_fwd<A, LOGB, 1>(c, src, dst, rows, sel, x, io);
+    }
+    constexpr int LOGT = logt_for(LOGB);
+    const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
+    const dim3 block(1 << LOGT);
+    if constexpr (IOMODE == 1) {
+        // digit lift, whole-transform blocks: read each source row once and produce all nw lifted transforms from it
+        if (x == 0 && c->variant != 3 && io.nw >= 2 && rows % io.nw == 0) {
+            const unsigned litems = (unsigned)(rows / io.nw);
+            return launch_prof(c, rows, k_ntt_fwd_lift<A, LOGB, LOGT>, dim3(persistent_grid(c, litems, lds, LOGT)), block, lds, src, dst,
+                               c->limbs_dev, sel, litems, io);
+        }
+    }
+    if constexpr (std::is_same<A, ArithFp>::value && LOGB == 14 && IOMODE == 0) {
+        if (x == 0 && c->variant == 0 && io.limb_mask == 0)  // next row prefetched into registers under the middle pass: +6 % stand-alone, neutral inside the BFV pipeline
+            return launch_prof(c, rows, k_ntt_fwd_pf<A, LOGB, LOGT>, dim3(cu_grid(c, (unsigned)rows)), block, lds, src, dst, c->limbs_dev, sel, (u32)rows);
+    }
+    const unsigned items = (unsigned)(rows << x);
+    return launch_prof(c, rows, k_ntt_fwd_block<A, LOGB, LOGT, IOMODE>, dim3(persistent_grid(c, items, lds, LOGT)), block, lds, src, dst,
+                       c->limbs_dev, sel, x, items, io);
+}
+template <class A, int LOGB, int IOMODE = 0>
+int launch_block_inv(tfhe_ctx* c, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, int x, const ntt_io_t& io) {
+    if constexpr (IOMODE == 0) {
+        if (io.mode == 2) return launch_block_inv<A, LOGB, 2>(c, src, dst, rows, sel, x, io);
+    }
+    constexpr int LOGT = logt_for(LOGB);
+    const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
+    const dim3 block(1 << LOGT);
+    if constexpr (std::is_same<A, ArithFp>::value && LOGB == 14) {
+        // whole 2^14 rows in fp64: the staged kernel (next row copied HBM -> LDS under the last pass)
+        if (x == 0 && c->variant != 3 && io.limb_mask == 0)
+            return launch_prof(c, rows, k_ntt_inv_staged<A, LOGB, LOGT, IOMODE>, dim3(cu_grid(c, (unsigned)rows)), block, lds, src, dst,
+                               c->limbs_dev, sel, (u32)rows, io);
+    }
+    const unsigned items = (unsigned)(rows << x);
+    return launch_prof(c, rows, k_ntt_inv_block<A, LOGB, LOGT, IOMODE>, dim3(persistent_grid(c, items, lds, LOGT)), block, lds, src, dst,
+                       c->limbs_dev, sel, x, items, io);
+}
+
+// sub-blocks of N >= 2^16 rows, two per workgroup (k_ntt_*_subpair); plain I/O, 16-byte aligned rows
+template <class A>
+int launch_subpair(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, int x, u32 mask) {
+    constexpr int LOGB = 14, LOGT = logt_for(LOGB);
+    const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
+    const unsigned items = (unsigned)(rows << (x - 1));
+    auto kern = inverse ? k_ntt_inv_subpair<A, LOGB, LOGT> : k_ntt_fwd_subpair<A, LOGB, LOGT>;
+    return launch_prof(c, rows, kern, dim3(cu_grid(c, items)), dim3(1 << LOGT), lds, src, dst, c->limbs_dev, sel, x, items, mask);
+}
+
+int launch_generic(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, const ntt_io_t& io) {
+    const size_t lds = (size_t)c->N * 8;
+    const int threads = (int)std::min<int64_t>(1024, std::max<int64_t>(64, c->N / 2));
+    return launch_prof(c, rows, inverse ? k_ntt_inv_generic : k_ntt_fwd_generic, dim3((unsigned)rows), dim3(threads), lds, src, dst, c->limbs_dev,
+                       sel, c->logN, io);
+}
+
+// N > 2^14 with one arithmetic policy (`fp`) for the block stage: x top stages on global memory + 2^14 blocks (needs an
+// out-of-place intermediate), or the one-kernel variants of the fp64 policy.  io.limb_mask restricts every kernel of the
+// call to those limbs (rings that mix modulus sizes: one call per policy).
+int run_ntt_large(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, const ntt_io_t& io,
+                  const ntt_io_t* iop, bool fp, bool wide_lift = false) {
+    const int n = c->logN, x = n - 14;
+    constexpr int LOGT = logt_for(14);
+    const size_t lds = (size_t)lds_words<14, LOGT>() * 8;
+    const dim3 block(1 << LOGT);
+    const bool pair15 = x == 1 && c->variant == 0 && fp;
+    if (iop && x == 1 && !(pair15 && !inverse && io.mode == 1))
+        return fail(TFHE_E_UNSUPPORTED, "fused NTT I/O transforms need N <= 2^14 (digit lift: N <= 2^16, fp64 policy)");
+    if (pair15) {
+        // N = 2^15, fp64 policy: top stage and both 2^14 sub-blocks in one kernel (one read + one write of the row)
+        const dim3 grid(cu_grid(c, (unsigned)rows));
+        if (inverse) return launch_prof(c, rows, k_ntt_inv_pair<ArithFp, 14, LOGT>, grid, block, lds, src, dst, c->limbs_dev, sel, (u32)rows, io.limb_mask);
+        auto pk = io.mode == 1 ? (wide_lift ? k_ntt_fwd_pair<ArithFpWide, 14, LOGT, true> : k_ntt_fwd_pair<ArithFp, 14, LOGT, true>)
+                               : k_ntt_fwd_pair<ArithFp, 14, LOGT>;
+        return launch_prof(c, rows, pk, grid, block, lds, src, dst, c->limbs_dev, sel, (u32)rows, io);
+    }
+    if (x > 3) return fail(TFHE_E_UNSUPPORTED, "N = 2^%d not supported (max 2^17)", n);
+    // fp64 policy: two sub-blocks per workgroup (16-byte pieces on the natural-order side)
+    const bool pairable = x >= 2 && c->variant == 0 && fp && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0;
+    if (iop && !(pairable && x == 2 && !inverse && io.mode == 1 && src != dst))
+        return fail(TFHE_E_UNSUPPORTED, "fused NTT I/O transforms need N <= 2^14 (digit lift: N <= 2^16, fp64 policy)");
+    if (!inverse && pairable && x == 2 && src != dst) {
+        // N = 2^16 forward in one kernel: top stages folded into the paired sub-block kernel (out of place only: the
+        // row's other workgroup reads the same source words)
+        auto qk = io.mode == 1 ? (wide_lift ? k_ntt_fwd_quad<ArithFpWide, 14, LOGT, true> : k_ntt_fwd_quad<ArithFp, 14, LOGT, true>)
+                               : k_ntt_fwd_quad<ArithFp, 14, LOGT, false>;
+        const unsigned items = (unsigned)(rows << 1);
+        return launch_prof(c, rows, qk, dim3(cu_grid(c, items)), block, lds, src, dst, c->limbs_dev, sel, items, io);
+    }
+    // There is no one-kernel inverse with the sub-blocks FIRST (one row per workgroup pass, sub-block results parked in a
+    // per-workgroup scratch row, top stages on the thread's own columns).  MEASURED (r03, 512 polys x 7 limbs of 50 bits): 1.75 TB/s
+    // against 1.98 for the two-kernel path below (1.64 with device-scope atomic loads of the parked words instead of an
+    // L1-invalidating acquire fence; 1.14 with a release fence, which writes the L2 back) -- one 512-thread workgroup per CU runs
+    // its load, four sub-block transforms, parking, read-back, top stages and stores strictly one after the other, where the
+    // two-kernel path has two workgroups per row in flight and streaming kernels around them (profiles/LOG.md r03).
+    // N = 2^16 inverse, out of place, in ONE pass (k_ntt_inv_quad2: the two top stages first, r04): 2 N 8 bytes per row instead of
+    // the 4 N 8 of the sub-block kernel + k_ntt_inv_top<2> below; TFHE_INV_I2=0 keeps the two-kernel path (comparisons)
+    static const bool inv_i2 = env_flag("TFHE_INV_I2", true);
+    if (inverse && pairable && x == 2 && !iop && src != dst && inv_i2) {
+        const unsigned items = (unsigned)(rows << 1);
+        return launch_prof(c, rows, k_ntt_inv_quad2<ArithFp, 14, LOGT>, dim3(cu_grid(c, items)), block, lds, src, dst, c->limbs_dev, sel, items, io.limb_mask);
+    }
+    void* tmp = nullptr;
+    int rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
+    if (rc) return rc;
+    u64* t = (u64*)tmp;
+    const dim3 tg((unsigned)((((c->N >> x) + 255) / 256) * rows));
+    if (!inverse) {
+        rc = dispatch_int<1, 3>(x, [&](auto xc) {
+            return launch_prof(c, 0, k_ntt_fwd_top<decltype(xc)::value>, tg, dim3(256), 0, src, t, c->limbs_dev, sel, n, io.limb_mask);
+        });
+        if (rc) return rc;
+        if (pairable) return launch_subpair<ArithFp>(c, false, t, dst, rows, sel, x, io.limb_mask);
+        return fp ? launch_block_fwd<ArithFp, 14>(c, t, dst, rows, sel, x, io) : launch_block_fwd<ArithInt, 14>(c, t, dst, rows, sel, x, io);
+    }
+    if (pairable) rc = launch_subpair<ArithFp>(c, true, src, t, rows, sel, x, io.limb_mask);
+    else rc = fp ? launch_block_inv<ArithFp, 14>(c, src, t, rows, sel, x, io) : launch_block_inv<ArithInt, 14>(c, src, t, rows, sel, x, io);
+    if (rc) return rc;
+    return dispatch_int<1, 3>(x, [&](auto xc) {
+        return launch_prof(c, 0, k_ntt_inv_top<decltype(xc)::value>, tg, dim3(256), 0, t, dst, c->limbs_dev, sel, n, io.limb_mask);
+    });
+}
+
+// forward / inverse transform of `rows` limb-polynomials; src == dst allowed
 // `io` (optional) selects the fused global-I/O transforms of ntt_io_t; only for N <= 2^14 (single-block transforms)
 int run_ntt(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, const ntt_io_t* iop = nullptr) {
     if (rows == 0) return TFHE_OK;
@@ -543,78 +448,58 @@ int run_ntt(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, c
     const int n = c->logN;
     const bool use_block = (c->variant != 1 && n >= 10) || n > 14;
     if (!use_block) return launch_generic(c, inverse, src, dst, rows, sel, io);
+    // a ring that mixes fp64-size moduli with larger ones (60-bit q0 / special prime next to 40-bit primes): one launch (N > 2^14:
+    // one pass) per policy, each taking its limbs (ntt_io_t::limb_mask)
+    const policy_split_t ps = policy_split(c, sel);
+    ntt_io_t a = io, b = io;
+    a.limb_mask = ps.fpmask;
+    b.limb_mask = ps.all & ~ps.fpmask;
+    const bool enough = sel.n <= 32 && ps.mixed_fp() && (rows << n) >= TFHE_MIXED_MIN_WORDS;
     if (n <= 14) {
         const bool fp = sel_fp(c, sel, 0);
-        // a ring that mixes fp64-size moduli with larger ones (60-bit q0 / special prime next to 40-bit primes): one launch
-        // per policy, each taking its limbs (ntt_io_t::limb_mask)
-        const u32 fpmask = mask_of(sel.n, [&](int j) { return c->limbs_host[sel.idx[j]].Wd != nullptr; });
-        const u32 all = mask_all(sel.n);
-        if (!fp && c->variant == 0 && sel.n <= 32 && fpmask != 0 && fpmask != all && (io.mode != 1 || n >= 12) && (rows << n) >= TFHE_MIXED_MIN_WORDS) {
-            // (digit-lift mode: the mask is on the TARGET limb j of item (b, i, j); the fp64 lift takes source limbs of either
-            // size through ArithFpWide, instantiated for N >= 2^12)
-            ntt_io_t a = io, b = io;
-            a.limb_mask = fpmask;
-            b.limb_mask = all & ~fpmask;
+        if (!fp && c->variant == 0 && enough && (io.mode != 1 || n >= 12)) {
             // the two policies side by side (lanes_t): the u64 launches -- the long pole -- first, on the main lane
             lanes_t lanes(c);
             if (io.mode == 1) {
-                int rc1 = TFHE_E_UNSUPPORTED;
+                // (digit-lift mode: the mask is on the TARGET limb j of item (b, i, j); the fp64 lift takes source limbs of either
+                // size through ArithFpWide, instantiated for N >= 2^12)
+                return dispatch_int<12, 14>(n, [&](auto lb) {
+                    constexpr int LB = decltype(lb)::value;
+                    lanes.use(0);
+                    const int rc1 = launch_block_fwd<ArithInt, LB, 1>(c, src, dst, rows, sel, 0, b);
+                    if (rc1) return rc1;
+                    lanes.use(1);
+                    return launch_block_fwd<ArithFpWide, LB, 1>(c, src, dst, rows, sel, 0, a);
+                });
+            }
+            return dispatch_int<10, 14>(n, [&](auto lb) {
+                constexpr int LB = decltype(lb)::value;
                 lanes.use(0);
-                switch (n) {
-                    case 12: rc1 = launch_block_fwd<ArithInt, 12, 1>(c, src, dst, rows, sel, 0, b); break;
-                    case 13: rc1 = launch_block_fwd<ArithInt, 13, 1>(c, src, dst, rows, sel, 0, b); break;
-                    case 14: rc1 = launch_block_fwd<ArithInt, 14, 1>(c, src, dst, rows, sel, 0, b); break;
-                }
+                const int rc1 = inverse ? launch_block_inv<ArithInt, LB>(c, src, dst, rows, sel, 0, b) : launch_block_fwd<ArithInt, LB>(c, src, dst, rows, sel, 0, b);
                 if (rc1) return rc1;
                 lanes.use(1);
-                switch (n) {
-                    case 12: return launch_block_fwd<ArithFpWide, 12, 1>(c, src, dst, rows, sel, 0, a);
-                    case 13: return launch_block_fwd<ArithFpWide, 13, 1>(c, src, dst, rows, sel, 0, a);
-                    default: return launch_block_fwd<ArithFpWide, 14, 1>(c, src, dst, rows, sel, 0, a);
-                }
-            }
-            switch (n) {
-#define CASE_(LB)                                                                                                  \
-    case LB: {                                                                                                     \
-        lanes.use(0);                                                                                              \
-        int rc1 = inverse ? launch_block_inv<ArithInt, LB>(c, src, dst, rows, sel, 0, b) : launch_block_fwd<ArithInt, LB>(c, src, dst, rows, sel, 0, b); \
-        if (rc1) return rc1;                                                                                       \
-        lanes.use(1);                                                                                              \
-        return inverse ? launch_block_inv<ArithFp, LB>(c, src, dst, rows, sel, 0, a) : launch_block_fwd<ArithFp, LB>(c, src, dst, rows, sel, 0, a); \
-    }
-                CASE_(10) CASE_(11) CASE_(12) CASE_(13) CASE_(14)
-#undef CASE_
-            }
+                return inverse ? launch_block_inv<ArithFp, LB>(c, src, dst, rows, sel, 0, a) : launch_block_fwd<ArithFp, LB>(c, src, dst, rows, sel, 0, a);
+            });
         }
-        switch (n) {
-#define CASE_(LB)                                                                                                  \
-    case LB:                                                                                                       \
-        if (fp) return inverse ? launch_block_inv<ArithFp, LB>(c, src, dst, rows, sel, 0, io) : launch_block_fwd<ArithFp, LB>(c, src, dst, rows, sel, 0, io); \
-        return inverse ? launch_block_inv<ArithInt, LB>(c, src, dst, rows, sel, 0, io) : launch_block_fwd<ArithInt, LB>(c, src, dst, rows, sel, 0, io);
-            CASE_(10) CASE_(11) CASE_(12) CASE_(13) CASE_(14)
-#undef CASE_
-        }
+        return dispatch_int<10, 14>(n, [&](auto lb) {
+            constexpr int LB = decltype(lb)::value;
+            if (fp) return inverse ? launch_block_inv<ArithFp, LB>(c, src, dst, rows, sel, 0, io) : launch_block_fwd<ArithFp, LB>(c, src, dst, rows, sel, 0, io);
+            return inverse ? launch_block_inv<ArithInt, LB>(c, src, dst, rows, sel, 0, io) : launch_block_fwd<ArithInt, LB>(c, src, dst, rows, sel, 0, io);
+        });
     }
     // N > 2^14
-    if (!iop && c->variant == 0) {
-        const u32 fpmask = mask_of(sel.n, [&](int j) { return c->limbs_host[sel.idx[j]].Wd != nullptr; });
-        const u32 all = mask_all(sel.n);
-        if (sel.n <= 32 && fpmask != 0 && fpmask != all && (rows << n) >= TFHE_MIXED_MIN_WORDS) {  // mixed modulus sizes: one pass per policy, each over its limbs
-            ntt_io_t a = io, b = io;
-            a.limb_mask = fpmask;
-            b.limb_mask = all & ~fpmask;
-            // the transform scratch of both policies (disjoint rows of it) is sized before the fork: growing it synchronises
-            void* tmp = nullptr;
-            int rc1 = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
-            if (rc1) return rc1;
-            lanes_t lanes(c);
-            // (which policy is enqueued first makes no difference: TFHE_LANE_FP_FIRST A/B, profiles/r06b_lane_order_ab.txt)
-            lanes.use(0);   // the u64 launches (top stages + block kernel: the long pole) first, on the main lane
-            rc1 = run_ntt_large(c, inverse, src, dst, rows, sel, b, nullptr, false);
-            if (rc1) return rc1;
-            lanes.use(1);
-            return run_ntt_large(c, inverse, src, dst, rows, sel, a, nullptr, true);
-        }
+    if (!iop && c->variant == 0 && enough) {
+        // the transform scratch of both policies (disjoint rows of it) is sized before the fork: growing it synchronises
+        void* tmp = nullptr;
+        int rc1 = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
+        if (rc1) return rc1;
+        lanes_t lanes(c);
+        // (which policy is enqueued first makes no difference: TFHE_LANE_FP_FIRST A/B, profiles/r06b_lane_order_ab.txt)
+        lanes.use(0);   // the u64 launches (top stages + block kernel: the long pole) first, on the main lane
+        rc1 = run_ntt_large(c, inverse, src, dst, rows, sel, b, nullptr, false);
+        if (rc1) return rc1;
+        lanes.use(1);
+        return run_ntt_large(c, inverse, src, dst, rows, sel, a, nullptr, true);
     }
     return run_ntt_large(c, inverse, src, dst, rows, sel, io, iop, sel_fp(c, sel, n - 14));
 }
@@ -630,51 +515,25 @@ bool bfv_core_fusable(const tfhe_ctx* c, const limb_sel_t& sel) { return c->vari
 #ifndef TFHE_GRID_MULT_KS
 #define TFHE_GRID_MULT_KS 1u
 #endif
-template <int LOGB>
-static int launch_bfv_core_fused_n(tfhe_ctx* c, const u64* Ea, const u64* Eb, u64* T, u64* scratch, int64_t nct, const limb_sel_t& sel,
-                                   const core_alt_t& alt, bool out_double) {
-    constexpr int LOGT = logt_for(LOGB);
-    const size_t lds = fused_lds_bytes<LOGB, LOGT, TFHE_TWL_CORE>();
-    auto kern = out_double ? k_bfv_core_fused<ArithFp, LOGB, LOGT, true> : k_bfv_core_fused<ArithFp, LOGB, LOGT, false>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        int rc = set_lds(k_bfv_core_fused<ArithFp, LOGB, LOGT, true>, lds);
-        if (!rc) rc = set_lds(k_bfv_core_fused<ArithFp, LOGB, LOGT, false>, lds);
-        if (rc) return rc;
-        attr_set = true;
-    }
-    const unsigned items = (unsigned)(nct * sel.n);
-    // one 512-thread workgroup fills a CU at 2^14; the 256-thread workgroups of the smaller rings leave room for a second one
-    const unsigned grid = std::min(items, (LOGB == 14 ? 1u : 2u) * (unsigned)c->num_cus * TFHE_GRID_MULT_CORE);
-    prof_begin(c, (int64_t)items * 7);  // limb transforms inside this launch: 4 forward + 3 inverse per item
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(1 << LOGT), lds, c->stream, Ea, Eb, T, scratch, c->limbs_dev, sel, items, alt);
-    prof_end(c);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
-}
 int launch_bfv_core_fused(tfhe_ctx* c, const u64* Ea, const u64* Eb, u64* T, u64* scratch, int64_t nct, const limb_sel_t& sel, bool* done,
                           const core_alt_t* altp = nullptr, bool out_double = false) {
     *done = false;
     if (!bfv_core_fusable(c, sel) || nct * sel.n > 0x7fffffffll) return TFHE_OK;
-    core_alt_t alt;
-    if (altp) alt = *altp; else { memset(&alt, 0, sizeof alt); alt.a = alt.b = nullptr; }
-    int rc;
-    switch (c->logN) {
-        case 12: rc = launch_bfv_core_fused_n<12>(c, Ea, Eb, T, scratch, nct, sel, alt, out_double); break;
-        case 13: rc = launch_bfv_core_fused_n<13>(c, Ea, Eb, T, scratch, nct, sel, alt, out_double); break;
-        default: rc = launch_bfv_core_fused_n<14>(c, Ea, Eb, T, scratch, nct, sel, alt, out_double); break;
-    }
+    core_alt_t alt{};
+    if (altp) alt = *altp;
+    const unsigned items = (unsigned)(nct * sel.n);
+    const int rc = dispatch_int<12, 14>(c->logN, [&](auto lb) {
+        constexpr int LOGB = decltype(lb)::value, LOGT = logt_for(LOGB);
+        auto kern = out_double ? k_bfv_core_fused<ArithFp, LOGB, LOGT, true> : k_bfv_core_fused<ArithFp, LOGB, LOGT, false>;
+        // one 512-thread workgroup fills a CU at 2^14; the 256-thread workgroups of the smaller rings leave room for a second one
+        const unsigned grid = cu_grid(c, items, (LOGB == 14 ? 1u : 2u) * TFHE_GRID_MULT_CORE);
+        // limb transforms inside this launch: 4 forward + 3 inverse per item
+        return launch_prof(c, (int64_t)items * 7, kern, dim3(grid), dim3(1 << LOGT), fused_lds_bytes<LOGB, LOGT, TFHE_TWL_CORE>(), Ea, Eb, T, scratch,
+                           c->limbs_dev, sel, items, alt);
+    });
     if (rc) return rc;
     *done = true;
     return TFHE_OK;
-}
-
-// grid of the row-wise kernels (one limb row per blockIdx.x): few rows -- a single ciphertext at N = 2^16 is 14 -- are
-// split over blockIdx.y so that the launch still covers the chip (about 2048 workgroups, at least 1024 coefficients each)
-static inline dim3 row_grid(unsigned rows, size_t n) {
-    const unsigned want = rows ? (2048u + rows - 1) / rows : 1u;
-    const unsigned cap = (unsigned)std::max<size_t>(1, n / 1024);
-    return dim3(rows, std::max(1u, std::min(want, cap)));
 }
 
 template <int OP>
@@ -686,12 +545,9 @@ int run_pointwise(tfhe_ctx* c, const u64* a, const u64* b, const u64* acc, u64* 
     if (rc) return rc;
     if (count == 0) return TFHE_OK;
     if (count < 0 || count * limbs > 0x7fffffffll) return fail(TFHE_E_BADARG, "bad polynomial count");
-    scal_arg_t s0;
-    if (!sc) { memset(&s0, 0, sizeof s0); sc = &s0; }
-    hipLaunchKernelGGL(k_pointwise<OP>, row_grid((unsigned)(count * limbs), (size_t)c->N), dim3(256), 0, c->stream, a, b, acc, dst,
-                       c->limbs_dev, sel, *sc, (u32)c->N);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    const scal_arg_t s0{};
+    return launch(c, k_pointwise<OP>, row_grid((unsigned)(count * limbs), (size_t)c->N), dim3(256), 0, a, b, acc, dst, c->limbs_dev, sel,
+                  sc ? *sc : s0, (u32)c->N);
 }
 
 }  // namespace
@@ -895,9 +751,7 @@ int tfhe_broadcast_poly(tfhe_ctx* c, uint64_t* dst, const uint64_t* src, size_t 
     if (!c || !dst || !src) return fail(TFHE_E_BADARG, "null argument");
     if (count < 0 || count > 65535 || (words & 1)) return fail(TFHE_E_BADARG, "count must be in [0, 65535], words even");
     if (count == 0 || words == 0) return TFHE_OK;
-    hipLaunchKernelGGL(k_broadcast, dim3((unsigned)((words + 511) / 512), (unsigned)count), dim3(256), 0, c->stream, dst, src, words);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(c, k_broadcast, dim3((unsigned)((words + 511) / 512), (unsigned)count), dim3(256), 0, dst, src, words);
 }
 int tfhe_memset(tfhe_ctx* c, void* d, int byte, size_t n) {
     if (!c) return fail(TFHE_E_BADARG, "null context");
@@ -930,8 +784,7 @@ int tfhe_scalar_mul(tfhe_ctx* c, const uint64_t* scal, const uint64_t* a, uint64
     limb_sel_t sel;
     int rc = make_sel(c, l, idx, &sel);
     if (rc) return rc;
-    scal_arg_t sc;
-    memset(&sc, 0, sizeof sc);
+    scal_arg_t sc{};
     for (int j = 0; j < l; j++) { const u64 q = c->q[sel.idx[j]]; sc.s[j] = hostmath::make_tw(scal[j] % q, q); }
     return run_pointwise<OP_SCAL>(c, a, nullptr, nullptr, d, n, l, idx, &sc);
 }
@@ -952,8 +805,8 @@ int tfhe_dot(tfhe_ctx* c, const uint64_t* acc, const uint64_t* const* a, const u
         dot_arg_t D;
         D.n = std::min(TFHE_DOT_MAX, n_terms - k0);
         for (int k = 0; k < D.n; k++) { D.a[k] = a[k0 + k]; D.b[k] = b[k0 + k]; }
-        hipLaunchKernelGGL(k_dot, row_grid((unsigned)(count * limbs), (size_t)c->N), dim3(256), 0, c->stream, D, running, dst, c->limbs_dev, sel, (u32)c->N);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_dot, row_grid((unsigned)(count * limbs), (size_t)c->N), dim3(256), 0, D, running, dst, c->limbs_dev, sel, (u32)c->N);
+        if (rc) return rc;
         running = dst;
     }
     return TFHE_OK;
@@ -990,11 +843,9 @@ int tfhe_lincomb(tfhe_ctx* c, const uint64_t* scalars, const uint64_t* const* a,
     dot_arg_t D;
     D.n = n_terms;
     for (int k = 0; k < n_terms; k++) { D.a[k] = a[k]; D.b[k] = nullptr; }
-    hipLaunchKernelGGL(k_lincomb, row_grid((unsigned)(count * limbs), (size_t)c->N), dim3(256), 0, c->stream, D, (const u64*)dsc, dst, c->limbs_dev, sel, (u32)c->N);
-    hipError_t le = hipGetLastError();
+    rc = launch(c, k_lincomb, row_grid((unsigned)(count * limbs), (size_t)c->N), dim3(256), 0, D, (const u64*)dsc, dst, c->limbs_dev, sel, (u32)c->N);
     devalloc::release(dsc);   // parked until the launch above has run
-    if (le != hipSuccess) return fail(TFHE_E_HIP, "k_lincomb: %s", hipGetErrorString(le));
-    return TFHE_OK;
+    return rc;
 }
 
 int tfhe_lincomb_many(tfhe_ctx* c, const uint64_t* scalars, const uint64_t* const* a, int n_terms, uint64_t* const* dst, int n_out, int64_t count,
@@ -1020,27 +871,27 @@ int tfhe_lincomb_many(tfhe_ctx* c, const uint64_t* scalars, const uint64_t* cons
     void* dsc = nullptr;
     hipError_t e = devalloc::alloc((size_t)n_out * per_out * 8, &dsc);
     if (e != hipSuccess) return fail(TFHE_E_NOMEM, "hipMalloc(%zu): %s", (size_t)n_out * per_out * 8, hipGetErrorString(e));
-    hipError_t le = hipMemcpyAsync(dsc, scalars, (size_t)n_out * per_out * 8, hipMemcpyHostToDevice, c->stream);   // pageable source: staged before the call returns
+    e = hipMemcpyAsync(dsc, scalars, (size_t)n_out * per_out * 8, hipMemcpyHostToDevice, c->stream);   // pageable source: staged before the call returns
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)devalloc::release(dsc);
+        return fail(TFHE_E_HIP, "hipMemcpyAsync: %s", hipGetErrorString(e));
+    }
     dot_arg_t D;
     D.n = n_terms;
     for (int k = 0; k < n_terms; k++) { D.a[k] = a[k]; D.b[k] = nullptr; }
     const dim3 grid = row_grid((unsigned)(count * limbs), (size_t)c->N);
-    for (int o0 = 0; o0 < n_out && le == hipSuccess; o0 += 4) {   // four outputs per pass over the operands
+    for (int o0 = 0; o0 < n_out && !rc; o0 += 4) {   // four outputs per pass over the operands
         const int no = std::min(4, n_out - o0);
         lincomb_out_t O;
         for (int o = 0; o < 4; o++) O.dst[o] = o < no ? dst[o0 + o] : nullptr;
         const u64* sc = (const u64*)dsc + (size_t)o0 * per_out;
-        switch (no) {
-            case 1: hipLaunchKernelGGL(k_lincomb_many<1>, grid, dim3(256), 0, c->stream, D, sc, O, c->limbs_dev, sel, (u32)c->N); break;
-            case 2: hipLaunchKernelGGL(k_lincomb_many<2>, grid, dim3(256), 0, c->stream, D, sc, O, c->limbs_dev, sel, (u32)c->N); break;
-            case 3: hipLaunchKernelGGL(k_lincomb_many<3>, grid, dim3(256), 0, c->stream, D, sc, O, c->limbs_dev, sel, (u32)c->N); break;
-            default: hipLaunchKernelGGL(k_lincomb_many<4>, grid, dim3(256), 0, c->stream, D, sc, O, c->limbs_dev, sel, (u32)c->N); break;
-        }
-        le = hipGetLastError();
+        rc = dispatch_int<1, 4>(no, [&](auto k) {
+            return launch(c, k_lincomb_many<decltype(k)::value>, grid, dim3(256), 0, D, sc, O, c->limbs_dev, sel, (u32)c->N);
+        });
     }
     devalloc::release(dsc);   // parked until the launches above have run
-    if (le != hipSuccess) return fail(TFHE_E_HIP, "k_lincomb_many: %s", hipGetErrorString(le));
-    return TFHE_OK;
+    return rc;
 }
 
 int tfhe_tensor(tfhe_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* out, int64_t batch, int limbs, const int32_t* idx) {
@@ -1049,31 +900,24 @@ int tfhe_tensor(tfhe_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t* out
     int rc = make_sel(c, limbs, idx, &sel);
     if (rc) return rc;
     if (batch == 0) return TFHE_OK;
-    hipLaunchKernelGGL(k_tensor, row_grid((unsigned)(batch * limbs), (size_t)c->N), dim3(256), 0, c->stream, a, b, out, c->limbs_dev, sel, (u32)c->N);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(c, k_tensor, row_grid((unsigned)(batch * limbs), (size_t)c->N), dim3(256), 0, a, b, out, c->limbs_dev, sel, (u32)c->N);
 }
 
 static int do_rescale(tfhe_ctx* c, const u64* src, u64* dst, int64_t count, const limb_sel_t& sel) {
     if (sel.n < 2) return fail(TFHE_E_LEVEL_MISMATCH, "modswitch needs at least 2 limbs");
-    rescale_arg_t ra;
-    memset(&ra, 0, sizeof ra);
+    rescale_arg_t ra{};
     const u64 ql = c->q[sel.idx[sel.n - 1]];
     for (int j = 0; j < sel.n - 1; j++) {
         const u64 qj = c->q[sel.idx[j]];
         ra.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(ql % qj, qj), qj);
     }
     if (count == 0) return TFHE_OK;
-    static const bool row_major = getenv("TFHE_RESCALE_ROWS") && getenv("TFHE_RESCALE_ROWS")[0] == '1';
+    static const bool row_major = env_flag("TFHE_RESCALE_ROWS", false);
     if (!row_major && c->N >= 512 && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0) {   // coefficient-major: the last limb read once per polynomial
         const unsigned want = (unsigned)((2048 + count - 1) / count), cap = (unsigned)(c->N / 512);
-        hipLaunchKernelGGL(k_rescale_cm, dim3((unsigned)count, std::max(1u, std::min(want, cap))), dim3(256), 0, c->stream, src, dst, c->limbs_dev, sel, ra, (u32)c->N);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
+        return launch(c, k_rescale_cm, dim3((unsigned)count, std::max(1u, std::min(want, cap))), dim3(256), 0, src, dst, c->limbs_dev, sel, ra, (u32)c->N);
     }
-    hipLaunchKernelGGL(k_rescale, row_grid((unsigned)(count * (sel.n - 1)), (size_t)c->N), dim3(256), 0, c->stream, src, dst, c->limbs_dev, sel, ra, (u32)c->N);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(c, k_rescale, row_grid((unsigned)(count * (sel.n - 1)), (size_t)c->N), dim3(256), 0, src, dst, c->limbs_dev, sel, ra, (u32)c->N);
 }
 int tfhe_rescale(tfhe_ctx* c, const uint64_t* src, uint64_t* dst, int64_t count, int limbs, const int32_t* idx) {
     if (!c || !src || !dst) return fail(TFHE_E_BADARG, "null argument");
@@ -1093,9 +937,7 @@ int tfhe_select_limbs(tfhe_ctx* c, const uint64_t* src, uint64_t* dst, int64_t c
         w.idx[j] = which[j];
     }
     if (count == 0) return TFHE_OK;
-    hipLaunchKernelGGL(k_select, row_grid((unsigned)(count * nw), (size_t)c->N), dim3(256), 0, c->stream, src, dst, w, src_limbs, (u32)c->N);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(c, k_select, row_grid((unsigned)(count * nw), (size_t)c->N), dim3(256), 0, src, dst, w, src_limbs, (u32)c->N);
 }
 
 static int do_galois(tfhe_ctx* c, const u64* src, u64* dst, u64 g, int64_t rows, const limb_sel_t& sel) {
@@ -1110,26 +952,18 @@ static int do_galois(tfhe_ctx* c, const u64* src, u64* dst, u64 g, int64_t rows,
         // rows that fit the LDS, enough of them to fill the chip: scatter through the LDS, coalesced on both sides
         constexpr int T = 512;
         const size_t lds = (size_t)c->N * 8;
-        static bool gattr = false;
-        if (!gattr) { int rc = set_lds(k_galois_lds<T>, 128 * 1024); if (rc) return rc; gattr = true; }
         const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(4, (size_t)(160 * 1024) / lds));
         const unsigned grid = (unsigned)std::min<int64_t>(rows, (int64_t)c->num_cus * per_cu);
-        hipLaunchKernelGGL(k_galois_lds<T>, dim3(grid), dim3(T), lds, c->stream, src, dst, c->limbs_dev, sel, g, (u32)c->N, (u32)rows);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
+        return launch(c, k_galois_lds<T>, dim3(grid), dim3(T), lds, src, dst, c->limbs_dev, sel, g, (u32)c->N, (u32)rows);
     }
 #ifndef TFHE_GALOIS_XCD
 #define TFHE_GALOIS_XCD 1
 #endif
     if (TFHE_GALOIS_XCD && c->variant == 0 && c->logN >= 15 && rows % sel.n == 0 && rows / sel.n >= 16) {
         // whole polynomials, enough of them: the XCD-cooperative scatter (k_galois_xcd)
-        hipLaunchKernelGGL(k_galois_xcd, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, c->stream, src, dst, c->limbs_dev, sel, g, (u32)c->N, (u32)(rows / sel.n));
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
+        return launch(c, k_galois_xcd, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, src, dst, c->limbs_dev, sel, g, (u32)c->N, (u32)(rows / sel.n));
     }
-    hipLaunchKernelGGL(k_galois, row_grid((unsigned)rows, (size_t)c->N), dim3(256), 0, c->stream, src, dst, c->limbs_dev, sel, ginv, (u32)c->N);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(c, k_galois, row_grid((unsigned)rows, (size_t)c->N), dim3(256), 0, src, dst, c->limbs_dev, sel, ginv, (u32)c->N);
 }
 int tfhe_galois(tfhe_ctx* c, const uint64_t* src, uint64_t* dst, uint64_t g, int64_t count, int limbs, const int32_t* idx) {
     if (!c || !src || !dst) return fail(TFHE_E_BADARG, "null argument");
@@ -1147,18 +981,15 @@ int tfhe_galois(tfhe_ctx* c, const uint64_t* src, uint64_t* dst, uint64_t g, int
 // the fused key switches (k_ks_fused at N = 2^14, k_ks_fused_sub at 2^15) read the key as doubles, prepared once per call
 // (k_evk_to_f64 in keyswitch_impl)
 static bool ks_fused14(const tfhe_ctx* c, int Lk, int level, int special) {
-    limb_sel_t w;
-    w.n = special ? level + 1 : level;
-    for (int j = 0; j < level; j++) w.idx[j] = j;
-    if (special) w.idx[level] = Lk - 1;
+    const limb_sel_t w = working_limbs(Lk, level, special);
     if (c->variant != 0) return false;
     if (c->logN == 14) return sel_fp(c, w, 0);
     if (c->logN == 13) {  // the 256 x 32 geometry: same fused kernel (it takes 256 VGPRs + 222 AGPRs: one workgroup per CU)
-        static const bool on = !(getenv("TFHE_FUSED13") && getenv("TFHE_FUSED13")[0] == '0');
+        static const bool on = env_flag("TFHE_FUSED13", true);
         return on && sel_fp(c, w, 0);
     }
     if (c->logN == 16) {  // k_ks_fused_sub at X = 2
-        static const bool on16 = !(getenv("TFHE_FUSED16") && getenv("TFHE_FUSED16")[0] == '0');
+        static const bool on16 = env_flag("TFHE_FUSED16", true);
         return on16 && level >= 2 && sel_fp(c, w, 2);
     }
     return c->logN == 15 && level >= 2 && sel_fp(c, w, 1);  // k_ks_fused_sub
@@ -1169,6 +1000,15 @@ static bool ks_prelift_ok(const tfhe_ctx* c, int level) {
     u64 lo = ~0ull, hi = 0;  // the bit-cast lift keeps |digit| <= q_i / 2 unreduced: needs q_i <= 2 q_j for every pair
     for (int j = 0; j < level; j++) { lo = std::min(lo, c->q[j]); hi = std::max(hi, c->q[j]); }
     return hi <= 2 * lo;
+}
+// the top stages of an N = 2^15 / 2^16 forward transform with the lift of ntt_io_t mode 1 fused into their loads (the u64 limbs of
+// rings that mix modulus sizes), into the transform scratch `t`
+static int launch_top_lift(tfhe_ctx* c, const u64* src, u64* t, int64_t rows, const limb_sel_t& sel, const ntt_io_t& io) {
+    const int x = c->logN - 14;
+    const dim3 tg((unsigned)((((c->N >> x) + 255) / 256) * rows));
+    return dispatch_int<1, 2>(x, [&](auto xc) {
+        return launch(c, k_ntt_fwd_top_lift<decltype(xc)::value>, tg, dim3(256), 0, src, t, c->limbs_dev, sel, c->logN, io);
+    });
 }
 // Part A of the unfused key switch: the NTT-domain RNS digits of c[end], dig [batch][level][nw][N]
 // (centred lift of limb i into every working limb, rlwe_she.jl:326-329, then forward transforms).
@@ -1181,9 +1021,9 @@ static int ks_digits_fwd(tfhe_ctx* c, const ks_arg_t& A, const u64* ct, u64* dig
     // rings that mix fp64-size moduli with larger ones (infer.jl:97-112: 60-bit q0 and special prime next to 40-bit primes)
     // at N = 2^15 / 2^16: the fp64-size working limbs take the lift-fused one-kernel transforms (the fp64 lift reads source
     // limbs of either size), the others go through the digit buffer and the u64 kernels
-    const u32 fpmask = mask_of(nw, [&](int j) { return c->limbs_host[A.w.idx[j]].Wd != nullptr; });
-    const u32 allmask = mask_all(nw);
-    const bool lift_mixed = !lift_fused && nw <= 32 && (c->logN == 15 || c->logN == 16) && c->variant == 0 && fpmask != 0 && fpmask != allmask &&
+    const policy_split_t ps = policy_split(c, A.w);
+    const u32 fpmask = ps.fpmask, allmask = ps.all;
+    const bool lift_mixed = !lift_fused && nw <= 32 && (c->logN == 15 || c->logN == 16) && c->variant == 0 && ps.mixed_fp() &&
                             (((uintptr_t)ct | (uintptr_t)dig) & 15u) == 0;
     if (lift_fused) {
         // digits: centred lift of limb i of c[end] into every working limb, fused into the forward NTT's loads
@@ -1207,17 +1047,15 @@ static int ks_digits_fwd(tfhe_ctx* c, const ks_arg_t& A, const u64* ct, u64* dig
         // the larger working limbs: lift fused into the top-stage kernel (into the transform scratch), then the u64 block kernels
         ntt_io_t iw = io;
         iw.limb_mask = allmask & ~fpmask;
-        const dim3 tg((unsigned)((((c->N >> x) + 255) / 256) * rows));
-        if (x == 1) hipLaunchKernelGGL(k_ntt_fwd_top_lift<1>, tg, dim3(256), 0, c->stream, ct, (u64*)tmp, c->limbs_dev, A.w, c->logN, iw);
-        else hipLaunchKernelGGL(k_ntt_fwd_top_lift<2>, tg, dim3(256), 0, c->stream, ct, (u64*)tmp, c->limbs_dev, A.w, c->logN, iw);
-        HIP_TRY(hipGetLastError());
+        rc = launch_top_lift(c, ct, (u64*)tmp, rows, A.w, iw);
+        if (rc) return rc;
         ntt_io_t ib = io_plain();
         ib.limb_mask = allmask & ~fpmask;
         rc = launch_block_fwd<ArithInt, 14>(c, (const u64*)tmp, dig, rows, A.w, x, ib);
         if (rc) return rc;
     } else {
-        hipLaunchKernelGGL(k_ks_digits, row_grid((unsigned)(batch * level * nw), (size_t)c->N), dim3(256), 0, c->stream, ct, dig, c->limbs_dev, A, n, 0u);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_ks_digits, row_grid((unsigned)(batch * level * nw), (size_t)c->N), dim3(256), 0, ct, dig, c->limbs_dev, A, n, 0u);
+        if (rc) return rc;
         rc = run_ntt(c, false, dig, dig, batch * level * nw, A.w);
         if (rc) return rc;
     }
@@ -1234,9 +1072,8 @@ static int ks_digits_fwd(tfhe_ctx* c, const ks_arg_t& A, const u64* ct, u64* dig
 // run_ntt's digit-lift mode -- except when every target limb is fp64-size and the special prime is not (the uniform fp64 policy
 // reads its source as one double).
 static bool md_lift_is_fused(const tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl) {
-    static const bool unfused = getenv("TFHE_MD_LIFT_UNFUSED") && getenv("TFHE_MD_LIFT_UNFUSED")[0] == '1';
     const int level = A.level;
-    if (unfused || level > 32 || c->logN > 16) return false;
+    if (level > 32 || c->logN > 16) return false;
     if (c->logN >= 15) return c->variant == 0;
     const bool special_fp = c->limbs_host[A.w.idx[level]].Wd != nullptr;
     return special_fp || !sel_fp(c, sl, 0);
@@ -1252,8 +1089,8 @@ static int md_lift_fwd(tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl, con
         *scaled = false;
         if (c->logN <= 14) return run_ntt(c, false, P, U, rows, sl, &io);
         const int x = c->logN - 14;
-        const u32 tmask = mask_of(level, [&](int j) { return c->limbs_host[sl.idx[j]].Wd != nullptr; });   // fp64-size target limbs
-        const u32 tall = mask_all(level);
+        const policy_split_t ps = policy_split(c, sl);
+        const u32 tmask = ps.fpmask, tall = ps.all;   // fp64-size target limbs
         const bool special_fp = c->limbs_host[A.w.idx[level]].Wd != nullptr;
         if ((rows << x) > 0x7fffffffll || (((uintptr_t)P | (uintptr_t)U) & 15u) != 0) return fail(TFHE_E_BADARG, "md_lift_fwd: row count / alignment");
         int rc;
@@ -1274,10 +1111,8 @@ static int md_lift_fwd(tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl, con
         if (tmask != tall) {   // the larger limbs: lift fused into the top stages (into the transform scratch), then the u64 block kernels
             ntt_io_t w = io;
             w.limb_mask = tmask ? (tall & ~tmask) : 0u;
-            const dim3 tg((unsigned)((((c->N >> x) + 255) / 256) * rows));
-            if (x == 1) hipLaunchKernelGGL(k_ntt_fwd_top_lift<1>, tg, dim3(256), 0, c->stream, P, (u64*)tmp, c->limbs_dev, sl, c->logN, w);
-            else hipLaunchKernelGGL(k_ntt_fwd_top_lift<2>, tg, dim3(256), 0, c->stream, P, (u64*)tmp, c->limbs_dev, sl, c->logN, w);
-            HIP_TRY(hipGetLastError());
+            rc = launch_top_lift(c, P, (u64*)tmp, rows, sl, w);
+            if (rc) return rc;
             ntt_io_t ib = io_plain();
             ib.limb_mask = w.limb_mask;
             rc = launch_block_fwd<ArithInt, 14>(c, (const u64*)tmp, U, rows, sl, x, ib);
@@ -1285,8 +1120,8 @@ static int md_lift_fwd(tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl, con
         }
         return TFHE_OK;
     }
-    hipLaunchKernelGGL(k_md_lift, row_grid((unsigned)rows, (size_t)c->N), dim3(256), 0, c->stream, P, LF, c->limbs_dev, sl, ra, n);
-    HIP_TRY(hipGetLastError());
+    const int rc = launch(c, k_md_lift, row_grid((unsigned)rows, (size_t)c->N), dim3(256), 0, P, LF, c->limbs_dev, sl, ra, n);
+    if (rc) return rc;
     *scaled = true;
     return run_ntt(c, false, LF, U, rows, sl);
 }
@@ -1297,8 +1132,7 @@ static int do_galois(tfhe_ctx* c, const u64* src, u64* dst, u64 g, int64_t rows,
 static int ks_inner_launch(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* evk, const u64* dig, u64* S, int64_t batch,
                            const uint64_t* const* keys = nullptr, int nkeys = 0, const u64* epi_x = nullptr) {
     const int nw = A.nw;
-    ks_keys_t K;
-    memset(&K, 0, sizeof K);
+    ks_keys_t K{};
     if (keys) {
         K.n = nkeys;
         K.s_stride = (size_t)batch * 2 * nw * (size_t)c->N;
@@ -1316,25 +1150,24 @@ static int ks_inner_launch(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* ev
     // limbs: all or nothing, see mask_of)
     // several keys: groups of eight x-blocks (one per XCD), each followed by its keys (ks_multi_key_block)
     auto multi = [&](unsigned nx) { return keys ? dim3(((nx + 7u) / 8u) * 8u * gy) : dim3(nx); };
-    u32 nmask = mask_of(nw, [&](int j) { return (c->limbs_host[A.w.idx[j]].q >> 52) == 0; });
-    const u32 amask = mask_all(nw);
-    if (n % 2 != 0) nmask = 0;
+    const policy_split_t ps = policy_split(c, A.w);
+    const u32 nmask = n % 2 != 0 ? 0u : ps.narrow, amask = ps.all;
     lanes_t lanes(c, nmask != 0 && nmask != amask);   // both kernels: side by side (disjoint working limbs)
     if (nmask) {
         lanes.use(1);
         const unsigned gx2 = (n / 2 + 255) / 256;
         const unsigned bs2 = (unsigned)std::max<int64_t>(1, std::min<int64_t>(batch, (4096 + nw * gx2 * gy - 1) / (nw * gx2 * gy)));
         auto kn = epi_x ? k_ks_inner_n2<8, true> : k_ks_inner_n2<8, false>;
-        hipLaunchKernelGGL(kn, multi((unsigned)nw * gx2 * bs2), dim3(256), 0, c->stream, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)batch, bs2,
-                           nmask == amask ? 0u : nmask, K);
+        const int rc = launch(c, kn, multi((unsigned)nw * gx2 * bs2), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)batch, bs2,
+                              nmask == amask ? 0u : nmask, K);
+        if (rc) return rc;
     }
     if (nmask != amask) {
         lanes.use(0);
         auto kg = epi_x ? k_ks_inner<8, true> : k_ks_inner<8, false>;
-        hipLaunchKernelGGL(kg, multi((unsigned)nw * gx * bsplit), dim3(256), 0, c->stream, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)batch, bsplit,
-                           nmask ? (amask & ~nmask) : 0u, K);
+        return launch(c, kg, multi((unsigned)nw * gx * bsplit), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)batch, bsplit,
+                      nmask ? (amask & ~nmask) : 0u, K);
     }
-    HIP_TRY(hipGetLastError());
     return TFHE_OK;
 }
 // Part B: S_s = sum_i evk_{i,s} (.) digit_i, inverse transforms, and the tail out_s = ct_s + ... (with the special prime: the
@@ -1346,8 +1179,18 @@ static int ks_inner_launch(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* ev
 // with sign changes -- into `tbuf`, which must not alias the digits (they are reused by the next rotation).
 // whether ks_finish takes the N = 2^16 path (paired sub-block inverse + k_ks_top_tail<2>)
 static bool ks_tail16(const tfhe_ctx* c, const ks_arg_t& A) {
-    const u32 fpm = mask_of(A.nw, [&](int j) { return c->limbs_host[A.w.idx[j]].Wd != nullptr; });
-    return c->logN == 16 && c->variant == 0 && fpm != 0 && A.level >= 2;
+    return c->logN == 16 && c->variant == 0 && policy_split(c, A.w).fpmask != 0 && A.level >= 2;
+}
+// the inverse top stages of N = 2^15 / 2^16 over the sub-block results T together with the tail ("+ c" / the special-prime
+// contraction); g_tail != 0: the automorphism rides on the tail's stores (XCD-cooperative scatter, k_ks_top_tail_rot)
+static int launch_top_tail(tfhe_ctx* c, const ks_arg_t& A, const rescale_arg_t& ra, const u64* T, const u64* ct, u64* out, int64_t batch, u64 g_tail) {
+    const u32 n = (u32)c->N, add_s = A.polys == 3 ? 2u : 1u;
+    return dispatch_int<1, 2>(c->logN - 14, [&](auto xc) {
+        constexpr int X = decltype(xc)::value;
+        if (g_tail)
+            return launch(c, k_ks_top_tail_rot<X>, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, T, ct, out, c->limbs_dev, A, ra, n, add_s, g_tail, (u32)(batch * 2));
+        return launch(c, k_ks_top_tail<X>, row_grid((unsigned)(batch * 2 * A.level), (size_t)c->N >> X), dim3(256), 0, T, ct, out, c->limbs_dev, A, ra, n, add_s);
+    });
 }
 // g_tail != 0: a rotation finished in the tail (k_ks_top_tail_rot<2>; N = 2^16 path only): `evk` is the prepared key, `ct` the
 // UNrotated input
@@ -1358,32 +1201,23 @@ static int ks_finish(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* evk, con
     const int level = A.level, nw = A.nw, polys = A.polys, special = A.special;
     const u32 n = (u32)c->N;
     const u32 add_s = polys == 3 ? 2u : 1u;  // c2 starts from zero for a 2-element input (rlwe_she.jl:324)
-    int rc;
-    const unsigned gx = (n + 255) / 256;
-    rc = ks_inner_launch(c, A, Lk, evk, dig, S, batch);
+    int rc = ks_inner_launch(c, A, Lk, evk, dig, S, batch);
     if (rc) return rc;
-    const u32 amask = mask_all(nw);
-    (void)gx;
+    const dim3 tail_grid = row_grid((unsigned)(batch * 2 * level), (size_t)c->N);
+    rescale_arg_t ra{};
+    if (special) special_inv_table(c, Lk, level, ra.qlinv);
     if (g != 0) {  // hoisted rotation: INTT, automorphism, tail
         if (outer) outer->join();
         rc = run_ntt(c, true, S, S, batch * 2 * nw, A.w);
         if (rc) return rc;
         rc = do_galois(c, S, tbuf, g, batch * 2 * nw, A.w);
         if (rc) return rc;
-        if (special) {
-            rescale_arg_t ra;
-            memset(&ra, 0, sizeof ra);
-            const u64 P = c->q[Lk - 1];
-            for (int j = 0; j < level; j++) ra.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
-            hipLaunchKernelGGL(k_ks_rescale_add, row_grid((unsigned)(batch * 2 * level), (size_t)c->N), dim3(256), 0, c->stream, tbuf, ct, out, c->limbs_dev, A, ra, n, add_s);
-        } else {
-            HIP_TRY(hipMemcpyAsync(out, tbuf, (size_t)batch * 2 * level * c->N * 8, hipMemcpyDeviceToDevice, c->stream));
-            hipLaunchKernelGGL(k_ks_add_ct, row_grid((unsigned)(batch * 2 * level), (size_t)c->N), dim3(256), 0, c->stream, ct, out, c->limbs_dev, A, n, add_s);
-        }
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
+        if (special) return launch(c, k_ks_rescale_add, tail_grid, dim3(256), 0, tbuf, ct, out, c->limbs_dev, A, ra, n, add_s);
+        HIP_TRY(hipMemcpyAsync(out, tbuf, (size_t)batch * 2 * level * c->N * 8, hipMemcpyDeviceToDevice, c->stream));
+        return launch(c, k_ks_add_ct, tail_grid, dim3(256), 0, ct, out, c->limbs_dev, A, n, add_s);
     }
-    const u32 fpm = mask_of(nw, [&](int j) { return c->limbs_host[A.w.idx[j]].Wd != nullptr; });
+    const policy_split_t ps = policy_split(c, A.w);
+    const u32 fpm = ps.fpmask, amask = ps.all;
     const bool tail16 = ks_tail16(c, A) && (((uintptr_t)S | (uintptr_t)tbuf) & 15u) == 0;
     if (g_tail && !tail16) return fail(TFHE_E_UNSUPPORTED, "internal: rotation in the tail needs the N = 2^16 sub-block path");
     if (tail16) {
@@ -1404,28 +1238,13 @@ static int ks_finish(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* evk, con
             }
         }
         if (outer) outer->join();
-        rescale_arg_t ra;
-        memset(&ra, 0, sizeof ra);
-        if (special) {
-            const u64 P = c->q[Lk - 1];
-            for (int j = 0; j < level; j++) ra.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
-        }
-        if (g_tail) hipLaunchKernelGGL(k_ks_top_tail_rot<2>, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, c->stream, tbuf, ct, out, c->limbs_dev, A, ra, n, add_s, g_tail, (u32)(batch * 2));
-        else hipLaunchKernelGGL(k_ks_top_tail<2>, row_grid((unsigned)(batch * 2 * level), (size_t)c->N / 4), dim3(256), 0, c->stream, tbuf, ct, out, c->limbs_dev, A, ra, n, add_s);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
+        return launch_top_tail(c, A, ra, tbuf, ct, out, batch, g_tail);
     }
     if (outer) outer->join();
     if (special) {
         rc = run_ntt(c, true, S, S, batch * 2 * nw, A.w);
         if (rc) return rc;
-        rescale_arg_t ra;
-        memset(&ra, 0, sizeof ra);
-        const u64 P = c->q[Lk - 1];
-        for (int j = 0; j < level; j++) ra.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
-        hipLaunchKernelGGL(k_ks_rescale_add, row_grid((unsigned)(batch * 2 * level), (size_t)c->N), dim3(256), 0, c->stream, S, ct, out, c->limbs_dev, A, ra, n, add_s);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
+        return launch(c, k_ks_rescale_add, tail_grid, dim3(256), 0, S, ct, out, c->limbs_dev, A, ra, n, add_s);
     }
     if (c->logN <= 14) {  // out = c + INTT(S), the addition fused into the inverse NTT's stores
         ntt_io_t io = io_plain();
@@ -1435,32 +1254,27 @@ static int ks_finish(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* evk, con
     }
     rc = run_ntt(c, true, S, out, batch * 2 * nw, A.w);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ks_add_ct, row_grid((unsigned)(batch * 2 * level), (size_t)c->N), dim3(256), 0, c->stream, ct, out, c->limbs_dev, A, n, add_s);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(c, k_ks_add_ct, tail_grid, dim3(256), 0, ct, out, c->limbs_dev, A, n, add_s);
 }
 
 // g_tail != 0: a rotation finished in the tail (k_ks_top_tail_rot) -- `ct` is the UNrotated input and `evd` was prepared for g
 static int ks_chunk(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, u64* out, int64_t batch,
                     u64* S, u64* dig, const u64* evd, bool prelifted, u64 g_tail = 0) {
-    const int nw = special ? level + 1 : level;
-    ks_arg_t A;
-    memset(&A, 0, sizeof A);
-    A.level = level; A.nw = nw; A.special = special; A.polys = polys;
-    A.w.n = nw;
-    for (int j = 0; j < level; j++) A.w.idx[j] = j;
-    if (special) A.w.idx[level] = Lk - 1;  // downswitch_keyelement, modulusraising.jl:43-49
+    ks_arg_t A = make_ks_arg(Lk, level, special, polys);
+    const int nw = A.nw;
     const u32 n = (u32)c->N;
     const u32 add_s = polys == 3 ? 2u : 1u;  // c2 starts from zero for a 2-element input (rlwe_she.jl:324)
+    const u64* const none = nullptr;
     int rc;
     if (evd && (c->logN == 14 || c->logN == 13)) {  // ks_fused14
         // everything in one kernel: digit lift, forward transforms, key inner product and the two inverse transforms;
         // with the special prime the transformed sums go to S and the contraction kernel finishes (modulusraising.jl:42)
         const unsigned items = (unsigned)(batch * nw);
+        const int64_t transforms = (int64_t)items * (level + 2);  // limb transforms inside the fused launch(es): `level` forward + 2 inverse per item
         // Special prime: two launches -- the special limb of every ciphertext first (its coefficient rows t_P into S), then the
         // ciphertext limbs with the ModulusRaised contraction and "+ c" in their final store (k_ks_fused SPMODE 1 / 2, ArithFpMD).
         // No T, no tail kernel.  TFHE_KS_TAIL=1 keeps the one-launch form with k_ks_rescale_add (comparisons).
-        static const bool ks_tail = getenv("TFHE_KS_TAIL") && getenv("TFHE_KS_TAIL")[0] == '1';
+        static const bool ks_tail = env_flag("TFHE_KS_TAIL", false);
         if (special && !prelifted && !ks_tail) {
             {
                 std::lock_guard<std::mutex> zg(c->zero_mu);         // a failed attempt (transient out-of-memory) is retried by the next call
@@ -1473,81 +1287,42 @@ static int ks_chunk(tfhe_ctx* c, int Lk, int level, int special, const u64* evk,
                 }
                 if (!c->zero_row) return fail(TFHE_E_NOMEM, "allocating the zero row failed");
             }
-            const u64 P = c->q[Lk - 1];
-            for (int j = 0; j < level; j++) A.pinv[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
+            special_inv_table(c, Lk, level, A.pinv);
             const unsigned it1 = (unsigned)batch, it2 = (unsigned)(batch * level);
-            auto launch2 = [&](auto k1, auto k2, int LOGT, size_t lds, unsigned per_cu, bool& attr_set) -> int {
-                if (!attr_set) {
-                    int r2 = set_lds(k1, lds);
-                    if (!r2) r2 = set_lds(k2, lds);
-                    if (r2) return r2;
-                    attr_set = true;
-                }
-                prof_begin(c, (int64_t)items * (level + 2));
-                hipLaunchKernelGGL(k1, dim3(std::min(it1, per_cu * (unsigned)c->num_cus)), dim3(1u << LOGT), lds, c->stream, evd, ct, S, c->limbs_dev, A, Lk, it1,
-                                   (const u64*)nullptr, (const u64*)nullptr);
-                hipLaunchKernelGGL(k2, dim3(std::min(it2, per_cu * (unsigned)c->num_cus)), dim3(1u << LOGT), lds, c->stream, evd, ct, out, c->limbs_dev, A, Lk, it2,
-                                   (const u64*)S, (const u64*)c->zero_row);
-                prof_end(c);
-                return TFHE_OK;
+            auto launch2 = [&](auto k1, auto k2, int LOGT, size_t lds, unsigned per_cu) -> int {   // both launches in ONE profiled region
+                prof_scope p(c, transforms);
+                const int r1 = launch(c, k1, dim3(cu_grid(c, it1, per_cu)), dim3(1u << LOGT), lds, evd, ct, S, c->limbs_dev, A, Lk, it1, none, none);
+                if (r1) return r1;
+                return launch(c, k2, dim3(cu_grid(c, it2, per_cu)), dim3(1u << LOGT), lds, evd, ct, out, c->limbs_dev, A, Lk, it2, (const u64*)S, (const u64*)c->zero_row);
             };
-            if (c->logN == 14 && g_tail) {   // rotation finished in the second launch's stores (SPMODE 3; `ct` is the unrotated input)
-                constexpr int LOGT = logt_for(14);
-                static bool a14r = false;
-                A.rot_g = (u32)(g_tail & (2 * (u64)c->N - 1));
-                rc = launch2(k_ks_fused<ArithFp, 14, LOGT, false, 1>, k_ks_fused<ArithFp, 14, LOGT, false, 3>, LOGT, fused_lds_bytes<14, LOGT, TFHE_TWL_KS>(), 1u, a14r);
-            } else if (g_tail) {
-                return fail(TFHE_E_UNSUPPORTED, "internal: rotation in the store is an N = 2^14 path");
-            } else if (c->logN == 14) {
-                constexpr int LOGT = logt_for(14);
-                static bool a14 = false;
-                rc = launch2(k_ks_fused<ArithFp, 14, LOGT, false, 1>, k_ks_fused<ArithFp, 14, LOGT, false, 2>, LOGT, fused_lds_bytes<14, LOGT, TFHE_TWL_KS>(), 1u, a14);
-            } else {
+            if (g_tail && c->logN != 14) return fail(TFHE_E_UNSUPPORTED, "internal: rotation in the store is an N = 2^14 path");
+            if (c->logN == 13) {
                 constexpr int LOGT = logt_for(13);
-                static bool a13 = false;
-                rc = launch2(k_ks_fused<ArithFp, 13, LOGT, false, 1>, k_ks_fused<ArithFp, 13, LOGT, false, 2>, LOGT, fused_lds_bytes<13, LOGT, TFHE_TWL_KS>(), 2u, a13);
+                return launch2(k_ks_fused<ArithFp, 13, LOGT, false, 1>, k_ks_fused<ArithFp, 13, LOGT, false, 2>, LOGT, fused_lds_bytes<13, LOGT, TFHE_TWL_KS>(), 2u);
             }
-            if (rc) return rc;
-            HIP_TRY(hipGetLastError());
-            return TFHE_OK;
+            constexpr int LOGT = logt_for(14);
+            const size_t lds = fused_lds_bytes<14, LOGT, TFHE_TWL_KS>();
+            if (!g_tail) return launch2(k_ks_fused<ArithFp, 14, LOGT, false, 1>, k_ks_fused<ArithFp, 14, LOGT, false, 2>, LOGT, lds, 1u);
+            // rotation finished in the second launch's stores (SPMODE 3; `ct` is the unrotated input)
+            A.rot_g = (u32)(g_tail & (2 * (u64)c->N - 1));
+            return launch2(k_ks_fused<ArithFp, 14, LOGT, false, 1>, k_ks_fused<ArithFp, 14, LOGT, false, 3>, LOGT, lds, 1u);
         }
         if (g_tail) return fail(TFHE_E_UNSUPPORTED, "internal: rotation in the store needs the two-launch special-prime form");
         if (c->logN == 14) {
             constexpr int LOGT = logt_for(14);
-            const size_t lds = fused_lds_bytes<14, LOGT, TFHE_TWL_KS>();
             auto fk = prelifted ? k_ks_fused<ArithFp, 14, LOGT, true> : k_ks_fused<ArithFp, 14, LOGT, false>;
-            static bool fattr_set = false;
-            if (!fattr_set) {
-                rc = set_lds(k_ks_fused<ArithFp, 14, LOGT, true>, lds);
-                if (!rc) rc = set_lds(k_ks_fused<ArithFp, 14, LOGT, false>, lds);
-                if (rc) return rc;
-                fattr_set = true;
-            }
-            const unsigned grid = std::min(items, (unsigned)c->num_cus * TFHE_GRID_MULT_KS);
-            prof_begin(c, (int64_t)items * (level + 2));  // limb transforms inside this launch: `level` forward + 2 inverse per item
-            hipLaunchKernelGGL(fk, dim3(grid), dim3(1 << LOGT), lds, c->stream, evd, ct, special ? S : out, c->limbs_dev, A, Lk, items, (const u64*)nullptr, (const u64*)nullptr);
-            prof_end(c);
+            rc = launch_prof(c, transforms, fk, dim3(cu_grid(c, items, TFHE_GRID_MULT_KS)), dim3(1 << LOGT), fused_lds_bytes<14, LOGT, TFHE_TWL_KS>(), evd, ct,
+                             special ? S : out, c->limbs_dev, A, Lk, items, none, none);
         } else {  // N = 2^13: 256 threads x 32 elements, 65 KiB of LDS; 478 registers per thread, so one workgroup per CU is resident
                   // (capped to two resident workgroups it measured 5 % slower)
             constexpr int LOGT = logt_for(13);
-            const size_t lds = fused_lds_bytes<13, LOGT, TFHE_TWL_KS>();
-            auto fk = k_ks_fused<ArithFp, 13, LOGT, false>;
-            static bool fattr13_set = false;
-            if (!fattr13_set) { rc = set_lds(fk, lds); if (rc) return rc; fattr13_set = true; }
-            const unsigned grid = std::min(items, 2u * (unsigned)c->num_cus);
-            prof_begin(c, (int64_t)items * (level + 2));
-            hipLaunchKernelGGL(fk, dim3(grid), dim3(1 << LOGT), lds, c->stream, evd, ct, special ? S : out, c->limbs_dev, A, Lk, items, (const u64*)nullptr, (const u64*)nullptr);
-            prof_end(c);
+            rc = launch_prof(c, transforms, k_ks_fused<ArithFp, 13, LOGT, false>, dim3(cu_grid(c, items, 2u)), dim3(1 << LOGT), fused_lds_bytes<13, LOGT, TFHE_TWL_KS>(),
+                             evd, ct, special ? S : out, c->limbs_dev, A, Lk, items, none, none);
         }
-        HIP_TRY(hipGetLastError());
-        if (!special) return TFHE_OK;
-        rescale_arg_t ra;
-        memset(&ra, 0, sizeof ra);
-        const u64 P = c->q[Lk - 1];
-        for (int j = 0; j < level; j++) ra.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
-        hipLaunchKernelGGL(k_ks_rescale_add, row_grid((unsigned)(batch * 2 * level), (size_t)c->N), dim3(256), 0, c->stream, S, ct, out, c->limbs_dev, A, ra, n, add_s);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
+        if (rc || !special) return rc;
+        rescale_arg_t ra{};
+        special_inv_table(c, Lk, level, ra.qlinv);
+        return launch(c, k_ks_rescale_add, row_grid((unsigned)(batch * 2 * level), (size_t)c->N), dim3(256), 0, S, ct, out, c->limbs_dev, A, ra, n, add_s);
     }
     if (evd && (c->logN == 15 || c->logN == 16)) {  // ks_fused14: variant 0, fp64 policy, level >= 2
         // N = 2^15 / 2^16 on fp64-size moduli: per-sub-block fused key switch (k_ks_fused_sub) into T = dig ([batch][2][nw] rows,
@@ -1563,46 +1338,22 @@ static int ks_chunk(tfhe_ctx* c, int Lk, int level, int special, const u64* evk,
         // sweeps, no reduced product operands, one sweep per inverse (ArithFpS): cfg#3 36.5 k -> 38.1 k key switches/s
         bool small = true;
         for (int j = 0; j < nw; j++) small = small && c->q[A.w.idx[j]] < TFHE_FPS_QMAX;
-        static const bool fps_on = !(getenv("TFHE_FPS") && getenv("TFHE_FPS")[0] == '0');
+        static const bool fps_on = env_flag("TFHE_FPS", true);
         auto fk = x == 2 ? ((small && fps_on) ? k_ks_fused_sub<ArithFpS, 14, LOGT, 2> : k_ks_fused_sub<ArithFp, 14, LOGT, 2>)
                          : ((small && fps_on) ? k_ks_fused_sub<ArithFpS, 14, LOGT, 1> : k_ks_fused_sub<ArithFp, 14, LOGT, 1>);
-        static bool sattr_set = false;
-        if (!sattr_set) {
-            rc = set_lds(k_ks_fused_sub<ArithFp, 14, LOGT, 1>, lds);
-            if (!rc) rc = set_lds(k_ks_fused_sub<ArithFpS, 14, LOGT, 1>, lds);
-            if (!rc) rc = set_lds(k_ks_fused_sub<ArithFp, 14, LOGT, 2>, lds);
-            if (!rc) rc = set_lds(k_ks_fused_sub<ArithFpS, 14, LOGT, 2>, lds);
-            if (rc) return rc;
-            sattr_set = true;
-        }
         const unsigned items = (unsigned)((batch * nw) << x);
-        const unsigned grid = std::min(items, (unsigned)c->num_cus);
-        prof_begin(c, (int64_t)batch * nw * (level + 2));
-        hipLaunchKernelGGL(fk, dim3(grid), dim3(1 << LOGT), lds, c->stream, evd, ct, dig, c->limbs_dev, A, Lk, items);
-        prof_end(c);
-        HIP_TRY(hipGetLastError());
+        rc = launch_prof(c, (int64_t)batch * nw * (level + 2), fk, dim3(cu_grid(c, items)), dim3(1 << LOGT), lds, evd, ct, dig, c->limbs_dev, A, Lk, items);
+        if (rc) return rc;
         // inverse top stage + "+ c" / special-prime contraction in one pass over the sub-block results
-        rescale_arg_t ra;
-        memset(&ra, 0, sizeof ra);
-        if (special) {
-            const u64 P = c->q[Lk - 1];
-            for (int j = 0; j < level; j++) ra.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
-        }
-        if (g_tail) {   // rotation: the automorphism rides on the tail's stores (XCD-cooperative scatter)
-            const dim3 rg(8 * TFHE_ROT_TAIL_SLOTS);
-            if (x == 1) hipLaunchKernelGGL(k_ks_top_tail_rot<1>, rg, dim3(256), 0, c->stream, dig, ct, out, c->limbs_dev, A, ra, n, add_s, g_tail, (u32)(batch * 2));
-            else hipLaunchKernelGGL(k_ks_top_tail_rot<2>, rg, dim3(256), 0, c->stream, dig, ct, out, c->limbs_dev, A, ra, n, add_s, g_tail, (u32)(batch * 2));
-        } else if (x == 1) hipLaunchKernelGGL(k_ks_top_tail<1>, row_grid((unsigned)(batch * 2 * level), (size_t)c->N / 2), dim3(256), 0, c->stream, dig, ct, out, c->limbs_dev, A, ra, n, add_s);
-        else hipLaunchKernelGGL(k_ks_top_tail<2>, row_grid((unsigned)(batch * 2 * level), (size_t)c->N / 4), dim3(256), 0, c->stream, dig, ct, out, c->limbs_dev, A, ra, n, add_s);
-        HIP_TRY(hipGetLastError());
-        return TFHE_OK;
+        rescale_arg_t ra{};
+        if (special) special_inv_table(c, Lk, level, ra.qlinv);
+        return launch_top_tail(c, A, ra, dig, ct, out, batch, g_tail);
     }
     // Rings of mixed modulus sizes at N = 2^16 (the three-kernel path): when the digit transforms, the key sums and the inverse
     // sub-block transforms all split the working limbs the same way (fp64-size = "narrow"), the two policies run as two lanes
     // from the lift to the inverse with ONE join before the tail; otherwise every step forks and joins by itself.
-    const u32 fpm = mask_of(nw, [&](int j) { return c->limbs_host[A.w.idx[j]].Wd != nullptr; });
-    const u32 nrw = mask_of(nw, [&](int j) { return (c->limbs_host[A.w.idx[j]].q >> 52) == 0; });
-    const bool two_lanes = nw <= 32 && c->variant == 0 && c->logN == 16 && fpm != 0 && fpm != mask_all(nw) && fpm == nrw && ks_tail16(c, A) &&
+    const policy_split_t ps = policy_split(c, A.w);
+    const bool two_lanes = nw <= 32 && c->variant == 0 && c->logN == 16 && ps.mixed_fp() && ps.fpmask == ps.narrow && ks_tail16(c, A) &&
                            (((uintptr_t)ct | (uintptr_t)dig | (uintptr_t)S) & 15u) == 0;
     if (two_lanes) {
         void* tmp = nullptr;
@@ -1639,7 +1390,7 @@ static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64
     // Rotations through the sub-block fused key switch (N = 2^15 / 2^16): no rotated copy of the input -- the key is prepared while
     // it is converted (k_evk_to_f64), the key sums are those of the unrotated digits, the automorphism rides on the tail's stores
     // (k_ks_top_tail_rot).  Same bits (the hoisting identity of tfhe_rotate_many).  TFHE_ROT_TAIL=0 keeps the separate pass.
-    static const bool rot_tail_on = !(getenv("TFHE_ROT_TAIL") && getenv("TFHE_ROT_TAIL")[0] == '0');
+    static const bool rot_tail_on = env_flag("TFHE_ROT_TAIL", true);
     // The tail scatters into `out` while other workgroups still read the unrotated `ct`: the two RANGES must be disjoint (r05, ADVICE
     // r04: pointer inequality let a partially overlapping out / ct race) -- otherwise the rotated-copy path below runs.
     const bool io_disjoint = (const char*)(out + (size_t)batch * 2 * level * N) <= (const char*)ct ||
@@ -1647,20 +1398,13 @@ static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64
     bool rot_in_tail = rotate && f14 && c->logN >= 15 && rot_tail_on && io_disjoint && batch >= 8;   // (one (ciphertext, component) per XCD at a time)
     // N = 2^14 with the special prime (the two-launch fused key switch): the rotation rides on the in-kernel contraction's stores
     // (k_ks_fused SPMODE 3) -- each workgroup scatters the row it owns
-    static const bool ks_tail_env = getenv("TFHE_KS_TAIL") && getenv("TFHE_KS_TAIL")[0] == '1';
+    static const bool ks_tail_env = env_flag("TFHE_KS_TAIL", false);
     if (rotate && f14 && c->logN == 14 && special && !prelifted && !ks_tail_env && rot_tail_on && io_disjoint) rot_in_tail = true;
     // the same for the N = 2^16 three-kernel path (rings with moduli beyond the fp64 size: the reference's CKKS ring): the key is
     // prepared into the workspace (k_ntt_perm), the rotation rides on k_ks_top_tail_rot<2>
     bool rot_key_prep = false;
-    if (rotate && !f14 && rot_tail_on && io_disjoint && batch >= 8) {
-        ks_arg_t KA;
-        memset(&KA, 0, sizeof KA);
-        KA.level = level; KA.nw = nw;
-        KA.w.n = nw;
-        for (int j = 0; j < level; j++) KA.w.idx[j] = j;
-        if (special) KA.w.idx[level] = Lk - 1;
-        if (ks_tail16(c, KA)) rot_in_tail = rot_key_prep = true;
-    }
+    const ks_arg_t KA = make_ks_arg(Lk, level, special, polys);
+    if (rotate && !f14 && rot_tail_on && io_disjoint && batch >= 8 && ks_tail16(c, KA)) rot_in_tail = rot_key_prep = true;
     if (key_prepared && !rot_in_tail) {
         const uint64_t* one[1] = {evk};
         return tfhe_rotate_many(c, Lk, level, special, one, level, 1, &galois, 1, ct, out, batch);
@@ -1687,30 +1431,21 @@ static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64
     u64* evd = nullptr;
     if (f14) {
         evd = (u64*)((char*)ws + ntt_tmp + chunk * per_ct);
-        ks_arg_t KA;
-        memset(&KA, 0, sizeof KA);
-        KA.level = level; KA.nw = nw; KA.special = special; KA.polys = polys;
-        KA.w.n = nw;
-        for (int j = 0; j < level; j++) KA.w.idx[j] = j;
-        if (special) KA.w.idx[level] = Lk - 1;
-        hipLaunchKernelGGL(k_evk_to_f64, row_grid((unsigned)(level * 2 * nw), N), dim3(256), 0, c->stream, evk, evd, c->limbs_dev, KA, Lk, (u32)N, c->logN <= 14 ? 1 : 0, c->logN == 16 ? 2 : 0,
-                           (rot_in_tail && !key_prepared) ? inv_mod_2n(galois, 2 * (u64)c->N) : (u64)0, 1);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_evk_to_f64, row_grid((unsigned)(level * 2 * nw), N), dim3(256), 0, evk, evd, c->limbs_dev, KA, Lk, (u32)N, c->logN <= 14 ? 1 : 0, c->logN == 16 ? 2 : 0,
+                    (rot_in_tail && !key_prepared) ? inv_mod_2n(galois, 2 * (u64)c->N) : (u64)0, 1);
+        if (rc) return rc;
     }
     if (rot_key_prep) {
         u64* keyp = (u64*)((char*)ws + ntt_tmp + chunk * per_ct);
-        hipLaunchKernelGGL(k_ntt_perm, row_grid((unsigned)(level * 2 * Lk), N), dim3(256), 0, c->stream, evk, keyp, inv_mod_2n(galois, 2 * (u64)c->N), (u32)N);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_ntt_perm, row_grid((unsigned)(level * 2 * Lk), N), dim3(256), 0, evk, keyp, inv_mod_2n(galois, 2 * (u64)c->N), (u32)N);
+        if (rc) return rc;
         evk = keyp;
     }
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
         const u64* cin = ct + (size_t)b0 * polys * level * N;
         if (rotate && !rot_in_tail) {
-            limb_sel_t s;
-            s.n = level;
-            for (int j = 0; j < level; j++) s.idx[j] = j;
-            rc = do_galois(c, cin, rot, galois, nb * polys * level, s);
+            rc = do_galois(c, cin, rot, galois, nb * polys * level, first_limbs(level));
             if (rc) return rc;
             cin = rot;
         }
@@ -1742,9 +1477,7 @@ int tfhe_galois_key_prepare(tfhe_ctx* c, int Lk, int n_digits, uint64_t g, const
     if (Lk < 1 || Lk > c->L || n_digits < 1) return fail(TFHE_E_LEVEL_MISMATCH, "key shape outside the ring");
     if ((g & 1) == 0 || g >= 2 * (u64)c->N) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
     const u64 ginv = inv_mod_2n(g, 2 * (u64)c->N);
-    hipLaunchKernelGGL(k_ntt_perm, row_grid((unsigned)(n_digits * 2 * Lk), (size_t)c->N), dim3(256), 0, c->stream, evk, evk_out, ginv, (u32)c->N);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    return launch(c, k_ntt_perm, row_grid((unsigned)(n_digits * 2 * Lk), (size_t)c->N), dim3(256), 0, evk, evk_out, ginv, (u32)c->N);
 }
 
 int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, int prepared,
@@ -1767,12 +1500,7 @@ int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
         }
         return TFHE_OK;
     }
-    ks_arg_t A;
-    memset(&A, 0, sizeof A);
-    A.level = level; A.nw = nw; A.special = special; A.polys = polys;
-    A.w.n = nw;
-    for (int j = 0; j < level; j++) A.w.idx[j] = j;
-    if (special) A.w.idx[level] = Lk - 1;
+    const ks_arg_t A = make_ks_arg(Lk, level, special, polys);
     // workspace per ciphertext: S (2 nw rows) + digits (level nw) + T (2 nw) + rotated input (2 level); + one prepared key
     const size_t per_ct = ((size_t)4 * nw + (size_t)level * nw + (size_t)polys * level) * N * 8;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)512, (int64_t)((8192ull << 20) / per_ct)}));
@@ -1786,9 +1514,7 @@ int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
     u64* T = dig + (size_t)chunk * level * nw * N;
     u64* rot = T + (size_t)chunk * 2 * nw * N;
     u64* keytmp = rot + (size_t)chunk * polys * level * N;
-    limb_sel_t sl;
-    sl.n = level;
-    for (int j = 0; j < level; j++) sl.idx[j] = j;
+    const limb_sel_t sl = first_limbs(level);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
         const u64* cin = ct + (size_t)b0 * polys * level * N;
@@ -1849,27 +1575,18 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
     const int nw = special ? level + 1 : level, polys = 2, R = n_rot;
     const size_t N = (size_t)c->N;
     const u32 n = (u32)c->N;
-    ks_arg_t A;
-    memset(&A, 0, sizeof A);
-    A.level = level; A.nw = nw; A.special = special; A.polys = polys;
-    A.w.n = nw;
-    for (int j = 0; j < level; j++) A.w.idx[j] = j;
-    if (special) A.w.idx[level] = Lk - 1;
-    limb_sel_t sl;
-    sl.n = level;
-    for (int j = 0; j < level; j++) sl.idx[j] = j;
-    rescale_arg_t ra;
-    memset(&ra, 0, sizeof ra);
+    ks_arg_t A = make_ks_arg(Lk, level, special, polys);
+    const limb_sel_t sl = first_limbs(level);
+    rescale_arg_t ra{};
     if (special) {
-        const u64 P = c->q[Lk - 1];
-        for (int j = 0; j < level; j++) A.pinv[j] = ra.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
+        special_inv_table(c, Lk, level, ra.qlinv);
+        std::copy(ra.qlinv, ra.qlinv + level, A.pinv);
     }
-    rot_tail_arg_t G;
-    memset(&G, 0, sizeof G);
+    rot_tail_arg_t G{};
     for (int r = 0; r < R; r++) G.g[r] = galois[r];
     // With a special prime the rotations are finished in the evaluation domain (k_md_*: only the special limb of every key sum is
     // inverse-transformed); TFHE_MD_COEFF=1 keeps the coefficient-domain tail (k_ks_rot_tail) for comparisons.
-    static const bool md_coeff = getenv("TFHE_MD_COEFF") && getenv("TFHE_MD_COEFF")[0] == '1';
+    static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
     const bool eval_form = special && R > 0 && !md_coeff;
     // workspace per ciphertext: digits (level nw rows) + S / T (R 2 nw) + rotated ciphertexts (R 2 level) + the ciphertext's own transform (2 level)
     // (+ evaluation-domain form: the lifted special limbs before their transforms (R 2 level) and the special limbs themselves (R 2))
@@ -1879,7 +1596,7 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
                            (eval_form ? (need_lf ? (size_t)R * 2 * level : 0) + (size_t)R * 2 : 0)) * N * 8;
     // The keys of all R rotations are read once per chunk (2.8 GB at N = 2^16, 6 limbs + special prime, 63 rotations): a chunk as
     // large as the memory allows (32 GiB of workspace unless TFHE_MD_WS_GIB says otherwise; halved while the allocation fails)
-    static const size_t ws_cap_env = [] { const char* e = getenv("TFHE_MD_WS_GIB"); const long g = e ? atol(e) : 0; return (size_t)(g > 0 ? g : 32) << 30; }();
+    static const size_t ws_cap_env = env_gib("TFHE_MD_WS_GIB", 32);
     // ... and never more than half of what the device has free right now (counting what this context and the allocator's cache
     // already hold, both of which the allocation below can reuse): other contexts, BFV plans and processes keep their room
     size_t ws_cap = ws_cap_env;
@@ -1946,9 +1663,9 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
             if (rc) return rc;
             rc = ks_inner_launch(c, A, Lk, nullptr, dig, S, nb, evks, R, X);   // limbs j < level leave as V = S' P^-1 + X0 [s = 0]
             if (rc) return rc;
-            hipLaunchKernelGGL(k_md_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, c->stream, S, PB, G, n, (u32)nw, (u32)level, (u32)nb, groups);
-            HIP_TRY(hipGetLastError());
-            limb_sel_t sp;
+            rc = launch(c, k_md_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, S, PB, G, n, (u32)nw, (u32)level, (u32)nb, groups);
+            if (rc) return rc;
+            limb_sel_t sp{};
             sp.n = 1;
             sp.idx[0] = Lk - 1;
             rc = run_ntt(c, true, PB, PB, (int64_t)groups, sp);
@@ -1957,9 +1674,9 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
             rc = md_lift_fwd(c, A, sl, ra, PB, LF, U, (int64_t)groups, &scaled);
             if (rc) return rc;
             auto acc = scaled ? k_md_acc<false> : k_md_acc<true>;
-            hipLaunchKernelGGL(acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, c->stream, X, S, U, diags, out + (size_t)b0 * 2 * level * N, c->limbs_dev, sl,
-                               G, ra, n, (u32)nw, (u32)R, (u32)nb);
-            HIP_TRY(hipGetLastError());
+            rc = launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, X, S, U, diags, out + (size_t)b0 * 2 * level * N, c->limbs_dev, sl,
+                        G, ra, n, (u32)nw, (u32)R, (u32)nb);
+            if (rc) return rc;
             continue;
         }
         if (R) {
@@ -1969,17 +1686,17 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
             if (rc) return rc;
             rc = run_ntt(c, true, S, S, (int64_t)R * nb * 2 * nw, A.w);
             if (rc) return rc;
-            hipLaunchKernelGGL(k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, c->stream, S, cin, ROT, c->limbs_dev, A, ra, G, n, (u32)nb,
-                               (u32)((int64_t)R * nb * 2));
-            HIP_TRY(hipGetLastError());
+            rc = launch(c, k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, S, cin, ROT, c->limbs_dev, A, ra, G, n, (u32)nb,
+                        (u32)((int64_t)R * nb * 2));
+            if (rc) return rc;
             rc = run_ntt(c, false, ROT, ROT, (int64_t)R * nb * 2 * level, sl);
             if (rc) return rc;
         }
         rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_matmul_acc, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, c->stream, X, ROT, diags, out + (size_t)b0 * 2 * level * N,
-                           c->limbs_dev, sl, n, (u32)R, (u32)(nb * 2 * level));
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_matmul_acc, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, X, ROT, diags, out + (size_t)b0 * 2 * level * N,
+                    c->limbs_dev, sl, n, (u32)R, (u32)(nb * 2 * level));
+        if (rc) return rc;
     }
     return TFHE_OK;
 }
@@ -2050,42 +1767,31 @@ int tfhe_keyswitch_window(tfhe_ctx* c, int key_limbs, int level, int special, in
     if (rc) return rc;
     u64* S = (u64*)((char*)ws + ntt_tmp);
     u64* dig = S + (size_t)chunk * 2 * nw * N;
-    ks_arg_t A;   // inner product: `level` field = number of digits, nw = working limbs
-    memset(&A, 0, sizeof A);
-    A.level = need; A.nw = nw; A.special = special ? 1 : 0; A.polys = polys;
-    A.w.n = nw;
-    for (int j = 0; j < level; j++) A.w.idx[j] = j;
-    if (special) A.w.idx[level] = Lk - 1;
-    ks_arg_t Al = A;  // row bookkeeping of the tail kernels: `level` = ciphertext limbs
-    Al.level = level;
+    const ks_arg_t Al = make_ks_arg(Lk, level, special ? 1 : 0, polys);  // row bookkeeping of the tail kernels: `level` = ciphertext limbs
+    ks_arg_t A = Al;   // inner product: `level` field = number of digits, nw = working limbs
+    A.level = need;
     const u32 add_s = polys == 3 ? 2u : 1u;
     const unsigned gx = (n + 255) / 256;
-    rescale_arg_t ra;
-    memset(&ra, 0, sizeof ra);
-    if (special) {
-        const u64 P = c->q[Lk - 1];
-        for (int j = 0; j < level; j++) ra.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(P % c->q[j], c->q[j]), c->q[j]);
-    }
+    rescale_arg_t ra{};
+    if (special) special_inv_table(c, Lk, level, ra.qlinv);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
         const u64* cin = ct + (size_t)b0 * polys * level * N;
         u64* cout = out + (size_t)b0 * 2 * level * N;
-        hipLaunchKernelGGL(k_ks_window_digits, dim3((unsigned)(nb * gx)), dim3(256), 0, c->stream, cin, dig, T, level, window_bits, need, polys, n, gx, nw);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_ks_window_digits, dim3((unsigned)(nb * gx)), dim3(256), 0, cin, dig, T, level, window_bits, need, polys, n, gx, nw);
+        if (rc) return rc;
         rc = run_ntt(c, false, dig, dig, nb * need * nw, A.w);
         if (rc) return rc;
         const unsigned bsplit = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nb, (4096 + nw * gx - 1) / (nw * gx)));
-        ks_keys_t K1;
-        memset(&K1, 0, sizeof K1);
-        hipLaunchKernelGGL(k_ks_inner<8>, dim3((unsigned)nw * gx * bsplit), dim3(256), 0, c->stream, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)nb, bsplit, 0u, K1);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_ks_inner<8>, dim3((unsigned)nw * gx * bsplit), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)nb, bsplit, 0u, ks_keys_t{});
+        if (rc) return rc;
         if (special) {
             // ModulusRaised: c1 = P c + S over [q_0 .. q_{level-1}, P], contracted by modswitch (modulusraising.jl:35-42):
             // out_j = c_j + (T_j - [T_P]) P^-1 with T = INTT(S)  (the tail of the RNS-digit path, k_ks_rescale_add)
             rc = run_ntt(c, true, S, S, nb * 2 * nw, A.w);
             if (rc) return rc;
-            hipLaunchKernelGGL(k_ks_rescale_add, row_grid((unsigned)(nb * 2 * level), (size_t)c->N), dim3(256), 0, c->stream, S, cin, cout, c->limbs_dev, Al, ra, n, add_s);
-            HIP_TRY(hipGetLastError());
+            rc = launch(c, k_ks_rescale_add, row_grid((unsigned)(nb * 2 * level), (size_t)c->N), dim3(256), 0, S, cin, cout, c->limbs_dev, Al, ra, n, add_s);
+            if (rc) return rc;
         } else if (c->logN <= 14) {
             ntt_io_t io = io_plain();
             io.mode = 2; io.gsz = (u32)(2 * level); io.src_gstride = io.gsz; io.dst_gstride = io.gsz;
@@ -2095,8 +1801,8 @@ int tfhe_keyswitch_window(tfhe_ctx* c, int key_limbs, int level, int special, in
         } else {
             rc = run_ntt(c, true, S, cout, nb * 2 * level, A.w);
             if (rc) return rc;
-            hipLaunchKernelGGL(k_ks_add_ct, row_grid((unsigned)(nb * 2 * level), (size_t)c->N), dim3(256), 0, c->stream, cin, cout, c->limbs_dev, Al, n, add_s);
-            HIP_TRY(hipGetLastError());
+            rc = launch(c, k_ks_add_ct, row_grid((unsigned)(nb * 2 * level), (size_t)c->N), dim3(256), 0, cin, cout, c->limbs_dev, Al, n, add_s);
+            if (rc) return rc;
         }
     }
     return TFHE_OK;
@@ -2153,10 +1859,10 @@ static int ckks_check(tfhe_ctx* c, int level, uint64_t smant, const void* a, con
 static int ckks_fft(tfhe_ctx* c, cplx_t* buf, int64_t nb, bool dif, bool conj_roots) {
     const u32 n = (u32)c->N;
     const dim3 grid((n / 2 + 255) / 256, (unsigned)nb);
-    if (dif) for (u32 h = n / 2; h >= 1; h >>= 1) hipLaunchKernelGGL(k_fft_pass, grid, dim3(256), 0, c->stream, buf, (const cplx_t*)c->ckks_roots, n, h, 1, conj_roots ? 1 : 0);
-    else for (u32 h = 1; h < n; h <<= 1) hipLaunchKernelGGL(k_fft_pass, grid, dim3(256), 0, c->stream, buf, (const cplx_t*)c->ckks_roots, n, h, 0, conj_roots ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return TFHE_OK;
+    int rc = TFHE_OK;
+    if (dif) for (u32 h = n / 2; h >= 1 && !rc; h >>= 1) rc = launch(c, k_fft_pass, grid, dim3(256), 0, buf, (const cplx_t*)c->ckks_roots, n, h, 1, conj_roots ? 1 : 0);
+    else for (u32 h = 1; h < n && !rc; h <<= 1) rc = launch(c, k_fft_pass, grid, dim3(256), 0, buf, (const cplx_t*)c->ckks_roots, n, h, 0, conj_roots ? 1 : 0);
+    return rc;
 }
 
 int tfhe_ckks_encode(tfhe_ctx* c, int level, uint64_t scale_mant, int scale_exp2, const double* slots, uint64_t* out, int64_t batch) {
@@ -2165,9 +1871,7 @@ int tfhe_ckks_encode(tfhe_ctx* c, int level, uint64_t scale_mant, int scale_exp2
     rc = ckks_tables(c);
     if (rc) return rc;
     const u32 n = (u32)c->N;
-    limb_sel_t sel;
-    sel.n = level;
-    for (int j = 0; j < level; j++) sel.idx[j] = j;
+    const limb_sel_t sel = first_limbs(level);
     const int64_t chunk = std::min<int64_t>(batch, 4096);
     void* ws = nullptr;
     rc = ensure_ws(c, (size_t)chunk * n * 16, &ws);
@@ -2175,13 +1879,14 @@ int tfhe_ckks_encode(tfhe_ctx* c, int level, uint64_t scale_mant, int scale_exp2
     cplx_t* buf = (cplx_t*)ws;
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
-        hipLaunchKernelGGL(k_ckks_scatter, dim3((n / 2 + 255) / 256, (unsigned)nb), dim3(256), 0, c->stream,
-                           (const cplx_t*)slots + (size_t)b0 * (n / 2), buf, (const u32*)c->ckks_pos, n);
+        rc = launch(c, k_ckks_scatter, dim3((n / 2 + 255) / 256, (unsigned)nb), dim3(256), 0, (const cplx_t*)slots + (size_t)b0 * (n / 2), buf,
+                    (const u32*)c->ckks_pos, n);
+        if (rc) return rc;
         rc = ckks_fft(c, buf, nb, false, true);  // inverse transform: conjugate roots, 1/N applied below
         if (rc) return rc;
-        hipLaunchKernelGGL(k_ckks_encode_finish, dim3((n + 255) / 256, (unsigned)nb), dim3(256), 0, c->stream, buf, (const cplx_t*)c->ckks_tw,
-                           out + (size_t)b0 * level * n, c->limbs_dev, sel, scale_mant, scale_exp2, n);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_ckks_encode_finish, dim3((n + 255) / 256, (unsigned)nb), dim3(256), 0, buf, (const cplx_t*)c->ckks_tw,
+                    out + (size_t)b0 * level * n, c->limbs_dev, sel, scale_mant, scale_exp2, n);
+        if (rc) return rc;
     }
     return TFHE_OK;
 }
@@ -2202,14 +1907,14 @@ int tfhe_ckks_decode(tfhe_ctx* c, int level, uint64_t scale_mant, int scale_exp2
     cplx_t* buf = (cplx_t*)ws;
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
-        hipLaunchKernelGGL(k_ckks_decode_start, dim3((n + 255) / 256, (unsigned)nb), dim3(256), 0, c->stream, in + (size_t)b0 * level * n, buf,
-                           (const cplx_t*)c->ckks_tw, T, level, c->q[0], scale_mant, scale_exp2, n);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_ckks_decode_start, dim3((n + 255) / 256, (unsigned)nb), dim3(256), 0, in + (size_t)b0 * level * n, buf,
+                    (const cplx_t*)c->ckks_tw, T, level, c->q[0], scale_mant, scale_exp2, n);
+        if (rc) return rc;
         rc = ckks_fft(c, buf, nb, true, false);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_ckks_gather, dim3((n / 2 + 255) / 256, (unsigned)nb), dim3(256), 0, c->stream, buf,
-                           (cplx_t*)slots + (size_t)b0 * (n / 2), (const u32*)c->ckks_gpos, n);
-        HIP_TRY(hipGetLastError());
+        rc = launch(c, k_ckks_gather, dim3((n / 2 + 255) / 256, (unsigned)nb), dim3(256), 0, buf, (cplx_t*)slots + (size_t)b0 * (n / 2),
+                    (const u32*)c->ckks_gpos, n);
+        if (rc) return rc;
     }
     return TFHE_OK;
 }
@@ -2223,10 +1928,10 @@ int tfhe_sample_uniform(tfhe_ctx* c, int level, uint64_t seed, uint32_t stream, 
     const u32 n = (u32)c->N;
     for (int64_t p0 = 0; p0 < count; p0 += 32768) {
         const unsigned np = (unsigned)std::min<int64_t>(32768, count - p0);
-        hipLaunchKernelGGL(k_sample_uniform, dim3((n + 255) / 256, (unsigned)level, np), dim3(256), 0, c->stream, out + (size_t)p0 * level * n,
-                           c->limbs_dev, level, seed, stream, n, first_poly + (u64)p0);
+        const int rc = launch(c, k_sample_uniform, dim3((n + 255) / 256, (unsigned)level, np), dim3(256), 0, out + (size_t)p0 * level * n,
+                              c->limbs_dev, level, seed, stream, n, first_poly + (u64)p0);
+        if (rc) return rc;
     }
-    HIP_TRY(hipGetLastError());
     return TFHE_OK;
 }
 int tfhe_sample_gaussian(tfhe_ctx* c, int level, double sigma, uint64_t multiplier, uint64_t seed, uint32_t stream, uint64_t first_poly,
@@ -2239,10 +1944,10 @@ int tfhe_sample_gaussian(tfhe_ctx* c, int level, double sigma, uint64_t multipli
     const u32 n = (u32)c->N;
     for (int64_t p0 = 0; p0 < count; p0 += 32768) {
         const unsigned np = (unsigned)std::min<int64_t>(32768, count - p0);
-        hipLaunchKernelGGL(k_sample_gaussian, dim3((n + 255) / 256, np), dim3(256), 0, c->stream, out + (size_t)p0 * level * n, c->limbs_dev,
-                           level, sigma, multiplier, seed, stream, n, first_poly + (u64)p0);
+        const int rc = launch(c, k_sample_gaussian, dim3((n + 255) / 256, np), dim3(256), 0, out + (size_t)p0 * level * n, c->limbs_dev,
+                              level, sigma, multiplier, seed, stream, n, first_poly + (u64)p0);
+        if (rc) return rc;
     }
-    HIP_TRY(hipGetLastError());
     return TFHE_OK;
 }
 
