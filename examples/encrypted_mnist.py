@@ -127,8 +127,11 @@ def load_model(path=GOLDEN_MODEL):
     return m
 
 
-def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None):
-    """`batches` = K ciphertext sets evaluated together (K * B images): every ring element carries a leading batch dimension
+def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None,
+        mul_relin=False):
+    """`mul_relin`: the two square layers as one device call each (she.mul_relin = tfhe_mul_relin) instead of
+    modswitch(keyswitch(ek, c * c)); same logits, bit for bit.
+    `batches` = K ciphertext sets evaluated together (K * B images): every ring element carries a leading batch dimension
     of K, so each device call covers K ciphertexts (the batch the engine shards across GPUs)."""
     N = 1 << logn
     B = N // 128                                                   # images per ciphertext
@@ -190,7 +193,9 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
           conved.append(tf.modswitch(add_bias(acc, float(model["conv_b"][ch]), cache, ("conv", ch))))
       if fused:    # the four channels' squares, relinearisations and rescales as ONE batch of 4 K ciphertexts
           big = tf.CipherText.concat(conved)
-          sq1 = tf.modswitch(tf.keyswitch(ek, big * big)).split([K] * 4)
+          sq1 = (tf.she.mul_relin(ek, big, big, rescale=True) if mul_relin else tf.modswitch(tf.keyswitch(ek, big * big))).split([K] * 4)
+      elif mul_relin:
+          sq1 = [tf.she.mul_relin(ek, c, c, rescale=True) for c in conved]
       else:
           sq1 = [tf.modswitch(tf.keyswitch(ek, c * c)) for c in conved]
       fq1 = None
@@ -198,7 +203,7 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
           part = encrypted_matmul(gk, fq1_blocks[i], sq1[i], B, cache, fused)
           fq1 = part if fq1 is None else fq1 + part
       fq1 = tf.modswitch(add_bias(fq1, np.repeat(model["fq1_b"], B), cache, "fq1"))
-      sq2 = tf.modswitch(tf.keyswitch(ek, fq1 * fq1))
+      sq2 = tf.she.mul_relin(ek, fq1, fq1, rescale=True) if mul_relin else tf.modswitch(tf.keyswitch(ek, fq1 * fq1))
       res = add_bias(encrypted_matmul(gk, W2, sq2, B, cache, fused), np.repeat(np.concatenate([model["fq2_b"], np.zeros(54)]), B), cache, "fq2")
       ev1.record(res[0].ring.ctx)
       t_enq = time.perf_counter() - t0                                # every launch of the circuit is enqueued; the device may still be running
@@ -230,5 +235,7 @@ if __name__ == "__main__":
     ap.add_argument("--repeat", type=int, default=1, help="evaluate this many times; from the second pass on the weight plaintexts are cached")
     ap.add_argument("--fused", action="store_true",
                     help="with --hoisted: each matrix product as one tfhe_matmul_diag call and each convolution channel as one tfhe_lincomb per component")
+    ap.add_argument("--mul-relin", action="store_true",
+                    help="the two square layers through she.mul_relin (one tfhe_mul_relin call each) instead of modswitch(keyswitch(ek, c * c))")
     a = ap.parse_args()
-    run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused)
+    run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin)

@@ -253,6 +253,22 @@ int tfhe_bfv_plan_set_variant(tfhe_bfv_plan *plan, int variant);
 /* ciphertexts processed per internal chunk (workspace = chunk * (7 nb + 3 ns) * N * 8 bytes); 0 = default (256) */
 int tfhe_bfv_plan_set_chunk(tfhe_bfv_plan *plan, int chunk);
 
+/* ---- CKKS / BGV: ciphertext product + relinearisation (+ modswitch) in one call ------------------------------------
+ * c1*c2 (rlwe_she.jl:247-262, mul_expand/mul_contract = identity) -> keyswitch(evk, .) (rlwe_she.jl:315-347; ModulusRaised
+ * modulusraising.jl:35-49) -> optionally modswitch of both components (crt.jl:215-228; ckksencoding.jl:127-130).
+ *   c1, c2: [batch][2][level][N]; ntt_in = 0: coefficient domain, 1: NTT domain (natural order).  c1 == c2 (squaring) allowed.
+ *   evk, key_limbs, level, special, n_digits: as tfhe_keyswitch (RNS digits).
+ *   rescale = 0: out [batch][2][level][N];  rescale = 1 (level >= 2): out [batch][2][level-1][N].  Coefficient domain.
+ * The words are those of tfhe_nntt x2 -> tfhe_tensor -> tfhe_inntt -> tfhe_keyswitch(polys = 3) -> tfhe_rescale on the same
+ * packed buffers, bit for bit; the intermediates live in the context workspace (no pack / unpack copies).
+ * The product (transforms + tensor) of a ring whose limbs are all of fp64 size (q < 2^50 + 2^40) at N = 2^12 .. 2^14 runs in one
+ * fused kernel per chunk (4 rows read + 3 written per limb; 2 read when squaring); rings with a larger limb, N < 2^12,
+ * N >= 2^15 and tfhe_ctx_set_ntt_variant != 0 run the batched transform / tensor kernels on the packed layout.
+ * Checks (host, before any device use): as tfhe_keyswitch; rescale with level < 2 is TFHE_E_LEVEL_MISMATCH; `out` overlapping
+ * c1 or c2 as address ranges is TFHE_E_BADARG; batch == 0 does nothing.  The BFV product is tfhe_bfv_mul_relin. */
+int tfhe_mul_relin(tfhe_ctx *ctx, int key_limbs, int level, int special, const uint64_t *evk, int n_digits,
+                   const uint64_t *c1, const uint64_t *c2, int ntt_in, int rescale, uint64_t *out, int64_t batch);
+
 /* ---- BFV / BGV plaintext codecs on the device (π⁻¹ / π, bfv.jl:21-29, bgv.jl:21-25; noise, bfv.jl:137-166) ---------
  * plan = (ring = ctx limbs limb_idx, t).  t in [2, 2^62) and t < Q (Q = product of the selected moduli); limb_idx entries
  * in range and distinct; else TFHE_E_BADARG (checked on the host before any device use).  Exact: bit-identical to the

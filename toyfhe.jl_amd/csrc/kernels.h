@@ -2282,8 +2282,15 @@ struct core_alt_t {  // limbs of ℛbig that are limbs of ℛ: read from the inp
     int ns;
     signed char idx[TFHE_MAX_LIMBS];  // limb j of ℛbig -> limb of ℛ, or -1
 };
+// MODE (tfhe_mul_relin: the product of CKKS / BGV ciphertexts, whose mul_expand / mul_contract are the identity; 0 = BFV, unchanged):
+//   CORE_PACKED: `sel` lists a SUBSET of the ciphertext's limbs (one arithmetic policy of a mixed ring); the operands are the packed
+//                ciphertexts alt.a / alt.b and the result rows land at their place in T [nct][3][alt.ns][N] (limb alt.idx[j])
+//   CORE_SQUARE: alt.b is alt.a: two forward transforms, (a0^2, 2 a0 a1, a1^2), nothing parked
+//   CORE_NTTIN : the operands are NTT images (natural order): no forward transforms, nothing held or parked -- the products are formed
+//                from the operand rows as they lie (each word is read twice, the second time from L2) into ONE row of registers
+enum { CORE_PACKED = 1, CORE_SQUARE = 2, CORE_NTTIN = 4 };
 // OUTD: the three result rows leave as reduced doubles (ArithFpD) for the narrow contraction (k_bfv_contract_fast<.., TD>)
-template <class A, int LOGB, int LOGT, bool OUTD = false>
+template <class A, int LOGB, int LOGT, bool OUTD = false, int MODE = 0>
 __global__ __launch_bounds__(1 << LOGT) void k_bfv_core_fused(const u64* __restrict__ Ea, const u64* __restrict__ Eb,
                                                                u64* __restrict__ T, u64* __restrict__ scratch,
                                                                const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 nitems,
@@ -2305,9 +2312,10 @@ __global__ __launch_bounds__(1 << LOGT) void k_bfv_core_fused(const u64* __restr
         typename A::ctx C = A::make(LT[sel.idx[j]]);
         if constexpr (TFHE_TWL_CORE != 0) fused_fill_tw<A, LOGB, LOGT, TFHE_TWL_CORE>(lds, C);
         const size_t r0 = ((size_t)(b * 2 + 0) * nb + j) << LOGB, r1 = ((size_t)(b * 2 + 1) * nb + j) << LOGB;
-        u64* const t0 = T + (((size_t)(b * 3 + 0) * nb + j) << LOGB);
-        u64* const t1 = T + (((size_t)(b * 3 + 1) * nb + j) << LOGB);
-        u64* const t2 = T + (((size_t)(b * 3 + 2) * nb + j) << LOGB);
+        const u32 onb = (MODE & CORE_PACKED) ? (u32)alt.ns : nb, oj = (MODE & CORE_PACKED) ? (u32)alt.idx[j] : j;
+        u64* const t0 = T + (((size_t)(b * 3 + 0) * onb + oj) << LOGB);
+        u64* const t1 = T + (((size_t)(b * 3 + 1) * onb + oj) << LOGB);
+        u64* const t2 = T + (((size_t)(b * 3 + 2) * onb + oj) << LOGB);
         typename A::elem A0[E], A1[E], v[E];
         // range (fp64arith.h): the held transforms are reduced to |A| <= p/2; the running one stays lazy (|v| <= 7.68 p at the end
         // of the forward plan), so |A v| / p <= 3.84 p and a product is exact with |r| <= (1/2 + 1.5 a 3.84) p = 1.94 p;
@@ -2317,12 +2325,50 @@ __global__ __launch_bounds__(1 << LOGT) void k_bfv_core_fused(const u64* __restr
             const size_t s0 = ((size_t)(b * 2 + 0) * alt.ns + alt.idx[j]) << LOGB, s1 = ((size_t)(b * 2 + 1) * alt.ns + alt.idx[j]) << LOGB;
             pa0 = alt.a + s0; pa1 = alt.a + s1; pb0 = alt.b + s0; pb1 = alt.b + s1;
         }
+        if constexpr ((MODE & CORE_NTTIN) != 0) {
+            // ranges: a word as it lies is < p, the multiplier is its centred image (|w| <= p/2): every product is exact with
+            // |r| < 1.94 p and the middle row's sum < 3.9 p, the bounds of the transformed form
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const u32 tid = fresh_tid();
+#pragma unroll
+                for (int u = 0; u < G3::SETS; u++) {
+                    u32 c0, hi, base;
+                    G3::template coords<true>(tid, u, c0, hi, base);
+#pragma unroll
+                    for (int r = 0; r < G3::R; r++) {
+                        const u32 nat = (brev_bits((u32)r, K3) << (LOGB - K3)) + c0;
+                        const u64* const x = k == 2 ? pa1 : pa0;
+                        const u64* const y = k == 0 ? pb0 : pb1;
+                        double m = fp_mulmod_c(A::from_global_plain(x[nat], C), ftw_t{A::from_global(y[nat], C)}, C.p, C.pinv);
+                        if (k == 1) m += (MODE & CORE_SQUARE) ? m : fp_mulmod_c(A::from_global_plain(pa1[nat], C), ftw_t{A::from_global(pb0[nat], C)}, C.p, C.pinv);
+                        v[u * G3::R + r] = m;
+                    }
+                }
+                fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, k == 0 ? t0 : k == 1 ? t1 : t2, C, nullptr);
+            }
+            continue;
+        }
         fused_fwd_to_regs<A, LOGB, LOGT, false, (TFHE_TWL_CORE & 1) != 0>(lds, pa0, C, first, A0);
 #pragma unroll
         for (int e = 0; e < E; e++) A0[e] = fp_reduce(A0[e], C.p, C.pinv);
         fused_fwd_to_regs<A, LOGB, LOGT, false, (TFHE_TWL_CORE & 1) != 0>(lds, pa1, C, first, A1);
 #pragma unroll
         for (int e = 0; e < E; e++) A1[e] = fp_reduce(A1[e], C.p, C.pinv);
+        if constexpr ((MODE & CORE_SQUARE) != 0) {
+            // both held rows are reduced (|A| <= p/2): every product is exact with |r| <= 1.94 p and 2 a0 a1 <= 3.9 p, the bounds of
+            // the general form; the held rows survive the inverse transforms of v
+#pragma unroll
+            for (int e = 0; e < E; e++) v[e] = fp_mulmod_c(A0[e], ftw_t{A0[e]}, C.p, C.pinv);
+            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, t0, C, nullptr);
+#pragma unroll
+            for (int e = 0; e < E; e++) { const double m = fp_mulmod_c(A1[e], ftw_t{A0[e]}, C.p, C.pinv); v[e] = m + m; }
+            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, t1, C, nullptr);
+#pragma unroll
+            for (int e = 0; e < E; e++) v[e] = fp_mulmod_c(A1[e], ftw_t{A1[e]}, C.p, C.pinv);
+            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, t2, C, nullptr);
+            continue;
+        }
         fused_fwd_to_regs<A, LOGB, LOGT, false, (TFHE_TWL_CORE & 1) != 0>(lds, pb0, C, first, v);
         {
             const u32 tid = fresh_tid();

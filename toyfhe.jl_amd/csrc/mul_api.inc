@@ -1,0 +1,190 @@
+// mul_api.inc -- tfhe_mul_relin: ciphertext product + relinearisation (+ modswitch) of the schemes whose mul_expand /
+// mul_contract are the identity (CKKS, BGV: rlwe_she.jl:39-40, :247-262); included by toyfhe_hip.hip.
+//
+// The call is the chain  nntt x2 -> tensor -> inntt -> keyswitch(polys = 3) -> rescale  run directly on the packed
+// ciphertexts ([batch][2][level][N] is 2 batch polynomials), with the intermediates in the context workspace:
+//     ws = [ key-switch region / transform scratch | F: 4 rows per limb (NTT images) | T: 3 rows | R: 2 rows | parking rows x 2 ]
+// keyswitch_impl sizes and carves ITS region from the start of the context workspace and would move the block if it had to
+// grow it, so the block is sized once, before the first launch, for both users (mr_ks_bytes mirrors keyswitch_impl).
+//
+// Routing of the product (forward transforms + tensor + inverse transforms) per limb:
+//   N = 2^12 .. 2^14, variant 0, fp64-size limb : k_bfv_core_fused (MODE: packed operands / squaring / NTT-domain input)
+//   N = 2^12 .. 2^14, variant 0, larger limb    : k_mul_core_int (mul_core.h), beside the fp64 core on the second lane
+//   everything else                             : batched transform kernels + k_tensor on the packed layout (not fused)
+// Every path leaves canonical residues, so the words are those of the chain through the public entry points.
+
+namespace {
+
+// bytes keyswitch_impl (rotate = false) asks of the context workspace for `batch` ciphertexts
+size_t mr_ks_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t batch) {
+    const int nw = special ? level + 1 : level;
+    const size_t N = (size_t)c->N;
+    const bool f14 = ks_fused14(c, Lk, level, special);
+    const size_t dig_rows = f14 ? (size_t)2 * nw : (size_t)level * nw;
+    const size_t per_ct = ((size_t)2 * nw + dig_rows) * N * 8;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)512, (int64_t)((8192ull << 20) / per_ct)}));
+    const size_t ntt_tmp = (c->logN > 14 && !f14) ? (size_t)chunk * std::max(2, level) * nw * N * 8 : 0;
+    const size_t evd_bytes = f14 ? (size_t)level * 2 * nw * N * 8 : 0;
+    return ntt_tmp + (size_t)chunk * per_ct + evd_bytes;
+}
+
+bool mr_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// parking rows (N words each) the two fused cores may ask for: one per workgroup (k_bfv_core_fused; k_mul_core_int below 2^14), two per
+// workgroup at 2^14 (k_mul_core_int) -- the grids are at most two workgroups per CU below 2^14 and one at 2^14
+size_t mr_park_rows(const tfhe_ctx* c) { return (size_t)2 * std::max(256, c->num_cus) * TFHE_GRID_MULT_CORE; }
+
+// the subset `mask` (positions in the ciphertext) of the first `level` limbs as a selection + its place in the packed buffers
+void mr_subset(int level, u32 mask, const u64* a, const u64* b, limb_sel_t* sel, core_alt_t* alt) {
+    *sel = limb_sel_t{};
+    *alt = core_alt_t{};
+    alt->a = a; alt->b = b; alt->ns = level;
+    for (int j = 0; j < level; j++)
+        if ((mask >> j) & 1u) { alt->idx[sel->n] = (signed char)j; sel->idx[sel->n++] = j; }
+}
+int64_t mr_transforms(unsigned items, bool square, bool ntt_in) { return (int64_t)items * ((ntt_in ? 0 : (square ? 2 : 4)) + 3); }
+
+// the fused product of the fp64-size limbs of one chunk (mask: positions in the ciphertext); T rows of the other limbs untouched
+int mr_core_fp(tfhe_ctx* c, const u64* a, const u64* b, u64* T, u64* scratch, int64_t nct, int level, u32 mask, bool whole, bool square, bool ntt_in) {
+    limb_sel_t sel;
+    core_alt_t alt;
+    mr_subset(level, mask, a, b, &sel, &alt);
+    if (sel.n == 0) return TFHE_OK;
+    if (whole && !square && !ntt_in) {
+        // every limb of the ring, general form: the BFV plan's own instantiation, fed from the packed ciphertexts (core_alt_t)
+        bool done = false;
+        const int rc = launch_bfv_core_fused(c, a, b, T, scratch, nct, sel, &done, &alt);
+        if (rc) return rc;
+        return done ? TFHE_OK : fail(TFHE_E_UNSUPPORTED, "internal: fused product core not available");
+    }
+    const unsigned items = (unsigned)(nct * sel.n);
+    return dispatch_int<12, 14>(c->logN, [&](auto lb) {
+        constexpr int LOGB = decltype(lb)::value, LOGT = logt_for(LOGB);
+        void (*kern)(const u64*, const u64*, u64*, u64*, const ntt_limb_t*, limb_sel_t, u32, core_alt_t) = nullptr;
+        if (square && ntt_in) kern = k_bfv_core_fused<ArithFp, LOGB, LOGT, false, CORE_PACKED | CORE_SQUARE | CORE_NTTIN>;
+        else if (square) kern = k_bfv_core_fused<ArithFp, LOGB, LOGT, false, CORE_PACKED | CORE_SQUARE>;
+        else if (ntt_in) kern = k_bfv_core_fused<ArithFp, LOGB, LOGT, false, CORE_PACKED | CORE_NTTIN>;
+        else if constexpr (LOGB < 14) kern = k_bfv_core_fused<ArithFp, LOGB, LOGT, false, CORE_PACKED>;
+        if (!kern) return fail(TFHE_E_UNSUPPORTED, "internal: this form of the fused product core is not built at N = 2^%d", LOGB);
+        const unsigned grid = cu_grid(c, items, (LOGB == 14 ? 1u : 2u) * TFHE_GRID_MULT_CORE);
+        return launch_prof(c, mr_transforms(items, square, ntt_in), kern, dim3(grid), dim3(1 << LOGT), fused_lds_bytes<LOGB, LOGT, TFHE_TWL_CORE>(), a, b, T,
+                           scratch, c->limbs_dev, sel, items, alt);
+    });
+}
+// the same for the limbs of the u64 policy (k_mul_core_int, mul_core.h)
+int mr_core_int(tfhe_ctx* c, const u64* a, const u64* b, u64* T, u64* scratch, int64_t nct, int level, u32 mask, bool square, bool ntt_in) {
+    limb_sel_t sel;
+    core_alt_t alt;
+    mr_subset(level, mask, a, b, &sel, &alt);
+    if (sel.n == 0) return TFHE_OK;
+    const unsigned items = (unsigned)(nct * sel.n);
+    return dispatch_int<12, 14>(c->logN, [&](auto lb) {
+        constexpr int LOGB = decltype(lb)::value, LOGT = logt_for(LOGB);
+        auto kern = (square && ntt_in) ? k_mul_core_int<LOGB, LOGT, CORE_PACKED | CORE_SQUARE | CORE_NTTIN>
+                    : square           ? k_mul_core_int<LOGB, LOGT, CORE_PACKED | CORE_SQUARE>
+                    : ntt_in           ? k_mul_core_int<LOGB, LOGT, CORE_PACKED | CORE_NTTIN>
+                                       : k_mul_core_int<LOGB, LOGT, CORE_PACKED>;
+        const unsigned grid = cu_grid(c, items, (LOGB == 14 ? 1u : 2u) * TFHE_GRID_MULT_CORE);
+        return launch_prof(c, mr_transforms(items, square, ntt_in), kern, dim3(grid), dim3(1 << LOGT), (size_t)lds_words<LOGB, LOGT>() * 8, T, scratch,
+                           c->limbs_dev, sel, items, alt);
+    });
+}
+
+// batched kernels on the packed layout, restricted to the limbs of `mask` (0 = all): T [nct][3][level][N] coefficient domain
+int mr_product_composed(tfhe_ctx* c, const u64* a, const u64* b, u64* F, u64* T, int64_t nct, int level, bool square, bool ntt_in) {
+    const size_t N = (size_t)c->N;
+    const limb_sel_t sel = first_limbs(level);
+    const u64 *fa = a, *fb = b;
+    int rc;
+    if (!ntt_in) {
+        u64* F2 = F + (size_t)nct * 2 * level * N;
+        rc = run_ntt(c, false, a, F, nct * 2 * level, sel);
+        if (rc) return rc;
+        if (!square) {
+            rc = run_ntt(c, false, b, F2, nct * 2 * level, sel);
+            if (rc) return rc;
+        }
+        fa = F;
+        fb = square ? F : F2;
+    }
+    rc = launch(c, k_tensor, row_grid((unsigned)(nct * level), N), dim3(256), 0, fa, fb, T, c->limbs_dev, sel, (u32)N);   // rlwe_she.jl:255-258
+    if (rc) return rc;
+    return run_ntt(c, true, T, T, nct * 3 * level, sel);
+}
+
+}  // namespace
+
+extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk, int n_digits, const uint64_t* c1,
+                              const uint64_t* c2, int ntt_in, int rescale, uint64_t* out, int64_t batch) {
+    // every check runs on the host before any device use
+    if (!evk || !c1 || !c2 || !out) return fail(TFHE_E_BADARG, "null argument");
+    if (batch < 0) return fail(TFHE_E_BADARG, "negative batch");
+    if ((ntt_in != 0 && ntt_in != 1) || (rescale != 0 && rescale != 1)) return fail(TFHE_E_BADARG, "ntt_in and rescale are 0 or 1");
+    if (rescale && level < 2) return fail(TFHE_E_LEVEL_MISMATCH, "modswitch after the product needs level >= 2, got %d", level);
+    if (out == c1 || out == c2) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    int rc = ks_check(c, Lk, level, special, evk, n_digits, c1, 3, out, batch);
+    if (rc) return rc;
+    const size_t N = (size_t)c->N;
+    const size_t in_bytes = (size_t)batch * 2 * level * N * 8, out_bytes = (size_t)batch * 2 * (level - (rescale ? 1 : 0)) * N * 8;
+    if (mr_ranges_overlap(out, out_bytes, c1, in_bytes) || mr_ranges_overlap(out, out_bytes, c2, in_bytes))
+        return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (batch == 0) return TFHE_OK;
+    if ((batch * 4 * level) << std::max(0, c->logN - 14) > 0x7fffffffll) return fail(TFHE_E_BADARG, "bad batch");
+
+    const bool square = c1 == c2;
+    const limb_sel_t sel = first_limbs(level);
+    const policy_split_t ps = policy_split(c, sel);
+    // fused product cores: N = 2^12 .. 2^14, variant 0.  The general form of the fp64 core with a limb subset is not built at 2^14
+    // (it does not fit the registers there, DESIGN.md): a ring that mixes the policies takes the batched kernels for that form.
+    const bool fused = c->variant == 0 && c->logN >= 12 && c->logN <= 14 && level <= 32 &&
+                       !(c->logN == 14 && ps.mixed_fp() && !square && !ntt_in);
+    const u32 fp_mask = fused ? ps.fpmask : 0u, int_mask = fused ? (ps.all & ~ps.fpmask) : 0u;
+
+    // chunk: F (NTT images of the operands: the batched path only), T (3 rows per limb), R (2: the key switch's result when a
+    // modswitch follows)
+    const size_t f_rows = (fused || ntt_in) ? 0 : (square ? 2 : 4), r_rows = rescale ? 2 : 0;
+    const size_t per_ct = (f_rows + 3 + r_rows) * level * N * 8;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)256, (int64_t)((4096ull << 20) / per_ct)}));
+    const size_t park = mr_park_rows(c) * N;   // words, per core
+    size_t region0 = mr_ks_bytes(c, Lk, level, special, chunk);
+    if (c->logN > 14) region0 = std::max(region0, (size_t)chunk * 3 * level * N * 8);   // run_ntt's scratch for N > 2^14
+    region0 = (region0 + 255) & ~(size_t)255;
+    void* ws = nullptr;
+    rc = ensure_ws(c, region0 + (size_t)chunk * per_ct + (fused ? 2 * park * 8 : 0), &ws);   // once, for both users, before any fork
+    if (rc) return rc;
+    u64* F = (u64*)((char*)ws + region0);
+    u64* T = F + (size_t)chunk * f_rows * level * N;
+    u64* R = T + (size_t)chunk * 3 * level * N;
+    u64* SCR = R + (size_t)chunk * r_rows * level * N;
+    const int lo = level - (rescale ? 1 : 0);
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nct = std::min(chunk, batch - b0);
+        const u64* a = c1 + (size_t)b0 * 2 * level * N;
+        const u64* b = c2 + (size_t)b0 * 2 * level * N;
+        if (fused) {
+            // a ring that mixes the policies runs both cores side by side on the context's two lanes, over disjoint rows of T; the
+            // u64 core (the long pole) first, on the main lane; the lanes join before the key switch reads T
+            lanes_t lanes(c, fp_mask != 0 && int_mask != 0);
+            lanes.use(0);
+            rc = mr_core_int(c, a, b, T, SCR, nct, level, int_mask, square, ntt_in != 0);
+            if (rc) return rc;
+            lanes.use(1);
+            rc = mr_core_fp(c, a, b, T, SCR + park, nct, level, fp_mask, int_mask == 0, square, ntt_in != 0);
+        } else {
+            rc = mr_product_composed(c, a, b, F, T, nct, level, square, ntt_in != 0);
+        }
+        if (rc) return rc;
+        u64* ks_out = rescale ? R : out + (size_t)b0 * 2 * level * N;
+        rc = keyswitch_impl(c, Lk, level, special, evk, T, 3, ks_out, nct, 0, false);   // rlwe_she.jl:315-347
+        if (rc) return rc;
+        if (c->ws != ws) return fail(TFHE_E_HIP, "internal: the key switch moved the workspace");
+        if (rescale) {
+            rc = do_rescale(c, R, out + (size_t)b0 * 2 * lo * N, nct * 2, sel);       // crt.jl:215-228 on both components
+            if (rc) return rc;
+        }
+    }
+    return TFHE_OK;
+}

@@ -20,6 +20,7 @@
 #include "plain_tables.h"
 #include "host_math.h"
 #include "kernels.h"
+#include "mul_core.h"
 #include "ckks_kernels.h"
 #include "sample_kernels.h"
 #include "ntt_tables.h"
@@ -2000,6 +2001,7 @@ int tfhe_event_elapsed_ms(void* a, void* b, float* ms) {
 #include "bfv_api.inc"
 #include "comm_api.inc"
 #include "plain_api.inc"
+#include "mul_api.inc"
 
 #ifdef TFHE_KS_TRACE
 extern "C" int tfhe_debug_kstrace(unsigned long long* out, unsigned* n, int reset) {

@@ -617,6 +617,40 @@ function mul_relin(ek::KeySwitchKey, c1::CipherText{E,BFVParams,<:RingElement{â„
     CipherText{E}(c1.params, unpack(ctx, out, â„›, 2))
 end
 
+# ---- CKKS / BGV: modswitch(keyswitch(ek, c1 * c2)) -- infer.jl:135-137, :165-167 -- as ONE call (tfhe_mul_relin) -----------------
+# The product's encoding: CKKS multiplies the scales (ckksencoding.jl:133-135); every other encoding is unchanged (rlwe_she.jl:247-262).
+product_encoding(::Type{CKKSEncoding{S1}}, ::Type{CKKSEncoding{S2}}) where {S1,S2} = CKKSEncoding{ToyFHE.scale(CKKSEncoding{S1}) * ToyFHE.scale(CKKSEncoding{S2})}
+product_encoding(::Type{E}, ::Type{E}) where {E} = E
+# the wrapper of modswitch(::CipherText) around components the device has rescaled already: CKKS divides the scale by the dropped
+# modulus and drops it from the parameters (ckksencoding.jl:127-130); `shell` carries the product's types at the input level
+function rescaled_like(shell::CipherText{CKKSEncoding{Tscale},P,T,N}, cs) where {scale,Tscale<:FixedRational{scale},CC<:CRTEncoded,P,T<:RingElement{<:Any,CC},N}
+    CipherText{CKKSEncoding{ToyFHE.drop_last(FixedRational{scale / ToyFHE.modulus(moduli(CC).parameters[end])})}}(ToyFHE.modswitch_drop(shell.params), cs)
+end
+rescaled_like(shell::CipherText{E}, cs) where {E} = CipherText{E}(shell.params, cs)
+# Bit-identical to modswitch(keyswitch(ek, c1 * c2)) (rescale = true) / keyswitch(ek, c1 * c2): the operands go in packed, the
+# transforms, the tensor product, the key switch and the rescale run on the device without a host round trip in between; the
+# N = 2^12 .. 2^14 rings run the product in fused kernels (include/toyfhe_hip.h).  c1 === c2 squares from one packed operand.
+# Windowed keys (relin_window != 0) and ciphertexts that are not 2-element take the composed path.
+function mul_relin(ek::KeySwitchKey, c1::CipherText{E1,P,<:RingElement{â„›,T,<:HipVector}}, c2::CipherText{E2,P}; rescale::Bool=false) where {E1,E2,P,â„›,T}
+    c1.params !== c2.params && throw(ToyFHE.UsageError("Attempting to multiply ciphertexts with differing parameters"))
+    if ToyFHE.relin_window(ek.params) != 0 || length(c1.cs) != 2 || length(c2.cs) != 2
+        r = ToyFHE.keyswitch(ek, c1 * c2)
+        return rescale ? ToyFHE.modswitch(r) : r
+    end
+    keyring = NTT.ring(ek.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T)
+    rescale && level < 2 && throw(ToyFHE.UsageError("modswitch needs at least two CRT moduli"))
+    ctx = hipring(keyring); key = pack(ek)
+    a = pack(ctx, c1); b = c1 === c2 ? a : pack(ctx, c2); cnt = samecount(a, b)
+    â„›o = rescale ? ToyFHE.drop_last(â„›) : â„›; To = eltype(â„›o)
+    out = HipVector{To}(2 * nlimbs(To), degree(â„›), cnt); on(ctx, (out,), (a, b, key))
+    GC.@preserve key a b out check(ccall((:tfhe_mul_relin, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{UInt64}, Cint, Ptr{UInt64}, Ptr{UInt64}, Cint, Cint, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, ek.params isa ModulusRaised ? 1 : 0, key.ptr, length(ek.key), a.ptr, b.ptr, 0, rescale ? 1 : 0, out.ptr, cnt))
+    Eo = product_encoding(E1, E2)
+    rescale || return CipherText{Eo}(c1.params, unpack(ctx, out, â„›o, 2))
+    rescaled_like(CipherText{Eo}(c1.params, c1.cs), unpack(ctx, out, â„›o, 2))
+end
+
 # ---- tensor for schemes whose mul_expand / mul_contract are the identity (BGV, CKKS; rlwe_she.jl:39-40,255-258) -----------
 function ToyFHE.enc_mul(c1::CipherText{E,P,<:RingElement{â„›,T,<:HipVector}}, c2::CipherText{E,P}) where {E,P,â„›,T}
     c1.params !== c2.params && throw(ToyFHE.UsageError("Attempting to multiply ciphertexts with differing parameters"))

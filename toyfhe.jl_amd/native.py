@@ -138,6 +138,7 @@ def lib():
         "tfhe_bfv_expand": [vp, vp, vp, i64],
         "tfhe_bfv_contract": [vp, vp, vp, i64],
         "tfhe_bfv_mul_relin": [vp, vp, i32, vp, vp, vp, i64],
+        "tfhe_mul_relin": [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, i64],
         "tfhe_plain_plan_create": [vp, i32p, i32, u64, C.POINTER(vp)],
         "tfhe_plain_plan_destroy": [vp],
         "tfhe_plain_encode": [vp, i32, vp, vp, i64],
@@ -164,7 +165,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
     "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
-    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
+    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
 ]
@@ -356,6 +357,12 @@ class Context:
 
     def keyswitch(self, key_limbs, level, special, evk, n_digits, ct, polys, out, batch):
         check(lib().tfhe_keyswitch(self.h, key_limbs, level, int(bool(special)), evk, n_digits, ct, polys, out, batch))
+
+    def mul_relin(self, key_limbs, level, special, evk, n_digits, c1, c2, out, batch, ntt_in=False, rescale=False):
+        """c1 * c2 -> keyswitch(evk, .) [-> modswitch] of CKKS / BGV ciphertexts in one call (tfhe_mul_relin); c1, c2
+        [batch][2][level][N], out [batch][2][level - rescale][N] coefficient domain; c1 == c2 squares"""
+        check(lib().tfhe_mul_relin(self.h, key_limbs, level, int(bool(special)), evk, n_digits, c1, c2, int(bool(ntt_in)),
+                                   int(bool(rescale)), out, batch))
 
     def keyswitch_window(self, level, window_bits, evk, n_windows, ct, polys, out, batch, key_limbs=None, special=False):
         check(lib().tfhe_keyswitch_window(self.h, level if key_limbs is None else key_limbs, level, int(bool(special)), window_bits,

@@ -1142,6 +1142,66 @@ def keyswitch(ek, c: CipherText, _galois=None, _gk=None) -> CipherText:
     return _PackedResult(c.params, c.scale, out, keyring.ctx, ring, n, batch)
 
 
+def mul_relin(ek, c1: CipherText, c2: CipherText, rescale: bool = False) -> CipherText:
+    """modswitch(keyswitch(ek, c1 * c2)) (rescale=True) or keyswitch(ek, c1 * c2) of CKKS / BGV ciphertexts -- the square layers of
+    infer.jl:135-137, :165-167 -- in ONE device call (tfhe_mul_relin) on the packed operands: same components, same scale
+    (scale_1 scale_2 [/ q_last], ckksencoding.jl:127-135).  An unsplit key-switch result is taken as it is; otherwise one pack
+    per operand (`c1 is c2` squares from one).  The result stays packed until its components are asked for, as keyswitch's.
+    BFV multiplies through its plan (BFVParams.plan().mul_relin); windowed keys (relin_window != 0) take the composed path."""
+    if isinstance(ek, (EvalMultKey, GaloisKey)):
+        ek = ek.key
+    if c1.params is not c2.params:
+        raise UsageError("Attempting to multiply ciphertexts with differing parameters")
+    inner = c1.params.params if isinstance(c1.params, ModulusRaised) else c1.params
+    if isinstance(inner, BFVParams):
+        raise UsageError("mul_relin serves the schemes without mul_expand / mul_contract (CKKS, BGV); "
+                         "BFV multiplies and relinearises through its plan: BFVParams.plan().mul_relin")
+    if (c1.scale is None) != (c2.scale is None):
+        raise UsageError("multiplying a scaled (CKKS) ciphertext by an unscaled one")
+    params = ek.params
+    if params.relin_window != 0 or len(c1) != 2 or len(c2) != 2:
+        r = keyswitch(ek, c1 * c2)
+        return modswitch(r) if rescale else r
+    special = isinstance(params, ModulusRaised)
+    keyring = ek.key[0].mask.ring
+    ring = c1.ring()
+    n, batch = c1._shape()
+    level = ring.L
+    if c2.ring() is not ring and (c2.ring().ctx is not ring.ctx or c2.ring().idx != ring.idx):
+        raise UsageError("the factors live in different rings")
+    if c2._shape() != (n, batch):
+        raise UsageError("the factors have different batch shapes")
+    if rescale and level < 2:
+        raise UsageError("modswitch needs at least two CRT moduli")
+    if keyring.idx != list(range(keyring.L)) or ring.idx != list(range(level)):
+        raise UsageError("ciphertext ring is not a prefix of the key ring")
+    if ring.ctx is not keyring.ctx and (ring.N != keyring.N or ring.moduli != keyring.moduli[:level] or ring.psi != keyring.psi[:level]):
+        raise UsageError("ciphertext and key belong to different rings")
+    factors = [c1] if c1 is c2 else [c1, c2]
+    images = [c._deferred_image(keyring.ctx) if isinstance(c, _PackedResult) else None for c in factors]
+    # operands that exist only as NTT images go in as they are (ntt_in): no inverse transforms just to transform them back
+    ntt_in = all(im is None for im in images) and all(x.primal is None and x.dual is not None for c in factors for x in c.cs)
+    bufs = [None if im is not None else [x.coeffs_dual() if ntt_in else x.coeffs_primal() for x in c.cs] for c, im in zip(factors, images)]
+    if ring.ctx is not keyring.ctx:
+        keyring.ctx.wait_for(ring.ctx)                     # the transforms above ran on the ciphertext ring's stream
+    for i, c in enumerate(factors):
+        if images[i] is None:
+            images[i] = (None if ntt_in else c._packed_for(bufs[i], keyring.ctx, consume=True)) or _pack(bufs[i], ring, n, ctx=keyring.ctx)
+    a, b = images[0], images[-1]
+    ring_out = ring.drop_last() if rescale else ring
+    out = DeviceBuffer(n * 2 * ring_out.L * ring.N)
+    keyring.ctx.mul_relin(keyring.L, level, special, ek.packed().ptr, len(ek.key), a.ptr, b.ptr, out.ptr, n, ntt_in=ntt_in, rescale=rescale)
+    scale = None if c1.scale is None else c1.scale * c2.scale   # ckksencoding.jl:133-135
+    if rescale and scale is not None:
+        scale = scale / ring.moduli[-1]                     # ckksencoding.jl:127-130
+    if ring.ctx is not keyring.ctx:
+        ring.ctx.wait_for(keyring.ctx)                     # the result belongs to the ciphertext ring: its stream must see it written
+    res = _PackedResult(c1.params, scale, out, keyring.ctx, ring_out, n, batch)
+    if not _LAZY_UNPACK:
+        res.cs                                             # split now (the image is remembered, as keyswitch does)
+    return res
+
+
 def apply_galois_element(c: CipherText, g: int) -> CipherText:
     return CipherText(c.params, [x.apply_galois_element(g) for x in c.cs], c.scale)  # rlwe_she.jl:355-357
 
