@@ -269,6 +269,40 @@ int tfhe_bfv_plan_set_chunk(tfhe_bfv_plan *plan, int chunk);
 int tfhe_mul_relin(tfhe_ctx *ctx, int key_limbs, int level, int special, const uint64_t *evk, int n_digits,
                    const uint64_t *c1, const uint64_t *c2, int ntt_in, int rescale, uint64_t *out, int64_t batch);
 
+/* ---- public-key encryption and the decryption phase of a batch, one call each (rlwe_she.jl:176-216) ------------------
+ * The ring is limbs 0..level-1 of ctx, 1 <= level <= key_limbs <= the context's limbs; level < key_limbs is the ModulusRaised
+ * case (modulusraising.jl:23-26): everything here is limb-wise, so "encrypt over the key ring, then drop the last limb" gives
+ * the words of never computing that limb.
+ * tfhe_encrypt (rlwe_she.jl:176-195):
+ *   pk  : [2][key_limbs][N], (mask, masked) as in the evaluation-key layout, NTT domain, natural order.
+ *   out : [batch][2][level][N], coefficient domain, canonical residues:
+ *           component 0 = masked u + e1 (+ msg),  component 1 = mask u + e2.
+ *   msg : NULL encrypts zero; else [batch][level][N], coefficient domain (tfhe_plain_encode / tfhe_ckks_encode output).
+ *   rand == NULL: the Gaussian stream of tfhe_sample_gaussian (Philox; counter convention): u_b is polynomial first_poly + b
+ *           with sigma_u and multiplier 1, e1_b is polynomial first_poly + batch + b and e2_b polynomial first_poly + 2 batch + b,
+ *           both with sigma_e and multiplier mult_e (1 for BFV / CKKS, t for BGV, bgv.jl:27-34) -- exactly the words of three
+ *           tfhe_sample_gaussian(.., stream, first_poly + k batch, .., batch) calls.  first_poly + 3 batch must not exceed 2^32.
+ *   rand != NULL: device int32 [batch][3][N] holding u, e1, e2 as signed integers (a host CSPRNG's draws); e is still
+ *           multiplied by mult_e; seed, stream, first_poly and the sigmas are ignored.
+ * tfhe_decrypt_phase (rlwe_she.jl:199-212): out = c1 + s c2 (+ s^2 c3).
+ *   secret : [key_limbs][N], NTT domain; its first `level` rows are used.
+ *   ct     : [batch][polys][level][N]; ntt_in = 0: coefficient domain, 1: NTT domain.  polys is 2 or 3, anything else is
+ *            TFHE_E_UNSUPPORTED.
+ *   out    : [batch][level][N], coefficient domain, canonical: the input of tfhe_plain_decode / tfhe_bfv_noise_max /
+ *            tfhe_ckks_decode.
+ * N = 2^12 .. 2^14 (tfhe_ctx_set_ntt_variant 0, level <= 32) runs as one fused kernel per arithmetic policy: per
+ * (ciphertext, limb) one message row read and two ciphertext rows written (encrypt), polys rows read and one written (decrypt);
+ * a ring that mixes 60-bit and fp64-size moduli runs its two launches side by side.  N < 2^12, N >= 2^15 and variant != 0 run
+ * the batched transforms on the packed layout with streaming kernels around them.  Same words on every path.
+ * Checks (host, before any device use, in this order): a null pk / secret / ct / out is TFHE_E_BADARG; negative batch
+ * TFHE_E_BADARG; level outside [1, key_limbs] or key_limbs above the context's TFHE_E_LEVEL_MISMATCH; counter overflow
+ * TFHE_E_BADARG; `out` overlapping pk, msg, rand, ct or secret as address ranges TFHE_E_BADARG; batch == 0 does nothing, but
+ * still needs a context. */
+int tfhe_encrypt(tfhe_ctx *ctx, int key_limbs, int level, const uint64_t *pk, double sigma_u, double sigma_e, uint64_t mult_e,
+                 uint64_t seed, uint32_t stream, uint64_t first_poly, const int32_t *rand, const uint64_t *msg, uint64_t *out, int64_t batch);
+int tfhe_decrypt_phase(tfhe_ctx *ctx, int key_limbs, int level, const uint64_t *secret, const uint64_t *ct, int polys, int ntt_in,
+                       uint64_t *out, int64_t batch);
+
 /* ---- BFV / BGV plaintext codecs on the device (π⁻¹ / π, bfv.jl:21-29, bgv.jl:21-25; noise, bfv.jl:137-166) ---------
  * plan = (ring = ctx limbs limb_idx, t).  t in [2, 2^62) and t < Q (Q = product of the selected moduli); limb_idx entries
  * in range and distinct; else TFHE_E_BADARG (checked on the host before any device use).  Exact: bit-identical to the

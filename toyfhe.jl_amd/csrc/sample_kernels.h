@@ -41,6 +41,12 @@ TFHE_HD long long sample_gauss_int(u64 idx, u32 stream, u64 seed, double sigma) 
     const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
     return (long long)rint(sigma * z);
 }
+// residue mod q of mult * e for a signed integer e (mq = mult mod q): the word the Gaussian sampler writes into a limb
+TFHE_HD u64 gauss_residue(long long e, u64 mq, const barrett_t& bt) {
+    const u64 mag = (u64)(e < 0 ? -e : e);
+    const u64 r = mulmod(barrett_reduce128(mag, 0, bt), mq, bt);
+    return e < 0 ? negmod(r, bt.q) : r;
+}
 
 #if defined(__HIPCC__)
 #include "ntt_core.h"
@@ -60,12 +66,9 @@ __global__ __launch_bounds__(256) void k_sample_gaussian(u64* __restrict__ out, 
     const u64 p = blockIdx.y;
     if (k >= n) return;
     const long long e = sample_gauss_int(((first_poly + p) << 32) | k, stream, seed, sigma);
-    const u64 mag = (u64)(e < 0 ? -e : e);
     for (int l = 0; l < level; l++) {
         const barrett_t& bt = LT[l].br;
-        u64 r = barrett_reduce128(mag, 0, bt);
-        r = mulmod(r, mult % bt.q, bt);
-        out[((size_t)p * level + l) * n + k] = e < 0 ? negmod(r, bt.q) : r;
+        out[((size_t)p * level + l) * n + k] = gauss_residue(e, mult % bt.q, bt);
     }
 }
 #endif

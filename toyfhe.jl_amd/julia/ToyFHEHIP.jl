@@ -13,7 +13,8 @@
 # type parameter of RingElement{ℛ,Field,Storage} (src/pow2_cyc_rings.jl:93-96).  `HipVector` is that
 # storage; the methods below override NTT.nntt / NTT.inntt, broadcast `+ - *`, `modswitch`, `modswitch_drop`,
 # `apply_galois_element`, `keyswitch`, CKKS encode / decode, BFV `enc_mul` and `rand(::HipRng, ::RingSampler)` for it.
-# Everything else in ToyFHE (keygen, encrypt, decrypt, π, π⁻¹, CipherText + -) is generic code over those and runs unchanged.
+# `encrypt(::HipRng, ::PubKey, .)` and `decrypt(::PrivKey, .)` of device-backed ciphertexts are one device call each (tfhe_encrypt /
+# tfhe_decrypt_phase).  Everything else in ToyFHE (keygen, π, π⁻¹, CipherText + -) is generic code over those and runs unchanged.
 #
 # BATCHES (north_star: "batches of independent ciphertexts").  A HipVector holds `count` polynomials, [count][limbs][N],
 # and every entry point of the C ABI takes that count, so a RingElement over a batched HipVector is `count` ring elements
@@ -696,6 +697,60 @@ function Random.rand(rng::HipRng, r::RingSampler{ℛ}) where {ℛ<:NegacyclicRin
     d isa Type && return sample_uniform(rng, NTT.ring(r))
     d isa ToyFHE.ShiftedDiscreteNormal && return sample_gaussian(rng, NTT.ring(r), Distributions.params(d.dn)[2], d.p)
     sample_gaussian(rng, NTT.ring(r), Distributions.params(d)[2])
+end
+
+# ---- encrypt / decrypt of a batch as ONE device call each (rlwe_she.jl:176-216; tfhe_encrypt / tfhe_decrypt_phase) -------------
+# With a HipRng the three draws of encrypt (u, then e1, then e2: rng.count polynomial counters each) are regenerated inside the
+# call from the same counters the generic code would have taken, so the ciphertext words and the generator state afterwards are
+# those of the generic path.  N = 2^12 .. 2^14 runs as one fused kernel per arithmetic policy (include/toyfhe_hip.h).
+# (σ, multiplier) of a Gaussian RingSampler -- DiscreteNormal, or ShiftedDiscreteNormal(p, .) for BGV (bgv.jl:27-34)
+function gauss_params(r::RingSampler)
+    d = r.coeff_distribution
+    d isa ToyFHE.ShiftedDiscreteNormal ? (Distributions.params(d.dn)[2], d.p) : (Distributions.params(d)[2], 1)
+end
+# public key: [mask, masked][Lk][N], NTT domain -- the layout of one evaluation-key digit, packed once per key
+function pack(pk::PubKey)
+    lock(KEY_LOCK) do
+        get!(PACKED_KEYS, pk) do
+            ℛk = NTT.ring(pk.key.mask)
+            pack(hipring(ℛk), HipVector[coeffs_dual(pk.key.mask).parent, coeffs_dual(pk.key.masked).parent], eltype(ℛk))
+        end
+    end
+end
+# msg: nothing (encrypt zero) or π⁻¹(params, plaintext) as an element of the ciphertext ring
+function encrypt_packed(rng::HipRng, pk::PubKey, msg)
+    params = pk.params; ℛk = NTT.ring(pk.key.mask); ℛ = ToyFHE.ℛ_cipher(params); T = eltype(ℛ)
+    σu = gauss_params(ToyFHE.𝒢(params))[1]; σe, mult = gauss_params(ToyFHE.𝒩(params))
+    ctx = hipring(ℛk); key = pack(pk); cnt = rng.count
+    m = msg === nothing ? nothing : coeffs_primal(msg).parent
+    m === nothing || m.count == cnt || throw(ToyFHE.UsageError("the plaintext batch differs from the generator's count"))
+    out = HipVector{T}(2 * nlimbs(T), degree(ℛ), cnt); on(ctx, (out,), m === nothing ? (key,) : (key, m))
+    GC.@preserve key m out check(ccall((:tfhe_encrypt, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Ptr{UInt64}, Cdouble, Cdouble, UInt64, UInt64, UInt32, UInt64, Ptr{Int32}, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, nlimbs(eltype(ℛk)), nlimbs(T), key.ptr, σu, σe, mult, rng.seed, 1, rng.next_poly, C_NULL,
+                m === nothing ? C_NULL : m.ptr, out.ptr, cnt))
+    rng.next_poly += 3 * cnt
+    unpack(ctx, out, ℛ, 2)
+end
+function ToyFHE.encrypt(rng::HipRng, pk::PubKey, ::ToyFHE.Zero)
+    CipherText{ToyFHE.Zero}(pk.params, encrypt_packed(rng, pk, nothing))
+end
+function ToyFHE.encrypt(rng::HipRng, pk::PubKey, plaintext)
+    EncT = typeof(plaintext)
+    EncT <: RingElement && (EncT = Any)                     # rlwe_she.jl:192-194
+    CipherText{EncT}(pk.params, encrypt_packed(rng, pk, ToyFHE.π⁻¹(pk.params, plaintext)))
+end
+# b = c1 + s c2 (+ s^2 c3): the first nlimbs(T) rows of the secret's NTT image are the image of the modswitch_drop'ped secret
+# (rlwe_she.jl:202-204); longer ciphertexts keep the generic loop
+function ToyFHE.decrypt(key::PrivKey, c::CipherText{E,P,<:RingElement{ℛ,T,<:HipVector}}) where {E,P,ℛ,T}
+    (length(c.cs) == 2 || length(c.cs) == 3) || return invoke(ToyFHE.decrypt, Tuple{PrivKey,CipherText}, key, c)
+    ℛk = NTT.ring(key.secret); ctx = hipring(ℛk); s = coeffs_dual(key.secret).parent
+    ct = pack(ctx, c); out = HipVector{T}(nlimbs(T), degree(ℛ), ct.count); on(ctx, (out,), (ct, s))
+    GC.@preserve s ct out check(ccall((:tfhe_decrypt_phase, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Ptr{UInt64}, Ptr{UInt64}, Cint, Cint, Ptr{UInt64}, Int64),
+                ctx.handle, nlimbs(eltype(ℛk)), nlimbs(T), s.ptr, ct.ptr, length(c.cs), 0, out.ptr, ct.count))
+    dec = ToyFHE.π(key.params, RingElement{ℛ}(OffsetArray(out, 0:degree(ℛ)-1), nothing))
+    E === Any ? dec : (E)(dec)
 end
 
 # ---- multi-GPU: one Julia process per GPU (Distributed / MPI.jl), batch sharded by ciphertext, final gather -------------

@@ -139,6 +139,8 @@ def lib():
         "tfhe_bfv_contract": [vp, vp, vp, i64],
         "tfhe_bfv_mul_relin": [vp, vp, i32, vp, vp, vp, i64],
         "tfhe_mul_relin": [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, i64],
+        "tfhe_encrypt": [vp, i32, i32, vp, C.c_double, C.c_double, u64, u64, C.c_uint32, u64, vp, vp, vp, i64],
+        "tfhe_decrypt_phase": [vp, i32, i32, vp, vp, i32, i32, vp, i64],
         "tfhe_plain_plan_create": [vp, i32p, i32, u64, C.POINTER(vp)],
         "tfhe_plain_plan_destroy": [vp],
         "tfhe_plain_encode": [vp, i32, vp, vp, i64],
@@ -165,7 +167,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
     "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
-    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
+    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
 ]
@@ -363,6 +365,18 @@ class Context:
         [batch][2][level][N], out [batch][2][level - rescale][N] coefficient domain; c1 == c2 squares"""
         check(lib().tfhe_mul_relin(self.h, key_limbs, level, int(bool(special)), evk, n_digits, c1, c2, int(bool(ntt_in)),
                                    int(bool(rescale)), out, batch))
+
+    def encrypt(self, key_limbs, level, pk, out, batch, msg=None, rand=None, sigma_u=0.0, sigma_e=0.0, mult_e=1, seed=0, stream=1, first_poly=0):
+        """public-key encryption of a batch in one call (tfhe_encrypt): pk [2][key_limbs][N] (mask, masked; NTT domain),
+        msg None or [batch][level][N], out [batch][2][level][N] coefficient domain.  rand None: u, e1, e2 are the polynomials
+        first_poly + b, + batch + b, + 2 batch + b of the Gaussian stream; else a device int32 [batch][3][N] buffer"""
+        check(lib().tfhe_encrypt(self.h, key_limbs, level, pk, float(sigma_u), float(sigma_e), int(mult_e), int(seed), int(stream),
+                                 int(first_poly), rand, msg, out, batch))
+
+    def decrypt_phase(self, key_limbs, level, secret, ct, polys, out, batch, ntt_in=False):
+        """c1 + s c2 (+ s^2 c3) of a batch in one call (tfhe_decrypt_phase): secret [key_limbs][N] NTT domain,
+        ct [batch][polys][level][N], out [batch][level][N] coefficient domain"""
+        check(lib().tfhe_decrypt_phase(self.h, key_limbs, level, secret, ct, polys, int(bool(ntt_in)), out, batch))
 
     def keyswitch_window(self, level, window_bits, evk, n_windows, ct, polys, out, batch, key_limbs=None, special=False):
         check(lib().tfhe_keyswitch_window(self.h, level if key_limbs is None else key_limbs, level, int(bool(special)), window_bits,

@@ -854,7 +854,72 @@ def keygen(rng, params) -> KeyPair:
     return KeyPair(PrivKey(params, secret), PubKey(params, KeyComponent(mask, masked)))
 
 
+# TFHE_FUSED_ENCRYPT=0: encrypt / decrypt as the reference's term-by-term expressions on ring elements (comparisons); the default
+# is one device call each (tfhe_encrypt / tfhe_decrypt_phase) -- the same residues, the same generator state afterwards.
+_FUSED_ENCRYPT = os.environ.get("TFHE_FUSED_ENCRYPT", "1") != "0"
+
+
+def _is_prefix(ring: NegacyclicRing) -> bool:
+    return ring.idx == list(range(ring.L))
+
+
+def _noise_multiplier(params):
+    """the multiplier of 𝒩 when the scheme draws 𝒢 and 𝒩 through the stock samplers (1; t for BGV, bgv.jl:27-34), else None"""
+    inner = params.params if isinstance(params, ModulusRaised) else params
+    if type(inner) in (BFVParams, CKKSParams):
+        return 1
+    return inner.t if type(inner) is BGVParams else None
+
+
+def _packed_pubkey(pub: PubKey, keyring: NegacyclicRing) -> DeviceBuffer:
+    """[2][L_key][N] (mask, masked), NTT domain: the layout of one evaluation-key digit, packed once per key"""
+    if getattr(pub, "_packed", None) is None:
+        pub._packed = _pack([pub.key.mask.coeffs_dual(), pub.key.masked.coeffs_dual()], keyring, 1)
+    return pub._packed
+
+
+def _encrypt_device(rng, pub: PubKey, batch, enc: RingElement | None, scale):
+    """encrypt_zero (+ the encoded message) as ONE device call, or None when this key / generator / message is not covered"""
+    params = pub.params
+    mult = _noise_multiplier(params)
+    keyring, ring = params.R_key(), params.R_cipher()
+    if not _FUSED_ENCRYPT or mult is None or not (isinstance(rng, (DeviceRng, np.random.Generator))):
+        return None
+    if not _is_prefix(keyring) or ring.ctx is not keyring.ctx or not _is_prefix(ring) or ring.L > keyring.L:
+        return None
+    if pub.key.mask.ring.ctx is not keyring.ctx or pub.key.mask.ring.idx != keyring.idx or pub.key.mask.batch is not None:
+        return None
+    if enc is not None and (enc.ring.ctx is not ring.ctx or enc.ring.idx != ring.idx or enc.batch != batch):
+        return None
+    n, N = (1 if batch is None else int(batch)), ring.N
+    ctx = keyring.ctx
+    pk = _packed_pubkey(pub, keyring)
+    msg = None if enc is None else enc.coeffs_primal()
+    out = DeviceBuffer(n * 2 * ring.L * N)
+    if isinstance(rng, DeviceRng):
+        # u, e1, e2: n counters each, in the order the three separate draws take them
+        ctx.encrypt(keyring.L, ring.L, pk.ptr, out.ptr, n, msg=None if msg is None else msg.ptr, sigma_u=params.sigma, sigma_e=params.sigma,
+                    mult_e=mult, seed=rng.seed, stream=1, first_poly=rng.take(3 * n))
+    else:
+        draws = [sample_normal_ints(rng, N, params.sigma, batch).reshape(n, N) for _ in range(3)]   # u, e1, e2 in today's order
+        ints = np.stack(draws, axis=1)
+        if np.abs(ints).max(initial=0) >= 2**31:
+            raise AssertionError("encrypt: a noise draw does not fit 32 bits")
+        rand = DeviceBuffer.from_numpy(np.ascontiguousarray(ints.astype(np.int32)).reshape(-1).view(np.uint64))
+        ctx.encrypt(keyring.L, ring.L, pk.ptr, out.ptr, n, msg=None if msg is None else msg.ptr, rand=rand.ptr, mult_e=mult)
+    # an ordinary ciphertext, as before: split into its components (one strided copy each), no packed image kept -- a fresh
+    # ciphertext is read component by component (serialisation, c + plain) at least as often as it goes to a key switch
+    return CipherText(params, _unpack(out, ring, n, 2, batch, primal=True, ctx=ctx), scale)
+
+
 def encrypt_zero(rng, pub: PubKey, batch=None) -> CipherText:
+    c = _encrypt_device(rng, pub, batch, None, None)
+    if c is not None:
+        return c
+    return _encrypt_zero_composed(rng, pub, batch)
+
+
+def _encrypt_zero_composed(rng, pub: PubKey, batch=None) -> CipherText:
     params = pub.params
     ring = params.R_key()
     u = params.secret_dist(rng, ring, batch)
@@ -878,14 +943,43 @@ def _broadcast(el: RingElement, batch: int) -> RingElement:
 def encrypt(rng, key, plaintext, scale=None) -> CipherText:
     pub = key.pub if isinstance(key, KeyPair) else key
     enc = pub.params.encode(plaintext)
-    c = encrypt_zero(rng, pub, enc.batch)
+    c = _encrypt_device(rng, pub, enc.batch, enc, scale) if isinstance(enc, RingElement) else None
+    if c is not None:
+        return c
+    c = _encrypt_zero_composed(rng, pub, enc.batch)
     c = c + enc  # rlwe_she.jl:190
     c.scale = scale
     return c
 
 
+def _decryption_device(secret: RingElement, c: CipherText):
+    """b = c_1 + s c_2 (+ s^2 c_3) as ONE device call (tfhe_decrypt_phase), or None when this ciphertext is not covered"""
+    P = len(c)
+    if not _FUSED_ENCRYPT or P not in (2, 3) or secret.batch is not None:
+        return None
+    ring, keyring = c.ring(), secret.ring
+    if not _is_prefix(keyring) or ring.ctx is not keyring.ctx or not _is_prefix(ring) or ring.L > keyring.L:
+        return None
+    if not 1 << 12 <= ring.N <= 1 << 14:
+        # outside the fused sizes the call's composed form measured SLOWER than the composition below (N = 2^16, reference ring:
+        # 0.61-0.72 x through the mirror, 0.79-0.95 x as a raw call; profiles/LOG.md): the composition stays
+        return None
+    n, batch = c._shape()
+    # decryption asks for the components, as before (an unsplit key-switch result is split here and keeps its packed image,
+    # which is then the call's operand: no second copy)
+    ntt_in = all(x.primal is None and x.dual is not None for x in c.cs)
+    bufs = [x.coeffs_dual() if ntt_in else x.coeffs_primal() for x in c.cs]
+    image = (None if ntt_in else c._packed_for(bufs, ring.ctx)) or _pack(bufs, ring, n)
+    out = DeviceBuffer(n * ring.L * ring.N)
+    ring.ctx.decrypt_phase(keyring.L, ring.L, secret.coeffs_dual().ptr, image.ptr, P, out.ptr, n, ntt_in=ntt_in)
+    return RingElement(ring, out, None, batch)
+
+
 def _decryption(key, c: CipherText):
     priv = key.priv if isinstance(key, KeyPair) else key
+    b = _decryption_device(priv.secret, c)
+    if b is not None:
+        return priv, b
     secret = priv.secret
     while secret.ring.L != c[0].ring.L:  # rlwe_she.jl:202-204
         secret = secret.modswitch_drop()
@@ -923,14 +1017,7 @@ def invariant_noise_budget(key, c: CipherText):
     params = priv.params
     if not isinstance(params, BFVParams):
         raise NotImplementedError("invariant_noise_budget: BFV ciphertexts")
-    secret = priv.secret
-    if c[0].batch is not None:
-        secret = _broadcast(secret, c[0].batch)
-    b, spow = c[0], secret
-    for i in range(1, len(c)):
-        b = b + spow * c[i]
-        if i + 1 < len(c):
-            spow = spow * secret
+    _, b = _decryption(priv, c)                            # (the secret and the ciphertext share params.ring: nothing is dropped)
     delta = params.delta
     plan = _plain_plan(params, b.ring) if params._device_ring(b) else None
     if plan is not None:
