@@ -88,6 +88,7 @@ TFHE_HD double ckks_words_to_double(const u64* w, int nwords, bool neg, u64 sman
     }
     // 64 -> 53 bits, round to nearest even with the sticky bit
     double d;
+    int e2 = 0;  // d * 2^e2 is the rounded magnitude
     if (sh <= 0 && bitlen <= 53) d = (double)hi64;
     else {
         const int drop = (sh <= 0 ? bitlen : 64) - 53;  // low bits of hi64 to drop
@@ -95,9 +96,11 @@ TFHE_HD double ckks_words_to_double(const u64* w, int nwords, bool neg, u64 sman
         const u64 rem = hi64 & ((1ull << drop) - 1), halfv = 1ull << (drop - 1);
         if (rem > halfv || (rem == halfv && (sticky || (keep & 1ull)))) keep += 1;
         d = (double)keep;  // exact (<= 2^53)
-        d = __builtin_ldexp(d, drop + (sh > 0 ? sh : 0));
+        e2 = drop + (sh > 0 ? sh : 0);
     }
-    d = __builtin_ldexp(d, -sexp);
+    // the division first and then one scaling by 2^(e2 - sexp) (the same bits: scaling by a power of two is exact): a magnitude
+    // of more than 1024 bits (17 limbs of 61 bits and up) is no double by itself, its quotient by the scale may well be
     if (smant != 1) d = d / (double)smant;
+    d = __builtin_ldexp(d, e2 - sexp);
     return neg ? -d : d;
 }

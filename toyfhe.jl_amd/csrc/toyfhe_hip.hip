@@ -284,7 +284,8 @@ void special_inv_table(const tfhe_ctx* c, int Lk, int level, tw_t* out) {
 }
 
 // Per-limb routing masks are 32 bits wide (ntt_io_t::limb_mask, the key-switch kernels' limb_mask); TFHE_MAX_LIMBS is 40
-// and a special prime makes 41 working limbs, so rings with more than 32 selected limbs cannot be split by policy: they
+// and the special prime is one of the key's at most 40 limbs (ks_check: level <= Lk - 1 with it), so a key switch has at most
+// 40 working limbs -- limb_sel_t::idx holds them all -- and rings with more than 32 selected limbs cannot be split by policy: they
 // run whole on the policy that takes every limb (all fp64-size / all narrow: the fast kernels unmasked; otherwise the
 // u64 / generic kernels unmasked).
 static inline u32 mask_all(int n) { return n >= 32 ? ~0u : ((1u << n) - 1u); }
