@@ -82,6 +82,9 @@ int tfhe_ctx_wait_for(tfhe_ctx *ctx, tfhe_ctx *producer);
  * BFV core / key-switch kernels, no next-row overlap (LDS-DMA staging in the inverse, register prefetch in the
  * forward), no read-once digit lift -- 1, 2 and 3 are cross-check paths for tests */
 int tfhe_ctx_set_ntt_variant(tfhe_ctx *ctx, int variant);
+/* upper bound on the ciphertexts (polynomials, for the samplers and codecs) per internal chunk of every chunked entry point
+ * driven through this context; 0 = default.  Same words for every value -- a cross-check knob for tests. */
+int tfhe_ctx_set_chunk(tfhe_ctx *ctx, int chunk);
 
 /* ---- device memory helpers (for callers without a GPU array package) -------------------------
  * tfhe_malloc / tfhe_free are a size-bucketed recycling allocator (csrc/dev_alloc.h): the reference allocates a fresh array

@@ -78,3 +78,6 @@ def test_argument_validation_precedes_device_use():
         tf.Context(64, [97])                       # 2N does not divide q-1
     with pytest.raises(AssertionError):
         tf.Context(4, [97, 97])                    # repeated modulus
+    lib = tf.native.lib()
+    assert lib.tfhe_ctx_set_chunk(None, 8) == tf.native.E_BADARG and b"null context" in lib.tfhe_last_error()
+    assert lib.tfhe_ctx_set_chunk(None, -1) == tf.native.E_BADARG and b"chunk cap" in lib.tfhe_last_error()   # the sign first

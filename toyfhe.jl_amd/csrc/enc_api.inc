@@ -91,8 +91,9 @@ extern "C" int tfhe_encrypt(tfhe_ctx* c, int key_limbs, int level, const uint64_
     if (enc_fused_ok(c, level)) {
         const policy_split_t ps = policy_split(c, sel);
         const u32 fp_mask = ps.fpmask, int_mask = ps.all & ~ps.fpmask;
-        for (int64_t b0 = 0; b0 < batch; b0 += ENC_CHUNK) {
-            const int64_t nct = std::min<int64_t>(ENC_CHUNK, batch - b0);
+        const int64_t chunk = chunk_of(c, batch, ENC_CHUNK);
+        for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+            const int64_t nct = std::min(chunk, batch - b0);
             R.b0 = (u64)b0;
             // the two policies side by side over disjoint limb rows; the u64 launch (the long pole) first, on the main lane
             lanes_t lanes(c, fp_mask != 0 && int_mask != 0);
@@ -109,7 +110,7 @@ extern "C" int tfhe_encrypt(tfhe_ctx* c, int key_limbs, int level, const uint64_
     const u32 logn = (u32)c->logN, n = (u32)N;
     const size_t row = (size_t)level * N;   // words of one polynomial
     const size_t scratch_rows = c->logN > 14 ? 2 : 0;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)4096, (int64_t)((2048ull << 20) / ((scratch_rows + 4) * row * 8))}));
+    const int64_t chunk = chunk_of(c, batch, 4096, (size_t)2048 << 20, (scratch_rows + 4) * row * 8);
     void* ws = nullptr;
     int rc = ensure_ws(c, (size_t)chunk * (scratch_rows + 4) * row * 8, &ws);   // once, before any lane fork of the transforms
     if (rc) return rc;
@@ -161,8 +162,9 @@ extern "C" int tfhe_decrypt_phase(tfhe_ctx* c, int key_limbs, int level, const u
     if (enc_fused_ok(c, level) && !(c->logN == 14 && polys == 3 && ntt_in)) {
         const policy_split_t ps = policy_split(c, sel);
         const u32 fp_mask = ps.fpmask, int_mask = ps.all & ~ps.fpmask;
-        for (int64_t b0 = 0; b0 < batch; b0 += ENC_CHUNK) {
-            const int64_t nct = std::min<int64_t>(ENC_CHUNK, batch - b0);
+        const int64_t chunk = chunk_of(c, batch, ENC_CHUNK);
+        for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+            const int64_t nct = std::min(chunk, batch - b0);
             lanes_t lanes(c, fp_mask != 0 && int_mask != 0);
             lanes.use(0);
             int rc = dec_launch_fused<ArithInt>(c, int_mask, level, secret, ct, polys, ntt_in != 0, out, nct, (u64)b0);
@@ -177,7 +179,7 @@ extern "C" int tfhe_decrypt_phase(tfhe_ctx* c, int key_limbs, int level, const u
     const u32 logn = (u32)c->logN, n = (u32)N;
     const size_t row = (size_t)level * N;
     const size_t scratch_rows = c->logN > 14 ? (size_t)polys : 0, f_rows = ntt_in ? 0 : (size_t)polys;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)4096, (int64_t)((2048ull << 20) / ((scratch_rows + f_rows + 1) * row * 8))}));
+    const int64_t chunk = chunk_of(c, batch, 4096, (size_t)2048 << 20, (scratch_rows + f_rows + 1) * row * 8);
     void* ws = nullptr;
     int rc = ensure_ws(c, (size_t)chunk * (scratch_rows + f_rows + 1) * row * 8, &ws);
     if (rc) return rc;

@@ -22,7 +22,7 @@ size_t mr_ks_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t ba
     const bool f14 = ks_fused14(c, Lk, level, special);
     const size_t dig_rows = f14 ? (size_t)2 * nw : (size_t)level * nw;
     const size_t per_ct = ((size_t)2 * nw + dig_rows) * N * 8;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)512, (int64_t)((8192ull << 20) / per_ct)}));
+    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
     const size_t ntt_tmp = (c->logN > 14 && !f14) ? (size_t)chunk * std::max(2, level) * nw * N * 8 : 0;
     const size_t evd_bytes = f14 ? (size_t)level * 2 * nw * N * 8 : 0;
     return ntt_tmp + (size_t)chunk * per_ct + evd_bytes;
@@ -147,7 +147,7 @@ extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const
     // modswitch follows)
     const size_t f_rows = (fused || ntt_in) ? 0 : (square ? 2 : 4), r_rows = rescale ? 2 : 0;
     const size_t per_ct = (f_rows + 3 + r_rows) * level * N * 8;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)256, (int64_t)((4096ull << 20) / per_ct)}));
+    const int64_t chunk = chunk_of(c, batch, 256, (size_t)4096 << 20, per_ct);
     const size_t park = mr_park_rows(c) * N;   // words, per core
     size_t region0 = mr_ks_bytes(c, Lk, level, special, chunk);
     if (c->logN > 14) region0 = std::max(region0, (size_t)chunk * 3 * level * N * 8);   // run_ntt's scratch for N > 2^14

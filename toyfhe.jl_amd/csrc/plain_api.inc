@@ -205,8 +205,9 @@ int tfhe_plain_encode(tfhe_plain_plan* p, int scheme, const uint64_t* m, uint64_
     const u32 n = (u32)p->ctx->N;
     const int L = p->sel.n;
     const unsigned gx = (n + PLAIN_BS - 1) / PLAIN_BS;
-    for (int64_t b0 = 0; b0 < count; b0 += PLAIN_MAX_GRID_Y) {
-        const int64_t nb = std::min<int64_t>(PLAIN_MAX_GRID_Y, count - b0);
+    const int64_t chunk = chunk_of(p->ctx, count, PLAIN_MAX_GRID_Y);
+    for (int64_t b0 = 0; b0 < count; b0 += chunk) {
+        const int64_t nb = std::min(chunk, count - b0);
         rc = launch(p->ctx, k_plain_encode, dim3(gx, (unsigned)nb), dim3(PLAIN_BS), 0, m + (size_t)b0 * n, out + (size_t)b0 * L * n, p->tab_dev,
                     scheme == TFHE_PLAIN_BGV ? 1 : 0, n);
         if (rc) return rc;
@@ -220,8 +221,9 @@ int tfhe_plain_decode(tfhe_plain_plan* p, int scheme, const uint64_t* in, uint64
     const u32 n = (u32)p->ctx->N;
     const int L = p->sel.n;
     const unsigned gx = (n + PLAIN_BS - 1) / PLAIN_BS;
-    for (int64_t b0 = 0; b0 < count; b0 += PLAIN_MAX_GRID_Y) {
-        const int64_t nb = std::min<int64_t>(PLAIN_MAX_GRID_Y, count - b0);
+    const int64_t chunk = chunk_of(p->ctx, count, PLAIN_MAX_GRID_Y);
+    for (int64_t b0 = 0; b0 < count; b0 += chunk) {
+        const int64_t nb = std::min(chunk, count - b0);
         const dim3 grid(gx, (unsigned)nb);
         const u64* src = in + (size_t)b0 * L * n;
         u64* dst = out + (size_t)b0 * n;
@@ -241,7 +243,7 @@ int tfhe_bfv_noise_max(tfhe_plain_plan* p, const uint64_t* in, uint64_t* out_wor
     const unsigned gx = (n + PLAIN_BS - 1) / PLAIN_BS;
     const u32 G = gx * PLAIN_WAVES;
     const size_t part_per_ct = (size_t)G * nd * 8;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({count, (int64_t)PLAIN_MAX_GRID_Y, (int64_t)((64ull << 20) / part_per_ct)}));
+    const int64_t chunk = chunk_of(p->ctx, count, PLAIN_MAX_GRID_Y, (size_t)64 << 20, part_per_ct);
     void* ws = nullptr;
     rc = ensure_ws(p->ctx, (size_t)chunk * part_per_ct, &ws);
     if (rc) return rc;

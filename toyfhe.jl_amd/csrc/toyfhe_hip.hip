@@ -87,6 +87,7 @@ struct tfhe_ctx {
     int lane_depth = 0;                  // > 0: inside a forked region (nested lanes_t objects only switch streams)
     bool lanes_broken = false;           // creating the second stream failed once: stay serial
     int variant = 0;
+    int chunk_cap = 0;                   // tfhe_ctx_set_chunk: bound on every internal chunk (0 = the defaults)
     // workspace (grown on demand, reused)
     void* ws = nullptr;
     size_t ws_bytes = 0;
@@ -137,6 +138,16 @@ int ensure_ws(tfhe_ctx* c, size_t bytes, void** out, bool pooled = false) {
     }
     *out = c->ws;
     return TFHE_OK;
+}
+// The ciphertexts (polynomials, for the samplers and codecs) one iteration of a chunked entry point takes: the whole batch, at
+// most `dflt` of it, at most what `bytes_cap` holds at `per_ct` bytes each (per_ct = 0: no such bound), at most the context's
+// cap (tfhe_ctx_set_chunk), at least one.  EVERY chunked entry point sizes its chunk here: a site that sizes a workspace for
+// another (mr_ks_bytes for keyswitch_impl) then agrees with it by construction.
+int64_t chunk_of(const tfhe_ctx* c, int64_t batch, int64_t dflt, size_t bytes_cap = 0, size_t per_ct = 0) {
+    int64_t m = std::min(batch, dflt);
+    if (per_ct) m = std::min(m, (int64_t)(bytes_cap / per_ct));
+    if (c->chunk_cap) m = std::min(m, (int64_t)c->chunk_cap);
+    return std::max<int64_t>(1, m);
 }
 // A pooled workspace lives for ONE call: the context's own (long-lived, small) workspace is set aside while the call runs --
 // the transforms inside it take their scratch from c->ws -- and comes back untouched when the call returns; the pooled block
@@ -691,6 +702,12 @@ int tfhe_ctx_wait_for(tfhe_ctx* c, tfhe_ctx* producer) {
 int tfhe_ctx_set_ntt_variant(tfhe_ctx* c, int v) {
     if (!c || v < 0 || v > 3) return fail(TFHE_E_BADARG, "variant must be 0, 1, 2 or 3");
     c->variant = v;
+    return TFHE_OK;
+}
+int tfhe_ctx_set_chunk(tfhe_ctx* c, int chunk) {
+    if (chunk < 0) return fail(TFHE_E_BADARG, "chunk cap must be >= 0 (0 = default), got %d", chunk);
+    if (!c) return fail(TFHE_E_BADARG, "null context");
+    c->chunk_cap = chunk;
     return TFHE_OK;
 }
 
@@ -1418,7 +1435,7 @@ static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64
     // launch (cfg#3, 512 ciphertexts: 248 + 248 + 16 before -- the 16 ran as two nearly empty item rounds of k_ks_fused_sub)
     const size_t dig_rows = f14 ? (size_t)2 * nw : (size_t)level * nw;
     const size_t per_ct = ((size_t)2 * nw + dig_rows + (rotate ? (size_t)polys * level : 0)) * N * 8;
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)512, (int64_t)((8192ull << 20) / per_ct)}));
+    int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
     void* ws = nullptr;
     // NTT of N > 2^14 uses the context workspace as well: keep ours separate by over-allocating (the fused paths run no
     // stand-alone transform)
@@ -1506,7 +1523,7 @@ int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
     const ks_arg_t A = make_ks_arg(Lk, level, special, polys);
     // workspace per ciphertext: S (2 nw rows) + digits (level nw) + T (2 nw) + rotated input (2 level); + one prepared key
     const size_t per_ct = ((size_t)4 * nw + (size_t)level * nw + (size_t)polys * level) * N * 8;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)512, (int64_t)((8192ull << 20) / per_ct)}));
+    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
     const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * std::max(2, level) * nw * N * 8 : 0;
     const size_t key_bytes = prepared ? 0 : (size_t)n_digits * 2 * Lk * N * 8;
     void* ws = nullptr;
@@ -1633,7 +1650,7 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
             ws_cap = std::min(ws_cap, std::max<size_t>((fr + c->ws_bytes + cached) / 2, (size_t)1 << 30));
         }
     }
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)512, (int64_t)(ws_cap / per_ct)}));
+    int64_t chunk = chunk_of(c, batch, 512, ws_cap, per_ct);
     size_t ntt_tmp = 0;
     void* ws = nullptr;
     int rc;
@@ -1763,7 +1780,7 @@ int tfhe_keyswitch_window(tfhe_ctx* c, int key_limbs, int level, int special, in
     const u32 n = (u32)c->N;
     const int nw = special ? level + 1 : level;  // working limbs: [0 .. level-1] (+ the special prime, downswitch_keyelement modulusraising.jl:43-49)
     const size_t per_ct = ((size_t)2 * nw + (size_t)need * nw) * N * 8;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({batch, (int64_t)512, (int64_t)((8192ull << 20) / per_ct)}));
+    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
     const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * need * nw * N * 8 : 0;
     void* ws = nullptr;
     rc = ensure_ws(c, ntt_tmp + chunk * per_ct, &ws);
@@ -1875,7 +1892,7 @@ int tfhe_ckks_encode(tfhe_ctx* c, int level, uint64_t scale_mant, int scale_exp2
     if (rc) return rc;
     const u32 n = (u32)c->N;
     const limb_sel_t sel = first_limbs(level);
-    const int64_t chunk = std::min<int64_t>(batch, 4096);
+    const int64_t chunk = chunk_of(c, batch, 4096);
     void* ws = nullptr;
     rc = ensure_ws(c, (size_t)chunk * n * 16, &ws);
     if (rc) return rc;
@@ -1903,7 +1920,7 @@ int tfhe_ckks_decode(tfhe_ctx* c, int level, uint64_t scale_mant, int scale_exp2
     rc = ksw_table(c, level, &T);
     if (rc) return rc;
     const u32 n = (u32)c->N;
-    const int64_t chunk = std::min<int64_t>(batch, 4096);
+    const int64_t chunk = chunk_of(c, batch, 4096);
     void* ws = nullptr;
     rc = ensure_ws(c, (size_t)chunk * n * 16, &ws);
     if (rc) return rc;
@@ -1929,8 +1946,9 @@ int tfhe_sample_uniform(tfhe_ctx* c, int level, uint64_t seed, uint32_t stream, 
     if (count < 0) return fail(TFHE_E_BADARG, "negative count");
     if (first_poly + (u64)count > (1ull << 32)) return fail(TFHE_E_BADARG, "polynomial counter exceeds 2^32");
     const u32 n = (u32)c->N;
-    for (int64_t p0 = 0; p0 < count; p0 += 32768) {
-        const unsigned np = (unsigned)std::min<int64_t>(32768, count - p0);
+    const int64_t chunk = chunk_of(c, count, 32768);   // polynomials per launch (grid dimension z / y)
+    for (int64_t p0 = 0; p0 < count; p0 += chunk) {
+        const unsigned np = (unsigned)std::min<int64_t>(chunk, count - p0);
         const int rc = launch(c, k_sample_uniform, dim3((n + 255) / 256, (unsigned)level, np), dim3(256), 0, out + (size_t)p0 * level * n,
                               c->limbs_dev, level, seed, stream, n, first_poly + (u64)p0);
         if (rc) return rc;
@@ -1945,8 +1963,9 @@ int tfhe_sample_gaussian(tfhe_ctx* c, int level, double sigma, uint64_t multipli
     if (count < 0) return fail(TFHE_E_BADARG, "negative count");
     if (first_poly + (u64)count > (1ull << 32)) return fail(TFHE_E_BADARG, "polynomial counter exceeds 2^32");
     const u32 n = (u32)c->N;
-    for (int64_t p0 = 0; p0 < count; p0 += 32768) {
-        const unsigned np = (unsigned)std::min<int64_t>(32768, count - p0);
+    const int64_t chunk = chunk_of(c, count, 32768);   // polynomials per launch (grid dimension z / y)
+    for (int64_t p0 = 0; p0 < count; p0 += chunk) {
+        const unsigned np = (unsigned)std::min<int64_t>(chunk, count - p0);
         const int rc = launch(c, k_sample_gaussian, dim3((n + 255) / 256, np), dim3(256), 0, out + (size_t)p0 * level * n, c->limbs_dev,
                               level, sigma, multiplier, seed, stream, n, first_poly + (u64)p0);
         if (rc) return rc;
