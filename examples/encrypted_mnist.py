@@ -159,7 +159,7 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
     kp = tf.keygen(rng, params)
     ek = tf.keygen_evalmult(rng, kp.priv)
     if hoisted:
-        gk = [tf.keygen_galois(rng, kp.priv, steps=k * B) for k in range(1, 64)]
+        gk = tf.keygen_galois_many(rng, kp.priv, steps=[k * B for k in range(1, 64)])   # one device call for the 63 keys
     else:
         gk = tf.keygen_galois(rng, kp.priv, steps=B)               # infer.jl:134 (steps = 64 there)
     scale = 2**40

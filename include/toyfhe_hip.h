@@ -306,6 +306,46 @@ int tfhe_encrypt(tfhe_ctx *ctx, int key_limbs, int level, const uint64_t *pk, do
 int tfhe_decrypt_phase(tfhe_ctx *ctx, int key_limbs, int level, const uint64_t *secret, const uint64_t *ct, int polys, int ntt_in,
                        uint64_t *out, int64_t batch);
 
+/* ---- key generation: public, relinearisation and Galois keys of a parameter set, one call (rlwe_she.jl:155-166, 273-304) ----
+ * The key ring is limbs 0..key_limbs-1 of ctx.  Component m = k n_digits + i (key k < n_keys, digit i < n_digits) has at limb j
+ *     evks[k][i][0][j] = NTT_j(a_m)                                                         (mask)
+ *     evks[k][i][1][j] = gadget[i][j] old_k[j] - ( NTT_j(a_m) secret[j] + NTT_j(mult_e e_m) )   (masked)
+ *   evks   : HOST array of n_keys device pointers, each [n_digits][2][key_limbs][N], NTT domain, natural order, canonical
+ *            residues: the layout tfhe_keyswitch, tfhe_keyswitch_window, tfhe_galois_key_prepare and (n_digits = 1) tfhe_encrypt's pk
+ *            consume.  Every word is written exactly once.
+ *   secret : device [key_limbs][N], NTT domain.
+ *   gadget : HOST [n_digits][key_limbs] canonical residues (a residue >= q_j is TFHE_E_BADARG).  RNS digits (rlwe_she.jl:287,
+ *            crt.jl:64-77): gadget[i][j] = (i == j); ModulusRaised (modulusraising.jl:28-32): (i == j) P mod q_j, the row and the
+ *            column of the special prime P zero; relin_window = w: (2^(i w) mod Q) mod q_j, under ModulusRaised P 2^(i w) mod Q P.
+ *            Where gadget[i][j] == 0 the old term is skipped.  gadget == NULL: all zero, the PUBLIC-KEY form -(a s + e)
+ *            (rlwe_she.jl:155-166); old and galois_elements are then ignored.
+ *   old    : device [n_keys][key_limbs][N], NTT domain: row k is old_k.  old == NULL: galois_elements (HOST [n_keys]) names it:
+ *            0 is secret . secret (the relinearisation key, rlwe_she.jl:299), an odd g < 2N is secret under x -> x^g (a Galois key,
+ *            rlwe_she.jl:301-304; an index permutation of the NTT-domain row); any other value is TFHE_E_BADARG.
+ *   mask_rand == noise_rand == NULL: a_m is polynomial mask_poly + m poly_stride of tfhe_sample_uniform's stream stream_mask over
+ *            key_limbs limbs, e_m polynomial noise_poly + m poly_stride of tfhe_sample_gaussian's stream stream_noise with sigma_e
+ *            and multiplier mult_e (1 for BFV / CKKS, t for BGV) -- exactly the words 2 n_keys n_digits sampler calls of count 1
+ *            would have written, regenerated inside the kernels.  No counter may reach 2^32: mask_poly + (n_keys n_digits - 1)
+ *            poly_stride < 2^32 and the same for noise_poly.  key_limbs <= 256 (the limb byte of the uniform counter).
+ *   both non-NULL: a host CSPRNG's draws.  mask_rand device [n_keys][n_digits][key_limbs][N] canonical residues, coefficient
+ *            domain; noise_rand device int32 [n_keys][n_digits][N] signed integers, still multiplied by mult_e; seed, the streams,
+ *            the counters and sigma_e are ignored.  Exactly one of the two NULL is TFHE_E_BADARG.
+ * N = 2^12 .. 2^14 (tfhe_ctx_set_ntt_variant 0, key_limbs <= 32) runs as one fused kernel per arithmetic policy: per (component,
+ * limb) one secret row read and two key rows written; a ring that mixes 60-bit and fp64-size moduli runs its two launches side by
+ * side.  Every other size fills rows 0 and 1 of the output itself, transforms them in place and finishes row 1.  Same words on
+ * every path, and for every tfhe_ctx_set_chunk (the chunk counts components (k, i)).
+ * Checks (host, before any device use, in this order): a null secret / evks is TFHE_E_BADARG; n_keys < 0 or n_digits < 1
+ * TFHE_E_BADARG; key_limbs < 1 TFHE_E_LEVEL_MISMATCH; exactly one of mask_rand / noise_rand TFHE_E_BADARG; with device randomness
+ * sigma_e out of range, a counter reaching 2^32 and key_limbs > 256 TFHE_E_BADARG; a null galois_elements where it is needed or a
+ * null evks[k] TFHE_E_BADARG; an output starting where secret, old, mask_rand, noise_rand or another output starts TFHE_E_BADARG;
+ * a null context TFHE_E_BADARG; key_limbs above the context's limbs TFHE_E_LEVEL_MISMATCH; a Galois element that is neither 0 nor
+ * odd and below 2N, then a gadget residue out of range, TFHE_E_BADARG; any output overlapping secret, old, mask_rand, noise_rand or
+ * another output as address ranges TFHE_E_BADARG; n_keys == 0 does nothing, but still needs a context. */
+int tfhe_evalkey_gen(tfhe_ctx *ctx, int key_limbs, const uint64_t *secret, const uint64_t *old, const uint64_t *galois_elements,
+                     int n_keys, const uint64_t *gadget, int n_digits, double sigma_e, uint64_t mult_e, uint64_t seed,
+                     uint32_t stream_mask, uint32_t stream_noise, uint64_t mask_poly, uint64_t noise_poly, uint64_t poly_stride,
+                     const uint64_t *mask_rand, const int32_t *noise_rand, uint64_t *const *evks);
+
 /* ---- BFV / BGV plaintext codecs on the device (π⁻¹ / π, bfv.jl:21-29, bgv.jl:21-25; noise, bfv.jl:137-166) ---------
  * plan = (ring = ctx limbs limb_idx, t).  t in [2, 2^62) and t < Q (Q = product of the selected moduli); limb_idx entries
  * in range and distinct; else TFHE_E_BADARG (checked on the host before any device use).  Exact: bit-identical to the

@@ -37,7 +37,7 @@ for seed in range(S0, S0 + 100000):
         c = tf.encrypt(rng, kp, tf.ckks_encode(rs.normal(0, 1, shape).astype(complex), params.R_cipher(), scale), scale=scale)
         if L > 1 and rs.integers(0, 2):
             c = tf.modswitch(c)                           # a lower level of the same keys
-        gks = [tf.keygen_galois(rng, kp.priv, steps=int(k)) for k in rs.choice(np.arange(1, N // 2), n_rot, replace=False)]
+        gks = tf.keygen_galois_many(rng, kp.priv, steps=[int(k) for k in rs.choice(np.arange(1, N // 2), n_rot, replace=False)])
         dv = rs.normal(0, 1, (n_rot + 1, N // 2)).astype(complex)
         singles = [tf.ckks_encode(dv[k], c.ring(), scale) for k in range(n_rot + 1)]
         want = tf.CipherText.dot_plain([c] + list(tf.rotate_many(gks, c)), [d if batch is None else d.broadcast_to(batch) for d in singles])

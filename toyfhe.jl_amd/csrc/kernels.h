@@ -1427,9 +1427,7 @@ __global__ __launch_bounds__(T) void k_galois_lds(const u64* __restrict__ src, u
 // ------------------------------------------------------------------------------------------------
 // keyswitch pieces (rlwe_she.jl:315-347, modulusraising.jl:35-49)
 // ------------------------------------------------------------------------------------------------
-// NTT-domain action of the Galois automorphism x -> x^g (pow2_cyc_rings.jl:321-329) in the library's natural order
-// a^[k] = a(psi^(2k+1)):  (sigma_g a)^[k] = a(psi^(g (2k+1))) = a^[k'] with 2k' + 1 = g (2k+1) mod 2N -- a pure permutation.
-TFHE_HD u32 galois_ntt_pos(u32 k, u64 g, u32 n) { return (u32)(((g * (2ull * k + 1ull)) - 1ull) >> 1) & (n - 1u); }
+// (galois_ntt_pos, the NTT-domain action of the Galois automorphism, lives in modarith.h: host code shares it)
 
 // dst[row][m] = src[row][pi_g(m)]: the automorphism applied to NTT-domain rows (key preparation of the hoisted rotations)
 __global__ __launch_bounds__(256) void k_ntt_perm(const u64* __restrict__ src, u64* __restrict__ dst, u64 g, u32 n) {

@@ -190,3 +190,7 @@ TFHE_HD u32 brev_bits(u32 x, int bits) {
     return r;
 #endif
 }
+
+// NTT-domain action of the Galois automorphism x -> x^g (pow2_cyc_rings.jl:321-329) in the library's natural order
+// a^[k] = a(psi^(2k+1)):  (sigma_g a)^[k] = a(psi^(g (2k+1))) = a^[k'] with 2k' + 1 = g (2k+1) mod 2N -- a pure permutation.
+TFHE_HD u32 galois_ntt_pos(u32 k, u64 g, u32 n) { return (u32)(((g * (2ull * k + 1ull)) - 1ull) >> 1) & (n - 1u); }

@@ -24,6 +24,7 @@
 #include "ckks_kernels.h"
 #include "sample_kernels.h"
 #include "enc_core.h"
+#include "keygen_core.h"
 #include "ntt_tables.h"
 #include "dev_alloc.h"
 
@@ -2024,6 +2025,7 @@ int tfhe_event_elapsed_ms(void* a, void* b, float* ms) {
 #include "plain_api.inc"
 #include "mul_api.inc"
 #include "enc_api.inc"
+#include "keygen_api.inc"
 
 #ifdef TFHE_KS_TRACE
 extern "C" int tfhe_debug_kstrace(unsigned long long* out, unsigned* n, int reset) {

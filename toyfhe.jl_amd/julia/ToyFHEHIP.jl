@@ -753,6 +753,72 @@ function ToyFHE.decrypt(key::PrivKey, c::CipherText{E,P,<:RingElement{ℛ,T,<:Hi
     E === Any ? dec : (E)(dec)
 end
 
+# ---- key generation as ONE device call (rlwe_she.jl:155-166, 273-298; modulusraising.jl:28-32; tfhe_evalkey_gen) ----------------
+# With a HipRng the draws of keygen (mask, secret, error) and of make_eval_key (per digit: mask, then error) are regenerated inside
+# the call from the counters the generic code would have taken: the key words and the generator state afterwards are those of
+# the generic path.  The gadget is a host table of residues γ[j, i] (limb j fastest: the C layout [n_digits][key_limbs]):
+# (i == j) for the CRT basis decomposition (rlwe_she.jl:287), 2^(i w) mod Q for relin_window = w (:281-283), both times the special
+# prime under ModulusRaised (modulusraising.jl:28-32).  The packed buffer the call wrote is registered as the key's packed form.
+function gadget_table(params, q::Vector{UInt64})
+    L = length(q); P = params isa ModulusRaised ? big(q[L]) : big(1); w = ToyFHE.relin_window(params)
+    if w != 0
+        Q = Base.prod(big.(q)); nwin = ndigits(Q, base=big(2)^w)
+        return UInt64[Base.mod(P * Base.powermod(big(2), i * w, Q), qj) for qj in q, i in 0:nwin-1]
+    end
+    UInt64[i == j ? Base.mod(P, q[j]) : 0 for j in 1:L, i in 1:L]
+end
+# one key: `o` the NTT image of old (or nothing), γ the gadget table (or nothing: the public-key form), out [nd][2][limbs][N]
+function evalkey_call(ctx::HipRing, limbs, s::HipVector, o, γ, nd, σe, mult, seed, mask_poly, noise_poly, stride, out::HipVector)
+    outs = Ptr{UInt64}[out.ptr]
+    GC.@preserve s o out outs γ check(ccall((:tfhe_evalkey_gen, lib), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Cint, Ptr{UInt64}, Cint, Cdouble, UInt64, UInt64, UInt32, UInt32, UInt64, UInt64, UInt64, Ptr{UInt64}, Ptr{Int32}, Ptr{Ptr{UInt64}}),
+                ctx.handle, limbs, s.ptr, o === nothing ? C_NULL : o.ptr, C_NULL, 1, γ === nothing ? C_NULL : γ, nd, σe, mult, seed, 0, 1,
+                mask_poly, noise_poly, stride, C_NULL, C_NULL, outs))
+    out
+end
+# `generic`: the signature of the reference's method, which takes over where the call does not apply (a generator that draws
+# several polynomials per sample, a batched `old` or secret: the call writes ONE key and advances the counter by 2 per digit)
+function evalkey_device(rng::HipRng, old::RingElement{ℛ,T}, new::PrivKey, generic) where {ℛ,T}
+    (rng.count == 1 && coeffs_dual(old).parent.count == 1 && coeffs_dual(new.secret).parent.count == 1) ||
+        return invoke(ToyFHE.make_eval_key, generic, rng, old => new)
+    params = new.params; ctx = hipring(ℛ); limbs = nlimbs(T); n = degree(ℛ)
+    σe, mult = gauss_params(ToyFHE.𝒩(params)); γ = gadget_table(params, ctx.q[1:limbs]); nd = size(γ, 2)
+    s = coeffs_dual(new.secret).parent; o = coeffs_dual(old).parent
+    out = HipVector{T}(2 * nd * limbs, n, 1); on(ctx, (out,), (s, o))
+    evalkey_call(ctx, limbs, s, o, γ, nd, σe, mult, rng.seed, rng.next_poly, rng.next_poly + 1, 2, out)
+    rng.next_poly += 2 * nd
+    els = unpack(ctx, out, ℛ, 2 * nd; dual=true)
+    ek = KeySwitchKey(params, map(i -> ToyFHE.KeyComponent(els[2i-1], els[2i]), 1:nd))
+    lock(KEY_LOCK) do
+        PACKED_KEYS[ek] = out
+    end
+    ek
+end
+# (two methods: the reference specialises make_eval_key on PrivKey{<:ModulusRaised}, modulusraising.jl:28-32; the gadget table
+# carries its factor P, so both run the same call)
+ToyFHE.make_eval_key(rng::HipRng, (old, new)::Pair{<:RingElement{ℛ,T,<:HipVector},<:PrivKey}) where {ℛ,T} =
+    evalkey_device(rng, old, new, Tuple{Random.AbstractRNG,Pair{<:Any,<:PrivKey}})
+ToyFHE.make_eval_key(rng::HipRng, (old, new)::Pair{<:RingElement{ℛ,T,<:HipVector},<:PrivKey{<:ModulusRaised}}) where {ℛ,T} =
+    evalkey_device(rng, old, new, Tuple{Random.AbstractRNG,Pair{<:Any,<:PrivKey{<:ModulusRaised}}})
+function ToyFHE.keygen(rng::HipRng, params::ToyFHE.SHEShemeParams)
+    ℛk = ToyFHE.ℛ_key(params)
+    (ℛk isa NegacyclicRing{<:CRTEncoded} && rng.count == 1) || return invoke(ToyFHE.keygen, Tuple{Random.AbstractRNG,ToyFHE.SHEShemeParams}, rng, params)
+    T = eltype(ℛk); ctx = hipring(ℛk); limbs = nlimbs(T); n = degree(ℛk)
+    σe, mult = gauss_params(ToyFHE.𝒩(params))
+    p0 = rng.next_poly; rng.next_poly += 1                 # the mask's counter; the secret takes the next one, the error the one after
+    secret = Random.rand(rng, ToyFHE.𝒢(params))
+    s = coeffs_dual(secret).parent
+    out = HipVector{T}(2 * limbs, n, 1); on(ctx, (out,), (s,))
+    evalkey_call(ctx, limbs, s, nothing, nothing, 1, σe, mult, rng.seed, p0, rng.next_poly, 1, out)
+    rng.next_poly += 1
+    mask, masked = unpack(ctx, out, ℛk, 2; dual=true)
+    pk = ToyFHE.PubKey(params, ToyFHE.KeyComponent(mask, masked))
+    lock(KEY_LOCK) do
+        PACKED_KEYS[pk] = out
+    end
+    ToyFHE.KeyPair(ToyFHE.PrivKey(params, secret), pk)
+end
+
 # ---- multi-GPU: one Julia process per GPU (Distributed / MPI.jl), batch sharded by ciphertext, final gather -------------
 set_device(dev::Integer) = check(ccall((:tfhe_set_device, lib), Cint, (Cint,), dev))
 function device_count()

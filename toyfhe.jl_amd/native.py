@@ -142,6 +142,8 @@ def lib():
         "tfhe_mul_relin": [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, i64],
         "tfhe_encrypt": [vp, i32, i32, vp, C.c_double, C.c_double, u64, u64, C.c_uint32, u64, vp, vp, vp, i64],
         "tfhe_decrypt_phase": [vp, i32, i32, vp, vp, i32, i32, vp, i64],
+        "tfhe_evalkey_gen": [vp, i32, vp, vp, u64p, i32, u64p, i32, C.c_double, u64, u64, C.c_uint32, C.c_uint32, u64, u64, u64, vp, vp,
+                             C.POINTER(vp)],
         "tfhe_plain_plan_create": [vp, i32p, i32, u64, C.POINTER(vp)],
         "tfhe_plain_plan_destroy": [vp],
         "tfhe_plain_encode": [vp, i32, vp, vp, i64],
@@ -168,7 +170,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
     "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
-    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
+    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
 ]
@@ -382,6 +384,30 @@ class Context:
         """c1 + s c2 (+ s^2 c3) of a batch in one call (tfhe_decrypt_phase): secret [key_limbs][N] NTT domain,
         ct [batch][polys][level][N], out [batch][level][N] coefficient domain"""
         check(lib().tfhe_decrypt_phase(self.h, key_limbs, level, secret, ct, polys, int(bool(ntt_in)), out, batch))
+
+    def evalkey_gen(self, key_limbs, secret, evks, n_digits, gadget=None, old=None, galois_elements=None, mask_rand=None, noise_rand=None,
+                    sigma_e=0.0, mult_e=1, seed=0, stream_mask=0, stream_noise=1, mask_poly=0, noise_poly=1, poly_stride=2):
+        """public (gadget None), relinearisation and Galois keys in one call (tfhe_evalkey_gen).  evks: device pointers, one
+        [n_digits][2][key_limbs][N] buffer per key (mask, masked; NTT domain); secret [key_limbs][N] NTT domain; gadget
+        [n_digits][key_limbs] residues; old a device [n_keys][key_limbs][N] buffer, or None with galois_elements (0: secret^2, odd g:
+        the secret under x -> x^g).  Component m = k n_digits + i takes polynomial mask_poly + m poly_stride of the uniform stream and
+        noise_poly + m poly_stride of the Gaussian stream, or the device buffers mask_rand / noise_rand (given together)"""
+        n = len(evks)
+        ptrs = (C.c_void_p * max(1, n))(*[int(p) for p in evks])
+        gad = None
+        if gadget is not None:
+            flat = [int(x) for row in gadget for x in row]
+            if len(flat) != n_digits * key_limbs:
+                raise AssertionError("tfhe_evalkey_gen: one gadget residue per digit and limb")
+            gad = (C.c_uint64 * len(flat))(*flat)
+        gal = None
+        if galois_elements is not None:
+            if len(galois_elements) != n:
+                raise AssertionError("tfhe_evalkey_gen: one Galois element per key")
+            gal = (C.c_uint64 * max(1, n))(*[int(g) for g in galois_elements])
+        check(lib().tfhe_evalkey_gen(self.h, key_limbs, secret, old, gal, n, gad, n_digits, float(sigma_e), int(mult_e), int(seed),
+                                     int(stream_mask), int(stream_noise), int(mask_poly), int(noise_poly), int(poly_stride),
+                                     mask_rand, noise_rand, ptrs))
 
     def keyswitch_window(self, level, window_bits, evk, n_windows, ct, polys, out, batch, key_limbs=None, special=False):
         check(lib().tfhe_keyswitch_window(self.h, level if key_limbs is None else key_limbs, level, int(bool(special)), window_bits,

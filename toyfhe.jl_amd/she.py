@@ -846,6 +846,15 @@ class _PackedResult(CipherText):
 
 
 def keygen(rng, params) -> KeyPair:
+    """keygen(rng, params), rlwe_she.jl:155-166.  With the stock samplers the public key -(mask s + e) is ONE device call
+    (tfhe_evalkey_gen without a gadget): the same words and the same generator state as the composition below."""
+    ring = params.R_key()
+    if _keygen_device_ok(rng, params, ring):
+        return _keygen_device(rng, params, ring)
+    return _keygen_composed(rng, params)
+
+
+def _keygen_composed(rng, params) -> KeyPair:
     ring = params.R_key()
     mask = sample_uniform(rng, ring)
     secret = params.secret_dist(rng, ring)
@@ -1125,9 +1134,115 @@ def _unpack(buf, ring, n, P, batch, primal=True, ctx=None):
 # --------------------------------------------------------------------------------------------------
 
 
+# TFHE_FUSED_KEYGEN=0: keys as the reference's term-by-term expressions on ring elements (comparisons; kept as the _composed
+# functions); the default is one device call (tfhe_evalkey_gen) -- the same residues, the same generator state afterwards.
+_FUSED_KEYGEN = os.environ.get("TFHE_FUSED_KEYGEN", "1") != "0"
+# The largest log2 N at which the mirror takes the call.  Above 2^14 the call runs its composed form (fill -> transform -> finish),
+# which has NOT been timed against the composition yet (tools/bench_keygen.py, profiles/LOG.md); the last call of this shape,
+# tfhe_decrypt_phase, measured slower than its composition at N = 2^16 (_decryption_device).  Until it is timed the composition
+# stays there; TFHE_FUSED_KEYGEN_MAX_LOG2=17 routes every size through the call.
+_FUSED_KEYGEN_MAX_LOG2 = int(os.environ.get("TFHE_FUSED_KEYGEN_MAX_LOG2", "14"))
+
+
+def _keygen_device_ok(rng, params, ring: NegacyclicRing, secret: RingElement | None = None) -> bool:
+    """the draws come from the stock samplers (uniform mask, rounded Gaussian noise) and the key ring is a prefix of its context"""
+    if not _FUSED_KEYGEN or _noise_multiplier(params) is None or not isinstance(rng, (DeviceRng, np.random.Generator)):
+        return False
+    if not _is_prefix(ring) or ring.N > 1 << _FUSED_KEYGEN_MAX_LOG2:
+        return False
+    return secret is None or (secret.batch is None and secret.ring.ctx is ring.ctx and secret.ring.idx == ring.idx)
+
+
+def _gadget_table(params, ring: NegacyclicRing):
+    """gamma[i][j]: the residue mod q_j that multiplies `old` in digit i of make_eval_key (rlwe_she.jl:281-287); ModulusRaised
+    pre-multiplies by the special prime P (modulusraising.jl:28-32), whose own row and column are therefore zero"""
+    mods = list(ring.moduli)
+    P = mods[-1] if isinstance(params, ModulusRaised) else 1
+    if params.relin_window != 0:                          # base-2^w gadget: 2^(i w) mod Q, Q the key ring's modulus
+        w, Q = params.relin_window, ring.modulus()
+        nwin = -(-Q.bit_length() // w)                    # ndigits(Q, base = 2^w)
+        return [[(P % q) * (pow(2, i * w, Q) % q) % q for q in mods] for i in range(nwin)]
+    return [[(P % q if i == j else 0) for j, q in enumerate(mods)] for i in range(ring.L)]   # CRTResidual, crt.jl:64-77
+
+
+def _host_draws(rng: np.random.Generator, ring: NegacyclicRing, sigma: float, n: int, between=None):
+    """n (mask, noise) pairs in the order the composition draws them -- per pair the limbs' `integers`, then `normal` -- as device
+    buffers: uint64 [n][L][N] and int32 [n][N].  `between()` runs after the mask of the first pair (keygen draws the secret there)."""
+    L, N = ring.L, ring.N
+    mask, noise = np.empty((n, L, N), dtype=np.uint64), np.empty((n, N), dtype=np.int64)
+    for i in range(n):
+        for l, q in enumerate(ring.moduli):
+            mask[i, l] = rng.integers(0, q, size=(N,), dtype=np.uint64)
+        if i == 0 and between is not None:
+            between()
+        noise[i] = sample_normal_ints(rng, N, sigma)
+    if np.abs(noise).max(initial=0) >= 2**31:
+        raise AssertionError("keygen: a noise draw does not fit 32 bits")
+    return (DeviceBuffer.from_numpy(mask),
+            DeviceBuffer.from_numpy(np.ascontiguousarray(noise.astype(np.int32)).reshape(-1).view(np.uint64)))
+
+
+def _key_from_buffer(params, ring: NegacyclicRing, buf: DeviceBuffer, n_digits: int) -> KeySwitchKey:
+    """the KeySwitchKey over the packed buffer tfhe_evalkey_gen wrote: its components are dual-domain views into it"""
+    sz = ring.L * ring.N
+    ksk = KeySwitchKey(params, [KeyComponent(RingElement(ring, None, _KeyView(buf, (2 * i) * sz, sz)),
+                                             RingElement(ring, None, _KeyView(buf, (2 * i + 1) * sz, sz))) for i in range(n_digits)])
+    ksk._packed = buf
+    return ksk
+
+
+def _keygen_device(rng, params, ring: NegacyclicRing) -> KeyPair:
+    ctx, sz = ring.ctx, ring.L * ring.N
+    buf = DeviceBuffer(2 * sz)
+    mult = _noise_multiplier(params)
+    if isinstance(rng, DeviceRng):
+        first = rng.take(1)                               # the mask; the secret takes first + 1, the error first + 2
+        secret = params.secret_dist(rng, ring)
+        ctx.evalkey_gen(ring.L, secret.coeffs_dual().ptr, [buf.ptr], 1, sigma_e=params.sigma, mult_e=mult, seed=rng.seed,
+                        stream_mask=0, stream_noise=1, mask_poly=first, noise_poly=rng.take(1), poly_stride=1)
+    else:
+        drawn = []
+        mask, noise = _host_draws(rng, ring, params.sigma, 1, between=lambda: drawn.append(params.secret_dist(rng, ring)))
+        secret = drawn[0]
+        ctx.evalkey_gen(ring.L, secret.coeffs_dual().ptr, [buf.ptr], 1, mask_rand=mask.ptr, noise_rand=noise.ptr, mult_e=mult)
+    pub = PubKey(params, KeyComponent(RingElement(ring, None, _KeyView(buf, 0, sz)), RingElement(ring, None, _KeyView(buf, sz, sz))))
+    pub._packed = buf                                     # what tfhe_encrypt takes (_packed_pubkey)
+    return KeyPair(PrivKey(params, secret), pub)
+
+
+def _evalkeys_device(rng, params, ring: NegacyclicRing, secret: RingElement, n_keys: int, old=None, galois=None):
+    """n_keys key-switching keys in one tfhe_evalkey_gen call (a numpy generator: one call per key, a key's draws being what is
+    staged on the host at a time).  old: a device buffer [1][L][N] (NTT domain; n_keys == 1), else galois[k]: 0 / g."""
+    ctx, L, sz = ring.ctx, ring.L, ring.L * ring.N
+    gadget = _gadget_table(params, ring)
+    nd, mult = len(gadget), _noise_multiplier(params)
+    s = secret.coeffs_dual()
+    bufs = [DeviceBuffer(nd * 2 * sz) for _ in range(n_keys)]
+    if isinstance(rng, DeviceRng):
+        first = rng.take(2 * n_keys * nd)                 # per component: the mask's counter, then the noise's
+        ctx.evalkey_gen(L, s.ptr, [b.ptr for b in bufs], nd, gadget=gadget, old=None if old is None else old.ptr, galois_elements=galois,
+                        sigma_e=params.sigma, mult_e=mult, seed=rng.seed, stream_mask=0, stream_noise=1, mask_poly=first,
+                        noise_poly=first + 1, poly_stride=2)
+    else:
+        for k, b in enumerate(bufs):
+            mask, noise = _host_draws(rng, ring, params.sigma, nd)
+            ctx.evalkey_gen(L, s.ptr, [b.ptr], nd, gadget=gadget, old=None if old is None else old.ptr,
+                            galois_elements=None if galois is None else [galois[k]], mask_rand=mask.ptr, noise_rand=noise.ptr, mult_e=mult)
+    return [_key_from_buffer(params, ring, b, nd) for b in bufs]
+
+
 def make_eval_key(rng, old: RingElement, new: PrivKey) -> KeySwitchKey:
-    """make_eval_key(rng, old => new), rlwe_she.jl:273-298 with the RNS gadget (:287); ModulusRaised
-    pre-multiplies ``old`` by the special prime (modulusraising.jl:28-32)."""
+    """make_eval_key(rng, old => new), rlwe_she.jl:273-298 with the RNS gadget (:287) or base-2^w digits (:281-283); ModulusRaised
+    pre-multiplies ``old`` by the special prime (modulusraising.jl:28-32).  One device call (tfhe_evalkey_gen) when the draws
+    come from the stock samplers."""
+    ring = old.ring
+    if _keygen_device_ok(rng, new.params, ring, new.secret) and old.batch is None:
+        return _evalkeys_device(rng, new.params, ring, new.secret, 1, old=old.coeffs_dual())[0]
+    return _make_eval_key_composed(rng, old, new)
+
+
+def _make_eval_key_composed(rng, old: RingElement, new: PrivKey) -> KeySwitchKey:
+    """the composition on ring elements: the gadget built on the host, per digit two draws, a product, a sum and a difference"""
     params = new.params
     ring = old.ring
     if isinstance(params, ModulusRaised):
@@ -1152,7 +1267,14 @@ def make_eval_key(rng, old: RingElement, new: PrivKey) -> KeySwitchKey:
 
 
 def keygen_evalmult(rng, priv: PrivKey) -> EvalMultKey:
-    return EvalMultKey(make_eval_key(rng, priv.secret * priv.secret, priv))  # rlwe_she.jl:299
+    ring = priv.secret.ring
+    if _keygen_device_ok(rng, priv.params, ring, priv.secret):     # s^2 is formed inside the call
+        return EvalMultKey(_evalkeys_device(rng, priv.params, ring, priv.secret, 1, galois=[0])[0])
+    return _keygen_evalmult_composed(rng, priv)
+
+
+def _keygen_evalmult_composed(rng, priv: PrivKey) -> EvalMultKey:
+    return EvalMultKey(_make_eval_key_composed(rng, priv.secret * priv.secret, priv))  # rlwe_she.jl:299
 
 
 def galois_element_for_steps(steps: int, N: int) -> int:
@@ -1163,7 +1285,30 @@ def keygen_galois(rng, priv: PrivKey, galois_element=None, steps=None) -> Galois
     assert (galois_element is None) != (steps is None)  # rlwe_she.jl:301
     if galois_element is None:
         galois_element = galois_element_for_steps(steps, priv.secret.ring.N)
-    return GaloisKey(galois_element, make_eval_key(rng, priv.secret.apply_galois_element(galois_element), priv))
+    return keygen_galois_many(rng, priv, galois_elements=[galois_element])[0]
+
+
+def _keygen_galois_composed(rng, priv: PrivKey, galois_element=None, steps=None) -> GaloisKey:
+    assert (galois_element is None) != (steps is None)  # rlwe_she.jl:301
+    if galois_element is None:
+        galois_element = galois_element_for_steps(steps, priv.secret.ring.N)
+    return GaloisKey(galois_element, _make_eval_key_composed(rng, priv.secret.apply_galois_element(galois_element), priv))
+
+
+def keygen_galois_many(rng, priv: PrivKey, galois_elements=None, steps=None) -> "list[GaloisKey]":
+    """[keygen_galois(rng, priv, g) for g in galois_elements] (or one key per entry of `steps`), word for word and with the same
+    generator state afterwards -- all keys in ONE device call (tfhe_evalkey_gen) when the draws come from a DeviceRng: the secret
+    under x -> x^g is read through an index permutation inside the call, never formed.  With a numpy generator the draws are made
+    on the host: one call and one upload PER KEY (a key's draws, n_digits (L + 1) rows, are what is staged at a time; 63 keys of
+    the MNIST ring at once would be 6.5 GB)."""
+    assert (galois_elements is None) != (steps is None)
+    ring = priv.secret.ring
+    gs = [int(g) for g in galois_elements] if steps is None else [galois_element_for_steps(int(st), ring.N) for st in steps]
+    if not gs:
+        return []
+    if _keygen_device_ok(rng, priv.params, ring, priv.secret) and all(g % 2 == 1 and 0 < g < 2 * ring.N for g in gs):
+        return [GaloisKey(g, k) for g, k in zip(gs, _evalkeys_device(rng, priv.params, ring, priv.secret, len(gs), galois=gs))]
+    return [_keygen_galois_composed(rng, priv, galois_element=g) for g in gs]
 
 
 def keyswitch(ek, c: CipherText, _galois=None, _gk=None) -> CipherText:
@@ -1400,6 +1545,19 @@ class _View:
 
     def __init__(self, parent, word_offset):
         self.parent, self.ptr = parent, parent.ptr + word_offset * 8
+
+
+class _KeyView(_View):
+    """`n_words` of a packed key buffer as a ring element's coefficient buffer (read-only: ring elements never write in place)"""
+
+    def __init__(self, parent, word_offset, n_words):
+        super().__init__(parent, word_offset)
+        self.n = int(n_words)
+
+    def to_numpy(self, shape=None) -> np.ndarray:
+        out = np.empty(self.n, dtype=np.uint64)
+        native.check(native.lib().tfhe_memcpy_d2h(out.ctypes.data, self.ptr, self.n * 8))
+        return out.reshape(shape) if shape is not None else out
 
 
 def modswitch(c: CipherText) -> CipherText:
