@@ -5,6 +5,7 @@
 //   N = 2^12 .. 2^14, variant 0, level <= 32 : (except decryption of three NTT-domain components at 2^14)
 //                                              k_encrypt_fused / k_decrypt_fused (enc_core.h), one (ciphertext, limb) item per workgroup
 //                                              pass; a ring that mixes the policies runs one launch per policy on the two lanes
+//                                              (the size test, the lanes and the launch: toyfhe_hip.hip, "the fused row kernels")
 //   everything else                          : the batched transforms on the packed layout + the streaming kernels of enc_core.h
 //       encrypt:  k_enc_fill -> nntt -> k_enc_keymul -> inntt (2 batch polynomials) -> k_enc_finish (in place)
 //       decrypt:  nntt of the whole ciphertext (unless ntt_in) -> k_dec_keymul (c1 + s c2 + s^2 c3 on the images) -> inntt
@@ -18,45 +19,32 @@ namespace {
 
 enum { ENC_CHUNK = 16384 };   // ciphertexts per launch: items = chunk x limbs stay far below 2^31, grid dimensions below 65536
 
-bool enc_fused_ok(const tfhe_ctx* c, int level) { return c->variant == 0 && c->logN >= 12 && c->logN <= 14 && level <= 32; }
-
-limb_sel_t enc_subset(int level, u32 mask) {
-    limb_sel_t s{};
-    for (int j = 0; j < level; j++)
-        if ((mask >> j) & 1u) s.idx[s.n++] = j;
-    return s;
-}
-
 template <class A>
 int enc_launch_fused(tfhe_ctx* c, u32 mask, int key_limbs, int level, const u64* pk, const u64* msg, u64* out, int64_t nct, const enc_rand_t& R) {
-    const limb_sel_t sel = enc_subset(level, mask);
+    const limb_sel_t sel = limb_subset(level, mask);
     if (sel.n == 0) return TFHE_OK;
     const unsigned items = (unsigned)(nct * sel.n);
-    return dispatch_int<12, 14>(c->logN, [&](auto lb) {
+    auto kern = [&](auto lb) {
         constexpr int LOGB = decltype(lb)::value, LOGT = logt_for(LOGB);
-        const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
-        auto kern = R.rand ? k_encrypt_fused<A, LOGB, LOGT, true> : k_encrypt_fused<A, LOGB, LOGT, false>;
-        return launch_prof(c, (int64_t)items * 3, kern, dim3(persistent_grid(c, items, lds, LOGT)), dim3(1 << LOGT), lds, out, pk, msg, c->limbs_dev,
-                           sel, items, (u32)key_limbs, (u32)level, R);
-    });
+        return R.rand ? k_encrypt_fused<A, LOGB, LOGT, true> : k_encrypt_fused<A, LOGB, LOGT, false>;
+    };
+    return launch_fused_rows(c, items, (int64_t)items * 3, kern, out, pk, msg, c->limbs_dev, sel, items, (u32)key_limbs, (u32)level, R);
 }
 
 template <class A>
 int dec_launch_fused(tfhe_ctx* c, u32 mask, int level, const u64* secret, const u64* ct, int polys, bool ntt_in, u64* out, int64_t nct, u64 b0) {
-    const limb_sel_t sel = enc_subset(level, mask);
+    const limb_sel_t sel = limb_subset(level, mask);
     if (sel.n == 0) return TFHE_OK;
+    if (c->logN == 14 && polys == 3 && ntt_in) return fail(TFHE_E_UNSUPPORTED, "internal: this form of the fused decryption is not built at N = 2^%d", 14);
     const unsigned items = (unsigned)(nct * sel.n);
-    return dispatch_int<12, 14>(c->logN, [&](auto lb) {
+    auto kern = [&](auto lb) {
         constexpr int LOGB = decltype(lb)::value, LOGT = logt_for(LOGB);
-        const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
-        void (*kern)(u64*, const u64*, const u64*, const ntt_limb_t*, limb_sel_t, u32, u32, u64) = nullptr;
-        if (polys == 2) kern = ntt_in ? k_decrypt_fused<A, LOGB, LOGT, 2, true> : k_decrypt_fused<A, LOGB, LOGT, 2, false>;
-        else if (!ntt_in) kern = k_decrypt_fused<A, LOGB, LOGT, 3, false>;
-        else if constexpr (LOGB < 14) kern = k_decrypt_fused<A, LOGB, LOGT, 3, true>;
-        if (!kern) return fail(TFHE_E_UNSUPPORTED, "internal: this form of the fused decryption is not built at N = 2^%d", LOGB);
-        return launch_prof(c, (int64_t)items * (ntt_in ? 1 : polys), kern, dim3(persistent_grid(c, items, lds, LOGT)), dim3(1 << LOGT), lds, out, ct,
-                           secret, c->limbs_dev, sel, items, (u32)level, b0);
-    });
+        if (polys == 2) return ntt_in ? k_decrypt_fused<A, LOGB, LOGT, 2, true> : k_decrypt_fused<A, LOGB, LOGT, 2, false>;
+        if constexpr (LOGB < 14)   // (three NTT-domain components are not built at 2^14: refused above)
+            if (ntt_in) return k_decrypt_fused<A, LOGB, LOGT, 3, true>;
+        return k_decrypt_fused<A, LOGB, LOGT, 3, false>;
+    };
+    return launch_fused_rows(c, items, (int64_t)items * (ntt_in ? 1 : polys), kern, out, ct, secret, c->limbs_dev, sel, items, (u32)level, b0);
 }
 
 }  // namespace
@@ -79,8 +67,8 @@ extern "C" int tfhe_encrypt(tfhe_ctx* c, int key_limbs, int level, const uint64_
     const size_t N = (size_t)c->N;
     if ((u64)batch > (1ull << 40) / ((u64)2 * level * N)) return fail(TFHE_E_BADARG, "bad batch");
     const size_t out_bytes = (size_t)batch * 2 * level * N * 8;
-    if (mr_ranges_overlap(out, out_bytes, pk, (size_t)2 * key_limbs * N * 8) || (msg && mr_ranges_overlap(out, out_bytes, msg, (size_t)batch * level * N * 8)) ||
-        (rand && mr_ranges_overlap(out, out_bytes, rand, (size_t)batch * 3 * N * 4)))
+    if (ranges_overlap(out, out_bytes, pk, (size_t)2 * key_limbs * N * 8) || (msg && ranges_overlap(out, out_bytes, msg, (size_t)batch * level * N * 8)) ||
+        (rand && ranges_overlap(out, out_bytes, rand, (size_t)batch * 3 * N * 4)))
         return fail(TFHE_E_BADARG, "out overlaps an operand");
     if (batch == 0) return TFHE_OK;
 
@@ -88,20 +76,15 @@ extern "C" int tfhe_encrypt(tfhe_ctx* c, int key_limbs, int level, const uint64_
     R.rand = rand; R.sigma_u = sigma_u; R.sigma_e = sigma_e; R.mult_e = mult_e; R.seed = seed; R.first_poly = first_poly; R.stream = stream;
     R.batch = (u64)batch;
     const limb_sel_t sel = first_limbs(level);
-    if (enc_fused_ok(c, level)) {
+    if (fused_rows_ok(c, level)) {
         const policy_split_t ps = policy_split(c, sel);
-        const u32 fp_mask = ps.fpmask, int_mask = ps.all & ~ps.fpmask;
         const int64_t chunk = chunk_of(c, batch, ENC_CHUNK);
         for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
             const int64_t nct = std::min(chunk, batch - b0);
             R.b0 = (u64)b0;
-            // the two policies side by side over disjoint limb rows; the u64 launch (the long pole) first, on the main lane
-            lanes_t lanes(c, fp_mask != 0 && int_mask != 0);
-            lanes.use(0);
-            int rc = enc_launch_fused<ArithInt>(c, int_mask, key_limbs, level, pk, msg, out, nct, R);
-            if (rc) return rc;
-            lanes.use(1);
-            rc = enc_launch_fused<ArithFp>(c, fp_mask, key_limbs, level, pk, msg, out, nct, R);
+            const int rc = both_policies(c, ps.all & ~ps.fpmask, ps.fpmask, [&](auto pol, u32 mask) {
+                return enc_launch_fused<decltype(pol)>(c, mask, key_limbs, level, pk, msg, out, nct, R);
+            });
             if (rc) return rc;
         }
         return TFHE_OK;
@@ -153,24 +136,20 @@ extern "C" int tfhe_decrypt_phase(tfhe_ctx* c, int key_limbs, int level, const u
     const size_t N = (size_t)c->N;
     if ((u64)batch > (1ull << 40) / ((u64)3 * level * N)) return fail(TFHE_E_BADARG, "bad batch");
     const size_t out_bytes = (size_t)batch * level * N * 8;
-    if (mr_ranges_overlap(out, out_bytes, ct, (size_t)batch * polys * level * N * 8) || mr_ranges_overlap(out, out_bytes, secret, (size_t)key_limbs * N * 8))
+    if (ranges_overlap(out, out_bytes, ct, (size_t)batch * polys * level * N * 8) || ranges_overlap(out, out_bytes, secret, (size_t)key_limbs * N * 8))
         return fail(TFHE_E_BADARG, "out overlaps an operand");
     if (batch == 0) return TFHE_OK;
 
     const limb_sel_t sel = first_limbs(level);
     // (three NTT-domain components at N = 2^14: the fused form does not fit the registers there, enc_core.h)
-    if (enc_fused_ok(c, level) && !(c->logN == 14 && polys == 3 && ntt_in)) {
+    if (fused_rows_ok(c, level) && !(c->logN == 14 && polys == 3 && ntt_in)) {
         const policy_split_t ps = policy_split(c, sel);
-        const u32 fp_mask = ps.fpmask, int_mask = ps.all & ~ps.fpmask;
         const int64_t chunk = chunk_of(c, batch, ENC_CHUNK);
         for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
             const int64_t nct = std::min(chunk, batch - b0);
-            lanes_t lanes(c, fp_mask != 0 && int_mask != 0);
-            lanes.use(0);
-            int rc = dec_launch_fused<ArithInt>(c, int_mask, level, secret, ct, polys, ntt_in != 0, out, nct, (u64)b0);
-            if (rc) return rc;
-            lanes.use(1);
-            rc = dec_launch_fused<ArithFp>(c, fp_mask, level, secret, ct, polys, ntt_in != 0, out, nct, (u64)b0);
+            const int rc = both_policies(c, ps.all & ~ps.fpmask, ps.fpmask, [&](auto pol, u32 mask) {
+                return dec_launch_fused<decltype(pol)>(c, mask, level, secret, ct, polys, ntt_in != 0, out, nct, (u64)b0);
+            });
             if (rc) return rc;
         }
         return TFHE_OK;

@@ -1,12 +1,12 @@
 // enc_core.h -- the two ends of a pipeline as fused row kernels, N = 2^12 .. 2^14, both arithmetic policies:
 //   tfhe_encrypt        out_b = ( INTT(masked . NTT(u_b)) + e1_b (+ msg_b),  INTT(mask . NTT(u_b)) + e2_b )      (rlwe_she.jl:176-195)
 //   tfhe_decrypt_phase  out_b = c1_b + INTT( s . NTT(c2_b) (+ s^2 . NTT(c3_b)) )                                 (rlwe_she.jl:199-212)
-// for one (ciphertext b, limb j) per workgroup pass, built from the policy-templated passes of ntt_core.h the way mul_core.h
-// builds the u64 product core.  The per-thread PHASES (everything between two barriers) are plain TFHE_HD functions, so that
-// the CPU emulation under tests/enc_core_emul/ runs the very code of the kernels: one loop over the thread ids per phase.
+// for one (ciphertext b, limb j) per workgroup pass.  The transform through registers -- schedule, register map, passes, the two
+// barrier sequences, the item walk -- is row_core.h; enc_core adds the phases that are encryption's own (u_form, the key products,
+// the decryption sums, the last pass with the noise in its store).  The per-thread PHASES (everything between two barriers) are
+// plain TFHE_HD functions, so that the CPU emulation under tests/enc_core_emul/ runs the very code of the kernels.
 //
-// Ranges.  u64 policy (ArithInt): as mul_core.h -- the forward passes keep [0, 4q), the last one canonicalises, a data x data
-// product goes through Barrett and is canonical, which is inside the [0, 2q) the inverse butterflies take.
+// Ranges.  u64 policy (ArithInt): as row_core.h; a data x data product goes through Barrett and is canonical.
 // fp64 policy (ArithFp, moduli up to TFHE_FP_QMAX; the plan of fp64arith.h is entered at its stated points and nowhere else):
 //   u        enters the forward transform as the canonical residue of the signed integer, |v| <= 1 p: the entry the forward
 //            sweep plan (fp_fwd_sweep_before) is made for; the last pass canonicalises (out_fwd);
@@ -22,7 +22,7 @@
 // where they are needed -- in place of the forward transform's load for u, at the last inverse pass's store for e -- or read
 // from a caller's int32 [batch][3][N] buffer.  No source row exists in memory: the words pass through the workgroup's LDS image.
 #pragma once
-#include "ntt_core.h"
+#include "row_core.h"
 #include "sample_kernels.h"
 
 struct enc_rand_t {
@@ -41,37 +41,16 @@ TFHE_HD long long enc_small(const enc_rand_t& R, u64 b, int k, u32 pos, u32 logn
 }
 
 template <class A, int LOGB, int LOGT>
-struct enc_core {
-    static constexpr int K1 = pass_k_fwd(LOGB, LOGT, 0), K2 = pass_k_fwd(LOGB, LOGT, K1), K3 = LOGB - K1 - K2;
-    static constexpr int KI1 = pass_k_inv(LOGB, LOGT, LOGB), S1 = LOGB - KI1, KI2 = pass_k_inv(LOGB, LOGT, S1), S2 = S1 - KI2;
-    static_assert(K3 >= 1 && pass_k_fwd(LOGB, LOGT, K1 + K2) == K3, "three-pass forward schedule expected");
-    static_assert(KI1 == K3, "forward last pass and inverse first pass must share the register map");
-    static_assert(S2 >= 1 && pass_k_inv(LOGB, LOGT, S2) == S2, "three-pass inverse schedule expected");
-    typedef pgeom<LOGB, LOGT, 0, K1> G1;            // forward first pass: where a thread's source words lie
-    typedef pgeom<LOGB, LOGT, LOGB - K3, K3> G3;    // the shared register map of the NTT image
-    typedef pgeom<LOGB, LOGT, 0, S2> GL;            // inverse last pass: where a thread's result words go
-    static constexpr int E = G3::E;
-    typedef typename A::elem elem;
-    typedef typename A::ctx actx;
+struct enc_core : row_core<A, LOGB, LOGT> {
+    typedef row_core<A, LOGB, LOGT> B;
+    using B::E;
+    using B::nat_of;
+    using B::src_of;
+    using B::dst_of;
+    using B::S2;
+    typedef typename B::elem elem;
+    typedef typename B::actx actx;
 
-    static TFHE_HD u32 nat_of(u32 tid, int e) {      // natural-order position (NTT domain) of register e
-        u32 c0, hi, base;
-        G3::template coords<true>(tid, e / G3::R, c0, hi, base);
-        return (brev_bits((u32)(e % G3::R), K3) << (LOGB - K3)) + c0;
-    }
-    static TFHE_HD u32 src_of(u32 tid, int e) {      // coefficient the forward transform's raw word e holds
-        u32 c0, hi, base;
-        G1::template coords<false>(tid, e / G1::R, c0, hi, base);
-        return base + ((u32)(e % G1::R) << G1::LO);
-    }
-    static TFHE_HD u32 dst_of(u32 tid, int e) {      // coefficient the inverse transform's result word e is
-        u32 c0, hi, base;
-        GL::template coords<false>(tid, e / GL::R, c0, hi, base);
-        return base + ((u32)(e % GL::R) << GL::LO);
-    }
-
-    // ---- forward transform: load (or form) | barrier | first | barrier | mid | barrier | last (canonical, in registers) ----
-    static TFHE_HD void fwd_load(u64* raw, const u64* grow, u32 tid) { fwd_load_data<LOGB, LOGT, 0, K1, true, false>(raw, nullptr, grow, tid); }
     // u of ciphertext b as canonical residues mod q, written to the LDS words the thread's own first pass reads (no barrier between
     // the two: a thread reads back what it wrote).  A ROLLED loop: a Gaussian draw is a Philox block plus log, sqrt and cos in
     // doubles, and E (16 or 32) of them unrolled side by side do not fit the registers; the LDS word takes the dynamic index.
@@ -82,23 +61,6 @@ struct enc_core {
             const u32 pos = src_of(tid, e);
             lds[lds_phi<LOGB, LOGT>(pos)] = gauss_residue(enc_small<RAND>(R, b, 0, pos, LOGB), 1, br);
         }
-    }
-    static TFHE_HD void u_load(u64* raw, const u64* lds, u32 tid) { fwd_load_data<LOGB, LOGT, 0, K1, false, false>(raw, lds, nullptr, tid); }
-    static TFHE_HD void fwd_first(const u64* raw, u64* lds, const actx& C, u32 tid) {
-        elem v[E];
-        fwd_compute<A, LOGB, LOGT, 0, K1, true, false, 0>(v, raw, nullptr, C, tid, 1u);
-        fwd_store<A, LOGB, LOGT, 0, K1, false>(v, lds, nullptr, C, tid, 0, 0u);
-    }
-    static TFHE_HD void fwd_mid(u64* lds, const actx& C, u32 tid) {
-        ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
-    }
-    static TFHE_HD void fwd_last(const u64* lds, const actx& C, u32 tid, u64* out) {
-        u64 r3[E];
-        elem v[E];
-        fwd_load_data<LOGB, LOGT, K1 + K2, K3, false, true>(r3, lds, nullptr, tid);
-        fwd_compute<A, LOGB, LOGT, K1 + K2, K3, false, true, 0>(v, r3, nullptr, C, tid, 1u);
-#pragma unroll
-        for (int e = 0; e < E; e++) out[e] = A::out_fwd(v[e], C);
     }
     // ---- products: canonical words in, the inverse transform's operand out ----
     static TFHE_HD void prod_key(elem* v, const u64* uh, const u64* key, const barrett_t& br, const actx& C, u32 tid) {
@@ -130,22 +92,6 @@ struct enc_core {
         TFHE_SCHED_FENCE();   // the next piece's loads stay behind this one's: 8 words of each row in flight, not E
         if constexpr (E0 + 8 < E) dec_acc_ntt<POLYS, E0 + 8>(acc, c1, c2, c3, s, br, tid);
     }
-    static TFHE_HD void to_elem(elem* v, const u64* acc, const actx& C) {
-#pragma unroll
-        for (int e = 0; e < E; e++) v[e] = A::from_global(acc[e], C);
-    }
-    // ---- inverse transform from registers: barrier | first | barrier | mid | barrier | last ----
-    static TFHE_HD void inv_first(u64* lds, const actx& C, u32 tid, elem* v) {
-        inv_compute<A, LOGB, LOGT, S1, KI1, true, true, 0, -1, no_hook, true>(v, nullptr, nullptr, C, tid, 1u);
-        inv_store<A, LOGB, LOGT, S1, KI1, true, true>(v, lds, nullptr, C, tid);
-    }
-    static TFHE_HD void inv_mid(u64* lds, const actx& C, u32 tid) {
-        ntt_inv_pass<A, LOGB, LOGT, S2, KI2, false, false, true>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
-    }
-    // last pass, canonical words to gdst (+ the addend row: decryption's c1)
-    static TFHE_HD void inv_last(u64* lds, u64* gdst, const actx& C, u32 tid, const u64* addend) {
-        ntt_inv_pass<A, LOGB, LOGT, 0, S2, false, true, true>(lds, nullptr, gdst, C, tid, 1u, 0, 0u, addend);
-    }
     // last pass of an encryption: + mult_e e_k (sampled or read here) + msg in the store.  The canonical results go back to the LDS
     // words the pass read them from (a thread's own), and a rolled loop -- see u_form -- finishes and stores them.
     template <bool RAND>
@@ -171,10 +117,6 @@ struct enc_core {
     // N = 2^14: NTT(u) waits in the second component's output row (which the last store overwrites) between the two products,
     // not in registers next to a running inverse transform; a thread reads back its own words only
     static constexpr bool PARK = LOGB >= 14;
-    static TFHE_HD void park_row(u64* park, const u64* v, u32 tid) {
-#pragma unroll
-        for (int e = 0; e < E; e++) park[nat_of(tid, e)] = v[e];
-    }
     static TFHE_HD void prod_key_parked(elem* v, const u64* park, const u64* key, const barrett_t& br, const actx& C, u32 tid) {
 #pragma unroll
         for (int e = 0; e < E; e++) {
@@ -185,30 +127,6 @@ struct enc_core {
 };
 
 #if defined(__HIPCC__)
-template <class A, int LOGB, int LOGT>
-__device__ __forceinline__ void enc_core_forward(u64* lds, const u64* raw, const typename A::ctx& C, bool& first, u64* out) {
-    typedef enc_core<A, LOGB, LOGT> M;
-    const u32 tid = fresh_tid();
-    if (!first) __syncthreads();  // the previous transform's last pass has read LDS
-    first = false;
-    M::fwd_first(raw, lds, C, tid);
-    __syncthreads();
-    M::fwd_mid(lds, C, tid);
-    __syncthreads();
-    M::fwd_last(lds, C, tid, out);
-}
-template <class A, int LOGB, int LOGT>
-__device__ __forceinline__ void enc_core_inverse_head(u64* lds, typename A::elem* v, const typename A::ctx& C, bool& first) {
-    typedef enc_core<A, LOGB, LOGT> M;
-    const u32 tid = fresh_tid();
-    if (!first) __syncthreads();  // the previous transform's last pass has read LDS
-    first = false;
-    M::inv_first(lds, C, tid, v);
-    __syncthreads();
-    M::inv_mid(lds, C, tid);
-    __syncthreads();
-}
-
 // `sel` lists the limbs of this launch's policy (positions in the ring = context moduli: the ring is a prefix of its context);
 // items are (ciphertext, selected limb).  pk [2][key_limbs][N] (mask, masked), msg [batch][level][N] or nullptr,
 // out [batch][2][level][N]; the pointers are those of the whole call, R.b0 is the launch's first ciphertext.
@@ -221,12 +139,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_encrypt_fused(u64* __restrict__ o
     constexpr int E = M::E;
     const u32 nb = (u32)sel.n;
     bool first = true;
-    const u32 niter = xcd_limb_niter(gridDim.x, nitems);
-    for (u32 it = 0; it < niter; it++) {
-        // (workgroup-uniform, but the walk's divisions run on the vector unit: say so, or every row pointer derived from it lives
-        // in vector registers across the whole item)
-        const u32 item = (u32)__builtin_amdgcn_readfirstlane((int)xcd_limb_walk(it, blockIdx.x, gridDim.x, nb, nitems));
-        if (item == ~0u) break;
+    for (u32 it = 0, item; row_item(it, nb, nitems, item); it++) {
         const u32 j = (u32)sel.idx[item % nb];
         const u64 b = R.b0 + item / nb;
         const ntt_limb_t& L = LT[j];
@@ -244,16 +157,16 @@ __global__ __launch_bounds__(1 << LOGT) void k_encrypt_fused(u64* __restrict__ o
             u64 raw[E];
             M::u_load(raw, lds, fresh_tid());
             first = true;                 // (that barrier is done)
-            enc_core_forward<A, LOGB, LOGT>(lds, raw, C, first, uh);
+            row_forward<A, LOGB, LOGT>(lds, raw, C, first, uh);
         }
         typename A::elem v[E];
         M::prod_key(v, uh, masked, br, C, fresh_tid());
         if constexpr (M::PARK) M::park_row(o1, uh, fresh_tid());
-        enc_core_inverse_head<A, LOGB, LOGT>(lds, v, C, first);
+        row_inverse_head<A, LOGB, LOGT>(lds, v, C, first);
         M::template inv_last_noise<RAND>(lds, o0, msg ? msg + ((b * level + j) << LOGB) : nullptr, C, R, b, 1, mq, br, fresh_tid());
         if constexpr (M::PARK) M::prod_key_parked(v, o1, mask, br, C, fresh_tid());
         else M::prod_key(v, uh, mask, br, C, fresh_tid());
-        enc_core_inverse_head<A, LOGB, LOGT>(lds, v, C, first);
+        row_inverse_head<A, LOGB, LOGT>(lds, v, C, first);
         M::template inv_last_noise<RAND>(lds, o1, nullptr, C, R, b, 2, mq, br, fresh_tid());
     }
 }
@@ -269,12 +182,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_decrypt_fused(u64* __restrict__ o
     constexpr int E = M::E;
     const u32 nb = (u32)sel.n;
     bool first = true;
-    const u32 niter = xcd_limb_niter(gridDim.x, nitems);
-    for (u32 it = 0; it < niter; it++) {
-        // (workgroup-uniform, but the walk's divisions run on the vector unit: say so, or every row pointer derived from it lives
-        // in vector registers across the whole item)
-        const u32 item = (u32)__builtin_amdgcn_readfirstlane((int)xcd_limb_walk(it, blockIdx.x, gridDim.x, nb, nitems));
-        if (item == ~0u) break;
+    for (u32 it = 0, item; row_item(it, nb, nitems, item); it++) {
         const u32 j = (u32)sel.idx[item % nb];
         const u64 b = b0 + item / nb;
         const ntt_limb_t& L = LT[j];
@@ -292,19 +200,19 @@ __global__ __launch_bounds__(1 << LOGT) void k_decrypt_fused(u64* __restrict__ o
             {
                 u64 raw[E];
                 M::fwd_load(raw, c2, fresh_tid());
-                enc_core_forward<A, LOGB, LOGT>(lds, raw, C, first, ch);
+                row_forward<A, LOGB, LOGT>(lds, raw, C, first, ch);
             }
             M::template dec_acc<true>(acc, ch, s, br, fresh_tid());
             if constexpr (POLYS == 3) {
                 u64 raw[E];
                 M::fwd_load(raw, c3, fresh_tid());
-                enc_core_forward<A, LOGB, LOGT>(lds, raw, C, first, ch);
+                row_forward<A, LOGB, LOGT>(lds, raw, C, first, ch);
                 M::template dec_acc<false>(acc, ch, s, br, fresh_tid());
             }
         }
         typename A::elem v[E];
         M::to_elem(v, acc, C);
-        enc_core_inverse_head<A, LOGB, LOGT>(lds, v, C, first);
+        row_inverse_head<A, LOGB, LOGT>(lds, v, C, first);
         M::inv_last(lds, out + ((b * level + j) << LOGB), C, fresh_tid(), NTTIN ? nullptr : c1);
     }
 }

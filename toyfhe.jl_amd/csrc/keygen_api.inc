@@ -3,7 +3,8 @@
 //
 // Routing:
 //   N = 2^12 .. 2^14, variant 0, key_limbs <= 32 : k_evalkey_fused, one (component, limb) item per workgroup pass; a ring that mixes
-//                                                  the policies runs one launch per policy on the two lanes
+//                                                  the policies runs one launch per policy on the two lanes (the size test, the
+//                                                  lanes and the launch: toyfhe_hip.hip, "the fused row kernels")
 //   everything else                              : k_key_fill -> in-place nntt of the chunk's rows (one per key the chunk touches)
 //                                                  -> k_key_finish
 // The chunk counts COMPONENTS (key k, digit i): a component is two whole polynomials, the unit the batched transform takes.
@@ -20,15 +21,14 @@ struct key_tab_t {           // the staged table, released (parked behind the st
 
 template <class A>
 int key_launch_fused(tfhe_ctx* c, u32 mask, int key_limbs, int64_t ncomp, const key_arg_t& K, const key_rand_t& R) {
-    const limb_sel_t sel = enc_subset(key_limbs, mask);
+    const limb_sel_t sel = limb_subset(key_limbs, mask);
     if (sel.n == 0) return TFHE_OK;
     const unsigned items = (unsigned)(ncomp * sel.n);
-    return dispatch_int<12, 14>(c->logN, [&](auto lb) {
+    auto kern = [&](auto lb) {
         constexpr int LOGB = decltype(lb)::value, LOGT = logt_for(LOGB);
-        const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
-        auto kern = R.mask_rand ? k_evalkey_fused<A, LOGB, LOGT, true> : k_evalkey_fused<A, LOGB, LOGT, false>;
-        return launch_prof(c, (int64_t)items * 2, kern, dim3(persistent_grid(c, items, lds, LOGT)), dim3(1 << LOGT), lds, c->limbs_dev, sel, items, K, R);
-    });
+        return R.mask_rand ? k_evalkey_fused<A, LOGB, LOGT, true> : k_evalkey_fused<A, LOGB, LOGT, false>;
+    };
+    return launch_fused_rows(c, items, (int64_t)items * 2, kern, c->limbs_dev, sel, items, K, R);
 }
 
 struct key_range_t {
@@ -104,7 +104,7 @@ extern "C" int tfhe_evalkey_gen(tfhe_ctx* c, int key_limbs, const uint64_t* secr
         }
     }
     if (n_keys == 0) return TFHE_OK;
-    const bool fused = c->variant == 0 && c->logN >= 12 && c->logN <= 14 && key_limbs <= 32;
+    const bool fused = fused_rows_ok(c, key_limbs);
     if (!fused && c->logN > 17) return fail(TFHE_E_UNSUPPORTED, "N = 2^%d not supported (max 2^17)", c->logN);
 
     // the table: output pointers | Galois elements | gadget residues
@@ -129,18 +129,13 @@ extern "C" int tfhe_evalkey_gen(tfhe_ctx* c, int key_limbs, const uint64_t* secr
     const limb_sel_t sel = first_limbs(key_limbs);
     if (fused) {
         const policy_split_t ps = policy_split(c, sel);
-        const u32 fp_mask = ps.fpmask, int_mask = ps.all & ~ps.fpmask;
         const int64_t chunk = chunk_of(c, (int64_t)M, KEY_CHUNK);
         for (int64_t m0 = 0; m0 < (int64_t)M; m0 += chunk) {
             const int64_t nc = std::min(chunk, (int64_t)M - m0);
             K.m0 = (u64)m0;
-            // the two policies side by side over disjoint limb rows; the u64 launch (the long pole) first, on the main lane
-            lanes_t lanes(c, fp_mask != 0 && int_mask != 0);
-            lanes.use(0);
-            int rc = key_launch_fused<ArithInt>(c, int_mask, key_limbs, nc, K, R);
-            if (rc) return rc;
-            lanes.use(1);
-            rc = key_launch_fused<ArithFp>(c, fp_mask, key_limbs, nc, K, R);
+            const int rc = both_policies(c, ps.all & ~ps.fpmask, ps.fpmask, [&](auto pol, u32 mask) {
+                return key_launch_fused<decltype(pol)>(c, mask, key_limbs, nc, K, R);
+            });
             if (rc) return rc;
         }
         return TFHE_OK;

@@ -6,7 +6,7 @@
 // s^ read through galois_ntt_pos (a Galois key: the automorphism is an index permutation without signs in the NTT domain).
 //
 // Fused form, N = 2^12 .. 2^14: k_evalkey_fused, one (component m, limb j) item per workgroup pass, built from the phases of
-// enc_core.h (the policy-templated passes of ntt_core.h).  The per-thread PHASES are plain TFHE_HD functions, so that the CPU
+// enc_core.h (the transform through registers, its barrier sequences and the item walk: row_core.h).  The per-thread PHASES are plain TFHE_HD functions, so that the CPU
 // emulation under tests/keygen_core_emul/ runs the very code of the kernel: one loop over the thread ids per phase.
 //   1. the uniform row a_m is generated (or read from the caller's buffer) in place of the forward transform's loads;
 //   2. forward transform; 3. row 0 stored, its canonical words kept in registers (N = 2^14: read back from row 0 by the thread
@@ -16,7 +16,7 @@
 // Where gamma[i][j] == 0 -- every off-diagonal item of the RNS gadget, every item of a public key -- the old term is skipped, not
 // multiplied by zero.
 //
-// Ranges.  u64 policy (ArithInt): as enc_core.h -- the forward passes keep [0, 4q), the last one canonicalises; every product of two
+// Ranges.  u64 policy (ArithInt): as row_core.h -- the forward passes keep [0, 4q), the last one canonicalises; every product of two
 // data words (a^ s^, gamma old^, s^ s^) goes through the limb's Barrett constants and is canonical; sums and differences are
 // addmod / negmod of canonical words.
 // fp64 policy (ArithFp, moduli below TFHE_FP_QMAX; the plan of fp64arith.h is entered at its stated point and nowhere else):
@@ -153,10 +153,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_evalkey_fused(const ntt_limb_t* _
     constexpr int E = M::E;
     const u32 nb = (u32)sel.n;
     bool first = true;
-    const u32 niter = xcd_limb_niter(gridDim.x, nitems);
-    for (u32 it = 0; it < niter; it++) {
-        const u32 item = (u32)__builtin_amdgcn_readfirstlane((int)xcd_limb_walk(it, blockIdx.x, gridDim.x, nb, nitems));
-        if (item == ~0u) break;
+    for (u32 it = 0, item; row_item(it, nb, nitems, item); it++) {
         const u32 j = (u32)sel.idx[item % nb];
         const u64 m = K.m0 + item / nb;
         const u32 k = (u32)(m / K.n_digits), i = (u32)(m % K.n_digits);
@@ -180,7 +177,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_evalkey_fused(const ntt_limb_t* _
                 M::u_load(raw, lds, fresh_tid());
                 first = true;                 // (that barrier is done)
             }
-            enc_core_forward<A, LOGB, LOGT>(lds, raw, C, first, ah);
+            row_forward<A, LOGB, LOGT>(lds, raw, C, first, ah);
         }
         KC::store_mask(row0, ah, fresh_tid());
         {
@@ -189,7 +186,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_evalkey_fused(const ntt_limb_t* _
             KC::template noise_form<RAND>(lds, R, m, R.mult_e % br.q, br, fresh_tid());
             M::u_load(raw, lds, fresh_tid());
             first = true;
-            enc_core_forward<A, LOGB, LOGT>(lds, raw, C, first, eh);
+            row_forward<A, LOGB, LOGT>(lds, raw, C, first, eh);
         }
         KC::combine(mode, row1, row0, ah, eh, s, o, g, gel, br, fresh_tid());
     }

@@ -10,6 +10,7 @@
 // Routing of the product (forward transforms + tensor + inverse transforms) per limb:
 //   N = 2^12 .. 2^14, variant 0, fp64-size limb : k_bfv_core_fused (MODE: packed operands / squaring / NTT-domain input)
 //   N = 2^12 .. 2^14, variant 0, larger limb    : k_mul_core_int (mul_core.h), beside the fp64 core on the second lane
+//   (the size test, the limb subsets and the two lanes: toyfhe_hip.hip, "the fused row kernels")
 //   everything else                             : batched transform kernels + k_tensor on the packed layout (not fused)
 // Every path leaves canonical residues, so the words are those of the chain through the public entry points.
 
@@ -28,22 +29,16 @@ size_t mr_ks_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t ba
     return ntt_tmp + (size_t)chunk * per_ct + evd_bytes;
 }
 
-bool mr_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // parking rows (N words each) the two fused cores may ask for: one per workgroup (k_bfv_core_fused; k_mul_core_int below 2^14), two per
 // workgroup at 2^14 (k_mul_core_int) -- the grids are at most two workgroups per CU below 2^14 and one at 2^14
 size_t mr_park_rows(const tfhe_ctx* c) { return (size_t)2 * std::max(256, c->num_cus) * TFHE_GRID_MULT_CORE; }
 
 // the subset `mask` (positions in the ciphertext) of the first `level` limbs as a selection + its place in the packed buffers
 void mr_subset(int level, u32 mask, const u64* a, const u64* b, limb_sel_t* sel, core_alt_t* alt) {
-    *sel = limb_sel_t{};
+    *sel = limb_subset(level, mask);
     *alt = core_alt_t{};
     alt->a = a; alt->b = b; alt->ns = level;
-    for (int j = 0; j < level; j++)
-        if ((mask >> j) & 1u) { alt->idx[sel->n] = (signed char)j; sel->idx[sel->n++] = j; }
+    for (int j = 0; j < sel->n; j++) alt->idx[j] = (signed char)sel->idx[j];
 }
 int64_t mr_transforms(unsigned items, bool square, bool ntt_in) { return (int64_t)items * ((ntt_in ? 0 : (square ? 2 : 4)) + 3); }
 
@@ -129,7 +124,7 @@ extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const
     if (rc) return rc;
     const size_t N = (size_t)c->N;
     const size_t in_bytes = (size_t)batch * 2 * level * N * 8, out_bytes = (size_t)batch * 2 * (level - (rescale ? 1 : 0)) * N * 8;
-    if (mr_ranges_overlap(out, out_bytes, c1, in_bytes) || mr_ranges_overlap(out, out_bytes, c2, in_bytes))
+    if (ranges_overlap(out, out_bytes, c1, in_bytes) || ranges_overlap(out, out_bytes, c2, in_bytes))
         return fail(TFHE_E_BADARG, "out overlaps an operand");
     if (batch == 0) return TFHE_OK;
     if ((batch * 4 * level) << std::max(0, c->logN - 14) > 0x7fffffffll) return fail(TFHE_E_BADARG, "bad batch");
@@ -139,8 +134,7 @@ extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const
     const policy_split_t ps = policy_split(c, sel);
     // fused product cores: N = 2^12 .. 2^14, variant 0.  The general form of the fp64 core with a limb subset is not built at 2^14
     // (it does not fit the registers there, DESIGN.md): a ring that mixes the policies takes the batched kernels for that form.
-    const bool fused = c->variant == 0 && c->logN >= 12 && c->logN <= 14 && level <= 32 &&
-                       !(c->logN == 14 && ps.mixed_fp() && !square && !ntt_in);
+    const bool fused = fused_rows_ok(c, level) && !(c->logN == 14 && ps.mixed_fp() && !square && !ntt_in);
     const u32 fp_mask = fused ? ps.fpmask : 0u, int_mask = fused ? (ps.all & ~ps.fpmask) : 0u;
 
     // chunk: F (NTT images of the operands: the batched path only), T (3 rows per limb), R (2: the key switch's result when a
@@ -165,14 +159,11 @@ extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const
         const u64* a = c1 + (size_t)b0 * 2 * level * N;
         const u64* b = c2 + (size_t)b0 * 2 * level * N;
         if (fused) {
-            // a ring that mixes the policies runs both cores side by side on the context's two lanes, over disjoint rows of T; the
-            // u64 core (the long pole) first, on the main lane; the lanes join before the key switch reads T
-            lanes_t lanes(c, fp_mask != 0 && int_mask != 0);
-            lanes.use(0);
-            rc = mr_core_int(c, a, b, T, SCR, nct, level, int_mask, square, ntt_in != 0);
-            if (rc) return rc;
-            lanes.use(1);
-            rc = mr_core_fp(c, a, b, T, SCR + park, nct, level, fp_mask, int_mask == 0, square, ntt_in != 0);
+            // both cores side by side (both_policies), over disjoint rows of T; the lanes join before the key switch reads T
+            rc = both_policies(c, int_mask, fp_mask, [&](auto pol, u32 mask) {
+                if constexpr (std::is_same<decltype(pol), ArithInt>::value) return mr_core_int(c, a, b, T, SCR, nct, level, mask, square, ntt_in != 0);
+                else return mr_core_fp(c, a, b, T, SCR + park, nct, level, mask, int_mask == 0, square, ntt_in != 0);
+            });
         } else {
             rc = mr_product_composed(c, a, b, F, T, nct, level, square, ntt_in != 0);
         }

@@ -1,52 +1,25 @@
 // mul_core.h -- the fused product core of tfhe_mul_relin for the u64 policy (ArithInt: moduli from TFHE_FP_QMAX up to 2^62),
 // N = 2^12 .. 2^14:   T_k[b][j] = INTT_j( tensor_k( NTT_j(a0), NTT_j(a1), NTT_j(b0), NTT_j(b1) ) ),  k = 0, 1, 2
 // (enc_mul, rlwe_she.jl:255-258, with mul_expand / mul_contract the identity: CKKS, BGV) for one (ciphertext b, limb j) per
-// workgroup pass -- the u64 counterpart of k_bfv_core_fused (kernels.h), built from the policy-templated passes of ntt_core.h.
+// workgroup pass -- the u64 counterpart of k_bfv_core_fused (kernels.h).  The transform through registers -- schedule, register
+// map, passes, the two barrier sequences -- is row_core<ArithInt, LOGB, LOGT> (row_core.h); this file holds the product phases,
+// the kernel with its four branches and the parking-row layout.
 //
 // The per-thread PHASES (everything between two barriers) are plain TFHE_HD functions, so that the CPU emulation under
 // tests/mul_core_emul/ runs the very code of the kernel: one loop over the thread ids per phase.  The kernel itself is device
 // code (needs kernels.h) and is compiled only under hipcc.
 //
-// Ranges: the forward passes keep Harvey's [0, 4q); the last one canonicalises (out_fwd), because a data x data product goes
-// through Barrett (ntt_limb_t::br), whose window z < 2^(k+62) admits q^2 but not (4q) q at 61- and 62-bit moduli.  Products
-// and their sum are canonical, which is inside the [0, 2q) the inverse butterflies take; the final store is canonical.
+// Ranges: as row_core.h.  The forward transform's last pass canonicalises because a data x data product goes through Barrett
+// (ntt_limb_t::br), whose window z < 2^(k+62) admits q^2 but not (4q) q at 61- and 62-bit moduli.
 #pragma once
-#include "ntt_core.h"
+#include "row_core.h"
 
 template <int LOGB, int LOGT>
-struct mul_core_int {
-    typedef ArithInt A;
-    static constexpr int K1 = pass_k_fwd(LOGB, LOGT, 0), K2 = pass_k_fwd(LOGB, LOGT, K1), K3 = LOGB - K1 - K2;
-    static constexpr int KI1 = pass_k_inv(LOGB, LOGT, LOGB), S1 = LOGB - KI1, KI2 = pass_k_inv(LOGB, LOGT, S1), S2 = S1 - KI2;
-    static_assert(K3 >= 1 && pass_k_fwd(LOGB, LOGT, K1 + K2) == K3, "three-pass forward schedule expected");
-    static_assert(KI1 == K3, "forward last pass and inverse first pass must share the register map");
-    static_assert(S2 >= 1 && pass_k_inv(LOGB, LOGT, S2) == S2, "three-pass inverse schedule expected");
-    typedef pgeom<LOGB, LOGT, LOGB - K3, K3> G3;
-    static constexpr int E = G3::E;
+struct mul_core_int : row_core<ArithInt, LOGB, LOGT> {
+    typedef row_core<ArithInt, LOGB, LOGT> B;
+    using B::E;
+    using B::nat_of;
 
-    // natural-order position (NTT domain) of register e of thread tid in the shared register map
-    static TFHE_HD u32 nat_of(u32 tid, int e) {
-        u32 c0, hi, base;
-        G3::template coords<true>(tid, e / G3::R, c0, hi, base);
-        return (brev_bits((u32)(e % G3::R), K3) << (LOGB - K3)) + c0;
-    }
-
-    // ---- forward transform of one row: load | barrier | first | barrier | mid | barrier | last (canonical, in registers) ----
-    static TFHE_HD void fwd_load(u64* raw, const u64* grow, u32 tid) { fwd_load_data<LOGB, LOGT, 0, K1, true, false>(raw, nullptr, grow, tid); }
-    static TFHE_HD void fwd_first(const u64* raw, u64* lds, const A::ctx& C, u32 tid, u64* v) {
-        fwd_compute<A, LOGB, LOGT, 0, K1, true, false, 0>(v, raw, nullptr, C, tid, 1u);
-        fwd_store<A, LOGB, LOGT, 0, K1, false>(v, lds, nullptr, C, tid, 0, 0u);
-    }
-    static TFHE_HD void fwd_mid(u64* lds, const A::ctx& C, u32 tid) {
-        ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
-    }
-    static TFHE_HD void fwd_last(const u64* lds, const A::ctx& C, u32 tid, u64* v) {
-        u64 r3[E];
-        fwd_load_data<LOGB, LOGT, K1 + K2, K3, false, true>(r3, lds, nullptr, tid);
-        fwd_compute<A, LOGB, LOGT, K1 + K2, K3, false, true, 0>(v, r3, nullptr, C, tid, 1u);
-#pragma unroll
-        for (int e = 0; e < E; e++) v[e] = A::out_fwd(v[e], C);
-    }
     // ---- products (canonical operands, canonical results) ----
     // b0 in v:  park[.] <- a1 b0,  v <- a0 b0      (park: the workgroup's scratch row; a thread reads back its own words only)
     static TFHE_HD void prod_b0(u64* v, const u64* A0, const u64* A1, u64* park, const barrett_t& br, u32 tid) {
@@ -86,10 +59,6 @@ struct mul_core_int {
     }
     // Two parking rows (N = 2^14, where three rows of 32 words do not fit the 256 registers of a 512-thread workgroup next to a
     // running transform): NTT(a1) goes to p1 as soon as it exists and is streamed back by the products, a1 b0 goes to p2.
-    static TFHE_HD void park_row(u64* park, const u64* v, u32 tid) {
-#pragma unroll
-        for (int e = 0; e < E; e++) park[nat_of(tid, e)] = v[e];
-    }
     static TFHE_HD void prod_b0_parked(u64* v, const u64* A0, const u64* p1, u64* p2, const barrett_t& br, u32 tid) {
 #pragma unroll
         for (int e = 0; e < E; e++) {
@@ -106,47 +75,21 @@ struct mul_core_int {
             A1[e] = mulmod(v[e], p1[nat], br);
         }
     }
-    // ---- inverse transform from registers: barrier | first | barrier | mid | barrier | last (canonical words to gdst) ----
-    static TFHE_HD void inv_first(u64* lds, const A::ctx& C, u32 tid, u64* v) {
-        inv_compute<A, LOGB, LOGT, S1, KI1, true, true, 0, -1, no_hook, true>(v, nullptr, nullptr, C, tid, 1u);
-        inv_store<A, LOGB, LOGT, S1, KI1, true, true>(v, lds, nullptr, C, tid);
-    }
-    static TFHE_HD void inv_mid(u64* lds, const A::ctx& C, u32 tid) {
-        ntt_inv_pass<A, LOGB, LOGT, S2, KI2, false, false, true>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
-    }
-    static TFHE_HD void inv_last(u64* lds, u64* gdst, const A::ctx& C, u32 tid) {
-        ntt_inv_pass<A, LOGB, LOGT, 0, S2, false, true, true>(lds, nullptr, gdst, C, tid, 1u, 0, 0u);
-    }
 };
 
 #if defined(__HIPCC__)
-// u64 counterparts of fused_fwd_to_regs / fused_inv_from_regs (kernels.h), phase by phase
+// a row from memory to its canonical NTT image in registers / a row of canonical products back to memory (row_core.h)
 template <int LOGB, int LOGT>
 __device__ __forceinline__ void mul_core_forward(u64* lds, const u64* grow, const ArithInt::ctx& C, bool& first, u64* v) {
-    typedef mul_core_int<LOGB, LOGT> M;
-    const u32 tid = fresh_tid();
-    {
-        u64 raw[M::E];
-        M::fwd_load(raw, grow, tid);
-        if (!first) __syncthreads();  // the previous transform's last pass has read LDS
-        first = false;
-        M::fwd_first(raw, lds, C, tid, v);
-    }
-    __syncthreads();
-    M::fwd_mid(lds, C, tid);
-    __syncthreads();
-    M::fwd_last(lds, C, tid, v);
+    u64 raw[mul_core_int<LOGB, LOGT>::E];
+    mul_core_int<LOGB, LOGT>::fwd_load(raw, grow, fresh_tid());
+    row_forward<ArithInt, LOGB, LOGT>(lds, raw, C, first, v);
 }
 template <int LOGB, int LOGT>
 __device__ __forceinline__ void mul_core_inverse(u64* lds, u64* v, u64* gdst, const ArithInt::ctx& C) {
-    typedef mul_core_int<LOGB, LOGT> M;
-    const u32 tid = fresh_tid();
-    __syncthreads();  // the previous transform's last pass has read LDS
-    M::inv_first(lds, C, tid, v);
-    __syncthreads();
-    M::inv_mid(lds, C, tid);
-    __syncthreads();
-    M::inv_last(lds, gdst, C, tid);
+    bool first = false;   // always the opening barrier: only the NTT-input forms could ever skip it, once per workgroup
+    row_inverse_head<ArithInt, LOGB, LOGT>(lds, v, C, first);
+    mul_core_int<LOGB, LOGT>::inv_last(lds, gdst, C, fresh_tid());
 }
 
 // `sel` lists the u64-policy limbs of the ring (context moduli), alt.idx[j] their positions in the packed ciphertexts
@@ -167,6 +110,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_mul_core_int(u64* __restrict__ T,
     u64* const p1 = scratch + (((size_t)blockIdx.x * (PARK2 ? 2u : 1u)) << LOGB);
     u64* const p2 = p1 + ((size_t)1 << LOGB);
     bool first = true;
+    // (row_item's walk without its readfirstlane: this kernel's register figures were taken with the item number as it is)
     const u32 niter = xcd_limb_niter(gridDim.x, nitems);
     for (u32 it = 0; it < niter; it++) {
         const u32 item = xcd_limb_walk(it, blockIdx.x, gridDim.x, nb, nitems);

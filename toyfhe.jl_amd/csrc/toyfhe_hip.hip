@@ -327,6 +327,42 @@ policy_split_t policy_split(const tfhe_ctx* c, const limb_sel_t& sel) {
     return p;
 }
 
+// ---- the fused row kernels (row_core.h): what tfhe_mul_relin, tfhe_encrypt, tfhe_decrypt_phase and tfhe_evalkey_gen route alike ----
+// the sizes they are built for; the per-policy limb masks hold 32 limbs
+bool fused_rows_ok(const tfhe_ctx* c, int limbs) { return c->variant == 0 && c->logN >= 12 && c->logN <= 14 && limbs <= 32; }
+// the limbs of `mask` among the first `level`
+limb_sel_t limb_subset(int level, u32 mask) {
+    limb_sel_t s{};
+    for (int j = 0; j < level; j++)
+        if ((mask >> j) & 1u) s.idx[s.n++] = j;
+    return s;
+}
+// The two policies side by side over disjoint limb rows, on the context's two lanes when both have limbs: run(policy, mask) for the
+// u64 limbs (the long pole) first, on the main lane, then for the fp64-size ones on the side lane.  The lanes join on return.
+template <class F>
+int both_policies(tfhe_ctx* c, u32 int_mask, u32 fp_mask, F&& run) {
+    lanes_t lanes(c, fp_mask != 0 && int_mask != 0);
+    lanes.use(0);
+    const int rc = run(ArithInt{}, int_mask);
+    if (rc) return rc;
+    lanes.use(1);
+    return run(ArithFp{}, fp_mask);
+}
+// One launch of persistent workgroups over `items` (item, limb) rows, N = 2^12 .. 2^14: the LDS image is the transform's padded
+// row; kernel_for(LOGB) names the kernel, `transforms` is the launch's count for the profile.
+template <class K, class... Args>
+int launch_fused_rows(tfhe_ctx* c, unsigned items, int64_t transforms, K&& kernel_for, const Args&... args) {
+    return dispatch_int<12, 14>(c->logN, [&](auto lb) {
+        constexpr int LOGB = decltype(lb)::value, LOGT = logt_for(LOGB);
+        const size_t lds = (size_t)lds_words<LOGB, LOGT>() * 8;
+        return launch_prof(c, transforms, kernel_for(lb), dim3(persistent_grid(c, items, lds, LOGT)), dim3(1 << LOGT), lds, args...);
+    });
+}
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
 template <class A, int LOGB, int IOMODE = 0>
 int launch_block_fwd(tfhe_ctx* c, const u64* src, u64* dst, int64_t rows, const limb_sel_t& sel, int x, const ntt_io_t& io) {
     if constexpr (IOMODE == 0) {
