@@ -19,7 +19,7 @@ from oracle import ref_cpu            # checker only
 
 HBM_PEAK_GBS = 8000.0
 PROFILE = os.environ.get("TFHE_CFG_PROFILE", "0") not in ("", "0")
-NOCHECK = os.environ.get("TFHE_CFG_NOCHECK", "0") not in ("", "0")   # ablation builds (-DTFHE_ABL_*: wrong results by design); records say so
+NOCHECK = os.environ.get("TFHE_CFG_NOCHECK", "0") not in ("", "0")   # builds that are wrong by design (ablations); records say so
 RECORDS = []                          # one dict per case (bench.py puts them into its JSON line as `other_configs`)
 
 

@@ -273,7 +273,7 @@ static int bfv_mul_impl(tfhe_bfv_plan* p, const u64* evk, int n_digits, const u6
     const size_t ntt_tmp = p->big->logN > 14 ? (size_t)chunk * 4 * nb * N * 8 : 0;  // run_ntt's own scratch lives in the ctx
     (void)ntt_tmp;
     void* ws = nullptr;
-    const size_t scr_rows = (size_t)2 * std::max(256, p->big->num_cus) * TFHE_GRID_MULT_CORE;  // k_bfv_core_fused: one scratch row per workgroup (up to two per CU below 2^14)
+    const size_t scr_rows = (size_t)2 * std::max(256, p->big->num_cus);  // k_bfv_core_fused: one scratch row per workgroup (up to two per CU below 2^14)
     int rc = plan_ws(p, ((size_t)chunk * (7 * (size_t)nb + (relin ? 3 * (size_t)ns : 0)) + scr_rows) * N * 8, &ws);
     if (rc) return rc;
     u64* E = (u64*)ws;

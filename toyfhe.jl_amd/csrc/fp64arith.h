@@ -24,10 +24,8 @@
 #include "modarith.h"
 
 #define TFHE_FP_QMAX 1126999418470400ull /* 2^50 + 2^40 */
-#ifndef TFHE_FP_A                   /* (overridable for design experiments: plans for a smaller size class of moduli) */
 #define TFHE_FP_A 0.25025          /* >= TFHE_FP_QMAX 2^-52 */
 #define TFHE_FP_LIMIT 7.9           /* < 2^53 / TFHE_FP_QMAX = 7.992 */
-#endif
 
 // A second size class (r04): moduli below 2^42 -- the 40-bit chains of the reference's CKKS parameter sets (test/ckks_*.jl,
 // infer.jl:98-107).  a = p 2^-52 < 2^-10, so a stage adds 1/2 + 0.0015 b and the exactness limit is 2^53 / p > 2048: a forward

@@ -35,28 +35,22 @@ struct limb_sel_t {  // which context modulus each buffer limb uses (crtselect, 
 // limb j of polynomial `poly`; x = log2(N) - LOGB (0 when the whole limb fits one LDS block).
 // ------------------------------------------------------------------------------------------------
 
-// Early LDS stores (ntt_core.h, fwd_compute / inv_compute `lds_early`), per kernel family: bit set = the pass writes its results to
-// LDS from inside its last butterfly stage.  Measured per site (r05, profiles/LOG.md; registers from the ISA):
-//   bit 0  k_ntt_fwd_quad middle pass     182 -> 234 VGPRs, no scratch: N = 2^16 forward 2.75 -> 3.00 TB/s (mixed ring 2.00 -> 2.12)   ON
-//   bit 5  k_ntt_inv_staged middle pass   140 -> 166 VGPRs: inverse at 2^14 + 0.7 %                                                     ON
-//   bit 7  k_ntt_inv_pair middle pass     scratch 164 -> 96 bytes                                                                       ON
-//   bit 8  k_ntt_inv_subpair middle pass  218 -> 222 VGPRs: cfg#5 key switch + 0.7 %, reference-shaped MNIST + 2 %                     ON
-//   bit 11 k_ntt_fwd_pf middle pass       234 -> 238 VGPRs: no change (3.93 / 3.95 TB/s)                                                off
-//   bit 3  fwd_schedule (block kernels)   u64 forward 117 -> 188 VGPRs: 60-bit transforms 2.06 -> 1.91 TB/s                              off
-//   bits 1, 2, 6, 9, 10 (quad first pass, k_ntt_fwd_pair, inv_schedule, k_ntt_inv_quad2, k_ntt_fwd_pf first pass): 80 - 830 bytes of scratch  off
-// The fused kernels sit at the 256-VGPR cap: the same change spills 13-20 accumulator registers per digit there (headline 61.2 k ->
-// 56.4 k ciphertext-mul/s, cfg#3 40.1 k -> 30.4 k key switches/s) -- they keep the store phase behind the pass.
-#ifndef TFHE_ES_SITES
-#define TFHE_ES_SITES 0x1a1
-#endif
-#define TFHE_ES(bit) (((TFHE_ES_SITES) >> (bit)) & 1)
+// Early LDS stores (ntt_core.h, fwd_compute / inv_compute `lds_early`; the ES argument of ntt_fwd_pass / ntt_inv_pass): the pass
+// writes its results to LDS from inside its last butterfly stage.  On at the four sites where it measured a gain (r05,
+// profiles/LOG.md; registers from the ISA):
+//   k_ntt_fwd_quad middle pass     182 -> 234 VGPRs, no scratch: N = 2^16 forward 2.75 -> 3.00 TB/s (mixed ring 2.00 -> 2.12)
+//   k_ntt_inv_staged middle pass   140 -> 166 VGPRs: inverse at 2^14 + 0.7 %
+//   k_ntt_inv_pair middle pass     scratch 164 -> 96 bytes
+//   k_ntt_inv_subpair middle pass  218 -> 222 VGPRs: cfg#5 key switch + 0.7 %, reference-shaped MNIST + 2 %
+// Every other site spilled (80 - 830 bytes of scratch), lost (u64 fwd_schedule 2.06 -> 1.91 TB/s) or tied (LOG r05); the fused
+// kernels, at the 256-VGPR cap, spill 13-20 accumulator registers per digit with it (headline 61.2 k -> 56.4 k ciphertext-mul/s).
 // ---- simple schedule: one workgroup per item, passes separated by barriers ----
 template <class A, int LOGB, int LOGT, int S0>
 __device__ __forceinline__ void fwd_schedule(u64* lds, const u64* gsrc, u64* gdst, const typename A::ctx& C, u32 tid,
                                              u32 pre, int x, u32 sbrev, const lift_t* lift) {
     constexpr int K = pass_k_fwd(LOGB, LOGT, S0);
     constexpr bool LAST = (S0 + K == LOGB);
-    ntt_fwd_pass<A, LOGB, LOGT, S0, K, S0 == 0, LAST, TFHE_ES(3) != 0>(lds, gsrc, gdst, C, tid, pre, x, sbrev, lift);
+    ntt_fwd_pass<A, LOGB, LOGT, S0, K, S0 == 0, LAST>(lds, gsrc, gdst, C, tid, pre, x, sbrev, lift);
     if constexpr (!LAST) {
         __syncthreads();
         fwd_schedule<A, LOGB, LOGT, S0 + K>(lds, gsrc, gdst, C, tid, pre, x, sbrev, lift);
@@ -97,7 +91,7 @@ __device__ __forceinline__ void inv_schedule(u64* lds, const u64* gsrc, u64* gds
                                              u32 pre, int x, u32 sbrev, const u64* addend) {
     constexpr int K = pass_k_inv(LOGB, LOGT, SEND);
     constexpr int S0 = SEND - K;
-    ntt_inv_pass<A, LOGB, LOGT, S0, K, SEND == LOGB, S0 == 0, SCALE, TFHE_ES(6) != 0>(lds, gsrc, gdst, C, tid, pre, x, sbrev, addend);
+    ntt_inv_pass<A, LOGB, LOGT, S0, K, SEND == LOGB, S0 == 0, SCALE>(lds, gsrc, gdst, C, tid, pre, x, sbrev, addend);
     if constexpr (S0 != 0) {
         __syncthreads();
         inv_schedule<A, LOGB, LOGT, S0, SCALE>(lds, gsrc, gdst, C, tid, pre, x, sbrev, addend);
@@ -131,18 +125,13 @@ __device__ __forceinline__ u32 xcd_walk_item(u32 it, u32 b, u32 grid, int x, u32
 // traffic of k_bfv_core_fused was 2.2 x its algorithmic bytes).  Here XCD x takes the x-th eighth of the items in LIMB-MAJOR
 // order (at most ceil(nb / 8) + 1 limbs), its workgroups striding through that share.  Returns ~0u past the end.
 // Used by k_bfv_core_fused (+ 1.1 % on the headline).
-#ifndef TFHE_XCD_LIMB
-#define TFHE_XCD_LIMB 1
-#endif
-template <bool ON = true>
 __device__ __forceinline__ u32 xcd_limb_niter(u32 grid, u32 nitems) {
-    if (!ON || !TFHE_XCD_LIMB || (grid & 7u)) return (nitems + grid - 1) / grid;
+    if (grid & 7u) return (nitems + grid - 1) / grid;
     const u32 per = (nitems + 7u) >> 3, nslots = grid >> 3;
     return (per + nslots - 1) / nslots;
 }
-template <bool ON = true>
 __device__ __forceinline__ u32 xcd_limb_walk(u32 it, u32 wg, u32 grid, u32 nb, u32 nitems) {
-    if (!ON || !TFHE_XCD_LIMB || (grid & 7u)) {
+    if (grid & 7u) {
         const u32 item = it * grid + wg;
         return item < nitems ? item : ~0u;
     }
@@ -255,12 +244,9 @@ __global__ __launch_bounds__(1 << LOGT, TFHE_NTT_WAVES) void k_ntt_fwd_pf(const 
         typename A::tw tw2[G2::SETS * G2::NTW];
         {
             typename A::elem v[E];
-            if constexpr (TFHE_ES(10) != 0) fwd_load_tw<A, LOGB, LOGT, K1, K2, false>(tw2, C, tid, 1u);  // arrive underneath the exchange
-            fwd_compute<A, LOGB, LOGT, 0, K1, true, false, 0>(v, raw, nullptr, C, tid, 1u, nullptr, no_hook(), TFHE_ES(10) ? lds : nullptr);
-            if constexpr (TFHE_ES(10) == 0) {
-                fwd_load_tw<A, LOGB, LOGT, K1, K2, false>(tw2, C, tid, 1u);
-                fwd_store<A, LOGB, LOGT, 0, K1, false>(v, lds, nullptr, C, tid, 0, 0u);
-            }
+            fwd_compute<A, LOGB, LOGT, 0, K1, true, false, 0>(v, raw, nullptr, C, tid, 1u);
+            fwd_load_tw<A, LOGB, LOGT, K1, K2, false>(tw2, C, tid, 1u);
+            fwd_store<A, LOGB, LOGT, 0, K1, false>(v, lds, nullptr, C, tid, 0, 0u);
         }
         __syncthreads();
         {
@@ -270,8 +256,8 @@ __global__ __launch_bounds__(1 << LOGT, TFHE_NTT_WAVES) void k_ntt_fwd_pf(const 
 #pragma unroll
             for (int i = 0; i < G2::SETS * G2::NTW; i++) pin_vgpr(tw2[i].w);  // landed before the prefetch starts
             const row_prefetcher<LOGB, LOGT> pf{raw, src + ((size_t)(next < nitems ? next : item) << LOGB) + tid, next < nitems};
-            fwd_compute<A, LOGB, LOGT, K1, K2, false, false, K2, -1, row_prefetcher<LOGB, LOGT>>(v, r2, tw2, C, tid, 1u, nullptr, pf, TFHE_ES(11) ? lds : nullptr);
-            if (!TFHE_ES(11)) fwd_store<A, LOGB, LOGT, K1, K2, false>(v, lds, nullptr, C, tid, 0, 0u);
+            fwd_compute<A, LOGB, LOGT, K1, K2, false, false, K2, -1, row_prefetcher<LOGB, LOGT>>(v, r2, tw2, C, tid, 1u, nullptr, pf);
+            fwd_store<A, LOGB, LOGT, K1, K2, false>(v, lds, nullptr, C, tid, 0, 0u);
         }
         __syncthreads();
         {
@@ -384,23 +370,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_ntt_inv_block(const u64* __restri
 // vmcnt is one in-order counter for loads, so every ordinary vector load whose result is needed while the
 // DMA is in flight (last-pass twiddles, addends) is issued and waited for BEFORE the DMA is started.
 // ------------------------------------------------------------------------------------------------
-#ifdef TFHE_TRACE  // design aid (tools/ntt_ablate.hip): shader-clock stamps of one workgroup's phases
-__device__ unsigned long long tfhe_trace[64 * 16];
-#define TFHE_STAMP(k)                                                                                   \
-    do {                                                                                                \
-        if (blockIdx.x == (TFHE_TRACE) && threadIdx.x == 0 && itc < 64) {                               \
-            tfhe_trace[itc * 16 + (k)] = __builtin_amdgcn_s_memtime();                                  \
-            if ((k) == 0) tfhe_trace[itc * 16 + 15] = __builtin_amdgcn_s_memrealtime();                 \
-        }                                                                                               \
-    } while (0)
-#else
-#define TFHE_STAMP(k) ((void)0)
-#endif
-
 __device__ __forceinline__ void glds16(const void* gsrc, u32 lds_byte) {  // one 1-KiB wave-wide piece
-#ifdef TFHE_ABL_NOMEM
-    return;
-#endif
     u32 keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
@@ -534,28 +504,22 @@ __global__ __launch_bounds__(1 << LOGT, IOMODE == 2 ? 2 : TFHE_NTT_WAVES) void k
     item_rows_t R = item_rows<IOMODE>(item, sel, io, lf, LT);
     row_stager<LOGB, LOGT>(lds, src + ((size_t)R.srow << LOGB), tid, true).all();
     TFHE_WAIT_VM0();
-    u32 itc = 0;
-    (void)itc;
     for (;;) {
         const u32 tid = IOMODE == 2 ? threadIdx.x : fresh_tid();  // (the addend variant measured faster with hoisted addresses)
         const typename A::ctx C = A::make(LT[sel.idx[R.j]]);
         u64* gdst = dst + ((size_t)R.drow << LOGB);
         __syncthreads();
-        TFHE_STAMP(0);
         {
             u64 raw[E];
             typename A::elem v[E];
             inv_load_data<LOGB, LOGT, LOGB - K1, K1, true>(raw, lds, lds, tid, 0, 0u);
             inv_compute<A, LOGB, LOGT, LOGB - K1, K1, true, true, 0>(v, raw, nullptr, C, tid, 1u);
             __syncthreads();
-            TFHE_STAMP(1);
             inv_store<A, LOGB, LOGT, LOGB - K1, K1, true, true>(v, lds, nullptr, C, tid);
         }
         __syncthreads();
-        TFHE_STAMP(2);
-        ntt_inv_pass<A, LOGB, LOGT, K3, K2, false, false, true, TFHE_ES(5) != 0>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
+        ntt_inv_pass<A, LOGB, LOGT, K3, K2, false, false, true, true>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
         __syncthreads();
-        TFHE_STAMP(3);
         const u32 next = item + gridDim.x;
         {
             u64 raw[E], add[IOMODE == 2 ? E : 1];
@@ -574,7 +538,6 @@ __global__ __launch_bounds__(1 << LOGT, IOMODE == 2 ? 2 : TFHE_NTT_WAVES) void k
 #pragma unroll
             for (int i = 0; i < E; i++) pin_vgpr(raw[i]);
             __syncthreads();  // LDS is free
-            TFHE_STAMP(4);
             item_rows_t Rn = R;
             if (next < nitems) Rn = item_rows<IOMODE>(next, sel, io, lf, LT);
             const row_stager<LOGB, LOGT> stager(lds, src + ((size_t)Rn.srow << LOGB), tid, next < nitems);
@@ -589,18 +552,14 @@ __global__ __launch_bounds__(1 << LOGT, IOMODE == 2 ? 2 : TFHE_NTT_WAVES) void k
                 }
             }
             TFHE_SCHED_FENCE();
-            TFHE_STAMP(6);
             TFHE_WAIT_VM0();
-            TFHE_STAMP(7);
             static_assert(G3::SETS == 1 && G3::LO == LOGT, "last inverse pass: one register set, stride 2^LOGT");
 #pragma unroll
             for (int r = 0; r < E; r++) gdst[tid + ((u32)r << LOGT)] = o[r];
-            TFHE_STAMP(8);
             R = Rn;
         }
         if (next >= nitems) break;
         item = next;
-        itc++;
     }
 }
 
@@ -673,7 +632,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_ntt_fwd_pair(const u64* __restric
                 fwd_store<A, LOGB, LOGT, 0, K1, false>(v, lds, nullptr, C, tid, 0, 0u);
             }
             __syncthreads();
-            ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false, TFHE_ES(2) != 0>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
+            ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
             __syncthreads();
             {
                 u64 r3[E];
@@ -717,7 +676,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_ntt_inv_pair(const u64* __restric
                 inv_store<A, LOGB, LOGT, S1, K1, true, false>(v, lds, nullptr, C, tid);
             }
             __syncthreads();
-            ntt_inv_pass<A, LOGB, LOGT, KL, K2, false, false, false, TFHE_ES(7) != 0>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
+            ntt_inv_pass<A, LOGB, LOGT, KL, K2, false, false, false, true>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
             __syncthreads();
             {
                 u64 r3[E];
@@ -777,9 +736,9 @@ __global__ __launch_bounds__(1 << LOGT) void k_ntt_fwd_subpair(const u64* __rest
             const u32 tid = fresh_tid();
             if (!first) __syncthreads();  // the previous transform's last pass has read LDS
             first = false;
-            ntt_fwd_pass<A, LOGB, LOGT, 0, K1, true, false, TFHE_ES(4) != 0>(lds, g, nullptr, C, tid, pre, 0, 0u);
+            ntt_fwd_pass<A, LOGB, LOGT, 0, K1, true, false>(lds, g, nullptr, C, tid, pre, 0, 0u);
             __syncthreads();
-            ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false, TFHE_ES(4) != 0>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
+            ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
             __syncthreads();
             {
                 u64 r3[E];
@@ -877,11 +836,11 @@ __global__ __launch_bounds__(1 << LOGT) void k_ntt_fwd_quad(const u64* __restric
             __syncthreads();  // every wave has read the last chunk / the previous transform's last pass has read LDS
             {
                 typename A::elem v[E];
-                fwd_compute<A, LOGB, LOGT, 0, K1, false, false, 0>(v, w[half], nullptr, C, tid, pre, nullptr, no_hook(), TFHE_ES(1) ? lds : nullptr);
-                if (!TFHE_ES(1)) fwd_store<A, LOGB, LOGT, 0, K1, false>(v, lds, nullptr, C, tid, 0, 0u);
+                fwd_compute<A, LOGB, LOGT, 0, K1, false, false, 0>(v, w[half], nullptr, C, tid, pre);
+                fwd_store<A, LOGB, LOGT, 0, K1, false>(v, lds, nullptr, C, tid, 0, 0u);
             }
             __syncthreads();
-            ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false, TFHE_ES(0) != 0>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
+            ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false, true>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
             __syncthreads();
             static_assert(G3::SETS == 2, "last pass: two register sets");
             // one register set at a time: halves the transient next to the 64 held / waiting registers
@@ -963,7 +922,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_ntt_inv_subpair(const u64* __rest
                 inv_store<A, LOGB, LOGT, S1, K1, true, false>(v, lds, nullptr, C, tid);
             }
             __syncthreads();
-            ntt_inv_pass<A, LOGB, LOGT, KL, K2, false, false, false, TFHE_ES(8) != 0>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
+            ntt_inv_pass<A, LOGB, LOGT, KL, K2, false, false, false, true>(lds, nullptr, nullptr, C, tid, pre, 0, 0u);
             __syncthreads();
             ntt_inv_pass<A, LOGB, LOGT, 0, KL, false, true, false>(lds, nullptr, g, C, tid, pre, 0, 0u);
         }
@@ -1676,80 +1635,17 @@ __global__ __launch_bounds__(256) void k_ks_inner_n2(const u64* __restrict__ evk
     }
 }
 
-#ifdef TFHE_KS_TRACE  // design aid (tools/ks_trace.py): 100 MHz stamps of workgroup 0's phases in the fused key switch
-__device__ unsigned long long tfhe_kst[4096];
-__device__ unsigned tfhe_kst_n;
-__device__ __forceinline__ void kst(unsigned tag) {
-    __builtin_amdgcn_sched_barrier(0);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const unsigned n = tfhe_kst_n;
-        if (n < 4096) {
-            tfhe_kst[n] = ((unsigned long long)tag << 56) | (__builtin_amdgcn_s_memrealtime() & ((1ull << 56) - 1));
-            tfhe_kst_n = n + 1;
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-}
-#else
-#define kst(tag) ((void)0)
-#endif
 // ---- shared pieces of the fused kernels: a forward transform that ends in registers (last pass's natural-order map)
 // and an inverse transform that starts from registers in that same map ----
-// middle-pass twiddles of the fused kernels from LDS tables (ArithFpL), per kernel: bit 0 -- forward transforms, bit 1 -- inverse
-// transforms (those keep their register prefetch when the bit is clear); 0: vector loads throughout, no tables.
-// MEASURED (r03, rocprof on one box, alternating bench runs): key switch 1 445 / 1 452 us with the forward / both tables against
-// 1 455 us without, the core kernel 1 905 against 1 870 us (+ 2 %), step 59.9 k against 59.8 k -- nothing: with the twiddles
-// pinned to one cache line (-DTFHE_ABL_NOTW=3) the two kernels gain 5 %, which is the whole prize, and the LDS reads cost
-// about what the L2 round trips did.  Off by default; the code stays as the record of the experiment.
-#ifndef TFHE_TWL_KS
-#define TFHE_TWL_KS 0
-#endif
-#ifndef TFHE_TWL_CORE
-#define TFHE_TWL_CORE 0
-#endif
-// words of the LDS twiddle tables of the fused kernels (one per direction): every stage below the boundary pass
-template <int LOGB, int LOGT>
-constexpr u32 fused_tw_entries() {
-    return 1u << (pass_k_fwd(LOGB, LOGT, 0) + pass_k_fwd(LOGB, LOGT, pass_k_fwd(LOGB, LOGT, 0)));
-}
-template <int LOGB, int LOGT>
-constexpr u32 fused_tw_words() {  // padded (tw_lds_pos)
-    return fused_tw_entries<LOGB, LOGT>() + (fused_tw_entries<LOGB, LOGT>() >> 4);
-}
-// fill the LDS twiddle tables of limb `C` (ArithFpL); the first reader is behind the barrier that follows the first pass, and
-// the previous item's last reader (its inverse middle pass) is behind the barrier that precedes its last pass
-template <class A, int LOGB, int LOGT, int MASK>
-__device__ __forceinline__ void fused_fill_tw(u64* lds, typename A::ctx& C) {
-    constexpr u32 TE = fused_tw_entries<LOGB, LOGT>(), T = 1u << LOGT;
-    static_assert(TE % T == 0, "table size vs workgroup size");
-    double* wl = reinterpret_cast<double*>(lds + lds_words<LOGB, LOGT>());
-    double* wil = wl + fused_tw_words<LOGB, LOGT>();
-    const u32 tid = fresh_tid();
-    typedef __attribute__((address_space(1))) const double* gptr_t;
-    const gptr_t gw = (gptr_t)C.W, gwi = (gptr_t)C.Winv;
-#pragma unroll
-    for (u32 i = 0; i < TE; i += T) {
-        if (MASK & 1) wl[tw_lds_pos(i + tid)] = gw[i + tid];
-        if (MASK & 2) wil[tw_lds_pos(i + tid)] = gwi[i + tid];
-    }
-    C.Wl = wl;
-    C.Winvl = wil;
-}
-template <class A, int LOGB, int LOGT, bool PRELIFT = false, bool TWL = false>
+template <class A, int LOGB, int LOGT, bool PRELIFT = false>
 __device__ __forceinline__ void fused_fwd_to_regs(u64* lds, const u64* grow, const typename A::ctx& C, bool& first,
                                                   typename A::elem* v, const lift_t* lift = nullptr) {
-    typedef typename std::conditional<TWL, ArithFpL, A>::type AM;  // policy of the middle pass
     constexpr int K1 = pass_k_fwd(LOGB, LOGT, 0), K2 = pass_k_fwd(LOGB, LOGT, K1), K3 = LOGB - K1 - K2;
     constexpr int E = 1 << (LOGB - LOGT);
     const u32 tid = fresh_tid();
     {
         u64 raw[E];
-#ifdef TFHE_ABL_NOROWS  // design aid: operands from arithmetic (wrong results, no row traffic)
-#pragma unroll
-        for (int i = 0; i < E; i++) { raw[i] = (u64)(tid * 131u + (u32)i * 7919u) + (u64)(size_t)grow; pin_vgpr(raw[i]); }
-#else
         fwd_load_data<LOGB, LOGT, 0, K1, true, false>(raw, lds, grow, tid);
-#endif
         if (!first) __syncthreads();  // the previous transform's last pass has read LDS
         first = false;
         if constexpr (PRELIFT) {
@@ -1768,26 +1664,19 @@ __device__ __forceinline__ void fused_fwd_to_regs(u64* lds, const u64* grow, con
         fwd_store<A, LOGB, LOGT, 0, K1, false>(v, lds, nullptr, C, tid, 0, 0u);
     }
     __syncthreads();
-    kst(2);
-    ntt_fwd_pass<AM, LOGB, LOGT, K1, K2, false, false>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
+    ntt_fwd_pass<A, LOGB, LOGT, K1, K2, false, false>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
     __syncthreads();
-    kst(3);
     {
         u64 r3[E];
         fwd_load_data<LOGB, LOGT, K1 + K2, K3, false, true>(r3, lds, nullptr, tid);
         fwd_compute<A, LOGB, LOGT, K1 + K2, K3, false, true, 0>(v, r3, nullptr, C, tid, 1u);
     }
-#ifdef TFHE_KS_TRACE
-#pragma unroll
-    for (int i = 0; i < E; i++) pin_vgpr(v[i]);
-#endif
-    kst(4);
 }
 // inverse transform of elements held in the forward-last-pass register map (v is reduced here and consumed); result
 // (+ addend) to gdst
 // SCALE = false: the caller has folded N^-1 into its operands (k_ks_fused: into the key rows), the last stage is a plain
 // butterfly instead of two scaling products per pair
-template <class A, int LOGB, int LOGT, bool SCALE = true, bool TWL = false, class AO = A>
+template <class A, int LOGB, int LOGT, bool SCALE = true, class AO = A>
 __device__ __forceinline__ void fused_inv_from_regs(u64* lds, typename A::elem* v, u64* gdst, const typename A::ctx& C, const u64* addend,
                                                     u64* keep = nullptr, u32 pre = 1u) {   // pre: sub-block prefix (2^x + sb) of a larger transform
     constexpr int KI1 = pass_k_inv(LOGB, LOGT, LOGB);
@@ -1796,31 +1685,16 @@ __device__ __forceinline__ void fused_inv_from_regs(u64* lds, typename A::elem* 
     __syncthreads();  // the previous transform's last pass has read LDS
     constexpr int S1 = LOGB - KI1, K2 = pass_k_inv(LOGB, LOGT, S1);
     typedef pgeom<LOGB, LOGT, S1 - K2, K2> G2;
-    if constexpr (TWL) {
-        // middle pass with its twiddles from the LDS table (no register prefetch, no vector loads), last pass as before
-        static_assert(S1 - K2 != 0, "three-pass inverse expected");
-        {
+    typename A::tw tw_next[G2::SETS * G2::NTW];  // middle-pass twiddles, requested before the exchange
+    {
 #pragma unroll
-            for (int e = 0; e < E; e++) v[e] = fp_reduce(v[e], C.p, C.pinv);
-            inv_compute<A, LOGB, LOGT, S1, KI1, true, SCALE, 0, -1, no_hook, true>(v, nullptr, nullptr, C, tid, 1u);
-            inv_store<A, LOGB, LOGT, S1, KI1, true, SCALE>(v, lds, nullptr, C, tid);
-        }
-        __syncthreads();
-        ntt_inv_pass<ArithFpL, LOGB, LOGT, S1 - K2, K2, false, false, SCALE>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
-        __syncthreads();
-        ntt_inv_pass<AO, LOGB, LOGT, 0, S1 - K2, false, true, SCALE>(lds, nullptr, gdst, C, tid, 1u, 0, 0u, addend);
-    } else {
-        typename A::tw tw_next[G2::SETS * G2::NTW];  // middle-pass twiddles, requested before the exchange
-        {
-#pragma unroll
-            for (int e = 0; e < E; e++) v[e] = fp_reduce(v[e], C.p, C.pinv);
-            inv_compute<A, LOGB, LOGT, S1, KI1, true, SCALE, 0, -1, no_hook, true>(v, nullptr, nullptr, C, tid, pre);
-            if constexpr (S1 - K2 != 0) inv_load_tw<A, LOGB, LOGT, S1 - K2, K2, false>(tw_next, C, tid, pre);
-            inv_store<A, LOGB, LOGT, S1, KI1, true, SCALE>(v, lds, nullptr, C, tid);
-        }
-        __syncthreads();
-        inv_schedule_ptw<A, LOGB, LOGT, S1, SCALE, AO>(lds, nullptr, gdst, C, tid, pre, addend, tw_next, keep);
+        for (int e = 0; e < E; e++) v[e] = fp_reduce(v[e], C.p, C.pinv);
+        inv_compute<A, LOGB, LOGT, S1, KI1, true, SCALE, 0, -1, no_hook, true>(v, nullptr, nullptr, C, tid, pre);
+        if constexpr (S1 - K2 != 0) inv_load_tw<A, LOGB, LOGT, S1 - K2, K2, false>(tw_next, C, tid, pre);
+        inv_store<A, LOGB, LOGT, S1, KI1, true, SCALE>(v, lds, nullptr, C, tid);
     }
+    __syncthreads();
+    inv_schedule_ptw<A, LOGB, LOGT, S1, SCALE, AO>(lds, nullptr, gdst, C, tid, pre, addend, tw_next, keep);
 }
 
 // N = 2^(LOGB+2) inverse, fp64 policy, ONE kernel with the two TOP stages FIRST (r04): decimation in frequency on the natural-order
@@ -1911,7 +1785,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_ntt_inv_quad2(const u64* __restri
                 inv_store<A, LOGB, LOGT, S1, K1, true, true>(v, lds, nullptr, C, tid);
             }
             __syncthreads();
-            ntt_inv_pass<A, LOGB, LOGT, KL, K2, false, false, true, TFHE_ES(9) != 0>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
+            ntt_inv_pass<A, LOGB, LOGT, KL, K2, false, false, true>(lds, nullptr, nullptr, C, tid, 1u, 0, 0u);
             __syncthreads();
             {
                 u64 r3[E];
@@ -1974,9 +1848,9 @@ __global__ __launch_bounds__(256) void k_evk_to_f64(const u64* __restrict__ evk,
     }
 }
 // PRELIFT: the rows of c[end] arrive as centred doubles (bfv_contract_narrow<.., LIFTED>): the lift is a bit cast
-template <int LOGB, int LOGT, int MASK>
-constexpr size_t fused_lds_bytes() {
-    return ((size_t)lds_words<LOGB, LOGT>() + (MASK ? 2 * (size_t)fused_tw_words<LOGB, LOGT>() : 0)) * 8;
+template <int LOGB, int LOGT>
+constexpr size_t fused_lds_bytes() {   // the padded row image
+    return (size_t)lds_words<LOGB, LOGT>() * 8;
 }
 // SPMODE (special prime, N <= 2^LOGB): the ModulusRaised contraction inside the kernel instead of a tail kernel over T.
 //   1: the items are the SPECIAL limb of every ciphertext only (nitems = batch); their two coefficient rows t_P go to
@@ -2003,18 +1877,16 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused(const u64* __restrict__ 
     const u32 level = (u32)KA.level, polys = (u32)KA.polys, nw = (u32)KA.nw;
     const u32 add_s = polys == 3 ? 2u : 1u;
     bool first = true;
-#ifndef TFHE_XCD_KS  // measured: nothing on the headline's key switch, - 6 % on a 7-limb one (one limb per XCD: its 32 CUs then
-#define TFHE_XCD_KS 0  // read the same key rows in step, through the same L2 channels) -- the plain walk stays
-#endif
-    const u32 niter = xcd_limb_niter<TFHE_XCD_KS>(gridDim.x, nitems);
+    // the plain walk, not xcd_limb_walk: that measured nothing on the headline's key switch and - 6 % on a 7-limb one (one limb per
+    // XCD: its 32 CUs then read the same key rows in step, through the same L2 channels)
+    const u32 niter = (nitems + gridDim.x - 1) / gridDim.x;
     for (u32 it = 0; it < niter; it++) {
         const u32 nper = SPMODE == 1 ? 1u : (SPMODE >= 2 ? level : nw);   // items per ciphertext
-        const u32 item = xcd_limb_walk<TFHE_XCD_KS>(it, blockIdx.x, gridDim.x, nper, nitems);
-        if (item == ~0u) break;
+        const u32 item = it * gridDim.x + blockIdx.x;
+        if (item >= nitems) break;
         const u32 b = item / nper, j = SPMODE == 1 ? level : item % nper;
         const ntt_limb_t& Lj = LT[KA.w.idx[j]];
         typename A::ctx C = A::make(Lj);
-        if constexpr (TFHE_TWL_KS != 0) fused_fill_tw<A, LOGB, LOGT, TFHE_TWL_KS>(lds, C);
         lift_t lf;
         lf.qj = Lj.q;
         lf.bj = Lj.br;
@@ -2027,8 +1899,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused(const u64* __restrict__ 
             lf.half = lf.qi >> 1;
             const u64* grow = ct + ((size_t)((b * polys + polys - 1) * level + i) << LOGB);
             typename A::elem v[E];
-            kst(1);
-            fused_fwd_to_regs<A, LOGB, LOGT, PRELIFT, (TFHE_TWL_KS & 1) != 0>(lds, grow, C, first, v, &lf);
+            fused_fwd_to_regs<A, LOGB, LOGT, PRELIFT>(lds, grow, C, first, v, &lf);
             // multiply-accumulate with the key: component 1 (masked) feeds out_0, component 0 (mask) feeds out_1
             const u64x2_t* e_pair = (const u64x2_t*)(evd + ((((size_t)i * nw + j) << LOGB) << 1));   // key words as doubles, (mask, masked) per position (k_evk_to_f64, pair)
 #pragma unroll
@@ -2039,12 +1910,8 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused(const u64* __restrict__ 
                 for (int r = 0; r < G3::R; r++) {
                     const u32 nat = (brev_bits((u32)r, K3) << (LOGB - K3)) + c0;
                     const int e = u * G3::R + r;
-#ifdef TFHE_ABL_NOKEYS  // design aid: key words from arithmetic (wrong results, no key traffic)
-                    const typename A::tw k1{(double)(nat | 1u) * 4097.0 + C.pinv}, k0{(double)(nat | 3u) * 257.0 + C.pinv};
-#else
                     const u64x2_t kw = e_pair[nat];
                     const typename A::tw k1{A::from_lds(kw.y)}, k0{A::from_lds(kw.x)};
-#endif
                     // range: y reduced to |y| <= p/2, so every term is <= (1/2 + 0.75 a) p = 0.69 p and eight of them stay
                     // below the 7.9 p exactness limit (fp64arith.h); the accumulators are swept every eighth digit
                     const double y = A::pre_product(v[e], C);
@@ -2061,31 +1928,24 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused(const u64* __restrict__ 
             }
         }
         // inverse transforms of the two accumulators; the first pass takes them from registers (same natural-order map)
-#ifdef TFHE_KS_TRACE
-#pragma unroll
-        for (int e = 0; e < E; e++) { pin_vgpr(acc[0][e]); pin_vgpr(acc[1][e]); }
-#endif
-        kst(5);
 #pragma unroll
         for (int sidx = 0; sidx < 2; sidx++) {
-            if (sidx) kst(6);
             if constexpr (SPMODE >= 2) {   // 3: a rotation finished in the store (ArithFpMDR; KA.rot_g, `ct` the unrotated input)
                 C.md_pinv = (double)KA.pinv[j].w;   // P^-1 mod q_j < 2^52: exact
                 C.md_c = (u32)sidx < add_s ? ct + ((size_t)((b * polys + sidx) * level + j) << LOGB) : zero_row;
                 C.md_g = KA.rot_g;
                 u64* gdst = out + ((size_t)((b * 2 + sidx) * level + j) << LOGB);
                 typedef typename std::conditional<SPMODE == 3, ArithFpMDR, ArithFpMD>::type AOUT;
-                fused_inv_from_regs<A, LOGB, LOGT, false, (TFHE_TWL_KS & 2) != 0, AOUT>(lds, acc[sidx], gdst, C, tsp + ((size_t)(b * 2 + sidx) << LOGB));
+                fused_inv_from_regs<A, LOGB, LOGT, false, AOUT>(lds, acc[sidx], gdst, C, tsp + ((size_t)(b * 2 + sidx) << LOGB));
             } else if constexpr (SPMODE == 1) {
                 u64* gdst = out + ((size_t)(b * 2 + sidx) << LOGB);
-                fused_inv_from_regs<A, LOGB, LOGT, false, (TFHE_TWL_KS & 2) != 0>(lds, acc[sidx], gdst, C, nullptr);
+                fused_inv_from_regs<A, LOGB, LOGT, false>(lds, acc[sidx], gdst, C, nullptr);
             } else {
                 const u64* addend = (!KA.special && (u32)sidx < add_s) ? ct + ((size_t)((b * polys + sidx) * level + j) << LOGB) : nullptr;
                 u64* gdst = out + ((size_t)((b * 2 + sidx) * nw + j) << LOGB);
-                fused_inv_from_regs<A, LOGB, LOGT, false, (TFHE_TWL_KS & 2) != 0>(lds, acc[sidx], gdst, C, addend);  // N^-1 is in the key rows (k_evk_to_f64)
+                fused_inv_from_regs<A, LOGB, LOGT, false>(lds, acc[sidx], gdst, C, addend);  // N^-1 is in the key rows (k_evk_to_f64)
             }
         }
-        kst(7);
     }
 }
 
@@ -2101,12 +1961,6 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused(const u64* __restrict__ 
 // and share the source rows in its L2.
 // ------------------------------------------------------------------------------------------------
 // load phase of k_ks_fused_sub: LDS-DMA streaming (dma_stream_load) at X = 2, piece-wise register loads at X = 1 (measured)
-#ifndef TFHE_FSUB_DMA2
-#define TFHE_FSUB_DMA2 1
-#endif
-#ifndef TFHE_FSUB_DMA1
-#define TFHE_FSUB_DMA1 0
-#endif
 template <class A, int LOGB, int LOGT, int X>
 __global__ __launch_bounds__(1 << LOGT) void k_ks_fused_sub(const u64* __restrict__ evd, const u64* __restrict__ ct,
                                                              u64* __restrict__ T, const ntt_limb_t* __restrict__ LT,
@@ -2144,13 +1998,13 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused_sub(const u64* __restric
             typename A::elem v[E];
             {
                 u64 op[E];  // first-pass operands of this sub-block (element bits)
-                // (the LDS-DMA streaming of dma_stream_load, which pays in k_ntt_fwd_quad, measured 7-9 % SLOWER here: cfg#3
-                // 32.6 k against 35.1 k key switches/s -- the piece-wise register loads below stay)
+                // (the LDS-DMA streaming of dma_stream_load, which pays in k_ntt_fwd_quad and here at X = 2, measured 7-9 % SLOWER at
+                // X = 1: cfg#3 32.6 k against 35.1 k key switches/s -- the piece-wise register loads below stay there)
                 // (r04: the same phase software-pipelined by hand -- inline-asm requests, pieces of 4 points, 24 requests in flight under
                 // the arithmetic of a piece, hand-counted vmcnt waits; bit-exact, scratch unchanged -- measured 7 % SLOWER: 34.1 k against
                 // 36.6 k key switches/s at cfg#3, although a build without the row loads gains 13 %.  profiles/LOG.md.)
                 constexpr int PC = 4 * X, PE = E / PC;  // pieces of the load phase (bounds the raw words in flight)
-                if constexpr (X == 2 ? TFHE_FSUB_DMA2 : TFHE_FSUB_DMA1) {
+                if constexpr (X == 2) {
                     // the 2^X parts: streamed through the LDS as in k_ntt_fwd_quad (the LDS holds no row image here)
                     if (!first) __syncthreads();  // the previous transform's last pass has read LDS
                     dma_stream_load<LOGB, LOGT, 1 << X, 2>(lds, grow, tid, [&](int e, const u64* q) {
@@ -2178,23 +2032,13 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused_sub(const u64* __restric
                         const u32 k = tp + ((u32)(h * PE + r) << LOGT);
 #pragma unroll
                         for (int m = 0; m < (1 << X); m++) {
-#ifdef TFHE_ABL_NOROWS  // design aid: operands from arithmetic (wrong results, no row traffic)
-                            q[m][r] = (u64)(k * 131u + (u32)m * 7919u) + (u64)(size_t)grow; pin_vgpr(q[m][r]);
-#elif defined(TFHE_ABL_TOPONCE)  // design aid (r06, wrong results): a sub-block workgroup loads and lifts ONE of the row's 2^X parts and
-                            // pays no top-stage product -- the upper bound of "the top stage paid once per row" 
-                            if (m == 0) q[m][r] = grow[k + ((sb & ((1u << X) - 1u)) << LOGB)];
-#else
                             q[m][r] = grow[k + ((u32)m << LOGB)];
-#endif
                         }
                     }
                     TFHE_SCHED_FENCE();
 #pragma unroll
                     for (int r = 0; r < PE; r++) {
                         // loosely lifted digits (|v| <= p): sums <= 1.88 p, products <= 1.21 p, <= 3.09 p before the reduction
-#ifdef TFHE_ABL_TOPONCE
-                        const double z = A::from_global_lift(q[0][r], C, lf, true);
-#else
                         double xin[1 << X];
 #pragma unroll
                         for (int m = 0; m < (1 << X); m++) xin[m] = A::from_global_lift(q[m][r], C, lf, true);
@@ -2206,12 +2050,11 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused_sub(const u64* __restric
                             const double yb = fp_fma(sgn_h, fp_mulmod_c(xin[3], w1, C.p, C.pinv), xin[1]);
                             z = fp_fma(sgn_q, fp_mulmod_c(yb, w2, C.p, C.pinv), ya);
                         }
-#endif
                         op[h * PE + r] = A::to_lds(A::top_reduce(z, C));
                     }
                     TFHE_SCHED_FENCE();
                 }
-                constexpr bool DMA = X == 2 ? TFHE_FSUB_DMA2 : TFHE_FSUB_DMA1;
+                constexpr bool DMA = X == 2;
                 if (!DMA && !first) __syncthreads();  // the previous transform's last pass has read LDS
                 first = false;
                 fwd_compute<A, LOGB, LOGT, 0, K1, false, false, 0>(v, op, nullptr, C, tid, pre);
@@ -2260,7 +2103,7 @@ __global__ __launch_bounds__(1 << LOGT) void k_ks_fused_sub(const u64* __restric
         for (int sidx = 0; sidx < 2; sidx++) {
             u64* gdst = T + ((size_t)((b * 2 + sidx) * nw + j) << (LOGB + X)) + ((size_t)sb << LOGB);
             // (r04: the middle pass's twiddles requested before the exchange, as in k_ks_fused)
-            fused_inv_from_regs<A, LOGB, LOGT, false, false, A>(lds, acc[sidx], gdst, C, nullptr, nullptr, pre);
+            fused_inv_from_regs<A, LOGB, LOGT, false>(lds, acc[sidx], gdst, C, nullptr, nullptr, pre);
         }
     }
 }
@@ -2308,7 +2151,6 @@ __global__ __launch_bounds__(1 << LOGT) void k_bfv_core_fused(const u64* __restr
         if (item == ~0u) break;
         const u32 b = item / nb, j = item % nb;
         typename A::ctx C = A::make(LT[sel.idx[j]]);
-        if constexpr (TFHE_TWL_CORE != 0) fused_fill_tw<A, LOGB, LOGT, TFHE_TWL_CORE>(lds, C);
         const size_t r0 = ((size_t)(b * 2 + 0) * nb + j) << LOGB, r1 = ((size_t)(b * 2 + 1) * nb + j) << LOGB;
         const u32 onb = (MODE & CORE_PACKED) ? (u32)alt.ns : nb, oj = (MODE & CORE_PACKED) ? (u32)alt.idx[j] : j;
         u64* const t0 = T + (((size_t)(b * 3 + 0) * onb + oj) << LOGB);
@@ -2343,14 +2185,14 @@ __global__ __launch_bounds__(1 << LOGT) void k_bfv_core_fused(const u64* __restr
                         v[u * G3::R + r] = m;
                     }
                 }
-                fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, k == 0 ? t0 : k == 1 ? t1 : t2, C, nullptr);
+                fused_inv_from_regs<A, LOGB, LOGT, true, AO>(lds, v, k == 0 ? t0 : k == 1 ? t1 : t2, C, nullptr);
             }
             continue;
         }
-        fused_fwd_to_regs<A, LOGB, LOGT, false, (TFHE_TWL_CORE & 1) != 0>(lds, pa0, C, first, A0);
+        fused_fwd_to_regs<A, LOGB, LOGT>(lds, pa0, C, first, A0);
 #pragma unroll
         for (int e = 0; e < E; e++) A0[e] = fp_reduce(A0[e], C.p, C.pinv);
-        fused_fwd_to_regs<A, LOGB, LOGT, false, (TFHE_TWL_CORE & 1) != 0>(lds, pa1, C, first, A1);
+        fused_fwd_to_regs<A, LOGB, LOGT>(lds, pa1, C, first, A1);
 #pragma unroll
         for (int e = 0; e < E; e++) A1[e] = fp_reduce(A1[e], C.p, C.pinv);
         if constexpr ((MODE & CORE_SQUARE) != 0) {
@@ -2358,16 +2200,16 @@ __global__ __launch_bounds__(1 << LOGT) void k_bfv_core_fused(const u64* __restr
             // the general form; the held rows survive the inverse transforms of v
 #pragma unroll
             for (int e = 0; e < E; e++) v[e] = fp_mulmod_c(A0[e], ftw_t{A0[e]}, C.p, C.pinv);
-            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, t0, C, nullptr);
+            fused_inv_from_regs<A, LOGB, LOGT, true, AO>(lds, v, t0, C, nullptr);
 #pragma unroll
             for (int e = 0; e < E; e++) { const double m = fp_mulmod_c(A1[e], ftw_t{A0[e]}, C.p, C.pinv); v[e] = m + m; }
-            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, t1, C, nullptr);
+            fused_inv_from_regs<A, LOGB, LOGT, true, AO>(lds, v, t1, C, nullptr);
 #pragma unroll
             for (int e = 0; e < E; e++) v[e] = fp_mulmod_c(A1[e], ftw_t{A1[e]}, C.p, C.pinv);
-            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, t2, C, nullptr);
+            fused_inv_from_regs<A, LOGB, LOGT, true, AO>(lds, v, t2, C, nullptr);
             continue;
         }
-        fused_fwd_to_regs<A, LOGB, LOGT, false, (TFHE_TWL_CORE & 1) != 0>(lds, pb0, C, first, v);
+        fused_fwd_to_regs<A, LOGB, LOGT>(lds, pb0, C, first, v);
         {
             const u32 tid = fresh_tid();
 #pragma unroll
@@ -2382,9 +2224,9 @@ __global__ __launch_bounds__(1 << LOGT) void k_bfv_core_fused(const u64* __restr
                     v[e] = fp_mulmod_c(v[e], ftw_t{A0[e]}, C.p, C.pinv);                                // a0 b0, in place
                 }
             }
-            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, v, t0, C, nullptr);
+            fused_inv_from_regs<A, LOGB, LOGT, true, AO>(lds, v, t0, C, nullptr);
         }
-        fused_fwd_to_regs<A, LOGB, LOGT, false, (TFHE_TWL_CORE & 1) != 0>(lds, pb1, C, first, v);
+        fused_fwd_to_regs<A, LOGB, LOGT>(lds, pb1, C, first, v);
         {
             const u32 tid = fresh_tid();
 #pragma unroll
@@ -2399,8 +2241,8 @@ __global__ __launch_bounds__(1 << LOGT) void k_bfv_core_fused(const u64* __restr
                     A1[e] = fp_mulmod_c(v[e], ftw_t{A1[e]}, C.p, C.pinv);
                 }
             }
-            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, A0, t1, C, nullptr);
-            fused_inv_from_regs<A, LOGB, LOGT, true, (TFHE_TWL_CORE & 2) != 0, AO>(lds, A1, t2, C, nullptr);
+            fused_inv_from_regs<A, LOGB, LOGT, true, AO>(lds, A0, t1, C, nullptr);
+            fused_inv_from_regs<A, LOGB, LOGT, true, AO>(lds, A1, t2, C, nullptr);
         }
     }
 }

@@ -31,7 +31,7 @@ size_t mr_ks_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t ba
 
 // parking rows (N words each) the two fused cores may ask for: one per workgroup (k_bfv_core_fused; k_mul_core_int below 2^14), two per
 // workgroup at 2^14 (k_mul_core_int) -- the grids are at most two workgroups per CU below 2^14 and one at 2^14
-size_t mr_park_rows(const tfhe_ctx* c) { return (size_t)2 * std::max(256, c->num_cus) * TFHE_GRID_MULT_CORE; }
+size_t mr_park_rows(const tfhe_ctx* c) { return (size_t)2 * std::max(256, c->num_cus); }
 
 // the subset `mask` (positions in the ciphertext) of the first `level` limbs as a selection + its place in the packed buffers
 void mr_subset(int level, u32 mask, const u64* a, const u64* b, limb_sel_t* sel, core_alt_t* alt) {
@@ -64,8 +64,8 @@ int mr_core_fp(tfhe_ctx* c, const u64* a, const u64* b, u64* T, u64* scratch, in
         else if (ntt_in) kern = k_bfv_core_fused<ArithFp, LOGB, LOGT, false, CORE_PACKED | CORE_NTTIN>;
         else if constexpr (LOGB < 14) kern = k_bfv_core_fused<ArithFp, LOGB, LOGT, false, CORE_PACKED>;
         if (!kern) return fail(TFHE_E_UNSUPPORTED, "internal: this form of the fused product core is not built at N = 2^%d", LOGB);
-        const unsigned grid = cu_grid(c, items, (LOGB == 14 ? 1u : 2u) * TFHE_GRID_MULT_CORE);
-        return launch_prof(c, mr_transforms(items, square, ntt_in), kern, dim3(grid), dim3(1 << LOGT), fused_lds_bytes<LOGB, LOGT, TFHE_TWL_CORE>(), a, b, T,
+        const unsigned grid = cu_grid(c, items, LOGB == 14 ? 1u : 2u);
+        return launch_prof(c, mr_transforms(items, square, ntt_in), kern, dim3(grid), dim3(1 << LOGT), fused_lds_bytes<LOGB, LOGT>(), a, b, T,
                            scratch, c->limbs_dev, sel, items, alt);
     });
 }
@@ -82,7 +82,7 @@ int mr_core_int(tfhe_ctx* c, const u64* a, const u64* b, u64* T, u64* scratch, i
                     : square           ? k_mul_core_int<LOGB, LOGT, CORE_PACKED | CORE_SQUARE>
                     : ntt_in           ? k_mul_core_int<LOGB, LOGT, CORE_PACKED | CORE_NTTIN>
                                        : k_mul_core_int<LOGB, LOGT, CORE_PACKED>;
-        const unsigned grid = cu_grid(c, items, (LOGB == 14 ? 1u : 2u) * TFHE_GRID_MULT_CORE);
+        const unsigned grid = cu_grid(c, items, LOGB == 14 ? 1u : 2u);
         return launch_prof(c, mr_transforms(items, square, ntt_in), kern, dim3(grid), dim3(1 << LOGT), (size_t)lds_words<LOGB, LOGT>() * 8, T, scratch,
                            c->limbs_dev, sel, items, alt);
     });

@@ -213,9 +213,6 @@ struct ArithFp {
         const ftwd_t *W, *Winv, *Wb, *Winvb;
         ftw_t ninv, w1n;
         u64 q;
-        // LDS copies of the first 2^(K1+K2) entries of W / Winv (the first and middle passes' twiddles), set by the fused
-        // kernels; read through ArithFpL
-        const ftwd_t *Wl = nullptr, *Winvl = nullptr;
         // ArithFpMD (k_ks_fused, SPMODE 2): P^-1 mod p and the addend row c (or a row of zeros) of the contraction
         double md_pinv = 0.0;
         const u64* md_c = nullptr;
@@ -249,26 +246,17 @@ struct ArithFp {
         return ftw_t{tab[i]};
 #endif
     }
-#ifndef TFHE_ABL_NOTW  // design aid: bit 0 -- first / middle pass twiddles all from one cache line, bit 1 -- boundary pass
-#define TFHE_ABL_NOTW 0  // (wrong results; same instructions and registers, the loads hit the vector L1)
-#endif
-    static TFHE_HD tw ld_fwd(const ctx& c, u32 i) { return ld(c.W, (TFHE_ABL_NOTW & 1) ? (i & 7u) : i); }
-    static TFHE_HD tw ld_inv(const ctx& c, u32 i) { return ld(c.Winv, (TFHE_ABL_NOTW & 1) ? (i & 7u) : i); }
-    static TFHE_HD tw ld_fwd_b(const ctx& c, u32 i) { return ld(c.Wb, (TFHE_ABL_NOTW & 2) ? (i & 7u) : i); }
-    static TFHE_HD tw ld_inv_b(const ctx& c, u32 i) { return ld(c.Winvb, (TFHE_ABL_NOTW & 2) ? (i & 7u) : i); }
+    static TFHE_HD tw ld_fwd(const ctx& c, u32 i) { return ld(c.W, i); }
+    static TFHE_HD tw ld_inv(const ctx& c, u32 i) { return ld(c.Winv, i); }
+    static TFHE_HD tw ld_fwd_b(const ctx& c, u32 i) { return ld(c.Wb, i); }
+    static TFHE_HD tw ld_inv_b(const ctx& c, u32 i) { return ld(c.Winvb, i); }
     static TFHE_HD bool has_b(const ctx& c) { return c.Wb != nullptr; }
     static TFHE_HD void bf_fwd(elem& x, elem& y, tw w, const ctx& c) {
-#ifdef TFHE_ABL_NOALU
-        x += w.w; return;
-#endif
         const double t = fp_mulmod_c(y, w, c.p, c.pinv);
         y = x - t;
         x = x + t;
     }
     static TFHE_HD void bf_inv(elem& x, elem& y, tw w, const ctx& c) {
-#ifdef TFHE_ABL_NOALU
-        x += w.w; return;
-#endif
         const double a = x + y, d = x - y;
         x = a;
         y = fp_mulmod_c(d, w, c.p, c.pinv);
@@ -286,18 +274,6 @@ struct ArithFp {
     static TFHE_HD u64 out_fwd(elem v, const ctx& c) { return fp_canon(v, c.p, c.pinv); }
     static TFHE_HD u64 out_inv_scaled(elem v, const ctx& c) { return fp_canon(v, c.p, c.pinv); }
     static TFHE_HD u64 out_inv_lazy(elem v, const ctx& c) { return fp_canon(v, c.p, c.pinv); }
-};
-// ArithFp with the middle pass's twiddles read from LDS (ctx::Wl / Winvl, filled once per item by the fused kernels).  In those
-// kernels the middle pass's 31 twiddle words per thread were vector loads requested a few butterflies ahead of their use
-// (256 registers leave no room to request them earlier): every stage began with an exposed L2 round trip in both waves of a
-// SIMD, and the loads shared the in-order vmcnt with the row traffic.  The table is 8 KiB per direction (stages < K1 + K2:
-// 2^10 entries) next to the 132 KiB row image; a 16-lane group reads one entry (broadcast).
-// The table is padded by one word per 16 (entry i at i + (i >> 4)): the 16-lane groups of a wave read entries 2^d apart, which
-// unpadded fall into the same banks for d = 4 (128 bytes apart) and d = 3.
-TFHE_HD u32 tw_lds_pos(u32 i) { return i + (i >> 4); }
-struct ArithFpL : ArithFp {
-    static TFHE_HD tw ld_fwd(const ctx& c, u32 i) { return ftw_t{c.Wl[tw_lds_pos(i)]}; }
-    static TFHE_HD tw ld_inv(const ctx& c, u32 i) { return ftw_t{c.Winvl[tw_lds_pos(i)]}; }
 };
 // ArithFp whose transform OUTPUT is the reduced lazy double (|r| <= p/2 + 1, as a bit pattern) instead of the canonical word:
 // three instructions per element instead of nine.  For the tensor rows between k_bfv_core_fused and the narrow contraction
@@ -466,36 +442,9 @@ TFHE_HD void fwd_load_tw(typename A::tw* tw, const typename A::ctx& C, u32 tid, 
                                                         : A::ld_fwd(C, (pre << (S0 + d)) + (hi << d) + (u32)g);
     }
 }
-// Design aid (r06, wrong results by design): -DTFHE_ABL_NOXCHG=<bits> takes the pass-to-pass exchange out of every transform so that
-// its share of a fused kernel's time can be MEASURED (profiles/LOG.md round 6): bit 0 -- __syncthreads() becomes a compiler barrier (no
-// s_barrier, the waits on the LDS counters stay where the data dependences put them); bit 1 -- the LDS reads / writes between two
-// passes are replaced by register pins (the address arithmetic stays: the "read" returns its own address); bit 2 -- only the writes;
-// bit 3 -- only the reads.  Same butterflies, same global loads and stores.  (r06: with bit 1 or bit 3 the fused kernels leave their
-// zero-scratch allocation -- 168-412 B -- and run 22 % SLOWER: the builds bound nothing; bit 0 and bit 2 keep the allocation.)
-#ifndef TFHE_ABL_NOXCHG
-#define TFHE_ABL_NOXCHG 0
-#endif
-#if (TFHE_ABL_NOXCHG & 1) && defined(__HIP_DEVICE_COMPILE__)
-#define __syncthreads() asm volatile("" ::: "memory")
-#endif
-TFHE_HD u64 xchg_rd(const u64* lds, u32 i) {
-#if (TFHE_ABL_NOXCHG & (2 | 8)) && defined(__HIP_DEVICE_COMPILE__)
-    u64 r = (u64)i;   // (not the pointer: a generic address of the LDS array costs an aperture test per read)
-    (void)lds;
-    asm volatile("" : "+v"(r));
-    return r;
-#else
-    return lds[i];
-#endif
-}
-TFHE_HD void xchg_wr(u64* lds, u32 i, u64 v) {
-#if (TFHE_ABL_NOXCHG & (2 | 4)) && defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" ::"v"(v), "v"(i));
-    (void)lds;
-#else
-    lds[i] = v;
-#endif
-}
+// the pass-to-pass exchange: one LDS word
+TFHE_HD u64 xchg_rd(const u64* lds, u32 i) { return lds[i]; }
+TFHE_HD void xchg_wr(u64* lds, u32 i, u64 v) { lds[i] = v; }
 // raw 64-bit words of the operands (global: residues; LDS: the policy's element bits)
 template <int LOGB, int LOGT, int S0, int K, bool FIRST, bool LAST, int USEL = -1>
 TFHE_HD void fwd_load_data(u64* raw, const u64* lds, const u64* gsrc, u32 tid, const lift_t* lift = nullptr) {

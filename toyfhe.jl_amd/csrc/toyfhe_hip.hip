@@ -560,12 +560,6 @@ bool bfv_core_fusable(const tfhe_ctx* c, const limb_sel_t& sel) { return c->vari
 // forward transforms + tensor + inverse transforms of one BFV multiplication chunk in one kernel (fp64 policy, N = 2^12 .. 2^14:
 // the reference's own BFV tests run at 2^11 - 2^12, test/bfv_crt.jl:8, and its MNIST parameters at 2^13, infer.jl:97);
 // *done = false when the configuration is not covered.  scratch: one row per workgroup.
-#ifndef TFHE_GRID_MULT_CORE  // workgroups per CU slot in the grids of the two fused kernels (> 1: the dispatcher balances the items)
-#define TFHE_GRID_MULT_CORE 1u
-#endif
-#ifndef TFHE_GRID_MULT_KS
-#define TFHE_GRID_MULT_KS 1u
-#endif
 int launch_bfv_core_fused(tfhe_ctx* c, const u64* Ea, const u64* Eb, u64* T, u64* scratch, int64_t nct, const limb_sel_t& sel, bool* done,
                           const core_alt_t* altp = nullptr, bool out_double = false) {
     *done = false;
@@ -577,9 +571,9 @@ int launch_bfv_core_fused(tfhe_ctx* c, const u64* Ea, const u64* Eb, u64* T, u64
         constexpr int LOGB = decltype(lb)::value, LOGT = logt_for(LOGB);
         auto kern = out_double ? k_bfv_core_fused<ArithFp, LOGB, LOGT, true> : k_bfv_core_fused<ArithFp, LOGB, LOGT, false>;
         // one 512-thread workgroup fills a CU at 2^14; the 256-thread workgroups of the smaller rings leave room for a second one
-        const unsigned grid = cu_grid(c, items, (LOGB == 14 ? 1u : 2u) * TFHE_GRID_MULT_CORE);
+        const unsigned grid = cu_grid(c, items, LOGB == 14 ? 1u : 2u);
         // limb transforms inside this launch: 4 forward + 3 inverse per item
-        return launch_prof(c, (int64_t)items * 7, kern, dim3(grid), dim3(1 << LOGT), fused_lds_bytes<LOGB, LOGT, TFHE_TWL_CORE>(), Ea, Eb, T, scratch,
+        return launch_prof(c, (int64_t)items * 7, kern, dim3(grid), dim3(1 << LOGT), fused_lds_bytes<LOGB, LOGT>(), Ea, Eb, T, scratch,
                            c->limbs_dev, sel, items, alt);
     });
     if (rc) return rc;
@@ -1013,10 +1007,7 @@ static int do_galois(tfhe_ctx* c, const u64* src, u64* dst, u64 g, int64_t rows,
         const unsigned grid = (unsigned)std::min<int64_t>(rows, (int64_t)c->num_cus * per_cu);
         return launch(c, k_galois_lds<T>, dim3(grid), dim3(T), lds, src, dst, c->limbs_dev, sel, g, (u32)c->N, (u32)rows);
     }
-#ifndef TFHE_GALOIS_XCD
-#define TFHE_GALOIS_XCD 1
-#endif
-    if (TFHE_GALOIS_XCD && c->variant == 0 && c->logN >= 15 && rows % sel.n == 0 && rows / sel.n >= 16) {
+    if (c->variant == 0 && c->logN >= 15 && rows % sel.n == 0 && rows / sel.n >= 16) {
         // whole polynomials, enough of them: the XCD-cooperative scatter (k_galois_xcd)
         return launch(c, k_galois_xcd, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, src, dst, c->limbs_dev, sel, g, (u32)c->N, (u32)(rows / sel.n));
     }
@@ -1355,10 +1346,10 @@ static int ks_chunk(tfhe_ctx* c, int Lk, int level, int special, const u64* evk,
             if (g_tail && c->logN != 14) return fail(TFHE_E_UNSUPPORTED, "internal: rotation in the store is an N = 2^14 path");
             if (c->logN == 13) {
                 constexpr int LOGT = logt_for(13);
-                return launch2(k_ks_fused<ArithFp, 13, LOGT, false, 1>, k_ks_fused<ArithFp, 13, LOGT, false, 2>, LOGT, fused_lds_bytes<13, LOGT, TFHE_TWL_KS>(), 2u);
+                return launch2(k_ks_fused<ArithFp, 13, LOGT, false, 1>, k_ks_fused<ArithFp, 13, LOGT, false, 2>, LOGT, fused_lds_bytes<13, LOGT>(), 2u);
             }
             constexpr int LOGT = logt_for(14);
-            const size_t lds = fused_lds_bytes<14, LOGT, TFHE_TWL_KS>();
+            const size_t lds = fused_lds_bytes<14, LOGT>();
             if (!g_tail) return launch2(k_ks_fused<ArithFp, 14, LOGT, false, 1>, k_ks_fused<ArithFp, 14, LOGT, false, 2>, LOGT, lds, 1u);
             // rotation finished in the second launch's stores (SPMODE 3; `ct` is the unrotated input)
             A.rot_g = (u32)(g_tail & (2 * (u64)c->N - 1));
@@ -1368,12 +1359,12 @@ static int ks_chunk(tfhe_ctx* c, int Lk, int level, int special, const u64* evk,
         if (c->logN == 14) {
             constexpr int LOGT = logt_for(14);
             auto fk = prelifted ? k_ks_fused<ArithFp, 14, LOGT, true> : k_ks_fused<ArithFp, 14, LOGT, false>;
-            rc = launch_prof(c, transforms, fk, dim3(cu_grid(c, items, TFHE_GRID_MULT_KS)), dim3(1 << LOGT), fused_lds_bytes<14, LOGT, TFHE_TWL_KS>(), evd, ct,
+            rc = launch_prof(c, transforms, fk, dim3(cu_grid(c, items)), dim3(1 << LOGT), fused_lds_bytes<14, LOGT>(), evd, ct,
                              special ? S : out, c->limbs_dev, A, Lk, items, none, none);
         } else {  // N = 2^13: 256 threads x 32 elements, 65 KiB of LDS; 478 registers per thread, so one workgroup per CU is resident
                   // (capped to two resident workgroups it measured 5 % slower)
             constexpr int LOGT = logt_for(13);
-            rc = launch_prof(c, transforms, k_ks_fused<ArithFp, 13, LOGT, false>, dim3(cu_grid(c, items, 2u)), dim3(1 << LOGT), fused_lds_bytes<13, LOGT, TFHE_TWL_KS>(),
+            rc = launch_prof(c, transforms, k_ks_fused<ArithFp, 13, LOGT, false>, dim3(cu_grid(c, items, 2u)), dim3(1 << LOGT), fused_lds_bytes<13, LOGT>(),
                              evd, ct, special ? S : out, c->limbs_dev, A, Lk, items, none, none);
         }
         if (rc || !special) return rc;
@@ -2062,13 +2053,3 @@ int tfhe_event_elapsed_ms(void* a, void* b, float* ms) {
 #include "mul_api.inc"
 #include "enc_api.inc"
 #include "keygen_api.inc"
-
-#ifdef TFHE_KS_TRACE
-extern "C" int tfhe_debug_kstrace(unsigned long long* out, unsigned* n, int reset) {
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(tfhe_kst), sizeof(unsigned long long) * 4096);
-    hipMemcpyFromSymbol(n, HIP_SYMBOL(tfhe_kst_n), sizeof(unsigned));
-    if (reset) { unsigned z = 0; hipMemcpyToSymbol(HIP_SYMBOL(tfhe_kst_n), &z, sizeof z); }
-    return 0;
-}
-#endif
