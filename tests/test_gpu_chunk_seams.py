@@ -114,7 +114,7 @@ def test_keyswitch_across_chunks(N, qspec, special):
 @pytest.mark.parametrize("N,qspec", KS_RINGS)
 def test_rotations_across_chunks(N, qspec, special):
     """tfhe_rotate, tfhe_rotate_prepared and tfhe_rotate_many (plain and prepared keys): the key prepared once outside the chunk
-    loop (k_evk_to_f64 with the rotation folded in, the rot_key_prep copy), the rotation finished in the tail on a last chunk
+    loop (k_evk_to_f64 with the rotation folded in, the k_ntt_perm copy of the key), the rotation finished in the tail on a last chunk
     below 8 ciphertexts, and the [n_rot][batch] layout of tfhe_rotate_many -- got[r, b] is rotation r of ciphertext b."""
     qs = ring_of(N, qspec)
     Lk = len(qs)

@@ -250,7 +250,7 @@ def test_fused_keyswitch_with_34_working_limbs_wraps_the_grid(logn, special):
 def test_keyswitch_sub_block_paths_on_both_sides_of_the_seam(logn, kind, nw):
     """N = 2^15 / 2^16 with the special prime at nw = 32 and 33 working limbs.  Uniform 40-bit ring: k_ks_fused_sub (X = 1 / 2,
     ArithFpS).  Mixed ring (60-bit q0 and special prime around 40-bit primes): at nw = 32 the last shape that takes lift_mixed,
-    the two lanes and ks_tail16's masked walk, at nw = 33 the first that must stay on the unmasked u64 kernels.  One
+    the two lanes and the tail16 form's masked walk, at nw = 33 the first that must stay on the unmasked u64 kernels.  One
     ciphertext (at 2^16 and nw = 33 the digit rows alone are 0.55 GB); 2 and 3 components at 2^15."""
     N, level = 1 << logn, nw - 1
     qs = H.chain(40, nw, N) if kind == "uniform" else ML.mixed(nw, N)

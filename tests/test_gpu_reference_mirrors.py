@@ -206,7 +206,7 @@ def test_matmul_diag_is_bit_identical_to_rotate_many_and_dot(logn, bits, n_rot, 
     finishes the rotations in the evaluation domain (k_md_*: one inverse transform per key sum, the unsigned lift of the
     permuted special limb; at N = 2^16 fused into the forward transforms, with an even number of limbs through the dense
     masked walk, with fp64-size limbs under a 60-bit special prime through the two-halves lift); rotate_many is the
-    coefficient-domain path (k_ks_rot_tail / ks_finish): the two must agree bit for bit.  Without the special prime both
+    coefficient-domain path (k_ks_rot_tail / tfhe_rotate_many): the two must agree bit for bit.  Without the special prime both
     take the coefficient-domain tail."""
     N = 1 << logn
     qs, used = [], set()

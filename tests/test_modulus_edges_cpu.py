@@ -54,7 +54,12 @@ def test_class_thresholds_match_the_engine_sources():
     h = _src("toyfhe_hip.hip")
     assert int(re.search(r"return 1ll << \(\(l >= 0 && l < 40\) \? l : (\d+)\);", h).group(1)) == 20 == H.MIXED_MIN_WORDS.bit_length() - 1
     assert "q[l] >= (1ull << 62)" in h and H.Q_LIMIT == 1 << 62
-    assert "small = small && c->q[A.w.idx[j]] < TFHE_FPS_QMAX" in h
+    # ArithFpS only behind the plan's flag, and the flag only after EVERY working limb was compared against TFHE_FPS_QMAX
+    ks = _src("ks_api.inc")
+    assert "for (int j = 0; j < nw; j++) small = small && c->q[A.w.idx[j]] < TFHE_FPS_QMAX;" in ks
+    assert len(re.findall(r"\bfps = ", ks)) == 1 and "P.fps = small && fps_on;" in ks
+    assert len(re.findall(r"\?\s*k_ks_fused_sub<ArithFpS", ks)) == 2 == len(re.findall(r"P\.fps \? k_ks_fused_sub<ArithFpS", ks))
+    assert "ArithFpS" not in h
 
 
 def test_range_plans_cover_their_class_tops():

@@ -2309,7 +2309,7 @@ __global__ __launch_bounds__(256) void k_ks_rescale_add(const u64* __restrict__ 
 // Hoisted rotations, the tail for ALL rotations of a diagonal product in one launch: T = INTT(S') [R][batch][2][nw][N] holds the
 // inverse-transformed key sums of the unrotated digits; rotation r's result is sigma_g( . ) applied per limb in the coefficient
 // domain (a signed permutation, BEFORE the floor of the ModulusRaised contraction, which does not commute with sign changes;
-// see ks_finish), then out_j = sigma_g(c)_j + (T'_j - [T'_P]) P^-1 (special) or sigma_g(c)_j + T'_j, for s = 0 only the addend.
+// see tfhe_rotate_many), then out_j = sigma_g(c)_j + (T'_j - [T'_P]) P^-1 (special) or sigma_g(c)_j + T'_j, for s = 0 only the addend.
 // Scatter form: the three source rows (T_j, T_P, c_j) are read in order -- coalesced -- and coefficient i goes to position
 // g i mod N with the sign of floor(g i / N); the 8-byte stores of a row land in a 512 KiB window that stays in the L2 until its
 // lines are complete.  (The gather form -- three scattered 8-byte reads per output -- ran at 0.85 TB/s and was 38 % of the

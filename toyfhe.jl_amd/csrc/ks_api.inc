@@ -1,0 +1,842 @@
+// ks_api.inc -- the key switch: tfhe_keyswitch, the rotations, tfhe_matmul_diag and tfhe_keyswitch_window; included by
+// toyfhe_hip.hip before bfv_api.inc and mul_api.inc, which call keyswitch_impl, ks_prelift_ok and ks_plan.
+//
+// Key switching (rlwe_she.jl:315-347).  By linearity of the NTT the expanded inputs never need transforming:
+// out_s = c_s + INTT(S_s)  (plain)   or   c_s + modswitch-part of INTT(S_s)  (ModulusRaised),
+// with S_s = Σ_i evk_{i,s} ⊙ NTT(digit_i)  (see k_ks_inner, k_ks_rescale_add); the buffers are laid out at ks_plan_t.
+
+// whether the fused key switches (k_ks_fused at N = 2^13 / 2^14, k_ks_fused_sub at 2^15 / 2^16) take this ring and level
+static bool ks_fused14(const tfhe_ctx* c, int Lk, int level, int special) {
+    const limb_sel_t w = working_limbs(Lk, level, special);
+    if (c->variant != 0) return false;
+    if (c->logN == 14) return sel_fp(c, w, 0);
+    if (c->logN == 13) {  // the 256 x 32 geometry: same fused kernel (it takes 256 VGPRs + 222 AGPRs: one workgroup per CU)
+        static const bool on = env_flag("TFHE_FUSED13", true);
+        return on && sel_fp(c, w, 0);
+    }
+    if (c->logN == 16) {  // k_ks_fused_sub at X = 2
+        static const bool on16 = env_flag("TFHE_FUSED16", true);
+        return on16 && level >= 2 && sel_fp(c, w, 2);
+    }
+    return c->logN == 15 && level >= 2 && sel_fp(c, w, 1);  // k_ks_fused_sub
+}
+// pre-lifted c[end] rows (centred doubles from the BFV contraction) are understood by k_ks_fused only
+static bool ks_prelift_ok(const tfhe_ctx* c, int level) {
+    if (c->logN != 14 || !ks_fused14(c, level, level, 0)) return false;
+    u64 lo = ~0ull, hi = 0;  // the bit-cast lift keeps |digit| <= q_i / 2 unreduced: needs q_i <= 2 q_j for every pair
+    for (int j = 0; j < level; j++) { lo = std::min(lo, c->q[j]); hi = std::max(hi, c->q[j]); }
+    return hi <= 2 * lo;
+}
+// the top stages of an N = 2^15 / 2^16 forward transform with the lift of ntt_io_t mode 1 fused into their loads (the u64 limbs of
+// rings that mix modulus sizes), into the transform scratch `t`
+static int launch_top_lift(tfhe_ctx* c, const u64* src, u64* t, int64_t rows, const limb_sel_t& sel, const ntt_io_t& io) {
+    const int x = c->logN - 14;
+    const dim3 tg((unsigned)((((c->N >> x) + 255) / 256) * rows));
+    return dispatch_int<1, 2>(x, [&](auto xc) {
+        return launch(c, k_ntt_fwd_top_lift<decltype(xc)::value>, tg, dim3(256), 0, src, t, c->limbs_dev, sel, c->logN, io);
+    });
+}
+// Part A of the unfused key switch: the NTT-domain RNS digits of c[end], dig [batch][level][nw][N]
+// (centred lift of limb i into every working limb, rlwe_she.jl:326-329, then forward transforms).
+static int ks_digits_fwd(tfhe_ctx* c, const ks_arg_t& A, const u64* ct, u64* dig, int64_t batch) {
+    const int level = A.level, nw = A.nw, polys = A.polys;
+    const u32 n = (u32)c->N;
+    int rc;
+    const bool lift_fused = c->logN <= 14 || ((c->logN == 15 || c->logN == 16) && c->variant == 0 && sel_fp(c, A.w, c->logN - 14) &&
+                                              (((uintptr_t)ct | (uintptr_t)dig) & 15u) == 0);
+    // rings that mix fp64-size moduli with larger ones (infer.jl:97-112: 60-bit q0 and special prime next to 40-bit primes)
+    // at N = 2^15 / 2^16: the fp64-size working limbs take the lift-fused one-kernel transforms (the fp64 lift reads source
+    // limbs of either size), the others go through the digit buffer and the u64 kernels
+    const policy_split_t ps = policy_split(c, A.w);
+    const u32 fpmask = ps.fpmask, allmask = ps.all;
+    const bool lift_mixed = !lift_fused && nw <= 32 && (c->logN == 15 || c->logN == 16) && c->variant == 0 && ps.mixed_fp() &&
+                            (((uintptr_t)ct | (uintptr_t)dig) & 15u) == 0;
+    if (lift_fused) {
+        // digits: centred lift of limb i of c[end] into every working limb, fused into the forward NTT's loads
+        ntt_io_t io = io_plain();
+        io.mode = 1; io.level = (u32)level; io.nw = (u32)nw; io.polys = (u32)polys;
+        rc = run_ntt(c, false, ct, dig, batch * level * nw, A.w, &io);
+        if (rc) return rc;
+    } else if (lift_mixed) {
+        ntt_io_t io = io_plain();
+        io.mode = 1; io.level = (u32)level; io.nw = (u32)nw; io.polys = (u32)polys; io.limb_mask = fpmask;
+        const int64_t rows = batch * level * nw;
+        const int x = c->logN - 14;
+        void* tmp = nullptr;
+        rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);   // (before the fork: growing the workspace synchronises)
+        if (rc) return rc;
+        lanes_t lanes(c);   // the fp64-size working limbs on the side lane, beside the u64 ones
+        lanes.use(1);
+        rc = run_ntt_large(c, false, ct, dig, rows, A.w, io, &io, true, true);
+        if (rc) return rc;
+        lanes.use(0);
+        // the larger working limbs: lift fused into the top-stage kernel (into the transform scratch), then the u64 block kernels
+        ntt_io_t iw = io;
+        iw.limb_mask = allmask & ~fpmask;
+        rc = launch_top_lift(c, ct, (u64*)tmp, rows, A.w, iw);
+        if (rc) return rc;
+        ntt_io_t ib = io_plain();
+        ib.limb_mask = allmask & ~fpmask;
+        rc = launch_block_fwd<ArithInt, 14>(c, (const u64*)tmp, dig, rows, A.w, x, ib);
+        if (rc) return rc;
+    } else {
+        rc = launch(c, k_ks_digits, row_grid((unsigned)(batch * level * nw), (size_t)c->N), dim3(256), 0, ct, dig, c->limbs_dev, A, n, 0u);
+        if (rc) return rc;
+        rc = run_ntt(c, false, dig, dig, batch * level * nw, A.w);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
+
+// tfhe_matmul_diag, evaluation-domain form: U[grp][j] = NTT_j( [P[grp]] mod q_j ) (x P^-1 unless *scaled comes back false) for
+// the `groups` special-limb rows P (coefficient domain, canonical) and the limbs j of `sl`.  At N = 2^16 the lift rides on the
+// forward transforms' loads (ntt_io_t::lift_unsigned: k_ntt_fwd_quad for the fp64-size limbs, k_ntt_fwd_top_lift + the u64 block
+// kernels for the others) and the factor P^-1 is left to k_md_acc; otherwise k_md_lift writes the scaled lifts to `LF` and plain
+// transforms follow.
+// Whether the unsigned lift can ride on the forward transforms' loads (ntt_io_t::lift_unsigned) for these target limbs and this
+// special prime: N = 2^15 / 2^16 through the pair / quad kernels (+ top-stage lift for the u64 limbs); N <= 2^14 through
+// run_ntt's digit-lift mode -- except when every target limb is fp64-size and the special prime is not (the uniform fp64 policy
+// reads its source as one double).
+static bool md_lift_is_fused(const tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl) {
+    const int level = A.level;
+    if (level > 32 || c->logN > 16) return false;
+    if (c->logN >= 15) return c->variant == 0;
+    const bool special_fp = c->limbs_host[A.w.idx[level]].Wd != nullptr;
+    return special_fp || !sel_fp(c, sl, 0);
+}
+static int md_lift_fwd(tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl, const rescale_arg_t& ra, const u64* P, u64* LF, u64* U,
+                       int64_t groups, bool* scaled) {
+    const int level = A.level;
+    const u32 n = (u32)c->N;
+    const int64_t rows = groups * level;
+    if (LF == nullptr) {   // the caller sized the workspace for the fused form (md_lift_is_fused)
+        ntt_io_t io = io_plain();
+        io.mode = 1; io.level = 1; io.nw = (u32)level; io.polys = 1; io.lift_unsigned = 1;
+        *scaled = false;
+        if (c->logN <= 14) return run_ntt(c, false, P, U, rows, sl, &io);
+        const int x = c->logN - 14;
+        const policy_split_t ps = policy_split(c, sl);
+        const u32 tmask = ps.fpmask, tall = ps.all;   // fp64-size target limbs
+        const bool special_fp = c->limbs_host[A.w.idx[level]].Wd != nullptr;
+        if ((rows << x) > 0x7fffffffll || (((uintptr_t)P | (uintptr_t)U) & 15u) != 0) return fail(TFHE_E_BADARG, "md_lift_fwd: row count / alignment");
+        int rc;
+        void* tmp = nullptr;
+        if (tmask != tall) {   // (before the fork: growing the workspace synchronises)
+            rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
+            if (rc) return rc;
+        }
+        lanes_t lanes(c, tmask != 0 && tmask != tall);   // both kinds of limbs: side by side
+        if (tmask) {   // the fp64-size limbs: one kernel per row (pair) (ArithFpWide reads a source above 2^52 in two halves)
+            ntt_io_t a = io;
+            a.limb_mask = tmask == tall ? 0u : tmask;
+            lanes.use(1);
+            rc = run_ntt_large(c, false, P, U, rows, sl, a, &a, true, !special_fp);
+            if (rc) return rc;
+            lanes.use(0);
+        }
+        if (tmask != tall) {   // the larger limbs: lift fused into the top stages (into the transform scratch), then the u64 block kernels
+            ntt_io_t w = io;
+            w.limb_mask = tmask ? (tall & ~tmask) : 0u;
+            rc = launch_top_lift(c, P, (u64*)tmp, rows, sl, w);
+            if (rc) return rc;
+            ntt_io_t ib = io_plain();
+            ib.limb_mask = w.limb_mask;
+            rc = launch_block_fwd<ArithInt, 14>(c, (const u64*)tmp, U, rows, sl, x, ib);
+            if (rc) return rc;
+        }
+        return TFHE_OK;
+    }
+    const int rc = launch(c, k_md_lift, row_grid((unsigned)rows, (size_t)c->N), dim3(256), 0, P, LF, c->limbs_dev, sl, ra, n);
+    if (rc) return rc;
+    *scaled = true;
+    return run_ntt(c, false, LF, U, rows, sl);
+}
+
+// S_s = sum_i evk_{i,s} (.) digit_i over the working limbs (NTT domain), S: [batch][2][nw][N]
+// keys != nullptr: `nkeys` keys against the same digits in one launch, key r writing S + r * batch*2*nw*N (tfhe_matmul_diag)
+static int ks_inner_launch(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* evk, const u64* dig, u64* S, int64_t batch,
+                           const uint64_t* const* keys = nullptr, int nkeys = 0, const u64* epi_x = nullptr) {
+    const int nw = A.nw;
+    ks_keys_t K{};
+    if (keys) {
+        K.n = nkeys;
+        K.s_stride = (size_t)batch * 2 * nw * (size_t)c->N;
+        for (int r = 0; r < nkeys; r++) K.key[r] = keys[r];
+        evk = keys[0];
+        K.epi_x = epi_x;
+    }
+    const unsigned gy = keys ? (unsigned)nkeys : 1u;
+    const u32 n = (u32)c->N;
+    const unsigned gx = (n + 255) / 256;
+    // enough workgroups to fill the chip: split the batch into slices (the key is re-read once per slice)
+    // (several keys in one launch multiply the grid by gy)
+    const unsigned bsplit = (unsigned)std::max<int64_t>(1, std::min<int64_t>(batch, (4096 + nw * gx * gy - 1) / (nw * gx * gy)));
+    // working limbs below 2^52: the two-coefficient, carry-free kernel; the others: the generic one (more than 32 working
+    // limbs: all or nothing, see mask_of)
+    // several keys: groups of eight x-blocks (one per XCD), each followed by its keys (ks_multi_key_block)
+    auto multi = [&](unsigned nx) { return keys ? dim3(((nx + 7u) / 8u) * 8u * gy) : dim3(nx); };
+    const policy_split_t ps = policy_split(c, A.w);
+    const u32 nmask = n % 2 != 0 ? 0u : ps.narrow, amask = ps.all;
+    lanes_t lanes(c, nmask != 0 && nmask != amask);   // both kernels: side by side (disjoint working limbs)
+    if (nmask) {
+        lanes.use(1);
+        const unsigned gx2 = (n / 2 + 255) / 256;
+        const unsigned bs2 = (unsigned)std::max<int64_t>(1, std::min<int64_t>(batch, (4096 + nw * gx2 * gy - 1) / (nw * gx2 * gy)));
+        auto kn = epi_x ? k_ks_inner_n2<8, true> : k_ks_inner_n2<8, false>;
+        const int rc = launch(c, kn, multi((unsigned)nw * gx2 * bs2), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)batch, bs2,
+                              nmask == amask ? 0u : nmask, K);
+        if (rc) return rc;
+    }
+    if (nmask != amask) {
+        lanes.use(0);
+        auto kg = epi_x ? k_ks_inner<8, true> : k_ks_inner<8, false>;
+        return launch(c, kg, multi((unsigned)nw * gx * bsplit), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)batch, bsplit,
+                      nmask ? (amask & ~nmask) : 0u, K);
+    }
+    return TFHE_OK;
+}
+// the inverse top stages of N = 2^15 / 2^16 over the sub-block results T together with the tail ("+ c" / the special-prime
+// contraction); g_tail != 0: the automorphism rides on the tail's stores (XCD-cooperative scatter, k_ks_top_tail_rot)
+static int launch_top_tail(tfhe_ctx* c, const ks_arg_t& A, const rescale_arg_t& ra, const u64* T, const u64* ct, u64* out, int64_t batch, u64 g_tail) {
+    const u32 n = (u32)c->N, add_s = A.polys == 3 ? 2u : 1u;
+    return dispatch_int<1, 2>(c->logN - 14, [&](auto xc) {
+        constexpr int X = decltype(xc)::value;
+        if (g_tail)
+            return launch(c, k_ks_top_tail_rot<X>, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, T, ct, out, c->limbs_dev, A, ra, n, add_s, g_tail, (u32)(batch * 2));
+        return launch(c, k_ks_top_tail<X>, row_grid((unsigned)(batch * 2 * A.level), (size_t)c->N >> X), dim3(256), 0, T, ct, out, c->limbs_dev, A, ra, n, add_s);
+    });
+}
+// The tail of every form that leaves whole key sums S ([batch][2][nw][N], NTT domain): out_s = ct_s + INTT(S_s), with the special
+// prime the ModulusRaised contraction of INTT(S) (k_ks_rescale_add).  `A` is the row bookkeeping (level = ciphertext limbs); `ct`
+// only supplies the addends.  S is transformed in place with the special prime and left as it is otherwise.
+static int ks_plain_tail(tfhe_ctx* c, const ks_arg_t& A, const rescale_arg_t& ra, u64* S, const u64* ct, u64* out, int64_t batch) {
+    const int level = A.level, polys = A.polys;
+    const u32 n = (u32)c->N;
+    const u32 add_s = polys == 3 ? 2u : 1u;  // c2 starts from zero for a 2-element input (rlwe_she.jl:324)
+    const dim3 tail_grid = row_grid((unsigned)(batch * 2 * level), (size_t)c->N);
+    int rc;
+    if (A.special) {
+        rc = run_ntt(c, true, S, S, batch * 2 * A.nw, A.w);
+        if (rc) return rc;
+        return launch(c, k_ks_rescale_add, tail_grid, dim3(256), 0, S, ct, out, c->limbs_dev, A, ra, n, add_s);
+    }
+    if (c->logN <= 14) {  // out = c + INTT(S), the addition fused into the inverse NTT's stores
+        ntt_io_t io = io_plain();
+        io.mode = 2; io.gsz = (u32)(2 * level); io.src_gstride = io.gsz; io.dst_gstride = io.gsz;
+        io.add_rows = add_s * (u32)level; io.add_gstride = (u32)(polys * level); io.addend = ct;
+        return run_ntt(c, true, S, out, batch * 2 * A.nw, A.w, &io);
+    }
+    rc = run_ntt(c, true, S, out, batch * 2 * A.nw, A.w);
+    if (rc) return rc;
+    return launch(c, k_ks_add_ct, tail_grid, dim3(256), 0, ct, out, c->limbs_dev, A, n, add_s);
+}
+
+// ---- the plan of one key switch ----------------------------------------------------------------------------------------
+// Everything a call decides -- its route, how a rotation is carried, what is done to the key, the chunk and the workspace -- is
+// decided once, by ks_plan; keyswitch_impl and ks_chunk read the plan, and so does whoever sizes a workspace for them
+// (mr_ks_bytes, mul_api.inc).  Every environment switch of the key switch is read here or in ks_fused14, once per process.
+//   KS_ROW: k_ks_fused, N = 2^13 / 2^14    KS_SUB: k_ks_fused_sub, N = 2^15 / 2^16, then the inverse top stages with the tail
+//   KS_THREE: digit transforms (ks_digits_fwd), key sums (ks_inner_launch), inverse transforms + tail
+enum ks_path_t { KS_ROW, KS_SUB, KS_THREE };
+//   KS_ROT_COPY: do_galois into the workspace first, then a plain key switch of the copy    KS_ROT_TAIL: the rotation rides on the
+//   final stores    KS_ROT_HOISTED: a prepared key on a path that cannot do that: the call is handed to tfhe_rotate_many
+enum ks_rot_t { KS_ROT_NONE, KS_ROT_COPY, KS_ROT_TAIL, KS_ROT_HOISTED };
+struct ks_plan_t {
+    ks_arg_t A;
+    rescale_arg_t ra;    // P^-1 mod q_j (special prime): not part of the decision, keyswitch_impl fills it for ks_chunk
+    int Lk; ks_path_t path;
+    bool two_launch;     // KS_ROW with the special prime: SPMODE 1, then 2 / 3; otherwise one launch (+ k_ks_rescale_add)
+    bool prelifted;      // KS_ROW: c[end] arrives as centred doubles (the BFV contraction)
+    bool fps;            // KS_SUB: every working modulus below TFHE_FPS_QMAX -- the range plan of that size class (ArithFpS)
+    bool tail16;         // KS_THREE at N = 2^16: paired sub-block inverse + k_ks_top_tail<2>
+    bool two_lanes;      // KS_THREE at N = 2^16: the two policies as two lanes from the lift to the inverse, ONE join before the tail
+    ks_rot_t rot;
+    u64 g_tail;          // KS_ROT_TAIL: the Galois element, otherwise 0
+    bool key_perm;       // the key is permuted by g^-1: in k_evk_to_f64 on the fused paths, by k_ntt_perm on KS_THREE (else read in place)
+    // workspace: [ transform scratch | S: [chunk][2][nw][N] | NTT'd digits: [chunk][level][nw][N], or T: [chunk][2][nw][N] on the fused
+    // paths | rotated copy: [chunk][polys][level][N] ], then the key as doubles (k_evk_to_f64, fused paths) or permuted (k_ntt_perm)
+    int64_t chunk;
+    size_t N, S_rows, dig_rows, rot_rows, ntt_tmp, key_bytes;
+    size_t bytes() const { return ntt_tmp + (size_t)chunk * (S_rows + dig_rows + rot_rows) * N * 8 + key_bytes; }
+    u64* region(void* ws, size_t before) const { return (u64*)((char*)ws + ntt_tmp) + (size_t)chunk * before * N; }   // after `before` rows
+};
+// `batch` is the CALL's batch; `ct` / `out` are the caller's operands (read for rotations and for the alignment of the lift's loads).
+// key_prepared (rotations only, tfhe_rotate_prepared): the key is the output of tfhe_galois_key_prepare for `galois` -- the paths
+// that finish the rotation in their tail consume it as it is (no per-call k_ntt_perm / permuting conversion); the others take the
+// hoisted form of tfhe_rotate_many, which is defined on prepared keys (same bits)
+static ks_plan_t ks_plan(const tfhe_ctx* c, int Lk, int level, int special, int polys, int64_t batch, const u64* ct = nullptr,
+                         const u64* out = nullptr, u64 galois = 0, bool rotate = false, bool prelifted = false, bool key_prepared = false) {
+    ks_plan_t P{};
+    P.A = make_ks_arg(Lk, level, special, polys);
+    const ks_arg_t& A = P.A;
+    const int nw = A.nw;
+    const size_t N = (size_t)c->N;
+    P.Lk = Lk; P.N = N; P.prelifted = prelifted;   // (pre-lifted rows: KS_ROW only, keyswitch_impl checks)
+    const bool f14 = ks_fused14(c, Lk, level, special);
+    P.path = !f14 ? KS_THREE : (c->logN <= 14 ? KS_ROW : KS_SUB);
+    if (P.path == KS_ROW) {
+        // TFHE_KS_TAIL=1 keeps the one-launch form with k_ks_rescale_add (comparisons)
+        static const bool ks_tail = env_flag("TFHE_KS_TAIL", false);
+        P.two_launch = special && !prelifted && !ks_tail;
+    } else if (P.path == KS_SUB) {
+        // moduli below 2^42 (the 40-bit chains of the reference's CKKS rings): the range plan of that size class -- no forward
+        // sweeps, no reduced product operands, one sweep per inverse (ArithFpS): cfg#3 36.5 k -> 38.1 k key switches/s
+        bool small = true;
+        for (int j = 0; j < nw; j++) small = small && c->q[A.w.idx[j]] < TFHE_FPS_QMAX;
+        static const bool fps_on = env_flag("TFHE_FPS", true);
+        P.fps = small && fps_on;
+    } else {
+        // two lanes: only when the digit transforms, the key sums and the inverse sub-block transforms all split the working limbs
+        // the same way (fp64-size = "narrow"); otherwise every step forks and joins by itself
+        const policy_split_t ps = policy_split(c, A.w);
+        P.tail16 = c->logN == 16 && c->variant == 0 && ps.fpmask != 0 && level >= 2;
+        P.two_lanes = P.tail16 && nw <= 32 && ps.mixed_fp() && ps.fpmask == ps.narrow;
+    }
+    // Rotations finished in the final stores: no rotated copy of the input -- the key sums are those of the unrotated digits
+    // against the key permuted by g^-1, the automorphism rides on the stores.  Same bits (the hoisting identity of tfhe_rotate_many).
+    //   KS_SUB, KS_THREE with tail16 : k_ks_top_tail_rot, one (ciphertext, component) per XCD at a time: the CALL's batch >= 8
+    //   KS_ROW at 2^14, two launches : k_ks_fused SPMODE 3 -- each workgroup scatters the row it owns
+    // The stores scatter into `out` while other workgroups still read the unrotated `ct`: the two RANGES must be disjoint (r05,
+    // ADVICE r04: pointer inequality let a partially overlapping out / ct race).  TFHE_ROT_TAIL=0 keeps the separate pass.
+    if (rotate) {
+        static const bool rot_tail_on = env_flag("TFHE_ROT_TAIL", true);
+        const bool io_disjoint = (const char*)(out + (size_t)batch * 2 * level * N) <= (const char*)ct ||
+                                 (const char*)(ct + (size_t)batch * polys * level * N) <= (const char*)out;
+        const bool can = P.path == KS_ROW ? (c->logN == 14 && P.two_launch) : (batch >= 8 && (P.path == KS_SUB || P.tail16));
+        P.rot = (can && rot_tail_on && io_disjoint) ? KS_ROT_TAIL : (key_prepared ? KS_ROT_HOISTED : KS_ROT_COPY);
+    }
+    if (P.rot == KS_ROT_HOISTED) return P;   // tfhe_rotate_many plans for itself
+    if (P.rot == KS_ROT_TAIL) P.g_tail = galois;
+    P.key_perm = P.rot == KS_ROT_TAIL && !key_prepared;
+    // the lift's 16-byte loads: of the caller's `ct` unless the rotated copy takes its place.  The workspace needs no test (ensure_ws
+    // hands out whole hipMalloc blocks, its own or the pool's, devalloc::alloc_ws: 256-byte aligned), nor does a chunk: every region
+    // and chunk offset is a multiple of 8 N bytes
+    P.two_lanes = P.two_lanes && (P.rot == KS_ROT_COPY || ((uintptr_t)ct & 15u) == 0);
+    // chunk the batch so that the digit tensor stays at a few GiB.  The fused key switches never write the digit rows: at
+    // N = 2^15 the "digit" buffer only carries the sub-block sums T (2 nw rows per ciphertext), so a whole batch is one launch
+    // (cfg#3, 512 ciphertexts: 248 + 248 + 16 before -- the 16 ran as two nearly empty item rounds of k_ks_fused_sub)
+    P.S_rows = (size_t)2 * nw;
+    P.dig_rows = f14 ? (size_t)2 * nw : (size_t)level * nw;
+    P.rot_rows = rotate ? (size_t)polys * level : 0;
+    P.chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, (P.S_rows + P.dig_rows + P.rot_rows) * N * 8);
+    // NTT of N > 2^14 and the mixed lift use the start of the context workspace as well: keep ours separate by over-allocating, so
+    // that nothing grows the workspace once the lanes have forked (the fused paths run no stand-alone transform)
+    P.ntt_tmp = (c->logN > 14 && !f14) ? (size_t)P.chunk * std::max(2, level) * nw * N * 8 : 0;
+    P.key_bytes = f14 ? (size_t)level * 2 * nw * N * 8 : (P.key_perm ? (size_t)level * 2 * Lk * N * 8 : 0);
+    return P;
+}
+
+// One chunk of `batch` ciphertexts by the plan.  `key`: the caller's key or the workspace copy keyswitch_impl made; `ct`: the
+// chunk's input -- the rotated copy under KS_ROT_COPY, the UNrotated input under KS_ROT_TAIL
+static int ks_chunk(tfhe_ctx* c, const ks_plan_t& P, const u64* key, const u64* ct, u64* out, int64_t batch, u64* S, u64* dig) {
+    const ks_arg_t& A = P.A;
+    const int Lk = P.Lk, level = A.level, nw = A.nw, special = A.special;
+    const u64* const none = nullptr;
+    int rc;
+    if (P.path == KS_ROW) {
+        // everything in one kernel: digit lift, forward transforms, key inner product and the two inverse transforms;
+        // with the special prime the transformed sums go to S and the contraction kernel finishes (modulusraising.jl:42)
+        const unsigned items = (unsigned)(batch * nw);
+        const int64_t transforms = (int64_t)items * (level + 2);  // limb transforms inside the fused launch(es): `level` forward + 2 inverse per item
+        // two launches: the special limb of every ciphertext first (its coefficient rows t_P into S), then the ciphertext limbs with
+        // the ModulusRaised contraction and "+ c" in their final store (k_ks_fused SPMODE 1 / 2, ArithFpMD).  No T, no tail kernel.
+        if (P.two_launch) {
+            {
+                std::lock_guard<std::mutex> zg(c->zero_mu);         // a failed attempt (transient out-of-memory) is retried by the next call
+                if (!c->zero_row) {
+                    void* z = nullptr;
+                    if (devalloc::malloc_retry(&z, (size_t)c->N * 8) == hipSuccess) {
+                        if (hipMemset(z, 0, (size_t)c->N * 8) == hipSuccess) c->zero_row = (u64*)z;
+                        else { (void)hipGetLastError(); (void)hipFree(z); }
+                    } else (void)hipGetLastError();
+                }
+                if (!c->zero_row) return fail(TFHE_E_NOMEM, "allocating the zero row failed");
+            }
+            ks_arg_t A2 = A;   // these two launches only: P^-1 mod q_j, and the Galois element of a rotation finished in the store
+            std::copy(P.ra.qlinv, P.ra.qlinv + level, A2.pinv);
+            A2.rot_g = (u32)(P.g_tail & (2 * (u64)c->N - 1));
+            const unsigned it1 = (unsigned)batch, it2 = (unsigned)(batch * level);
+            auto launch2 = [&](auto k1, auto k2, int LOGT, size_t lds, unsigned per_cu) -> int {   // both launches in ONE profiled region
+                prof_scope p(c, transforms);
+                const int r1 = launch(c, k1, dim3(cu_grid(c, it1, per_cu)), dim3(1u << LOGT), lds, key, ct, S, c->limbs_dev, A2, Lk, it1, none, none);
+                if (r1) return r1;
+                return launch(c, k2, dim3(cu_grid(c, it2, per_cu)), dim3(1u << LOGT), lds, key, ct, out, c->limbs_dev, A2, Lk, it2, (const u64*)S, (const u64*)c->zero_row);
+            };
+            if (c->logN == 13) {
+                constexpr int LOGT = logt_for(13);
+                return launch2(k_ks_fused<ArithFp, 13, LOGT, false, 1>, k_ks_fused<ArithFp, 13, LOGT, false, 2>, LOGT, fused_lds_bytes<13, LOGT>(), 2u);
+            }
+            constexpr int LOGT = logt_for(14);
+            // SPMODE 3: a rotation finished in the second launch's stores (`ct` is the unrotated input)
+            auto k1 = k_ks_fused<ArithFp, 14, LOGT, false, 1>, k2 = !P.g_tail ? k_ks_fused<ArithFp, 14, LOGT, false, 2> : k_ks_fused<ArithFp, 14, LOGT, false, 3>;
+            return launch2(k1, k2, LOGT, fused_lds_bytes<14, LOGT>(), 1u);
+        }
+        if (c->logN == 14) {
+            constexpr int LOGT = logt_for(14);
+            auto fk = P.prelifted ? k_ks_fused<ArithFp, 14, LOGT, true> : k_ks_fused<ArithFp, 14, LOGT, false>;
+            rc = launch_prof(c, transforms, fk, dim3(cu_grid(c, items)), dim3(1 << LOGT), fused_lds_bytes<14, LOGT>(), key, ct,
+                             special ? S : out, c->limbs_dev, A, Lk, items, none, none);
+        } else {  // N = 2^13: 256 threads x 32 elements, 65 KiB of LDS; 478 registers per thread, so one workgroup per CU is resident
+                  // (capped to two resident workgroups it measured 5 % slower, DESIGN.md section 8)
+            constexpr int LOGT = logt_for(13);
+            rc = launch_prof(c, transforms, k_ks_fused<ArithFp, 13, LOGT, false>, dim3(cu_grid(c, items, 2u)), dim3(1 << LOGT), fused_lds_bytes<13, LOGT>(),
+                             key, ct, special ? S : out, c->limbs_dev, A, Lk, items, none, none);
+        }
+        if (rc || !special) return rc;
+        return launch(c, k_ks_rescale_add, row_grid((unsigned)(batch * 2 * level), (size_t)c->N), dim3(256), 0, S, ct, out, c->limbs_dev, A, P.ra, (u32)c->N, A.polys == 3 ? 2u : 1u);
+    }
+    if (P.path == KS_SUB) {
+        // N = 2^15 / 2^16 on fp64-size moduli: per-sub-block fused key switch (k_ks_fused_sub) into T = dig ([batch][2][nw] rows,
+        // level >= 2 makes room), then the inverse top stages over T together with the tail.  At 2^16 (X = 2) the four quarters
+        // of a digit row stream through the LDS (dma_stream_load, no spills: 33.0 k against 32.1 k key switches/s for the
+        // three-kernel path on 7 x 50 bit; with register loads the X = 2 load phase either spilled 237 registers or ran as 32
+        // serial rounds: 26-28 k).  At 2^15 the register loads stay (the streamed form measured 36.2 k against 40.2 k, cfg#3).
+        constexpr int LOGT = logt_for(14);
+        const size_t lds = (size_t)lds_words<14, LOGT>() * 8;
+        const int x = c->logN - 14;
+        auto fk = x == 2 ? (P.fps ? k_ks_fused_sub<ArithFpS, 14, LOGT, 2> : k_ks_fused_sub<ArithFp, 14, LOGT, 2>)
+                         : (P.fps ? k_ks_fused_sub<ArithFpS, 14, LOGT, 1> : k_ks_fused_sub<ArithFp, 14, LOGT, 1>);
+        const unsigned items = (unsigned)((batch * nw) << x);
+        rc = launch_prof(c, (int64_t)batch * nw * (level + 2), fk, dim3(cu_grid(c, items)), dim3(1 << LOGT), lds, key, ct, dig, c->limbs_dev, A, Lk, items);
+        if (rc) return rc;
+        // inverse top stage + "+ c" / special-prime contraction in one pass over the sub-block results
+        return launch_top_tail(c, A, P.ra, dig, ct, out, batch, P.g_tail);
+    }
+    // the steps up to the inverse sub-block transforms stay on their lanes; the join comes before the tail, which reads every limb
+    lanes_t outer(c, P.two_lanes);
+    rc = ks_digits_fwd(c, A, ct, dig, batch);
+    if (rc) return rc;
+    rc = ks_inner_launch(c, A, Lk, key, dig, S, batch);
+    if (rc) return rc;
+    if (P.tail16) {
+        // N = 2^16: the paired sub-block inverse into the (now free) digit buffer, then the two inverse top stages together with
+        // the tail (k_ks_top_tail<2>) instead of k_ntt_inv_top<2> + k_ks_rescale_add / k_ks_add_ct.  Rings of mixed modulus sizes:
+        // the larger limbs' sub-blocks come from the u64 block kernel (same sub-block layout, lazy [0, 2q) outputs).
+        const policy_split_t ps = policy_split(c, A.w);
+        const u32 fpm = ps.fpmask, amask = ps.all;
+        {
+            lanes_t lanes(c, fpm != amask);
+            lanes.use(1);
+            rc = launch_subpair<ArithFp>(c, true, S, dig, batch * 2 * nw, A.w, 2, fpm == amask ? 0u : fpm);
+            if (rc) return rc;
+            if (fpm != amask) {
+                lanes.use(0);
+                ntt_io_t iw = io_plain();
+                iw.limb_mask = amask & ~fpm;
+                rc = launch_block_inv<ArithInt, 14>(c, S, dig, batch * 2 * nw, A.w, 2, iw);
+                if (rc) return rc;
+            }
+        }
+        outer.join();
+        return launch_top_tail(c, A, P.ra, dig, ct, out, batch, P.g_tail);
+    }
+    outer.join();
+    return ks_plain_tail(c, A, P.ra, S, ct, out, batch);
+}
+
+static int ks_check(tfhe_ctx* c, int Lk, int level, int special, const void* evk, int n_digits, const void* ct, int polys, const void* out, int64_t batch) {
+    if (!c || !evk || !ct || !out) return fail(TFHE_E_BADARG, "null argument");
+    if (polys != 2 && polys != 3) return fail(TFHE_E_BADARG, "keyswitch needs a 2- or 3-element ciphertext (rlwe_she.jl:318), got %d", polys);
+    if (Lk < 1 || Lk > c->L) return fail(TFHE_E_LEVEL_MISMATCH, "key_limbs=%d outside [1,%d]", Lk, c->L);
+    const int maxlevel = special ? Lk - 1 : Lk;
+    if (level < 1 || level > maxlevel) return fail(TFHE_E_LEVEL_MISMATCH, "level=%d outside [1,%d]", level, maxlevel);
+    if (n_digits < level) return fail(TFHE_E_PARAMS_MISMATCH, "evaluation key has %d components, level %d needs %d", n_digits, level, level);
+    if (batch < 0) return fail(TFHE_E_BADARG, "negative batch");
+    return TFHE_OK;
+}
+// every entry point that takes a Galois element but tfhe_rotate
+static int galois_check(const tfhe_ctx* c, u64 g) {
+    if ((g & 1) == 0 || g >= 2 * (u64)c->N) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
+    return TFHE_OK;
+}
+static u64 inv_mod_2n(u64 g, u64 twoN) {  // g odd, twoN a power of two: Newton iteration
+    u64 x = g;
+    for (int i = 0; i < 6; i++) x *= 2 - g * x;
+    return x & (twoN - 1);
+}
+static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, u64* out, int64_t batch,
+                          u64 galois, bool rotate, bool prelifted = false, bool key_prepared = false) {
+    if (prelifted && (rotate || special || !ks_prelift_ok(c, level))) return fail(TFHE_E_UNSUPPORTED, "internal: pre-lifted rows need the fused key switch");
+    ks_plan_t P = ks_plan(c, Lk, level, special, polys, batch, ct, out, galois, rotate, prelifted, key_prepared);
+    if (P.rot == KS_ROT_HOISTED) {
+        const uint64_t* one[1] = {evk};
+        return tfhe_rotate_many(c, Lk, level, special, one, level, 1, &galois, 1, ct, out, batch);
+    }
+    if (special) special_inv_table(c, Lk, level, P.ra.qlinv);
+    const size_t N = P.N;
+    void* ws = nullptr;
+    int rc = ensure_ws(c, P.bytes(), &ws);
+    if (rc) return rc;
+    u64 *const S = P.region(ws, 0), *const dig = P.region(ws, P.S_rows), *const rot = P.region(ws, P.S_rows + P.dig_rows),
+        *const kw = P.region(ws, P.S_rows + P.dig_rows + P.rot_rows);
+    const u64 ginv = P.key_perm ? inv_mod_2n(galois, 2 * (u64)c->N) : (u64)0;
+    if (P.path != KS_THREE) {
+        rc = launch(c, k_evk_to_f64, row_grid((unsigned)(level * 2 * P.A.nw), N), dim3(256), 0, evk, kw, c->limbs_dev, P.A, Lk, (u32)N, c->logN <= 14 ? 1 : 0,
+                    c->logN == 16 ? 2 : 0, ginv, 1);
+    } else if (P.key_perm) {
+        rc = launch(c, k_ntt_perm, row_grid((unsigned)(level * 2 * Lk), N), dim3(256), 0, evk, kw, ginv, (u32)N);
+    }
+    if (rc) return rc;
+    if (P.path != KS_THREE || P.key_perm) evk = kw;
+    for (int64_t b0 = 0; b0 < batch; b0 += P.chunk) {
+        const int64_t nb = std::min(P.chunk, batch - b0);
+        const u64* cin = ct + (size_t)b0 * polys * level * N;
+        if (P.rot == KS_ROT_COPY) {
+            rc = do_galois(c, cin, rot, galois, nb * polys * level, first_limbs(level));
+            if (rc) return rc;
+            cin = rot;
+        }
+        rc = ks_chunk(c, P, evk, cin, out + (size_t)b0 * 2 * level * N, nb, S, dig);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
+
+int tfhe_keyswitch(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk, int n_digits, const uint64_t* ct, int polys, uint64_t* out, int64_t batch) {
+    int rc = ks_check(c, Lk, level, special, evk, n_digits, ct, polys, out, batch);
+    if (rc) return rc;
+    return keyswitch_impl(c, Lk, level, special, evk, ct, polys, out, batch, 0, false);
+}
+// Hoisted rotations: rotate(gk_r, c) for r < n_rot from ONE digit decomposition.  The centred RNS digits commute with the
+// automorphism (a signed permutation of coefficients; the centred representative of -x is the negative of that of x, q odd),
+// and in the NTT domain the automorphism is the permutation galois_ntt_pos.  With the key rows permuted by g^-1 once per key
+// (tfhe_galois_key_prepare) the inner product runs coalesced on the transformed digits of the UNrotated ciphertext and yields
+// sigma_g^-1 of the sums; the automorphism is applied after the inverse transform, over 2 nw rows instead of level nw:
+// level * nw forward transforms once instead of per rotation.  Bit-identical to n_rot calls of tfhe_rotate.
+// evk_out = the Galois key of x -> x^g with every NTT-domain row permuted by g^-1 (tfhe_rotate_many with prepared = 1)
+int tfhe_galois_key_prepare(tfhe_ctx* c, int Lk, int n_digits, uint64_t g, const uint64_t* evk, uint64_t* evk_out) {
+    if (!c || !evk || !evk_out || evk == evk_out) return fail(TFHE_E_BADARG, "null or aliased argument");
+    if (Lk < 1 || Lk > c->L || n_digits < 1) return fail(TFHE_E_LEVEL_MISMATCH, "key shape outside the ring");
+    if (int rc = galois_check(c, g)) return rc;
+    const u64 ginv = inv_mod_2n(g, 2 * (u64)c->N);
+    return launch(c, k_ntt_perm, row_grid((unsigned)(n_digits * 2 * Lk), (size_t)c->N), dim3(256), 0, evk, evk_out, ginv, (u32)c->N);
+}
+
+int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, int prepared,
+                     const uint64_t* galois, int n_rot, const uint64_t* ct, uint64_t* out, int64_t batch) {
+    if (!evks || !galois || n_rot < 0) return fail(TFHE_E_BADARG, "null argument");
+    if (n_rot == 0) return TFHE_OK;
+    for (int r = 0; r < n_rot; r++) {
+        int rc = ks_check(c, Lk, level, special, evks[r], n_digits, ct, 2, out, batch);
+        if (!rc) rc = galois_check(c, galois[r]);
+        if (rc) return rc;
+    }
+    const int nw = special ? level + 1 : level, polys = 2;
+    const size_t N = (size_t)c->N;
+    if (!prepared && c->logN <= 14 && ks_fused14(c, Lk, level, special)) {
+        // N = 2^14 on fp64-size moduli: the fused key switch (digits never leave the registers) beats the hoisted three-kernel
+        // path (measured 126 k against 110 k rotations/s at 6 limbs + special prime) -- same bits either way
+        for (int r = 0; r < n_rot; r++) {
+            int rc = keyswitch_impl(c, Lk, level, special, evks[r], ct, 2, out + (size_t)r * batch * 2 * level * N, batch, galois[r], true);
+            if (rc) return rc;
+        }
+        return TFHE_OK;
+    }
+    const ks_arg_t A = make_ks_arg(Lk, level, special, polys);
+    // workspace per ciphertext: S (2 nw rows) + digits (level nw) + T (2 nw) + rotated input (2 level); + one prepared key
+    const size_t per_ct = ((size_t)4 * nw + (size_t)level * nw + (size_t)polys * level) * N * 8;
+    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
+    const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * std::max(2, level) * nw * N * 8 : 0;
+    const size_t key_bytes = prepared ? 0 : (size_t)n_digits * 2 * Lk * N * 8;
+    void* ws = nullptr;
+    int rc = ensure_ws(c, ntt_tmp + chunk * per_ct + key_bytes, &ws);
+    if (rc) return rc;
+    u64* S = (u64*)((char*)ws + ntt_tmp);
+    u64* dig = S + (size_t)chunk * 2 * nw * N;
+    u64* T = dig + (size_t)chunk * level * nw * N;
+    u64* rot = T + (size_t)chunk * 2 * nw * N;
+    u64* keytmp = rot + (size_t)chunk * polys * level * N;
+    const limb_sel_t sl = first_limbs(level);
+    rescale_arg_t ra{};
+    if (special) special_inv_table(c, Lk, level, ra.qlinv);
+    auto tail_grid = [&](int64_t nb) { return row_grid((unsigned)(nb * 2 * level), N); };
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const u64* cin = ct + (size_t)b0 * polys * level * N;
+        rc = ks_digits_fwd(c, A, cin, dig, nb);
+        if (rc) return rc;
+        for (int r = 0; r < n_rot; r++) {
+            const u64* key = evks[r];
+            if (!prepared) {
+                rc = tfhe_galois_key_prepare(c, Lk, n_digits, galois[r], evks[r], keytmp);
+                if (rc) return rc;
+                key = keytmp;
+            }
+            rc = do_galois(c, cin, rot, galois[r], nb * polys * level, sl);   // the addend sigma_g(c_1) (and sigma_g(c_2), unused)
+            if (rc) return rc;
+            // key sums up to the key's permutation, S' = sigma_g^-1(S); the automorphism is applied to INTT(S') BEFORE the tail (the
+            // ModulusRaised floor does not commute with sign changes), into T -- not over the digits, which the next rotation reuses
+            u64* const o = out + ((size_t)r * batch + b0) * 2 * level * N;
+            rc = ks_inner_launch(c, A, Lk, key, dig, S, nb);
+            if (rc) return rc;
+            rc = run_ntt(c, true, S, S, nb * 2 * nw, A.w);
+            if (rc) return rc;
+            rc = do_galois(c, S, T, galois[r], nb * 2 * nw, A.w);
+            if (rc) return rc;
+            if (special) {
+                rc = launch(c, k_ks_rescale_add, tail_grid(nb), dim3(256), 0, T, rot, o, c->limbs_dev, A, ra, (u32)N, 1u);
+            } else {
+                HIP_TRY(hipMemcpyAsync(o, T, (size_t)nb * 2 * level * N * 8, hipMemcpyDeviceToDevice, c->stream));
+                rc = launch(c, k_ks_add_ct, tail_grid(nb), dim3(256), 0, rot, o, c->limbs_dev, A, (u32)N, 1u);
+            }
+            if (rc) return rc;
+        }
+    }
+    return TFHE_OK;
+}
+
+int tfhe_rotate(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk, int n_digits, uint64_t g, const uint64_t* ct, uint64_t* out, int64_t batch) {
+    int rc = ks_check(c, Lk, level, special, evk, n_digits, ct, 2, out, batch);
+    if (rc) return rc;
+    if ((g & 1) == 0) return fail(TFHE_E_BADARG, "galois element must be odd");   // deliberately not galois_check: this entry point never bounded g
+    return keyswitch_impl(c, Lk, level, special, evk, ct, 2, out, batch, g, true);
+}
+// the same with the key as tfhe_galois_key_prepare left it (r06): a caller that rotates by ONE Galois element again and again
+// (infer.jl:140-149: 63 chained rotations per matrix product, one key) prepares it once instead of once per call
+int tfhe_rotate_prepared(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk_prepared, int n_digits, uint64_t g, const uint64_t* ct, uint64_t* out,
+                         int64_t batch) {
+    int rc = ks_check(c, Lk, level, special, evk_prepared, n_digits, ct, 2, out, batch);
+    if (rc) return rc;
+    if ((rc = galois_check(c, g))) return rc;
+    return keyswitch_impl(c, Lk, level, special, evk_prepared, ct, 2, out, batch, g, true, false, true);
+}
+
+// ---- diagonal matrix-vector product (infer.jl:140-149, test/ckks_matmul.jl:33-41) in one call ---------------------------
+// out = diag_0 (.) c + sum_r diag_{r+1} (.) rotate(gk_r, c): the hoisted rotations of tfhe_rotate_many (one digit decomposition
+// of c) with every step -- key sums, inverse transforms, automorphism + tail, forward transforms, accumulation -- run over ALL
+// rotations at once instead of rotation by rotation (R x more rows per launch: about 15 launches per product instead of
+// about 8 R + 2 R + 2), and the rotated ciphertexts never return to the caller.  Same arithmetic, term by term, as
+// rotate_many -> nntt -> dot: bit-identical results.
+int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, const uint64_t* galois,
+                     int n_rot, const uint64_t* diags, const uint64_t* ct, uint64_t* out, int64_t batch) {
+    if (!evks || !galois || !diags || n_rot < 0) return fail(TFHE_E_BADARG, "null argument");
+    if (n_rot > TFHE_DOT_MAX) return fail(TFHE_E_UNSUPPORTED, "tfhe_matmul_diag takes at most %d rotations per call", TFHE_DOT_MAX);
+    for (int r = 0; r < n_rot; r++) {
+        int rc = ks_check(c, Lk, level, special, evks[r], n_digits, ct, 2, out, batch);
+        if (!rc) rc = galois_check(c, galois[r]);
+        if (rc) return rc;
+    }
+    if (n_rot == 0) {
+        int rc = ks_check(c, Lk, level, special, diags, n_digits, ct, 2, out, batch);
+        if (rc) return rc;
+    }
+    if (batch == 0) return TFHE_OK;
+    const int nw = special ? level + 1 : level, polys = 2, R = n_rot;
+    const size_t N = (size_t)c->N;
+    const u32 n = (u32)c->N;
+    ks_arg_t A = make_ks_arg(Lk, level, special, polys);
+    const limb_sel_t sl = first_limbs(level);
+    rescale_arg_t ra{};
+    if (special) {
+        special_inv_table(c, Lk, level, ra.qlinv);
+        std::copy(ra.qlinv, ra.qlinv + level, A.pinv);
+    }
+    rot_tail_arg_t G{};
+    for (int r = 0; r < R; r++) G.g[r] = galois[r];
+    // With a special prime the rotations are finished in the evaluation domain (k_md_*: only the special limb of every key sum is
+    // inverse-transformed); TFHE_MD_COEFF=1 keeps the coefficient-domain tail (k_ks_rot_tail) for comparisons.
+    static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
+    const bool eval_form = special && R > 0 && !md_coeff;
+    // workspace per ciphertext: digits (level nw rows) + S / T (R 2 nw) + rotated ciphertexts (R 2 level) + the ciphertext's own transform (2 level)
+    // (+ evaluation-domain form: the lifted special limbs before their transforms (R 2 level) and the special limbs themselves (R 2))
+    // (the untransformed lifts only where the lift is not fused into the transforms' loads)
+    const bool need_lf = eval_form && !(md_lift_is_fused(c, A, sl) && (size_t)R * 2 * level * 4 * 512 <= 0x7fffffffull);
+    const size_t per_ct = ((size_t)level * nw + (size_t)R * 2 * nw + (size_t)R * 2 * level + (size_t)2 * level +
+                           (eval_form ? (need_lf ? (size_t)R * 2 * level : 0) + (size_t)R * 2 : 0)) * N * 8;
+    // The keys of all R rotations are read once per chunk (2.8 GB at N = 2^16, 6 limbs + special prime, 63 rotations): a chunk as
+    // large as the memory allows (32 GiB of workspace unless TFHE_MD_WS_GIB says otherwise; halved while the allocation fails)
+    static const size_t ws_cap_env = env_gib("TFHE_MD_WS_GIB", 32);
+    // ... and never more than half of what the device has free right now (counting what this context and the allocator's cache
+    // already hold, both of which the allocation below can reuse): other contexts, BFV plans and processes keep their room
+    size_t ws_cap = ws_cap_env;
+    {
+        // (hipMemGetInfo is a driver round trip -- milliseconds in a process with many allocations -- and this call sits in the
+        // launch path of a host-bound circuit: the reading is kept for two seconds)
+        // (r05, ADVICE r04: the reading and the allocator's cached bytes are those of THIS context's device -- a process driving
+        // several GPUs computed the cap from whichever device had asked last and from the cache summed over all of them)
+        struct mi_t { size_t free_bytes = 0; std::chrono::steady_clock::time_point at{}; };
+        static std::mutex mi_mu;
+        static std::map<int, mi_t> mi_dev;
+        size_t fr = 0, tot = 0;
+        bool have = false;
+        const int cur_dev = devalloc::current_device();          // what hipMemGetInfo reads and where the workspace will be allocated
+        {
+            std::lock_guard<std::mutex> g(mi_mu);
+            mi_t& mi = mi_dev[cur_dev];
+            const auto now = std::chrono::steady_clock::now();
+            if (mi.free_bytes && now - mi.at < std::chrono::seconds(2)) { fr = mi.free_bytes; have = true; }
+            else if (hipMemGetInfo(&fr, &tot) == hipSuccess) { mi.free_bytes = fr; mi.at = now; have = true; }
+            else (void)hipGetLastError();
+        }
+        if (have) {
+            size_t cached = 0;
+            {
+                devalloc::state_t& as = devalloc::S();
+                std::lock_guard<std::mutex> g(as.mu);
+                auto it = as.devs.find(cur_dev);
+                if (it != as.devs.end()) cached = it->second.cached_bytes;
+            }
+            ws_cap = std::min(ws_cap, std::max<size_t>((fr + c->ws_bytes + cached) / 2, (size_t)1 << 30));
+        }
+    }
+    int64_t chunk = chunk_of(c, batch, 512, ws_cap, per_ct);
+    size_t ntt_tmp = 0;
+    void* ws = nullptr;
+    int rc;
+    ws_borrow_t borrow(c);    // a workspace above ws_keep_bytes() is this call's: back to the allocator on every return path
+    for (bool first_try = true;; first_try = false) {
+        const size_t ntt_rows = (size_t)chunk * std::max<size_t>({(size_t)level * nw, (size_t)R * 2 * nw, (size_t)2 * level});
+        ntt_tmp = c->logN > 14 ? ntt_rows * N * 8 : 0;
+        const size_t need = ntt_tmp + chunk * per_ct;
+        if (first_try && need > ws_keep_bytes() && need > c->ws_bytes) borrow.begin();
+        rc = ensure_ws(c, need, &ws, borrow.active);
+        if (rc != TFHE_E_NOMEM || chunk == 1) break;
+        chunk = (chunk + 1) / 2;
+    }
+    if (rc) return rc;
+    u64* dig = (u64*)((char*)ws + ntt_tmp);
+    u64* S = dig + (size_t)chunk * level * nw * N;
+    u64* ROT = S + (size_t)chunk * R * 2 * nw * N;
+    u64* X = ROT + (size_t)chunk * R * 2 * level * N;
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const u64* cin = ct + (size_t)b0 * polys * level * N;
+        if (eval_form) {
+            u64* const U = ROT;                                  // [R][nb][2][level][N]
+            u64* const LF = need_lf ? X + (size_t)chunk * 2 * level * N : nullptr;   // lifted special limbs, untransformed (same shape)
+            u64* const PB = X + (size_t)chunk * 2 * level * N + (need_lf ? (size_t)chunk * R * 2 * level * N : 0);   // [R][nb][2][N]
+            const u32 groups = (u32)((int64_t)R * nb * 2);
+            rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
+            if (rc) return rc;
+            rc = ks_digits_fwd(c, A, cin, dig, nb);
+            if (rc) return rc;
+            rc = ks_inner_launch(c, A, Lk, nullptr, dig, S, nb, evks, R, X);   // limbs j < level leave as V = S' P^-1 + X0 [s = 0]
+            if (rc) return rc;
+            rc = launch(c, k_md_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, S, PB, G, n, (u32)nw, (u32)level, (u32)nb, groups);
+            if (rc) return rc;
+            limb_sel_t sp{};
+            sp.n = 1;
+            sp.idx[0] = Lk - 1;
+            rc = run_ntt(c, true, PB, PB, (int64_t)groups, sp);
+            if (rc) return rc;
+            bool scaled = true;
+            rc = md_lift_fwd(c, A, sl, ra, PB, LF, U, (int64_t)groups, &scaled);
+            if (rc) return rc;
+            auto acc = scaled ? k_md_acc<false> : k_md_acc<true>;
+            rc = launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, X, S, U, diags, out + (size_t)b0 * 2 * level * N, c->limbs_dev, sl,
+                        G, ra, n, (u32)nw, (u32)R, (u32)nb);
+            if (rc) return rc;
+            continue;
+        }
+        if (R) {
+            rc = ks_digits_fwd(c, A, cin, dig, nb);
+            if (rc) return rc;
+            rc = ks_inner_launch(c, A, Lk, nullptr, dig, S, nb, evks, R);   // key sums of the unrotated digits against every prepared key
+            if (rc) return rc;
+            rc = run_ntt(c, true, S, S, (int64_t)R * nb * 2 * nw, A.w);
+            if (rc) return rc;
+            rc = launch(c, k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, S, cin, ROT, c->limbs_dev, A, ra, G, n, (u32)nb,
+                        (u32)((int64_t)R * nb * 2));
+            if (rc) return rc;
+            rc = run_ntt(c, false, ROT, ROT, (int64_t)R * nb * 2 * level, sl);
+            if (rc) return rc;
+        }
+        rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
+        if (rc) return rc;
+        rc = launch(c, k_matmul_acc, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, X, ROT, diags, out + (size_t)b0 * 2 * level * N,
+                    c->limbs_dev, sl, n, (u32)R, (u32)(nb * 2 * level));
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
+
+// ---- digit-window key switch (relin_window != 0, rlwe_she.jl:330-338) -----------------------------------------------
+static int ksw_table(tfhe_ctx* c, int level, const conv_tab_t** out) {
+    *out = nullptr;
+    if (level == 1) return TFHE_OK;
+    std::lock_guard<std::mutex> g(c->ksw_mu);
+    auto it = c->ksw_tabs.find(level);
+    if (it != c->ksw_tabs.end()) { *out = it->second; return TFHE_OK; }
+    conv_host_t H;
+    build_conv_host(std::vector<u64>(c->q.begin(), c->q.begin() + level), std::vector<u64>(), &H);
+    conv_tab_t T = H.tab;
+    auto up = [&](const std::vector<u64>& v, const u64** d) -> bool {
+        *d = nullptr;
+        if (v.empty()) return true;
+        void* p = nullptr;
+        if (devalloc::malloc_retry(&p, v.size() * 8) != hipSuccess) return false;
+        c->ksw_allocs.push_back(p);
+        if (hipMemcpy(p, v.data(), v.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return false;
+        *d = (const u64*)p;
+        return true;
+    };
+    void* dt = nullptr;
+    if (!up(H.C, &T.C) || !up(H.M, &T.M) || !up(H.Aw, &T.Aw) || devalloc::malloc_retry(&dt, sizeof T) != hipSuccess)
+        return fail(TFHE_E_NOMEM, "allocating the window-digit tables failed");
+    c->ksw_allocs.push_back(dt);
+    HIP_TRY(hipMemcpy(dt, &T, sizeof T, hipMemcpyHostToDevice));
+    c->ksw_tabs[level] = (conv_tab_t*)dt;
+    *out = (conv_tab_t*)dt;
+    return TFHE_OK;
+}
+
+int tfhe_keyswitch_window(tfhe_ctx* c, int key_limbs, int level, int special, int window_bits, const uint64_t* evk, int n_windows,
+                          const uint64_t* ct, int polys, uint64_t* out, int64_t batch) {
+    if (!c || !evk || !ct || !out) return fail(TFHE_E_BADARG, "null argument");
+    if (polys != 2 && polys != 3) return fail(TFHE_E_BADARG, "keyswitch needs a 2- or 3-element ciphertext (rlwe_she.jl:318), got %d", polys);
+    const int Lk = key_limbs;
+    if (Lk < 1 || Lk > c->L) return fail(TFHE_E_BADARG, "key_limbs=%d outside [1,%d]", Lk, c->L);
+    if (level < 1 || level > (special ? Lk - 1 : Lk)) return fail(TFHE_E_LEVEL_MISMATCH, "level=%d outside [1,%d]", level, special ? Lk - 1 : Lk);
+    if (batch < 0) return fail(TFHE_E_BADARG, "negative batch");
+    hostmath::bigint Q = hostmath::big_from(1);
+    u64 qmin = special ? c->q[Lk - 1] : ~0ull;
+    for (int j = 0; j < level; j++) { Q = hostmath::big_mul_u64(Q, c->q[j]); qmin = std::min(qmin, c->q[j]); }
+    if (window_bits < 1 || window_bits > 32 || (qmin >> window_bits) == 0)
+        return fail(TFHE_E_BADARG, "window of %d bits: need 1 <= w <= 32 and 2^w below every modulus", window_bits);
+    int qbits = 0;
+    for (int w = (int)Q.size() - 1; w >= 0 && !qbits; w--)
+        if (Q[w]) qbits = w * 64 + hostmath::bitlen(Q[w]);
+    // ndigits(modulus of the CIPHERTEXT ring, base = 2^w), rlwe_she.jl:333; a key made for a larger ring (a higher level, or the
+    // ModulusRaised key ring Q P, modulusraising.jl:28-32) has more components: the loop rlwe_she.jl:340 uses the first `need`
+    const int need = (qbits + window_bits - 1) / window_bits;
+    if (n_windows < need)
+        return fail(TFHE_E_PARAMS_MISMATCH, "evaluation key has %d components, a %d-bit modulus in %d-bit windows has %d digits", n_windows, qbits, window_bits, need);
+    if (batch == 0) return TFHE_OK;
+    const conv_tab_t* T = nullptr;
+    int rc = ksw_table(c, level, &T);
+    if (rc) return rc;
+    const size_t N = (size_t)c->N;
+    const u32 n = (u32)c->N;
+    const int nw = special ? level + 1 : level;  // working limbs: [0 .. level-1] (+ the special prime, downswitch_keyelement modulusraising.jl:43-49)
+    const size_t per_ct = ((size_t)2 * nw + (size_t)need * nw) * N * 8;
+    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
+    const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * need * nw * N * 8 : 0;
+    void* ws = nullptr;
+    rc = ensure_ws(c, ntt_tmp + chunk * per_ct, &ws);
+    if (rc) return rc;
+    u64* S = (u64*)((char*)ws + ntt_tmp);
+    u64* dig = S + (size_t)chunk * 2 * nw * N;
+    const ks_arg_t Al = make_ks_arg(Lk, level, special ? 1 : 0, polys);  // row bookkeeping of the tail kernels: `level` = ciphertext limbs
+    ks_arg_t A = Al;   // inner product: `level` field = number of digits, nw = working limbs
+    A.level = need;
+    const unsigned gx = (n + 255) / 256;
+    rescale_arg_t ra{};
+    if (special) special_inv_table(c, Lk, level, ra.qlinv);
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const u64* cin = ct + (size_t)b0 * polys * level * N;
+        u64* cout = out + (size_t)b0 * 2 * level * N;
+        rc = launch(c, k_ks_window_digits, dim3((unsigned)(nb * gx)), dim3(256), 0, cin, dig, T, level, window_bits, need, polys, n, gx, nw);
+        if (rc) return rc;
+        rc = run_ntt(c, false, dig, dig, nb * need * nw, A.w);
+        if (rc) return rc;
+        const unsigned bsplit = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nb, (4096 + nw * gx - 1) / (nw * gx)));
+        rc = launch(c, k_ks_inner<8>, dim3((unsigned)nw * gx * bsplit), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)nb, bsplit, 0u, ks_keys_t{});
+        if (rc) return rc;
+        // with the special prime, ModulusRaised: c1 = P c + S over [q_0 .. q_{level-1}, P], contracted by modswitch
+        // (modulusraising.jl:35-42): out_j = c_j + (T_j - [T_P]) P^-1 with T = INTT(S)  (the tail of the RNS-digit path)
+        rc = ks_plain_tail(c, Al, ra, S, cin, cout, nb);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}

@@ -5,7 +5,7 @@
 // ciphertexts ([batch][2][level][N] is 2 batch polynomials), with the intermediates in the context workspace:
 //     ws = [ key-switch region / transform scratch | F: 4 rows per limb (NTT images) | T: 3 rows | R: 2 rows | parking rows x 2 ]
 // keyswitch_impl sizes and carves ITS region from the start of the context workspace and would move the block if it had to
-// grow it, so the block is sized once, before the first launch, for both users (mr_ks_bytes mirrors keyswitch_impl).
+// grow it, so the block is sized once, before the first launch, for both users (mr_ks_bytes asks ks_plan, as keyswitch_impl does).
 //
 // Routing of the product (forward transforms + tensor + inverse transforms) per limb:
 //   N = 2^12 .. 2^14, variant 0, fp64-size limb : k_bfv_core_fused (MODE: packed operands / squaring / NTT-domain input)
@@ -16,17 +16,9 @@
 
 namespace {
 
-// bytes keyswitch_impl (rotate = false) asks of the context workspace for `batch` ciphertexts
+// bytes keyswitch_impl (rotate = false) asks of the context workspace for `batch` ciphertexts: its own plan's
 size_t mr_ks_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t batch) {
-    const int nw = special ? level + 1 : level;
-    const size_t N = (size_t)c->N;
-    const bool f14 = ks_fused14(c, Lk, level, special);
-    const size_t dig_rows = f14 ? (size_t)2 * nw : (size_t)level * nw;
-    const size_t per_ct = ((size_t)2 * nw + dig_rows) * N * 8;
-    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
-    const size_t ntt_tmp = (c->logN > 14 && !f14) ? (size_t)chunk * std::max(2, level) * nw * N * 8 : 0;
-    const size_t evd_bytes = f14 ? (size_t)level * 2 * nw * N * 8 : 0;
-    return ntt_tmp + (size_t)chunk * per_ct + evd_bytes;
+    return ks_plan(c, Lk, level, special, 3, batch).bytes();   // no rotation: sizes only, no table is computed
 }
 
 // parking rows (N words each) the two fused cores may ask for: one per workgroup (k_bfv_core_fused; k_mul_core_int below 2^14), two per

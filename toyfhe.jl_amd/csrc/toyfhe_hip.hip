@@ -142,8 +142,7 @@ int ensure_ws(tfhe_ctx* c, size_t bytes, void** out, bool pooled = false) {
 }
 // The ciphertexts (polynomials, for the samplers and codecs) one iteration of a chunked entry point takes: the whole batch, at
 // most `dflt` of it, at most what `bytes_cap` holds at `per_ct` bytes each (per_ct = 0: no such bound), at most the context's
-// cap (tfhe_ctx_set_chunk), at least one.  EVERY chunked entry point sizes its chunk here: a site that sizes a workspace for
-// another (mr_ks_bytes for keyswitch_impl) then agrees with it by construction.
+// cap (tfhe_ctx_set_chunk), at least one.  EVERY chunked entry point sizes its chunk here.
 int64_t chunk_of(const tfhe_ctx* c, int64_t batch, int64_t dflt, size_t bytes_cap = 0, size_t per_ct = 0) {
     int64_t m = std::min(batch, dflt);
     if (per_ct) m = std::min(m, (int64_t)(bytes_cap / per_ct));
@@ -1021,840 +1020,7 @@ int tfhe_galois(tfhe_ctx* c, const uint64_t* src, uint64_t* dst, uint64_t g, int
     return do_galois(c, src, dst, g, count * limbs, sel);
 }
 
-// ---- keyswitch ------------------------------------------------------------------------------------
-// One chunk of key switching (rlwe_she.jl:315-347).  By linearity of the NTT the expanded inputs never need
-// transforming:  out_s = c_s + INTT(S_s)  (plain)   or   c_s + modswitch-part of INTT(S_s)  (ModulusRaised),
-// with S_s = Σ_i evk_{i,s} ⊙ NTT(digit_i)  (see k_ks_inner, k_ks_rescale_add).
-//   dig: [batch][level][nw][N]  NTT'd digits      S: [batch][2][nw][N]
-// the fused key switches (k_ks_fused at N = 2^14, k_ks_fused_sub at 2^15) read the key as doubles, prepared once per call
-// (k_evk_to_f64 in keyswitch_impl)
-static bool ks_fused14(const tfhe_ctx* c, int Lk, int level, int special) {
-    const limb_sel_t w = working_limbs(Lk, level, special);
-    if (c->variant != 0) return false;
-    if (c->logN == 14) return sel_fp(c, w, 0);
-    if (c->logN == 13) {  // the 256 x 32 geometry: same fused kernel (it takes 256 VGPRs + 222 AGPRs: one workgroup per CU)
-        static const bool on = env_flag("TFHE_FUSED13", true);
-        return on && sel_fp(c, w, 0);
-    }
-    if (c->logN == 16) {  // k_ks_fused_sub at X = 2
-        static const bool on16 = env_flag("TFHE_FUSED16", true);
-        return on16 && level >= 2 && sel_fp(c, w, 2);
-    }
-    return c->logN == 15 && level >= 2 && sel_fp(c, w, 1);  // k_ks_fused_sub
-}
-// pre-lifted c[end] rows (centred doubles from the BFV contraction) are understood by k_ks_fused only
-static bool ks_prelift_ok(const tfhe_ctx* c, int level) {
-    if (c->logN != 14 || !ks_fused14(c, level, level, 0)) return false;
-    u64 lo = ~0ull, hi = 0;  // the bit-cast lift keeps |digit| <= q_i / 2 unreduced: needs q_i <= 2 q_j for every pair
-    for (int j = 0; j < level; j++) { lo = std::min(lo, c->q[j]); hi = std::max(hi, c->q[j]); }
-    return hi <= 2 * lo;
-}
-// the top stages of an N = 2^15 / 2^16 forward transform with the lift of ntt_io_t mode 1 fused into their loads (the u64 limbs of
-// rings that mix modulus sizes), into the transform scratch `t`
-static int launch_top_lift(tfhe_ctx* c, const u64* src, u64* t, int64_t rows, const limb_sel_t& sel, const ntt_io_t& io) {
-    const int x = c->logN - 14;
-    const dim3 tg((unsigned)((((c->N >> x) + 255) / 256) * rows));
-    return dispatch_int<1, 2>(x, [&](auto xc) {
-        return launch(c, k_ntt_fwd_top_lift<decltype(xc)::value>, tg, dim3(256), 0, src, t, c->limbs_dev, sel, c->logN, io);
-    });
-}
-// Part A of the unfused key switch: the NTT-domain RNS digits of c[end], dig [batch][level][nw][N]
-// (centred lift of limb i into every working limb, rlwe_she.jl:326-329, then forward transforms).
-static int ks_digits_fwd(tfhe_ctx* c, const ks_arg_t& A, const u64* ct, u64* dig, int64_t batch) {
-    const int level = A.level, nw = A.nw, polys = A.polys;
-    const u32 n = (u32)c->N;
-    int rc;
-    const bool lift_fused = c->logN <= 14 || ((c->logN == 15 || c->logN == 16) && c->variant == 0 && sel_fp(c, A.w, c->logN - 14) &&
-                                              (((uintptr_t)ct | (uintptr_t)dig) & 15u) == 0);
-    // rings that mix fp64-size moduli with larger ones (infer.jl:97-112: 60-bit q0 and special prime next to 40-bit primes)
-    // at N = 2^15 / 2^16: the fp64-size working limbs take the lift-fused one-kernel transforms (the fp64 lift reads source
-    // limbs of either size), the others go through the digit buffer and the u64 kernels
-    const policy_split_t ps = policy_split(c, A.w);
-    const u32 fpmask = ps.fpmask, allmask = ps.all;
-    const bool lift_mixed = !lift_fused && nw <= 32 && (c->logN == 15 || c->logN == 16) && c->variant == 0 && ps.mixed_fp() &&
-                            (((uintptr_t)ct | (uintptr_t)dig) & 15u) == 0;
-    if (lift_fused) {
-        // digits: centred lift of limb i of c[end] into every working limb, fused into the forward NTT's loads
-        ntt_io_t io = io_plain();
-        io.mode = 1; io.level = (u32)level; io.nw = (u32)nw; io.polys = (u32)polys;
-        rc = run_ntt(c, false, ct, dig, batch * level * nw, A.w, &io);
-        if (rc) return rc;
-    } else if (lift_mixed) {
-        ntt_io_t io = io_plain();
-        io.mode = 1; io.level = (u32)level; io.nw = (u32)nw; io.polys = (u32)polys; io.limb_mask = fpmask;
-        const int64_t rows = batch * level * nw;
-        const int x = c->logN - 14;
-        void* tmp = nullptr;
-        rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);   // (before the fork: growing the workspace synchronises)
-        if (rc) return rc;
-        lanes_t lanes(c);   // the fp64-size working limbs on the side lane, beside the u64 ones
-        lanes.use(1);
-        rc = run_ntt_large(c, false, ct, dig, rows, A.w, io, &io, true, true);
-        if (rc) return rc;
-        lanes.use(0);
-        // the larger working limbs: lift fused into the top-stage kernel (into the transform scratch), then the u64 block kernels
-        ntt_io_t iw = io;
-        iw.limb_mask = allmask & ~fpmask;
-        rc = launch_top_lift(c, ct, (u64*)tmp, rows, A.w, iw);
-        if (rc) return rc;
-        ntt_io_t ib = io_plain();
-        ib.limb_mask = allmask & ~fpmask;
-        rc = launch_block_fwd<ArithInt, 14>(c, (const u64*)tmp, dig, rows, A.w, x, ib);
-        if (rc) return rc;
-    } else {
-        rc = launch(c, k_ks_digits, row_grid((unsigned)(batch * level * nw), (size_t)c->N), dim3(256), 0, ct, dig, c->limbs_dev, A, n, 0u);
-        if (rc) return rc;
-        rc = run_ntt(c, false, dig, dig, batch * level * nw, A.w);
-        if (rc) return rc;
-    }
-    return TFHE_OK;
-}
-
-// tfhe_matmul_diag, evaluation-domain form: U[grp][j] = NTT_j( [P[grp]] mod q_j ) (x P^-1 unless *scaled comes back false) for
-// the `groups` special-limb rows P (coefficient domain, canonical) and the limbs j of `sl`.  At N = 2^16 the lift rides on the
-// forward transforms' loads (ntt_io_t::lift_unsigned: k_ntt_fwd_quad for the fp64-size limbs, k_ntt_fwd_top_lift + the u64 block
-// kernels for the others) and the factor P^-1 is left to k_md_acc; otherwise k_md_lift writes the scaled lifts to `LF` and plain
-// transforms follow.
-// Whether the unsigned lift can ride on the forward transforms' loads (ntt_io_t::lift_unsigned) for these target limbs and this
-// special prime: N = 2^15 / 2^16 through the pair / quad kernels (+ top-stage lift for the u64 limbs); N <= 2^14 through
-// run_ntt's digit-lift mode -- except when every target limb is fp64-size and the special prime is not (the uniform fp64 policy
-// reads its source as one double).
-static bool md_lift_is_fused(const tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl) {
-    const int level = A.level;
-    if (level > 32 || c->logN > 16) return false;
-    if (c->logN >= 15) return c->variant == 0;
-    const bool special_fp = c->limbs_host[A.w.idx[level]].Wd != nullptr;
-    return special_fp || !sel_fp(c, sl, 0);
-}
-static int md_lift_fwd(tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl, const rescale_arg_t& ra, const u64* P, u64* LF, u64* U,
-                       int64_t groups, bool* scaled) {
-    const int level = A.level;
-    const u32 n = (u32)c->N;
-    const int64_t rows = groups * level;
-    if (LF == nullptr) {   // the caller sized the workspace for the fused form (md_lift_is_fused)
-        ntt_io_t io = io_plain();
-        io.mode = 1; io.level = 1; io.nw = (u32)level; io.polys = 1; io.lift_unsigned = 1;
-        *scaled = false;
-        if (c->logN <= 14) return run_ntt(c, false, P, U, rows, sl, &io);
-        const int x = c->logN - 14;
-        const policy_split_t ps = policy_split(c, sl);
-        const u32 tmask = ps.fpmask, tall = ps.all;   // fp64-size target limbs
-        const bool special_fp = c->limbs_host[A.w.idx[level]].Wd != nullptr;
-        if ((rows << x) > 0x7fffffffll || (((uintptr_t)P | (uintptr_t)U) & 15u) != 0) return fail(TFHE_E_BADARG, "md_lift_fwd: row count / alignment");
-        int rc;
-        void* tmp = nullptr;
-        if (tmask != tall) {   // (before the fork: growing the workspace synchronises)
-            rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
-            if (rc) return rc;
-        }
-        lanes_t lanes(c, tmask != 0 && tmask != tall);   // both kinds of limbs: side by side
-        if (tmask) {   // the fp64-size limbs: one kernel per row (pair) (ArithFpWide reads a source above 2^52 in two halves)
-            ntt_io_t a = io;
-            a.limb_mask = tmask == tall ? 0u : tmask;
-            lanes.use(1);
-            rc = run_ntt_large(c, false, P, U, rows, sl, a, &a, true, !special_fp);
-            if (rc) return rc;
-            lanes.use(0);
-        }
-        if (tmask != tall) {   // the larger limbs: lift fused into the top stages (into the transform scratch), then the u64 block kernels
-            ntt_io_t w = io;
-            w.limb_mask = tmask ? (tall & ~tmask) : 0u;
-            rc = launch_top_lift(c, P, (u64*)tmp, rows, sl, w);
-            if (rc) return rc;
-            ntt_io_t ib = io_plain();
-            ib.limb_mask = w.limb_mask;
-            rc = launch_block_fwd<ArithInt, 14>(c, (const u64*)tmp, U, rows, sl, x, ib);
-            if (rc) return rc;
-        }
-        return TFHE_OK;
-    }
-    const int rc = launch(c, k_md_lift, row_grid((unsigned)rows, (size_t)c->N), dim3(256), 0, P, LF, c->limbs_dev, sl, ra, n);
-    if (rc) return rc;
-    *scaled = true;
-    return run_ntt(c, false, LF, U, rows, sl);
-}
-
-static int do_galois(tfhe_ctx* c, const u64* src, u64* dst, u64 g, int64_t rows, const limb_sel_t& sel);
-// S_s = sum_i evk_{i,s} (.) digit_i over the working limbs (NTT domain), S: [batch][2][nw][N]
-// keys != nullptr: `nkeys` keys against the same digits in one launch, key r writing S + r * batch*2*nw*N (tfhe_matmul_diag)
-static int ks_inner_launch(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* evk, const u64* dig, u64* S, int64_t batch,
-                           const uint64_t* const* keys = nullptr, int nkeys = 0, const u64* epi_x = nullptr) {
-    const int nw = A.nw;
-    ks_keys_t K{};
-    if (keys) {
-        K.n = nkeys;
-        K.s_stride = (size_t)batch * 2 * nw * (size_t)c->N;
-        for (int r = 0; r < nkeys; r++) K.key[r] = keys[r];
-        evk = keys[0];
-        K.epi_x = epi_x;
-    }
-    const unsigned gy = keys ? (unsigned)nkeys : 1u;
-    const u32 n = (u32)c->N;
-    const unsigned gx = (n + 255) / 256;
-    // enough workgroups to fill the chip: split the batch into slices (the key is re-read once per slice)
-    // (several keys in one launch multiply the grid by gy)
-    const unsigned bsplit = (unsigned)std::max<int64_t>(1, std::min<int64_t>(batch, (4096 + nw * gx * gy - 1) / (nw * gx * gy)));
-    // working limbs below 2^52: the two-coefficient, carry-free kernel; the others: the generic one (more than 32 working
-    // limbs: all or nothing, see mask_of)
-    // several keys: groups of eight x-blocks (one per XCD), each followed by its keys (ks_multi_key_block)
-    auto multi = [&](unsigned nx) { return keys ? dim3(((nx + 7u) / 8u) * 8u * gy) : dim3(nx); };
-    const policy_split_t ps = policy_split(c, A.w);
-    const u32 nmask = n % 2 != 0 ? 0u : ps.narrow, amask = ps.all;
-    lanes_t lanes(c, nmask != 0 && nmask != amask);   // both kernels: side by side (disjoint working limbs)
-    if (nmask) {
-        lanes.use(1);
-        const unsigned gx2 = (n / 2 + 255) / 256;
-        const unsigned bs2 = (unsigned)std::max<int64_t>(1, std::min<int64_t>(batch, (4096 + nw * gx2 * gy - 1) / (nw * gx2 * gy)));
-        auto kn = epi_x ? k_ks_inner_n2<8, true> : k_ks_inner_n2<8, false>;
-        const int rc = launch(c, kn, multi((unsigned)nw * gx2 * bs2), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)batch, bs2,
-                              nmask == amask ? 0u : nmask, K);
-        if (rc) return rc;
-    }
-    if (nmask != amask) {
-        lanes.use(0);
-        auto kg = epi_x ? k_ks_inner<8, true> : k_ks_inner<8, false>;
-        return launch(c, kg, multi((unsigned)nw * gx * bsplit), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)batch, bsplit,
-                      nmask ? (amask & ~nmask) : 0u, K);
-    }
-    return TFHE_OK;
-}
-// Part B: S_s = sum_i evk_{i,s} (.) digit_i, inverse transforms, and the tail out_s = ct_s + ... (with the special prime: the
-// ModulusRaised contraction).  `ct` only supplies the addends.  `tbuf` ([batch][2][nw][N]) receives the sub-block inverse at
-// N = 2^16; the plain key switch passes the digit buffer (free by then).
-// Hoisted rotations (g != 0): `evk` is the key of x -> x^g prepared by tfhe_galois_key_prepare (its NTT-domain rows permuted by
-// g^-1), so the sums are those of the rotated digits up to that permutation: S' = sigma_g^-1(S).  The automorphism is applied
-// to INTT(S') in the coefficient domain (a signed permutation) BEFORE the tail -- the ModulusRaised floor does not commute
-// with sign changes -- into `tbuf`, which must not alias the digits (they are reused by the next rotation).
-// whether ks_finish takes the N = 2^16 path (paired sub-block inverse + k_ks_top_tail<2>)
-static bool ks_tail16(const tfhe_ctx* c, const ks_arg_t& A) {
-    return c->logN == 16 && c->variant == 0 && policy_split(c, A.w).fpmask != 0 && A.level >= 2;
-}
-// the inverse top stages of N = 2^15 / 2^16 over the sub-block results T together with the tail ("+ c" / the special-prime
-// contraction); g_tail != 0: the automorphism rides on the tail's stores (XCD-cooperative scatter, k_ks_top_tail_rot)
-static int launch_top_tail(tfhe_ctx* c, const ks_arg_t& A, const rescale_arg_t& ra, const u64* T, const u64* ct, u64* out, int64_t batch, u64 g_tail) {
-    const u32 n = (u32)c->N, add_s = A.polys == 3 ? 2u : 1u;
-    return dispatch_int<1, 2>(c->logN - 14, [&](auto xc) {
-        constexpr int X = decltype(xc)::value;
-        if (g_tail)
-            return launch(c, k_ks_top_tail_rot<X>, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, T, ct, out, c->limbs_dev, A, ra, n, add_s, g_tail, (u32)(batch * 2));
-        return launch(c, k_ks_top_tail<X>, row_grid((unsigned)(batch * 2 * A.level), (size_t)c->N >> X), dim3(256), 0, T, ct, out, c->limbs_dev, A, ra, n, add_s);
-    });
-}
-// g_tail != 0: a rotation finished in the tail (k_ks_top_tail_rot<2>; N = 2^16 path only): `evk` is the prepared key, `ct` the
-// UNrotated input
-// `outer`: the caller's forked region (ks_chunk) -- the steps up to the inverse sub-block transforms stay on their lanes, the
-// join comes before the tail, which reads every limb
-static int ks_finish(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* evk, const u64* ct, u64* out, int64_t batch, u64* S,
-                     const u64* dig, u64* tbuf, u64 g, u64 g_tail = 0, lanes_t* outer = nullptr) {
-    const int level = A.level, nw = A.nw, polys = A.polys, special = A.special;
-    const u32 n = (u32)c->N;
-    const u32 add_s = polys == 3 ? 2u : 1u;  // c2 starts from zero for a 2-element input (rlwe_she.jl:324)
-    int rc = ks_inner_launch(c, A, Lk, evk, dig, S, batch);
-    if (rc) return rc;
-    const dim3 tail_grid = row_grid((unsigned)(batch * 2 * level), (size_t)c->N);
-    rescale_arg_t ra{};
-    if (special) special_inv_table(c, Lk, level, ra.qlinv);
-    if (g != 0) {  // hoisted rotation: INTT, automorphism, tail
-        if (outer) outer->join();
-        rc = run_ntt(c, true, S, S, batch * 2 * nw, A.w);
-        if (rc) return rc;
-        rc = do_galois(c, S, tbuf, g, batch * 2 * nw, A.w);
-        if (rc) return rc;
-        if (special) return launch(c, k_ks_rescale_add, tail_grid, dim3(256), 0, tbuf, ct, out, c->limbs_dev, A, ra, n, add_s);
-        HIP_TRY(hipMemcpyAsync(out, tbuf, (size_t)batch * 2 * level * c->N * 8, hipMemcpyDeviceToDevice, c->stream));
-        return launch(c, k_ks_add_ct, tail_grid, dim3(256), 0, ct, out, c->limbs_dev, A, n, add_s);
-    }
-    const policy_split_t ps = policy_split(c, A.w);
-    const u32 fpm = ps.fpmask, amask = ps.all;
-    const bool tail16 = ks_tail16(c, A) && (((uintptr_t)S | (uintptr_t)tbuf) & 15u) == 0;
-    if (g_tail && !tail16) return fail(TFHE_E_UNSUPPORTED, "internal: rotation in the tail needs the N = 2^16 sub-block path");
-    if (tail16) {
-        // N = 2^16: the paired sub-block inverse into the (now free) digit buffer, then the two inverse top stages together with
-        // the tail (k_ks_top_tail<2>) instead of k_ntt_inv_top<2> + k_ks_rescale_add / k_ks_add_ct.  Rings of mixed modulus sizes:
-        // the larger limbs' sub-blocks come from the u64 block kernel (same sub-block layout, lazy [0, 2q) outputs).
-        {
-            lanes_t lanes(c, fpm != amask);
-            lanes.use(1);
-            rc = launch_subpair<ArithFp>(c, true, S, tbuf, batch * 2 * nw, A.w, 2, fpm == amask ? 0u : fpm);
-            if (rc) return rc;
-            if (fpm != amask) {
-                lanes.use(0);
-                ntt_io_t iw = io_plain();
-                iw.limb_mask = amask & ~fpm;
-                rc = launch_block_inv<ArithInt, 14>(c, S, tbuf, batch * 2 * nw, A.w, 2, iw);
-                if (rc) return rc;
-            }
-        }
-        if (outer) outer->join();
-        return launch_top_tail(c, A, ra, tbuf, ct, out, batch, g_tail);
-    }
-    if (outer) outer->join();
-    if (special) {
-        rc = run_ntt(c, true, S, S, batch * 2 * nw, A.w);
-        if (rc) return rc;
-        return launch(c, k_ks_rescale_add, tail_grid, dim3(256), 0, S, ct, out, c->limbs_dev, A, ra, n, add_s);
-    }
-    if (c->logN <= 14) {  // out = c + INTT(S), the addition fused into the inverse NTT's stores
-        ntt_io_t io = io_plain();
-        io.mode = 2; io.gsz = (u32)(2 * level); io.src_gstride = io.gsz; io.dst_gstride = io.gsz;
-        io.add_rows = add_s * (u32)level; io.add_gstride = (u32)(polys * level); io.addend = ct;
-        return run_ntt(c, true, S, out, batch * 2 * nw, A.w, &io);
-    }
-    rc = run_ntt(c, true, S, out, batch * 2 * nw, A.w);
-    if (rc) return rc;
-    return launch(c, k_ks_add_ct, tail_grid, dim3(256), 0, ct, out, c->limbs_dev, A, n, add_s);
-}
-
-// g_tail != 0: a rotation finished in the tail (k_ks_top_tail_rot) -- `ct` is the UNrotated input and `evd` was prepared for g
-static int ks_chunk(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, u64* out, int64_t batch,
-                    u64* S, u64* dig, const u64* evd, bool prelifted, u64 g_tail = 0) {
-    ks_arg_t A = make_ks_arg(Lk, level, special, polys);
-    const int nw = A.nw;
-    const u32 n = (u32)c->N;
-    const u32 add_s = polys == 3 ? 2u : 1u;  // c2 starts from zero for a 2-element input (rlwe_she.jl:324)
-    const u64* const none = nullptr;
-    int rc;
-    if (evd && (c->logN == 14 || c->logN == 13)) {  // ks_fused14
-        // everything in one kernel: digit lift, forward transforms, key inner product and the two inverse transforms;
-        // with the special prime the transformed sums go to S and the contraction kernel finishes (modulusraising.jl:42)
-        const unsigned items = (unsigned)(batch * nw);
-        const int64_t transforms = (int64_t)items * (level + 2);  // limb transforms inside the fused launch(es): `level` forward + 2 inverse per item
-        // Special prime: two launches -- the special limb of every ciphertext first (its coefficient rows t_P into S), then the
-        // ciphertext limbs with the ModulusRaised contraction and "+ c" in their final store (k_ks_fused SPMODE 1 / 2, ArithFpMD).
-        // No T, no tail kernel.  TFHE_KS_TAIL=1 keeps the one-launch form with k_ks_rescale_add (comparisons).
-        static const bool ks_tail = env_flag("TFHE_KS_TAIL", false);
-        if (special && !prelifted && !ks_tail) {
-            {
-                std::lock_guard<std::mutex> zg(c->zero_mu);         // a failed attempt (transient out-of-memory) is retried by the next call
-                if (!c->zero_row) {
-                    void* z = nullptr;
-                    if (devalloc::malloc_retry(&z, (size_t)c->N * 8) == hipSuccess) {
-                        if (hipMemset(z, 0, (size_t)c->N * 8) == hipSuccess) c->zero_row = (u64*)z;
-                        else { (void)hipGetLastError(); (void)hipFree(z); }
-                    } else (void)hipGetLastError();
-                }
-                if (!c->zero_row) return fail(TFHE_E_NOMEM, "allocating the zero row failed");
-            }
-            special_inv_table(c, Lk, level, A.pinv);
-            const unsigned it1 = (unsigned)batch, it2 = (unsigned)(batch * level);
-            auto launch2 = [&](auto k1, auto k2, int LOGT, size_t lds, unsigned per_cu) -> int {   // both launches in ONE profiled region
-                prof_scope p(c, transforms);
-                const int r1 = launch(c, k1, dim3(cu_grid(c, it1, per_cu)), dim3(1u << LOGT), lds, evd, ct, S, c->limbs_dev, A, Lk, it1, none, none);
-                if (r1) return r1;
-                return launch(c, k2, dim3(cu_grid(c, it2, per_cu)), dim3(1u << LOGT), lds, evd, ct, out, c->limbs_dev, A, Lk, it2, (const u64*)S, (const u64*)c->zero_row);
-            };
-            if (g_tail && c->logN != 14) return fail(TFHE_E_UNSUPPORTED, "internal: rotation in the store is an N = 2^14 path");
-            if (c->logN == 13) {
-                constexpr int LOGT = logt_for(13);
-                return launch2(k_ks_fused<ArithFp, 13, LOGT, false, 1>, k_ks_fused<ArithFp, 13, LOGT, false, 2>, LOGT, fused_lds_bytes<13, LOGT>(), 2u);
-            }
-            constexpr int LOGT = logt_for(14);
-            const size_t lds = fused_lds_bytes<14, LOGT>();
-            if (!g_tail) return launch2(k_ks_fused<ArithFp, 14, LOGT, false, 1>, k_ks_fused<ArithFp, 14, LOGT, false, 2>, LOGT, lds, 1u);
-            // rotation finished in the second launch's stores (SPMODE 3; `ct` is the unrotated input)
-            A.rot_g = (u32)(g_tail & (2 * (u64)c->N - 1));
-            return launch2(k_ks_fused<ArithFp, 14, LOGT, false, 1>, k_ks_fused<ArithFp, 14, LOGT, false, 3>, LOGT, lds, 1u);
-        }
-        if (g_tail) return fail(TFHE_E_UNSUPPORTED, "internal: rotation in the store needs the two-launch special-prime form");
-        if (c->logN == 14) {
-            constexpr int LOGT = logt_for(14);
-            auto fk = prelifted ? k_ks_fused<ArithFp, 14, LOGT, true> : k_ks_fused<ArithFp, 14, LOGT, false>;
-            rc = launch_prof(c, transforms, fk, dim3(cu_grid(c, items)), dim3(1 << LOGT), fused_lds_bytes<14, LOGT>(), evd, ct,
-                             special ? S : out, c->limbs_dev, A, Lk, items, none, none);
-        } else {  // N = 2^13: 256 threads x 32 elements, 65 KiB of LDS; 478 registers per thread, so one workgroup per CU is resident
-                  // (capped to two resident workgroups it measured 5 % slower)
-            constexpr int LOGT = logt_for(13);
-            rc = launch_prof(c, transforms, k_ks_fused<ArithFp, 13, LOGT, false>, dim3(cu_grid(c, items, 2u)), dim3(1 << LOGT), fused_lds_bytes<13, LOGT>(),
-                             evd, ct, special ? S : out, c->limbs_dev, A, Lk, items, none, none);
-        }
-        if (rc || !special) return rc;
-        rescale_arg_t ra{};
-        special_inv_table(c, Lk, level, ra.qlinv);
-        return launch(c, k_ks_rescale_add, row_grid((unsigned)(batch * 2 * level), (size_t)c->N), dim3(256), 0, S, ct, out, c->limbs_dev, A, ra, n, add_s);
-    }
-    if (evd && (c->logN == 15 || c->logN == 16)) {  // ks_fused14: variant 0, fp64 policy, level >= 2
-        // N = 2^15 / 2^16 on fp64-size moduli: per-sub-block fused key switch (k_ks_fused_sub) into T = dig ([batch][2][nw] rows,
-        // level >= 2 makes room), then the inverse top stages over T together with the tail.  At 2^16 (X = 2) the four quarters
-        // of a digit row stream through the LDS (dma_stream_load, no spills: 33.0 k against 32.1 k key switches/s for the
-        // three-kernel path on 7 x 50 bit; with register loads the X = 2 load phase either spilled 237 registers or ran as 32
-        // serial rounds: 26-28 k).  At 2^15 the register loads stay (the streamed form measured 36.2 k against 40.2 k, cfg#3).
-        // TFHE_FUSED16=0 keeps the three-kernel path at 2^16.
-        constexpr int LOGT = logt_for(14);
-        const size_t lds = (size_t)lds_words<14, LOGT>() * 8;
-        const int x = c->logN - 14;
-        // moduli below 2^42 (the 40-bit chains of the reference's CKKS rings): the range plan of that size class -- no forward
-        // sweeps, no reduced product operands, one sweep per inverse (ArithFpS): cfg#3 36.5 k -> 38.1 k key switches/s
-        bool small = true;
-        for (int j = 0; j < nw; j++) small = small && c->q[A.w.idx[j]] < TFHE_FPS_QMAX;
-        static const bool fps_on = env_flag("TFHE_FPS", true);
-        auto fk = x == 2 ? ((small && fps_on) ? k_ks_fused_sub<ArithFpS, 14, LOGT, 2> : k_ks_fused_sub<ArithFp, 14, LOGT, 2>)
-                         : ((small && fps_on) ? k_ks_fused_sub<ArithFpS, 14, LOGT, 1> : k_ks_fused_sub<ArithFp, 14, LOGT, 1>);
-        const unsigned items = (unsigned)((batch * nw) << x);
-        rc = launch_prof(c, (int64_t)batch * nw * (level + 2), fk, dim3(cu_grid(c, items)), dim3(1 << LOGT), lds, evd, ct, dig, c->limbs_dev, A, Lk, items);
-        if (rc) return rc;
-        // inverse top stage + "+ c" / special-prime contraction in one pass over the sub-block results
-        rescale_arg_t ra{};
-        if (special) special_inv_table(c, Lk, level, ra.qlinv);
-        return launch_top_tail(c, A, ra, dig, ct, out, batch, g_tail);
-    }
-    // Rings of mixed modulus sizes at N = 2^16 (the three-kernel path): when the digit transforms, the key sums and the inverse
-    // sub-block transforms all split the working limbs the same way (fp64-size = "narrow"), the two policies run as two lanes
-    // from the lift to the inverse with ONE join before the tail; otherwise every step forks and joins by itself.
-    const policy_split_t ps = policy_split(c, A.w);
-    const bool two_lanes = nw <= 32 && c->variant == 0 && c->logN == 16 && ps.mixed_fp() && ps.fpmask == ps.narrow && ks_tail16(c, A) &&
-                           (((uintptr_t)ct | (uintptr_t)dig | (uintptr_t)S) & 15u) == 0;
-    if (two_lanes) {
-        void* tmp = nullptr;
-        rc = ensure_ws(c, (size_t)batch * level * nw * c->N * 8, &tmp);   // (no-op under keyswitch_impl; before the fork)
-        if (rc) return rc;
-    }
-    lanes_t outer(c, two_lanes);
-    rc = ks_digits_fwd(c, A, ct, dig, batch);
-    if (rc) return rc;
-    return ks_finish(c, A, Lk, evk, ct, out, batch, S, dig, dig, 0, g_tail, &outer);
-}
-
-static int ks_check(tfhe_ctx* c, int Lk, int level, int special, const void* evk, int n_digits, const void* ct, int polys, const void* out, int64_t batch) {
-    if (!c || !evk || !ct || !out) return fail(TFHE_E_BADARG, "null argument");
-    if (polys != 2 && polys != 3) return fail(TFHE_E_BADARG, "keyswitch needs a 2- or 3-element ciphertext (rlwe_she.jl:318), got %d", polys);
-    if (Lk < 1 || Lk > c->L) return fail(TFHE_E_LEVEL_MISMATCH, "key_limbs=%d outside [1,%d]", Lk, c->L);
-    const int maxlevel = special ? Lk - 1 : Lk;
-    if (level < 1 || level > maxlevel) return fail(TFHE_E_LEVEL_MISMATCH, "level=%d outside [1,%d]", level, maxlevel);
-    if (n_digits < level) return fail(TFHE_E_PARAMS_MISMATCH, "evaluation key has %d components, level %d needs %d", n_digits, level, level);
-    if (batch < 0) return fail(TFHE_E_BADARG, "negative batch");
-    return TFHE_OK;
-}
-
-static u64 inv_mod_2n(u64 g, u64 twoN);
-// key_prepared (rotations only, tfhe_rotate_prepared): `evk` is the output of tfhe_galois_key_prepare for `galois` -- the paths that
-// finish the rotation in their tail consume it as it is (no per-call k_ntt_perm / permuting conversion); the others take the
-// hoisted form of tfhe_rotate_many, which is defined on prepared keys (same bits)
-static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, u64* out, int64_t batch,
-                          u64 galois, bool rotate, bool prelifted = false, bool key_prepared = false) {
-    if (prelifted && (rotate || special || !ks_prelift_ok(c, level))) return fail(TFHE_E_UNSUPPORTED, "internal: pre-lifted rows need the fused key switch");
-    const int nw = special ? level + 1 : level;
-    const size_t N = (size_t)c->N;
-    const bool f14 = ks_fused14(c, Lk, level, special);
-    // Rotations through the sub-block fused key switch (N = 2^15 / 2^16): no rotated copy of the input -- the key is prepared while
-    // it is converted (k_evk_to_f64), the key sums are those of the unrotated digits, the automorphism rides on the tail's stores
-    // (k_ks_top_tail_rot).  Same bits (the hoisting identity of tfhe_rotate_many).  TFHE_ROT_TAIL=0 keeps the separate pass.
-    static const bool rot_tail_on = env_flag("TFHE_ROT_TAIL", true);
-    // The tail scatters into `out` while other workgroups still read the unrotated `ct`: the two RANGES must be disjoint (r05, ADVICE
-    // r04: pointer inequality let a partially overlapping out / ct race) -- otherwise the rotated-copy path below runs.
-    const bool io_disjoint = (const char*)(out + (size_t)batch * 2 * level * N) <= (const char*)ct ||
-                             (const char*)(ct + (size_t)batch * polys * level * N) <= (const char*)out;
-    bool rot_in_tail = rotate && f14 && c->logN >= 15 && rot_tail_on && io_disjoint && batch >= 8;   // (one (ciphertext, component) per XCD at a time)
-    // N = 2^14 with the special prime (the two-launch fused key switch): the rotation rides on the in-kernel contraction's stores
-    // (k_ks_fused SPMODE 3) -- each workgroup scatters the row it owns
-    static const bool ks_tail_env = env_flag("TFHE_KS_TAIL", false);
-    if (rotate && f14 && c->logN == 14 && special && !prelifted && !ks_tail_env && rot_tail_on && io_disjoint) rot_in_tail = true;
-    // the same for the N = 2^16 three-kernel path (rings with moduli beyond the fp64 size: the reference's CKKS ring): the key is
-    // prepared into the workspace (k_ntt_perm), the rotation rides on k_ks_top_tail_rot<2>
-    bool rot_key_prep = false;
-    const ks_arg_t KA = make_ks_arg(Lk, level, special, polys);
-    if (rotate && !f14 && rot_tail_on && io_disjoint && batch >= 8 && ks_tail16(c, KA)) rot_in_tail = rot_key_prep = true;
-    if (key_prepared && !rot_in_tail) {
-        const uint64_t* one[1] = {evk};
-        return tfhe_rotate_many(c, Lk, level, special, one, level, 1, &galois, 1, ct, out, batch);
-    }
-    if (key_prepared) rot_key_prep = false;   // the three-kernel path reads the prepared key where it lies
-    // chunk the batch so that the digit tensor stays at a few GiB.  The fused key switches (ks_fused14) never write the digit
-    // rows: at N = 2^15 the "digit" buffer only carries the sub-block sums T (2 nw rows per ciphertext), so a whole batch is one
-    // launch (cfg#3, 512 ciphertexts: 248 + 248 + 16 before -- the 16 ran as two nearly empty item rounds of k_ks_fused_sub)
-    const size_t dig_rows = f14 ? (size_t)2 * nw : (size_t)level * nw;
-    const size_t per_ct = ((size_t)2 * nw + dig_rows + (rotate ? (size_t)polys * level : 0)) * N * 8;
-    int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
-    void* ws = nullptr;
-    // NTT of N > 2^14 uses the context workspace as well: keep ours separate by over-allocating (the fused paths run no
-    // stand-alone transform)
-    const size_t ntt_tmp = (c->logN > 14 && !f14) ? (size_t)chunk * std::max(2, level) * nw * N * 8 : 0;
-    const size_t evd_bytes = f14 ? (size_t)level * 2 * nw * N * 8                  // the key rows of this call as doubles
-                                 : (rot_key_prep ? (size_t)level * 2 * Lk * N * 8 : 0);   // ... or the prepared key of a rotation
-    int rc = ensure_ws(c, ntt_tmp + chunk * per_ct + evd_bytes, &ws);
-    if (rc) return rc;
-    u64* base = (u64*)((char*)ws + ntt_tmp);
-    u64* acc = base;
-    u64* dig = acc + (size_t)chunk * 2 * nw * N;
-    u64* rot = dig + (size_t)chunk * dig_rows * N;
-    u64* evd = nullptr;
-    if (f14) {
-        evd = (u64*)((char*)ws + ntt_tmp + chunk * per_ct);
-        rc = launch(c, k_evk_to_f64, row_grid((unsigned)(level * 2 * nw), N), dim3(256), 0, evk, evd, c->limbs_dev, KA, Lk, (u32)N, c->logN <= 14 ? 1 : 0, c->logN == 16 ? 2 : 0,
-                    (rot_in_tail && !key_prepared) ? inv_mod_2n(galois, 2 * (u64)c->N) : (u64)0, 1);
-        if (rc) return rc;
-    }
-    if (rot_key_prep) {
-        u64* keyp = (u64*)((char*)ws + ntt_tmp + chunk * per_ct);
-        rc = launch(c, k_ntt_perm, row_grid((unsigned)(level * 2 * Lk), N), dim3(256), 0, evk, keyp, inv_mod_2n(galois, 2 * (u64)c->N), (u32)N);
-        if (rc) return rc;
-        evk = keyp;
-    }
-    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-        const int64_t nb = std::min(chunk, batch - b0);
-        const u64* cin = ct + (size_t)b0 * polys * level * N;
-        if (rotate && !rot_in_tail) {
-            rc = do_galois(c, cin, rot, galois, nb * polys * level, first_limbs(level));
-            if (rc) return rc;
-            cin = rot;
-        }
-        rc = ks_chunk(c, Lk, level, special, evk, cin, polys, out + (size_t)b0 * 2 * level * N, nb, acc, dig, evd, prelifted, rot_in_tail ? galois : (u64)0);
-        if (rc) return rc;
-    }
-    return TFHE_OK;
-}
-
-int tfhe_keyswitch(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk, int n_digits, const uint64_t* ct, int polys, uint64_t* out, int64_t batch) {
-    int rc = ks_check(c, Lk, level, special, evk, n_digits, ct, polys, out, batch);
-    if (rc) return rc;
-    return keyswitch_impl(c, Lk, level, special, evk, ct, polys, out, batch, 0, false);
-}
-// Hoisted rotations: rotate(gk_r, c) for r < n_rot from ONE digit decomposition.  The centred RNS digits commute with the
-// automorphism (a signed permutation of coefficients; the centred representative of -x is the negative of that of x, q odd),
-// and in the NTT domain the automorphism is the permutation galois_ntt_pos.  With the key rows permuted by g^-1 once per key
-// (tfhe_galois_key_prepare) the inner product runs coalesced on the transformed digits of the UNrotated ciphertext and yields
-// sigma_g^-1 of the sums; the automorphism is applied after the inverse transform, over 2 nw rows instead of level nw:
-// level * nw forward transforms once instead of per rotation.  Bit-identical to n_rot calls of tfhe_rotate.
-static u64 inv_mod_2n(u64 g, u64 twoN) {  // g odd, twoN a power of two: Newton iteration
-    u64 x = g;
-    for (int i = 0; i < 6; i++) x *= 2 - g * x;
-    return x & (twoN - 1);
-}
-// evk_out = the Galois key of x -> x^g with every NTT-domain row permuted by g^-1 (tfhe_rotate_many with prepared = 1)
-int tfhe_galois_key_prepare(tfhe_ctx* c, int Lk, int n_digits, uint64_t g, const uint64_t* evk, uint64_t* evk_out) {
-    if (!c || !evk || !evk_out || evk == evk_out) return fail(TFHE_E_BADARG, "null or aliased argument");
-    if (Lk < 1 || Lk > c->L || n_digits < 1) return fail(TFHE_E_LEVEL_MISMATCH, "key shape outside the ring");
-    if ((g & 1) == 0 || g >= 2 * (u64)c->N) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
-    const u64 ginv = inv_mod_2n(g, 2 * (u64)c->N);
-    return launch(c, k_ntt_perm, row_grid((unsigned)(n_digits * 2 * Lk), (size_t)c->N), dim3(256), 0, evk, evk_out, ginv, (u32)c->N);
-}
-
-int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, int prepared,
-                     const uint64_t* galois, int n_rot, const uint64_t* ct, uint64_t* out, int64_t batch) {
-    if (!evks || !galois || n_rot < 0) return fail(TFHE_E_BADARG, "null argument");
-    if (n_rot == 0) return TFHE_OK;
-    for (int r = 0; r < n_rot; r++) {
-        int rc = ks_check(c, Lk, level, special, evks[r], n_digits, ct, 2, out, batch);
-        if (rc) return rc;
-        if ((galois[r] & 1) == 0 || galois[r] >= 2 * (u64)c->N) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
-    }
-    const int nw = special ? level + 1 : level, polys = 2;
-    const size_t N = (size_t)c->N;
-    if (!prepared && c->logN <= 14 && ks_fused14(c, Lk, level, special)) {
-        // N = 2^14 on fp64-size moduli: the fused key switch (digits never leave the registers) beats the hoisted three-kernel
-        // path (measured 126 k against 110 k rotations/s at 6 limbs + special prime) -- same bits either way
-        for (int r = 0; r < n_rot; r++) {
-            int rc = keyswitch_impl(c, Lk, level, special, evks[r], ct, 2, out + (size_t)r * batch * 2 * level * N, batch, galois[r], true);
-            if (rc) return rc;
-        }
-        return TFHE_OK;
-    }
-    const ks_arg_t A = make_ks_arg(Lk, level, special, polys);
-    // workspace per ciphertext: S (2 nw rows) + digits (level nw) + T (2 nw) + rotated input (2 level); + one prepared key
-    const size_t per_ct = ((size_t)4 * nw + (size_t)level * nw + (size_t)polys * level) * N * 8;
-    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
-    const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * std::max(2, level) * nw * N * 8 : 0;
-    const size_t key_bytes = prepared ? 0 : (size_t)n_digits * 2 * Lk * N * 8;
-    void* ws = nullptr;
-    int rc = ensure_ws(c, ntt_tmp + chunk * per_ct + key_bytes, &ws);
-    if (rc) return rc;
-    u64* S = (u64*)((char*)ws + ntt_tmp);
-    u64* dig = S + (size_t)chunk * 2 * nw * N;
-    u64* T = dig + (size_t)chunk * level * nw * N;
-    u64* rot = T + (size_t)chunk * 2 * nw * N;
-    u64* keytmp = rot + (size_t)chunk * polys * level * N;
-    const limb_sel_t sl = first_limbs(level);
-    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-        const int64_t nb = std::min(chunk, batch - b0);
-        const u64* cin = ct + (size_t)b0 * polys * level * N;
-        rc = ks_digits_fwd(c, A, cin, dig, nb);
-        if (rc) return rc;
-        for (int r = 0; r < n_rot; r++) {
-            const u64* key = evks[r];
-            if (!prepared) {
-                rc = tfhe_galois_key_prepare(c, Lk, n_digits, galois[r], evks[r], keytmp);
-                if (rc) return rc;
-                key = keytmp;
-            }
-            rc = do_galois(c, cin, rot, galois[r], nb * polys * level, sl);   // the addend sigma_g(c_1) (and sigma_g(c_2), unused)
-            if (rc) return rc;
-            rc = ks_finish(c, A, Lk, key, rot, out + ((size_t)r * batch + b0) * 2 * level * N, nb, S, dig, T, galois[r]);
-            if (rc) return rc;
-        }
-    }
-    return TFHE_OK;
-}
-
-int tfhe_rotate(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk, int n_digits, uint64_t g, const uint64_t* ct, uint64_t* out, int64_t batch) {
-    int rc = ks_check(c, Lk, level, special, evk, n_digits, ct, 2, out, batch);
-    if (rc) return rc;
-    if ((g & 1) == 0) return fail(TFHE_E_BADARG, "galois element must be odd");
-    return keyswitch_impl(c, Lk, level, special, evk, ct, 2, out, batch, g, true);
-}
-// the same with the key as tfhe_galois_key_prepare left it (r06): a caller that rotates by ONE Galois element again and again
-// (infer.jl:140-149: 63 chained rotations per matrix product, one key) prepares it once instead of once per call
-int tfhe_rotate_prepared(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk_prepared, int n_digits, uint64_t g, const uint64_t* ct, uint64_t* out,
-                         int64_t batch) {
-    int rc = ks_check(c, Lk, level, special, evk_prepared, n_digits, ct, 2, out, batch);
-    if (rc) return rc;
-    if ((g & 1) == 0 || g >= 2 * (u64)c->N) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
-    return keyswitch_impl(c, Lk, level, special, evk_prepared, ct, 2, out, batch, g, true, false, true);
-}
-
-// ---- diagonal matrix-vector product (infer.jl:140-149, test/ckks_matmul.jl:33-41) in one call ---------------------------
-// out = diag_0 (.) c + sum_r diag_{r+1} (.) rotate(gk_r, c): the hoisted rotations of tfhe_rotate_many (one digit decomposition
-// of c) with every step -- key sums, inverse transforms, automorphism + tail, forward transforms, accumulation -- run over ALL
-// rotations at once instead of rotation by rotation (R x more rows per launch: about 15 launches per product instead of
-// about 8 R + 2 R + 2), and the rotated ciphertexts never return to the caller.  Same arithmetic, term by term, as
-// rotate_many -> nntt -> dot: bit-identical results.
-int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, const uint64_t* galois,
-                     int n_rot, const uint64_t* diags, const uint64_t* ct, uint64_t* out, int64_t batch) {
-    if (!evks || !galois || !diags || n_rot < 0) return fail(TFHE_E_BADARG, "null argument");
-    if (n_rot > TFHE_DOT_MAX) return fail(TFHE_E_UNSUPPORTED, "tfhe_matmul_diag takes at most %d rotations per call", TFHE_DOT_MAX);
-    for (int r = 0; r < n_rot; r++) {
-        int rc = ks_check(c, Lk, level, special, evks[r], n_digits, ct, 2, out, batch);
-        if (rc) return rc;
-        if ((galois[r] & 1) == 0 || galois[r] >= 2 * (u64)c->N) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
-    }
-    if (n_rot == 0) {
-        int rc = ks_check(c, Lk, level, special, diags, n_digits, ct, 2, out, batch);
-        if (rc) return rc;
-    }
-    if (batch == 0) return TFHE_OK;
-    const int nw = special ? level + 1 : level, polys = 2, R = n_rot;
-    const size_t N = (size_t)c->N;
-    const u32 n = (u32)c->N;
-    ks_arg_t A = make_ks_arg(Lk, level, special, polys);
-    const limb_sel_t sl = first_limbs(level);
-    rescale_arg_t ra{};
-    if (special) {
-        special_inv_table(c, Lk, level, ra.qlinv);
-        std::copy(ra.qlinv, ra.qlinv + level, A.pinv);
-    }
-    rot_tail_arg_t G{};
-    for (int r = 0; r < R; r++) G.g[r] = galois[r];
-    // With a special prime the rotations are finished in the evaluation domain (k_md_*: only the special limb of every key sum is
-    // inverse-transformed); TFHE_MD_COEFF=1 keeps the coefficient-domain tail (k_ks_rot_tail) for comparisons.
-    static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
-    const bool eval_form = special && R > 0 && !md_coeff;
-    // workspace per ciphertext: digits (level nw rows) + S / T (R 2 nw) + rotated ciphertexts (R 2 level) + the ciphertext's own transform (2 level)
-    // (+ evaluation-domain form: the lifted special limbs before their transforms (R 2 level) and the special limbs themselves (R 2))
-    // (the untransformed lifts only where the lift is not fused into the transforms' loads)
-    const bool need_lf = eval_form && !(md_lift_is_fused(c, A, sl) && (size_t)R * 2 * level * 4 * 512 <= 0x7fffffffull);
-    const size_t per_ct = ((size_t)level * nw + (size_t)R * 2 * nw + (size_t)R * 2 * level + (size_t)2 * level +
-                           (eval_form ? (need_lf ? (size_t)R * 2 * level : 0) + (size_t)R * 2 : 0)) * N * 8;
-    // The keys of all R rotations are read once per chunk (2.8 GB at N = 2^16, 6 limbs + special prime, 63 rotations): a chunk as
-    // large as the memory allows (32 GiB of workspace unless TFHE_MD_WS_GIB says otherwise; halved while the allocation fails)
-    static const size_t ws_cap_env = env_gib("TFHE_MD_WS_GIB", 32);
-    // ... and never more than half of what the device has free right now (counting what this context and the allocator's cache
-    // already hold, both of which the allocation below can reuse): other contexts, BFV plans and processes keep their room
-    size_t ws_cap = ws_cap_env;
-    {
-        // (hipMemGetInfo is a driver round trip -- milliseconds in a process with many allocations -- and this call sits in the
-        // launch path of a host-bound circuit: the reading is kept for two seconds)
-        // (r05, ADVICE r04: the reading and the allocator's cached bytes are those of THIS context's device -- a process driving
-        // several GPUs computed the cap from whichever device had asked last and from the cache summed over all of them)
-        struct mi_t { size_t free_bytes = 0; std::chrono::steady_clock::time_point at{}; };
-        static std::mutex mi_mu;
-        static std::map<int, mi_t> mi_dev;
-        size_t fr = 0, tot = 0;
-        bool have = false;
-        const int cur_dev = devalloc::current_device();          // what hipMemGetInfo reads and where the workspace will be allocated
-        {
-            std::lock_guard<std::mutex> g(mi_mu);
-            mi_t& mi = mi_dev[cur_dev];
-            const auto now = std::chrono::steady_clock::now();
-            if (mi.free_bytes && now - mi.at < std::chrono::seconds(2)) { fr = mi.free_bytes; have = true; }
-            else if (hipMemGetInfo(&fr, &tot) == hipSuccess) { mi.free_bytes = fr; mi.at = now; have = true; }
-            else (void)hipGetLastError();
-        }
-        if (have) {
-            size_t cached = 0;
-            {
-                devalloc::state_t& as = devalloc::S();
-                std::lock_guard<std::mutex> g(as.mu);
-                auto it = as.devs.find(cur_dev);
-                if (it != as.devs.end()) cached = it->second.cached_bytes;
-            }
-            ws_cap = std::min(ws_cap, std::max<size_t>((fr + c->ws_bytes + cached) / 2, (size_t)1 << 30));
-        }
-    }
-    int64_t chunk = chunk_of(c, batch, 512, ws_cap, per_ct);
-    size_t ntt_tmp = 0;
-    void* ws = nullptr;
-    int rc;
-    ws_borrow_t borrow(c);    // a workspace above ws_keep_bytes() is this call's: back to the allocator on every return path
-    for (bool first_try = true;; first_try = false) {
-        const size_t ntt_rows = (size_t)chunk * std::max<size_t>({(size_t)level * nw, (size_t)R * 2 * nw, (size_t)2 * level});
-        ntt_tmp = c->logN > 14 ? ntt_rows * N * 8 : 0;
-        const size_t need = ntt_tmp + chunk * per_ct;
-        if (first_try && need > ws_keep_bytes() && need > c->ws_bytes) borrow.begin();
-        rc = ensure_ws(c, need, &ws, borrow.active);
-        if (rc != TFHE_E_NOMEM || chunk == 1) break;
-        chunk = (chunk + 1) / 2;
-    }
-    if (rc) return rc;
-    u64* dig = (u64*)((char*)ws + ntt_tmp);
-    u64* S = dig + (size_t)chunk * level * nw * N;
-    u64* ROT = S + (size_t)chunk * R * 2 * nw * N;
-    u64* X = ROT + (size_t)chunk * R * 2 * level * N;
-    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-        const int64_t nb = std::min(chunk, batch - b0);
-        const u64* cin = ct + (size_t)b0 * polys * level * N;
-        if (eval_form) {
-            u64* const U = ROT;                                  // [R][nb][2][level][N]
-            u64* const LF = need_lf ? X + (size_t)chunk * 2 * level * N : nullptr;   // lifted special limbs, untransformed (same shape)
-            u64* const PB = X + (size_t)chunk * 2 * level * N + (need_lf ? (size_t)chunk * R * 2 * level * N : 0);   // [R][nb][2][N]
-            const u32 groups = (u32)((int64_t)R * nb * 2);
-            rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
-            if (rc) return rc;
-            rc = ks_digits_fwd(c, A, cin, dig, nb);
-            if (rc) return rc;
-            rc = ks_inner_launch(c, A, Lk, nullptr, dig, S, nb, evks, R, X);   // limbs j < level leave as V = S' P^-1 + X0 [s = 0]
-            if (rc) return rc;
-            rc = launch(c, k_md_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, S, PB, G, n, (u32)nw, (u32)level, (u32)nb, groups);
-            if (rc) return rc;
-            limb_sel_t sp{};
-            sp.n = 1;
-            sp.idx[0] = Lk - 1;
-            rc = run_ntt(c, true, PB, PB, (int64_t)groups, sp);
-            if (rc) return rc;
-            bool scaled = true;
-            rc = md_lift_fwd(c, A, sl, ra, PB, LF, U, (int64_t)groups, &scaled);
-            if (rc) return rc;
-            auto acc = scaled ? k_md_acc<false> : k_md_acc<true>;
-            rc = launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, X, S, U, diags, out + (size_t)b0 * 2 * level * N, c->limbs_dev, sl,
-                        G, ra, n, (u32)nw, (u32)R, (u32)nb);
-            if (rc) return rc;
-            continue;
-        }
-        if (R) {
-            rc = ks_digits_fwd(c, A, cin, dig, nb);
-            if (rc) return rc;
-            rc = ks_inner_launch(c, A, Lk, nullptr, dig, S, nb, evks, R);   // key sums of the unrotated digits against every prepared key
-            if (rc) return rc;
-            rc = run_ntt(c, true, S, S, (int64_t)R * nb * 2 * nw, A.w);
-            if (rc) return rc;
-            rc = launch(c, k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, S, cin, ROT, c->limbs_dev, A, ra, G, n, (u32)nb,
-                        (u32)((int64_t)R * nb * 2));
-            if (rc) return rc;
-            rc = run_ntt(c, false, ROT, ROT, (int64_t)R * nb * 2 * level, sl);
-            if (rc) return rc;
-        }
-        rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
-        if (rc) return rc;
-        rc = launch(c, k_matmul_acc, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, X, ROT, diags, out + (size_t)b0 * 2 * level * N,
-                    c->limbs_dev, sl, n, (u32)R, (u32)(nb * 2 * level));
-        if (rc) return rc;
-    }
-    return TFHE_OK;
-}
-
-// ---- digit-window key switch (relin_window != 0, rlwe_she.jl:330-338) -----------------------------------------------
-static int ksw_table(tfhe_ctx* c, int level, const conv_tab_t** out) {
-    *out = nullptr;
-    if (level == 1) return TFHE_OK;
-    std::lock_guard<std::mutex> g(c->ksw_mu);
-    auto it = c->ksw_tabs.find(level);
-    if (it != c->ksw_tabs.end()) { *out = it->second; return TFHE_OK; }
-    conv_host_t H;
-    build_conv_host(std::vector<u64>(c->q.begin(), c->q.begin() + level), std::vector<u64>(), &H);
-    conv_tab_t T = H.tab;
-    auto up = [&](const std::vector<u64>& v, const u64** d) -> bool {
-        *d = nullptr;
-        if (v.empty()) return true;
-        void* p = nullptr;
-        if (devalloc::malloc_retry(&p, v.size() * 8) != hipSuccess) return false;
-        c->ksw_allocs.push_back(p);
-        if (hipMemcpy(p, v.data(), v.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return false;
-        *d = (const u64*)p;
-        return true;
-    };
-    void* dt = nullptr;
-    if (!up(H.C, &T.C) || !up(H.M, &T.M) || !up(H.Aw, &T.Aw) || devalloc::malloc_retry(&dt, sizeof T) != hipSuccess)
-        return fail(TFHE_E_NOMEM, "allocating the window-digit tables failed");
-    c->ksw_allocs.push_back(dt);
-    HIP_TRY(hipMemcpy(dt, &T, sizeof T, hipMemcpyHostToDevice));
-    c->ksw_tabs[level] = (conv_tab_t*)dt;
-    *out = (conv_tab_t*)dt;
-    return TFHE_OK;
-}
-
-int tfhe_keyswitch_window(tfhe_ctx* c, int key_limbs, int level, int special, int window_bits, const uint64_t* evk, int n_windows,
-                          const uint64_t* ct, int polys, uint64_t* out, int64_t batch) {
-    if (!c || !evk || !ct || !out) return fail(TFHE_E_BADARG, "null argument");
-    if (polys != 2 && polys != 3) return fail(TFHE_E_BADARG, "keyswitch needs a 2- or 3-element ciphertext (rlwe_she.jl:318), got %d", polys);
-    const int Lk = key_limbs;
-    if (Lk < 1 || Lk > c->L) return fail(TFHE_E_BADARG, "key_limbs=%d outside [1,%d]", Lk, c->L);
-    if (level < 1 || level > (special ? Lk - 1 : Lk)) return fail(TFHE_E_LEVEL_MISMATCH, "level=%d outside [1,%d]", level, special ? Lk - 1 : Lk);
-    if (batch < 0) return fail(TFHE_E_BADARG, "negative batch");
-    hostmath::bigint Q = hostmath::big_from(1);
-    u64 qmin = special ? c->q[Lk - 1] : ~0ull;
-    for (int j = 0; j < level; j++) { Q = hostmath::big_mul_u64(Q, c->q[j]); qmin = std::min(qmin, c->q[j]); }
-    if (window_bits < 1 || window_bits > 32 || (qmin >> window_bits) == 0)
-        return fail(TFHE_E_BADARG, "window of %d bits: need 1 <= w <= 32 and 2^w below every modulus", window_bits);
-    int qbits = 0;
-    for (int w = (int)Q.size() - 1; w >= 0 && !qbits; w--)
-        if (Q[w]) qbits = w * 64 + hostmath::bitlen(Q[w]);
-    // ndigits(modulus of the CIPHERTEXT ring, base = 2^w), rlwe_she.jl:333; a key made for a larger ring (a higher level, or the
-    // ModulusRaised key ring Q P, modulusraising.jl:28-32) has more components: the loop rlwe_she.jl:340 uses the first `need`
-    const int need = (qbits + window_bits - 1) / window_bits;
-    if (n_windows < need)
-        return fail(TFHE_E_PARAMS_MISMATCH, "evaluation key has %d components, a %d-bit modulus in %d-bit windows has %d digits", n_windows, qbits, window_bits, need);
-    if (batch == 0) return TFHE_OK;
-    const conv_tab_t* T = nullptr;
-    int rc = ksw_table(c, level, &T);
-    if (rc) return rc;
-    const size_t N = (size_t)c->N;
-    const u32 n = (u32)c->N;
-    const int nw = special ? level + 1 : level;  // working limbs: [0 .. level-1] (+ the special prime, downswitch_keyelement modulusraising.jl:43-49)
-    const size_t per_ct = ((size_t)2 * nw + (size_t)need * nw) * N * 8;
-    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
-    const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * need * nw * N * 8 : 0;
-    void* ws = nullptr;
-    rc = ensure_ws(c, ntt_tmp + chunk * per_ct, &ws);
-    if (rc) return rc;
-    u64* S = (u64*)((char*)ws + ntt_tmp);
-    u64* dig = S + (size_t)chunk * 2 * nw * N;
-    const ks_arg_t Al = make_ks_arg(Lk, level, special ? 1 : 0, polys);  // row bookkeeping of the tail kernels: `level` = ciphertext limbs
-    ks_arg_t A = Al;   // inner product: `level` field = number of digits, nw = working limbs
-    A.level = need;
-    const u32 add_s = polys == 3 ? 2u : 1u;
-    const unsigned gx = (n + 255) / 256;
-    rescale_arg_t ra{};
-    if (special) special_inv_table(c, Lk, level, ra.qlinv);
-    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-        const int64_t nb = std::min(chunk, batch - b0);
-        const u64* cin = ct + (size_t)b0 * polys * level * N;
-        u64* cout = out + (size_t)b0 * 2 * level * N;
-        rc = launch(c, k_ks_window_digits, dim3((unsigned)(nb * gx)), dim3(256), 0, cin, dig, T, level, window_bits, need, polys, n, gx, nw);
-        if (rc) return rc;
-        rc = run_ntt(c, false, dig, dig, nb * need * nw, A.w);
-        if (rc) return rc;
-        const unsigned bsplit = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nb, (4096 + nw * gx - 1) / (nw * gx)));
-        rc = launch(c, k_ks_inner<8>, dim3((unsigned)nw * gx * bsplit), dim3(256), 0, evk, dig, S, c->limbs_dev, A, Lk, n, (u32)nb, bsplit, 0u, ks_keys_t{});
-        if (rc) return rc;
-        if (special) {
-            // ModulusRaised: c1 = P c + S over [q_0 .. q_{level-1}, P], contracted by modswitch (modulusraising.jl:35-42):
-            // out_j = c_j + (T_j - [T_P]) P^-1 with T = INTT(S)  (the tail of the RNS-digit path, k_ks_rescale_add)
-            rc = run_ntt(c, true, S, S, nb * 2 * nw, A.w);
-            if (rc) return rc;
-            rc = launch(c, k_ks_rescale_add, row_grid((unsigned)(nb * 2 * level), (size_t)c->N), dim3(256), 0, S, cin, cout, c->limbs_dev, Al, ra, n, add_s);
-            if (rc) return rc;
-        } else if (c->logN <= 14) {
-            ntt_io_t io = io_plain();
-            io.mode = 2; io.gsz = (u32)(2 * level); io.src_gstride = io.gsz; io.dst_gstride = io.gsz;
-            io.add_rows = add_s * (u32)level; io.add_gstride = (u32)(polys * level); io.addend = cin;
-            rc = run_ntt(c, true, S, cout, nb * 2 * level, A.w, &io);
-            if (rc) return rc;
-        } else {
-            rc = run_ntt(c, true, S, cout, nb * 2 * level, A.w);
-            if (rc) return rc;
-            rc = launch(c, k_ks_add_ct, row_grid((unsigned)(nb * 2 * level), (size_t)c->N), dim3(256), 0, cin, cout, c->limbs_dev, Al, n, add_s);
-            if (rc) return rc;
-        }
-    }
-    return TFHE_OK;
-}
+#include "ks_api.inc"
 
 // ---- CKKS encode / decode (float; ckksencoding.jl:56-97, ckks.jl:35-59) -------------------------------------------
 static int ckks_tables(tfhe_ctx* c) {
