@@ -346,6 +346,35 @@ int tfhe_evalkey_gen(tfhe_ctx *ctx, int key_limbs, const uint64_t *secret, const
                      uint32_t stream_mask, uint32_t stream_noise, uint64_t mask_poly, uint64_t noise_poly, uint64_t poly_stride,
                      const uint64_t *mask_rand, const int32_t *noise_rand, uint64_t *const *evks);
 
+/* ---- ciphertext x plaintext sums with the forward transforms inside, one call (infer.jl:140-149) -------------------------------
+ *     dst_i = (acc_i +) sum_{k < n_terms} T_k(a[k]_i) .* b[k]_i        for items i < count, limb-wise
+ *   T_k = NTT (tfhe_nntt, pow2_cyc_rings.jl:295-318) if a_ntt[k] == 0, the identity if a_ntt[k] == 1: the accumulation
+ *   `result += rotated_k * diagonal_k` of the diagonal matrix product over rotated ciphertexts that are still in the coefficient
+ *   domain.  The words are the canonical residues of tfhe_nntt followed by tfhe_mad term by term.
+ * Every operand is a VIEW, a base pointer and an item stride in words: item i is [limbs][N] words at base + i * stride.
+ *   a[k], acc, dst : stride >= limbs * N.  A ring element is the view (base, limbs * N); component p of a packed
+ *                    [count][P][limbs][N] ciphertext is the view (base + p * limbs * N, P * limbs * N), an operand where it lies.
+ *   b[k]           : NTT domain; stride 0 = one plaintext shared by the whole batch, else >= limbs * N.
+ *   dst            : NTT domain.  acc is NULL or NTT domain and may be the SAME view as dst (same base, same stride); dst may
+ *                    overlap no other operand and acc in no other way.
+ *   a, a_stride, a_ntt, b, b_stride : HOST arrays of n_terms entries.  n_terms >= 1 with no upper limit: more than 64 terms
+ *                    accumulate over further passes onto dst, as tfhe_dot does.
+ * N = 2^12 .. 2^14 (tfhe_ctx_set_ntt_variant 0, limbs <= 32) runs as one fused kernel per arithmetic policy: per (item, limb) the
+ * running sum stays in registers, a coefficient-domain term is transformed through the workgroup's LDS and multiplied by its
+ * plaintext row as it comes out, so every source row and plaintext row is read once and the sum written once; a ring that mixes
+ * 60-bit and fp64-size moduli runs its two launches side by side.  N < 2^12, N >= 2^15, variant != 0 and more than 32 limbs gather
+ * the coefficient-domain terms into the context workspace, transform them in one batch and accumulate with a strided tfhe_dot.
+ * Same words on every path, and for every tfhe_ctx_set_chunk (the chunk bounds the items and the terms of one pass).
+ * Checks (host, before any device use, in this order): a null a / a_stride / a_ntt / b / b_stride / dst is TFHE_E_BADARG;
+ * n_terms < 1 TFHE_E_BADARG; negative count TFHE_E_BADARG; a null a[k] / b[k], an a_ntt[k] outside {0, 1} and dst starting where an
+ * a[k] / b[k] starts TFHE_E_BADARG; a null context TFHE_E_BADARG; limbs / limb_idx as every limb-wise entry point (TFHE_E_BADARG /
+ * TFHE_E_LEVEL_MISMATCH); count * limbs above 2^31 - 1 TFHE_E_BADARG; a stride below limbs * N (other than a b stride of 0), or
+ * with count * stride above 2^40 words, TFHE_E_BADARG; dst overlapping an a[k] / b[k] as strided address ranges (first item to the end of the last), or acc
+ * other than as the same view, TFHE_E_BADARG and nothing is written; count == 0 does nothing, but still needs a context. */
+int tfhe_dot_plain(tfhe_ctx *ctx, const uint64_t *acc, size_t acc_stride, const uint64_t *const *a, const size_t *a_stride,
+                   const uint8_t *a_ntt, const uint64_t *const *b, const size_t *b_stride, int n_terms, uint64_t *dst,
+                   size_t dst_stride, int64_t count, int limbs, const int32_t *limb_idx);
+
 /* ---- BFV / BGV plaintext codecs on the device (π⁻¹ / π, bfv.jl:21-29, bgv.jl:21-25; noise, bfv.jl:137-166) ---------
  * plan = (ring = ctx limbs limb_idx, t).  t in [2, 2^62) and t < Q (Q = product of the selected moduli); limb_idx entries
  * in range and distinct; else TFHE_E_BADARG (checked on the host before any device use).  Exact: bit-identical to the

@@ -74,9 +74,11 @@ inline dim3 row_grid(unsigned rows, size_t n) {
     return dim3(rows, std::max(1u, std::min(want, cap)));
 }
 // persistent workgroups of 2^logt threads, LDS-limited: as many as are co-resident, each loops over items
+inline unsigned persistent_per_cu(size_t lds, int logt) {
+    return (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)(160 * 1024) / lds, (size_t)2048 >> logt}));
+}
 inline unsigned persistent_grid(const tfhe_ctx* c, unsigned items, size_t lds, int logt) {
-    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)(160 * 1024) / lds, (size_t)2048 >> logt}));
-    return std::min(items, (unsigned)c->num_cus * per_cu);
+    return std::min(items, (unsigned)c->num_cus * persistent_per_cu(lds, logt));
 }
 // one workgroup per CU (`per_cu`: where two fit), each loops over items
 inline unsigned cu_grid(const tfhe_ctx* c, unsigned items, unsigned per_cu = 1u) { return std::min(items, per_cu * (unsigned)c->num_cus); }

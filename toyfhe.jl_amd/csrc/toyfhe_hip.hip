@@ -25,6 +25,7 @@
 #include "sample_kernels.h"
 #include "enc_core.h"
 #include "keygen_core.h"
+#include "dot_core.h"
 #include "ntt_tables.h"
 #include "dev_alloc.h"
 
@@ -1219,3 +1220,4 @@ int tfhe_event_elapsed_ms(void* a, void* b, float* ms) {
 #include "mul_api.inc"
 #include "enc_api.inc"
 #include "keygen_api.inc"
+#include "dot_api.inc"

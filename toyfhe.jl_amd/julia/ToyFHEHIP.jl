@@ -226,6 +226,50 @@ function dot(as::Vector{<:DevVec{T}}, bs::Vector{<:DevVec{T}}) where {T<:CRTEnco
                 ctx.handle, C_NULL, ap, bp, length(as), dst.ptr, cnt, dst.limbs, C_NULL))
     OffsetArray(dst, axes(as[1])...)
 end
+# ---- the same accumulation with the forward transforms inside (tfhe_dot_plain): operands are VIEWS ------------------------------
+# item i of a view is [limbs][N] words at buf.ptr + 8 * (offset + i * stride); ntt: an NTT image already (else the call transforms it)
+struct DotView
+    buf::HipVector
+    offset::Int
+    stride::Int
+    ntt::Bool
+end
+# a ring element as a dense view: its cached transform if there is one, else its coefficients
+dense_view(x::RingElement) = x.dual !== nothing ? DotView(x.dual.parent, 0, words(x.dual.parent), true) : DotView(x.primal.parent, 0, words(x.primal.parent), false)
+# component p (0-based) of a packed [count][polys][limbs][N] buffer as a key switch leaves it (coefficient domain), where it lies
+packed_view(buf::HipVector, polys::Integer, p::Integer) = DotView(buf, p * (buf.limbs ÷ polys) * buf.n, buf.limbs * buf.n, false)
+# sum_k T_k(as[k]) .* bs[k] for `cnt` items in ONE call: no staging copy, no transform call per rotated ciphertext (infer.jl:140-149).
+# A plaintext of one polynomial is shared by the batch (stride 0).  The result is in the NTT domain like that of `dot`.
+function dot_plain(ℛ, as::Vector{DotView}, bs::Vector{<:RingElement}, cnt::Integer)
+    T = eltype(ℛ); limbs = nlimbs(T); n = degree(ℛ)
+    @assert length(as) == length(bs) && !isempty(as)
+    xs = HipVector[a.buf for a in as]; ys = HipVector[coeffs_dual(b).parent for b in bs]
+    dst = HipVector{T}(limbs, n, cnt); ctx = on(hipring(ℛ), (dst,), (xs..., ys...))
+    ap = Ptr{UInt64}[a.buf.ptr + 8 * a.offset for a in as]; astr = Csize_t[a.stride for a in as]; antt = UInt8[a.ntt ? 1 : 0 for a in as]
+    bp = Ptr{UInt64}[y.ptr for y in ys]; bstr = Csize_t[y.count == 1 ? 0 : words(y) for y in ys]
+    GC.@preserve xs ys dst check(ccall((:tfhe_dot_plain, lib), Cint,
+                (Ptr{Cvoid}, Ptr{UInt64}, Csize_t, Ptr{Ptr{UInt64}}, Ptr{Csize_t}, Ptr{UInt8}, Ptr{Ptr{UInt64}}, Ptr{Csize_t}, Cint, Ptr{UInt64}, Csize_t, Int64, Cint, Ptr{Int32}),
+                ctx.handle, C_NULL, 0, ap, astr, antt, bp, bstr, length(as), dst.ptr, limbs * n, cnt, limbs, C_NULL))
+    RingElement{ℛ}(nothing, OffsetArray(dst, 0:n-1))
+end
+# sum_k cts[k] .* plains[k] over ciphertexts of one ring and batch: one call per component on the ring elements as they are.  A
+# ciphertext-by-plaintext product: the result sits at the squared scale (ckksencoding.jl:106-111), as matmul_diag's.
+function dot_plain(cts::Vector{<:CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}}, plains::Vector{<:RingElement{ℛ,T,<:HipVector}}) where {Enc,P,ℛ,T}
+    @assert length(cts) == length(plains) && !isempty(cts)
+    cnt = batchsize(cts[1])
+    els = map(1:length(cts[1].cs)) do p
+        dot_plain(ℛ, DotView[dense_view(c.cs[p]) for c in cts], plains, cnt)
+    end
+    CipherText{squared_encoding(Enc)}(cts[1].params, tuple(els...))
+end
+# ... and over key-switch results a caller kept packed ([count][polys][limbs][N] each): the components are read where they lie
+function dot_plain_packed(ℛ, bufs::Vector{<:HipVector}, plains::Vector{<:RingElement}, polys::Integer=2)
+    @assert !isempty(bufs)
+    els = map(0:polys-1) do p
+        dot_plain(ℛ, DotView[packed_view(b, polys, p) for b in bufs], plains, bufs[1].count)
+    end
+    tuple(els...)
+end
 function Base.broadcasted(::typeof(-), a::DevVec{T}) where {T<:CRTEncoded}
     x = a.parent; dst = HipVector{T}(x.limbs, x.n, x.count); ctx = on(modring(T, dst.n), (dst,), (x,))
     GC.@preserve x dst check(ccall((:tfhe_neg, lib), Cint, (Ptr{Cvoid}, Ptr{UInt64}, Ptr{UInt64}, Int64, Cint, Ptr{Int32}),

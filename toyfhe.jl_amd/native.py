@@ -142,6 +142,7 @@ def lib():
         "tfhe_mul_relin": [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, i64],
         "tfhe_encrypt": [vp, i32, i32, vp, C.c_double, C.c_double, u64, u64, C.c_uint32, u64, vp, vp, vp, i64],
         "tfhe_decrypt_phase": [vp, i32, i32, vp, vp, i32, i32, vp, i64],
+        "tfhe_dot_plain": [vp, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint8), C.POINTER(vp), C.POINTER(sz), i32, vp, sz, i64, i32, i32p],
         "tfhe_evalkey_gen": [vp, i32, vp, vp, u64p, i32, u64p, i32, C.c_double, u64, u64, C.c_uint32, C.c_uint32, u64, u64, u64, vp, vp,
                              C.POINTER(vp)],
         "tfhe_plain_plan_create": [vp, i32p, i32, u64, C.POINTER(vp)],
@@ -170,7 +171,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
     "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
-    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
+    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
 ]
@@ -320,6 +321,21 @@ class Context:
         A = (C.c_void_p * n)(*a_ptrs)
         B = (C.c_void_p * n)(*b_ptrs)
         check(lib().tfhe_dot(self.h, acc, A, B, n, dst, count, limbs, _idx(idx)))
+
+    def dot_plain(self, acc, a_views, b_views, dst, count, limbs, idx=None):
+        """dst = (acc +) sum_k T_k(a_k) .* b_k over view operands (tfhe_dot_plain).  acc: None or (ptr, stride); a_views: a list of
+        (ptr, stride, ntt) -- ntt false: the term is in the coefficient domain and is transformed inside the call; b_views: an equally
+        long list of (ptr, stride), stride 0 = one plaintext for the whole batch; dst: (ptr, stride).  Strides in words."""
+        if len(a_views) != len(b_views):
+            raise AssertionError("tfhe_dot_plain: as many a operands as b operands")
+        n = len(a_views)
+        A = (C.c_void_p * n)(*[v[0] for v in a_views])
+        AS = (C.c_size_t * n)(*[int(v[1]) for v in a_views])
+        AN = (C.c_uint8 * n)(*[int(bool(v[2])) for v in a_views])
+        B = (C.c_void_p * n)(*[v[0] for v in b_views])
+        BS = (C.c_size_t * n)(*[int(v[1]) for v in b_views])
+        acc_ptr, acc_stride = (None, 0) if acc is None else acc
+        check(lib().tfhe_dot_plain(self.h, acc_ptr, acc_stride, A, AS, AN, B, BS, n, dst[0], dst[1], count, limbs, _idx(idx)))
 
     def lincomb(self, scalars, a_ptrs, dst, count, limbs, idx=None):
         """dst = sum_k scalars[k] * a_k (tfhe_lincomb); scalars: [n_terms][limbs] residues, a_ptrs: device pointers"""

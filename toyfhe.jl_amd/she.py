@@ -469,6 +469,31 @@ def _component_source(c, p):
     return c.cs[p]
 
 
+# TFHE_DOT_PLAIN_CALL=0: CipherText.dot_plain stages and transforms its operands itself (_dot_batched below: copies into the context's
+# staging buffers, one tfhe_nntt, tfhe_dot) -- comparisons; the default is ONE tfhe_dot_plain call per component on view operands,
+# with no staging copy and no staging buffer: the same words.
+_DOT_PLAIN_CALL = os.environ.get("TFHE_DOT_PLAIN_CALL", "1") != "0"
+# the largest log2 N at which dot_plain takes the call (TFHE_DOT_PLAIN_CALL_MAX_LOG2).  Above the fused sizes the call's composed form
+# does the staging route's work below the ABI and measured level with it at N = 2^16, not faster (profiles/LOG.md), so the staging route stays
+# there.
+_DOT_PLAIN_CALL_MAX_LOG2 = int(os.environ.get("TFHE_DOT_PLAIN_CALL_MAX_LOG2", "14"))
+
+
+def _dot_call(ring, n, cts, p, plains, dst):
+    """dst = sum_k component p of cts[k] .* plains[k] in one tfhe_dot_plain call.  A ring element is a dense view (its cached
+    transform, if there is one, as a transformed term); component p of a key-switch result that has not been split is a view into
+    its packed buffer [n][2][L][N], which stays unsplit."""
+    words = ring.L * ring.N
+    views = []
+    for c in cts:
+        if isinstance(c, _PackedResult) and c._cs is None:
+            views.append((c._packed_image[0].ptr + p * words * 8, 2 * words, False))
+        else:
+            e = c.cs[p]
+            views.append((e.dual.ptr, words, True) if e.dual is not None else (e.coeffs_primal().ptr, words, False))
+    ring.ctx.dot_plain(None, views, [(x.ptr, words) for x in plains], (dst.ptr, words), n, ring.L, ring.idx)
+
+
 def _dot_batched(ring, n, elems, pb_ptrs, dst):
     """dst = sum_k elems[k] .* plain_k for ring elements of ONE ring and batch size, the plaintexts given by their evaluation-domain
     pointers.  Elements whose transform is cached are used where they lie.  When two or more are still in the coefficient domain
@@ -640,7 +665,8 @@ class CipherText:
     def dot_plain(cts, plains) -> "CipherText":
         """sum_k cts[k] .* plains[k] for ciphertexts of one ring, length and scale and plaintexts already encoded at that scale
         (ring elements): the accumulation loop of the diagonal matrix product (infer.jl:140-149) as one device pass per
-        component (tfhe_dot) instead of a ring multiplication and a ring addition per term; bit-identical to
+        component (tfhe_dot_plain: the operands' forward transforms run inside the call, unsplit key-switch results are read
+        where they lie) instead of a ring multiplication and a ring addition per term; bit-identical to
         `sum(c.mul_plain(p) for c, p in zip(cts, plains))`."""
         cts, plains = list(cts), list(plains)
         if not cts or len(cts) != len(plains):
@@ -659,7 +685,10 @@ class CipherText:
         out = []
         for s_ in range(len(c0)):
             o = DeviceBuffer(n * ring.L * ring.N)
-            _dot_batched(ring, n, [_component_source(c, s_) for c in cts], [x.ptr for x in pb], o)
+            if _DOT_PLAIN_CALL and ring.N <= (1 << _DOT_PLAIN_CALL_MAX_LOG2):
+                _dot_call(ring, n, cts, s_, pb, o)
+            else:
+                _dot_batched(ring, n, [_component_source(c, s_) for c in cts], [x.ptr for x in pb], o)
             out.append(RingElement(ring, None, o, batch))
         return CipherText(c0.params, out, Fraction(c0.scale) ** 2)
 
