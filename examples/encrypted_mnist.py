@@ -58,6 +58,13 @@ def plain_model(model, batch):
     return (plain_matmul(W2, sq2) + np.concatenate([model["fq2_b"], np.zeros(54)])[:, None])[:10]
 
 
+class BsgsKeys:
+    """the two key sets of the baby-step/giant-step product: n1 - 1 keys for the steps B, 2B, .. and 64 / n1 - 1 for n1 B, 2 n1 B, .."""
+
+    def __init__(self, n1, baby, giant):
+        self.n1, self.baby, self.giant = n1, list(baby), list(giant)
+
+
 def encrypted_matmul(gk, W, x, B, cache=None, fused=False):
     """infer.jl:140-149: diagonal method; `rotate` by B slots moves every window's value to the next window.
     gk = one Galois key (the reference's loop: 63 chained rotations by B slots) or a list of 63 keys for the steps B, 2B, ...,
@@ -79,6 +86,19 @@ def encrypted_matmul(gk, W, x, B, cache=None, fused=False):
         pt.coeffs_dual()
         cache[key] = pt
         return pt
+    if isinstance(gk, BsgsKeys):
+        # the whole product in one device call by baby and giant steps (tfhe_matmul_bsgs): n1 + 64 / n1 - 2 keys instead of 63; the
+        # diagonals are pre-rotated on the host (bsgs_diagonals) and encoded once per (matrix, level, scale)
+        key = (id(W), "bsgs", gk.n1, x.ring().L, x.scale)
+        if cache is None or key not in cache:
+            vs = np.stack([np.repeat(np.array([W[i, (i - k) % n] for i in range(n)]), B) for k in range(n)])
+            D = tf.bsgs_diagonals(vs, gk.n1, block=B)[0]
+            enc = tf.ckks_encode(D.reshape(-1, D.shape[-1]).astype(np.complex128), x.ring(), x.scale)
+            enc.coeffs_dual()
+            if cache is None:
+                return tf.matmul_bsgs(gk.baby, gk.giant, enc, x)
+            cache[key] = enc
+        return tf.matmul_bsgs(gk.baby, gk.giant, cache[key], x)
     if isinstance(gk, (list, tuple)) and cache is not None and fused:
         # the whole product in one device call (tfhe_matmul_diag): the diagonals are single plaintexts shared by the batch
         key = (id(W), "fused", x.ring().L, x.scale)
@@ -128,8 +148,10 @@ def load_model(path=GOLDEN_MODEL):
 
 
 def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None,
-        mul_relin=False):
-    """`mul_relin`: the two square layers as one device call each (she.mul_relin = tfhe_mul_relin) instead of
+        mul_relin=False, bsgs=0):
+    """`bsgs` = n1 > 0: every matrix product as one tfhe_matmul_bsgs call with n1 - 1 baby and ceil(64 / n1) - 1 giant keys (a third
+    circuit shape beside the chained loop and the 63 hoisted keys; the other layers as chosen by the remaining switches).
+    `mul_relin`: the two square layers as one device call each (she.mul_relin = tfhe_mul_relin) instead of
     modswitch(keyswitch(ek, c * c)); same logits, bit for bit.
     `batches` = K ciphertext sets evaluated together (K * B images): every ring element carries a leading batch dimension
     of K, so each device call covers K ciphertexts (the batch the engine shards across GPUs)."""
@@ -158,7 +180,11 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
     t0 = time.perf_counter()
     kp = tf.keygen(rng, params)
     ek = tf.keygen_evalmult(rng, kp.priv)
-    if hoisted:
+    if bsgs:
+        _, bsteps, gsteps = tf.bsgs_diagonals(np.zeros((64, 1)), int(bsgs), block=B)
+        keys = tf.keygen_galois_many(rng, kp.priv, steps=bsteps + gsteps)               # one device call for both key sets
+        gk = BsgsKeys(int(bsgs), keys[:len(bsteps)], keys[len(bsteps):])
+    elif hoisted:
         gk = tf.keygen_galois_many(rng, kp.priv, steps=[k * B for k in range(1, 64)])   # one device call for the 63 keys
     else:
         gk = tf.keygen_galois(rng, kp.priv, steps=B)               # infer.jl:134 (steps = 64 there)
@@ -237,5 +263,7 @@ if __name__ == "__main__":
                     help="with --hoisted: each matrix product as one tfhe_matmul_diag call and each convolution channel as one tfhe_lincomb per component")
     ap.add_argument("--mul-relin", action="store_true",
                     help="the two square layers through she.mul_relin (one tfhe_mul_relin call each) instead of modswitch(keyswitch(ek, c * c))")
+    ap.add_argument("--bsgs", type=int, default=0, metavar="N1",
+                    help="each matrix product as one tfhe_matmul_bsgs call: N1 - 1 baby and ceil(64 / N1) - 1 giant Galois keys instead of 63")
     a = ap.parse_args()
-    run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin)
+    run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin, bsgs=a.bsgs)

@@ -195,6 +195,26 @@ int tfhe_rotate_many(tfhe_ctx *ctx, int key_limbs, int level, int special, const
  *   ct: [batch][2][level][N] coefficient domain; out: [batch][2][level][N] NTT domain (the product's scale is the caller's business). */
 int tfhe_matmul_diag(tfhe_ctx *ctx, int key_limbs, int level, int special, const uint64_t *const *evks, int n_digits,
                      const uint64_t *galois_elements, int n_rot, const uint64_t *diags, const uint64_t *ct, uint64_t *out, int64_t batch);
+/* The same product by baby and giant steps, in one call.  With the rotation index written k = j n1 + i,
+ *     sum_k d_k .* rho^k(x) = sum_j rho^(j n1)( sum_i rho^(-j n1)(d_k) .* rho^i(x) ):
+ * n_baby + n_giant Galois keys and key sums instead of one per diagonal (a 64 x 64 layer with n1 = 8: 7 + 7 instead of 63).
+ *     inner_j = sum_{i = 0 .. n_baby} diags[j][i] .* NTT(r_i(ct))      (r_0 = identity, r_i = rotate(baby key i - 1, .)),  j = 0 .. n_giant
+ *     out     = INTT(inner_0) + sum_{j = 1 .. n_giant} rotate(giant key j - 1, INTT(inner_j))
+ *   baby_evks / giant_evks: HOST arrays of n_baby / n_giant device pointers to PREPARED Galois keys (tfhe_galois_key_prepare), as for
+ *   tfhe_matmul_diag; baby_galois / giant_galois: HOST arrays of their Galois elements; n_baby, n_giant in [0, 64];
+ *   diags: device [n_giant + 1][n_baby + 1][level][N], NTT domain, shared by the batch -- pre-rotating them (rho^(-j n1)) is the
+ *   caller's business;  ct, out: [batch][2][level][N], coefficient domain, as for tfhe_rotate.
+ * The result equals, word for word, tfhe_rotate_many over the baby keys -> tfhe_nntt -> tfhe_dot per giant step -> tfhe_inntt ->
+ * tfhe_rotate_prepared per giant step j >= 1 -> tfhe_add: every step is exact arithmetic on canonical residues, so every path
+ * (evaluation-domain or coefficient tail, every route of the nested key switch) and every tfhe_ctx_set_chunk gives the same bits.
+ * Checked on the host before any device use, in this order: null arrays or a null key among the first n_baby / n_giant, n_baby /
+ * n_giant outside [0, 64], an even Galois element, out starting where ct or diags start (all TFHE_E_BADARG); then the context;
+ * then the level / key-limb rules of tfhe_keyswitch, Galois elements not below 2N and out overlapping ct or diags anywhere
+ * (TFHE_E_BADARG).  batch == 0 does nothing, but still needs a context. */
+int tfhe_matmul_bsgs(tfhe_ctx *ctx, int key_limbs, int level, int special,
+                     const uint64_t *const *baby_evks, const uint64_t *baby_galois, int n_baby,
+                     const uint64_t *const *giant_evks, const uint64_t *giant_galois, int n_giant,
+                     int n_digits, const uint64_t *diags, const uint64_t *ct, uint64_t *out, int64_t batch);
 /* the one-time key preparation of the hoisted rotations: evk_out = the Galois key of x -> x^g (layout of tfhe_keyswitch,
  * n_digits components over key_limbs moduli) with every NTT-domain row permuted by g^-1, so that the key products run on the
  * transformed digits of the unrotated ciphertext.  prepared = 0 above takes plain keys and prepares them per call. */

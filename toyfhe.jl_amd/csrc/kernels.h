@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "bfv_core.h"
 #include "bfv_fast.h"
+#include "bsgs_core.h"
 #include "ntt_core.h"
 
 typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
@@ -2515,6 +2516,158 @@ __global__ __launch_bounds__(256) void k_md_acc(const u64* __restrict__ X, const
                 }
             }
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// tfhe_matmul_bsgs: the accumulations with more than one output.  With k = j n1 + i the diagonal product regroups into
+//     sum_j rho^(j n1)( inner_j ),   inner_j = sum_{i = 0 .. nrot} diag[j][i] (.) NTT(r_i(c))      (r_0 = identity),
+// so the rotations r_i of the baby phase (tfhe_matmul_diag's, up to its accumulation) feed ngiant1 = n_giant + 1 sums.  Each
+// rotated value of a coefficient is formed once per tile of NG <= 4 giant steps and multiplied into the tile's NG sums
+// (bsgs_core.h); within a tile only the diagonal words differ.  With more than four sums the gathers, the U loads and the
+// USCALE product are repeated once per tile, out of the L2.
+//   diag: [ngiant1][nrot + 1][level][N]      inner: [ngiant1][batch][2][level][N], NTT domain
+// The outputs are tiled NG giant steps per pass with the coefficients per thread reduced to match (KB NG = TFHE_MD_KB: the
+// same 2 KB NG accumulators as k_md_acc, in registers, no scratch); a ragged last tile repeats its last step unstored.
+//   k_bsgs_acc         the evaluation-domain form: rotated value V[pi_r k] - U[k] as k_md_acc, same XCD-cooperative walk -- the
+//                      tiles of a coefficient block run back to back, so the V windows of the row pair are still in the XCD's L2
+//                      when the next tile gathers them again
+//   k_bsgs_acc_dense   the coefficient tail (no special prime, TFHE_MD_COEFF=1): dense ROT rows as k_matmul_acc
+//   k_bsgs_sum         out = first + sum_t rest[t], limb-wise: INTT(inner_0) and the n_giant rotated inner sums
+// ------------------------------------------------------------------------------------------------
+template <bool USCALE, int NG>
+__global__ __launch_bounds__(256) void k_bsgs_acc(const u64* __restrict__ X, const u64* __restrict__ V, const u64* __restrict__ U,
+                                                   const u64* __restrict__ diag, u64* __restrict__ inner, const ntt_limb_t* __restrict__ LT,
+                                                   limb_sel_t sel, rot_tail_arg_t G, rescale_arg_t ra, u32 n, u32 nw, u32 nrot, u32 batch,
+                                                   u32 ngiant1) {
+    constexpr int KB = TFHE_MD_KB / NG;
+    static_assert(KB >= 1 && KB * NG == TFHE_MD_KB, "the output tile divides the coefficient block");
+    const u32 level = (u32)sel.n;
+    const u32 xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
+    // (teams for small rows: as k_md_acc)
+    const u32 per = blockDim.x * KB, spt = n / per >= nslot ? nslot : (n / per ? n / per : 1u), teams = nslot / spt, team = slot / spt, ts = slot % spt;
+    if (team >= teams) return;
+    const u32 stride = spt * blockDim.x;
+    const size_t dstride = (size_t)level * n, jstride = (size_t)(nrot + 1u) * dstride;   // one diagonal; one giant step's diagonals
+    const size_t gstride = (size_t)batch * 2, ostride = gstride * dstride;               // groups per rotation; one inner sum
+    struct term_t { u64 v0[KB], v1[KB], u0[KB], u1[KB], d[KB][NG]; };
+    for (u32 pr = team * 8u + xcd; pr < batch * level; pr += 8u * teams) {
+        const u32 j = pr % level, b = pr / level;
+        const ntt_limb_t L = LT[sel.idx[j]];
+        const tw_t pinv = ra.qlinv[j];
+        const u32 chunk = bsgs_lazy_chunk(L.q);
+        const size_t row0 = ((size_t)b * 2 * level + j) * n, row1 = row0 + (size_t)level * n;
+        const u64* dj = diag + (size_t)j * n;
+        for (u32 kb = ts * blockDim.x + threadIdx.x; kb < n; kb += stride * KB) {
+            u32 k[KB];
+#pragma unroll
+            for (int i = 0; i < KB; i++) k[i] = kb + (u32)i * stride < n ? kb + (u32)i * stride : kb;   // (a clamped lane repeats kb; not stored)
+            for (u32 j0 = 0; j0 < ngiant1; j0 += NG) {
+                const u64* dg[NG];   // diag[step][0][j]
+#pragma unroll
+                for (int o = 0; o < NG; o++) dg[o] = dj + (size_t)bsgs_tile_step(j0, (u32)o, ngiant1) * jstride;
+                auto fetch = [&](u32 t, term_t& T) {
+                    const size_t g0 = (size_t)t * gstride + (size_t)b * 2;
+                    const u64 g = G.g[t];
+                    const u64x2_t* pv = (const u64x2_t*)(V + epi_pair((u32)(g0 >> 1), j, 0u, nw, n));   // both components of a position: one gather
+                    const u64 *pu0 = U + (g0 * level + j) * n, *pu1 = U + ((g0 + 1) * level + j) * n;
+                    const size_t dt = (size_t)(t + 1) * dstride;
+#pragma unroll
+                    for (int i = 0; i < KB; i++) {
+                        const u64x2_t vv = pv[galois_ntt_pos(k[i], g, n)];
+                        T.v0[i] = vv.x; T.v1[i] = vv.y; T.u0[i] = pu0[k[i]]; T.u1[i] = pu1[k[i]];
+#pragma unroll
+                        for (int o = 0; o < NG; o++) T.d[i][o] = dg[o][dt + k[i]];
+                    }
+                };
+                bsgs_sums<NG> a0[KB], a1[KB];
+#pragma unroll
+                for (int i = 0; i < KB; i++) {
+                    u64 d0[NG];
+#pragma unroll
+                    for (int o = 0; o < NG; o++) d0[o] = dg[o][k[i]];
+                    a0[i].clear(); a1[i].clear();
+                    a0[i].mac(X[row0 + k[i]], d0);
+                    a1[i].mac(X[row1 + k[i]], d0);
+                }
+                u32 pend = 1;
+                term_t cur;
+                fetch(0, cur);
+                for (u32 t = 0; t < nrot; t++) {
+                    term_t nxt;
+                    fetch(t + 1 < nrot ? t + 1 : t, nxt);
+                    if (bsgs_fold_due(pend, chunk)) {
+#pragma unroll
+                        for (int i = 0; i < KB; i++) { a0[i].fold(L.br); a1[i].fold(L.br); }
+                    }
+#pragma unroll
+                    for (int i = 0; i < KB; i++) {
+                        a0[i].mac(bsgs_gather_term<USCALE>(cur.v0[i], cur.u0[i], pinv, L.q), cur.d[i]);
+                        a1[i].mac(bsgs_gather_term<USCALE>(cur.v1[i], cur.u1[i], pinv, L.q), cur.d[i]);
+                    }
+                    pend++;
+                    cur = nxt;
+                }
+#pragma unroll
+                for (int i = 0; i < KB; i++) {
+                    if (kb + (u32)i * stride < n) {
+#pragma unroll
+                        for (int o = 0; o < NG; o++) {
+                            if (j0 + (u32)o < ngiant1) {
+                                u64* oj = inner + (size_t)(j0 + (u32)o) * ostride;
+                                oj[row0 + k[i]] = a0[i].word(o, L.br);
+                                oj[row1 + k[i]] = a1[i].word(o, L.br);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+// rows = batch * 2 * level, row = (b * 2 + s) * level + j; ROT: [nrot][rows][N] (rows_per_rot = rows)
+template <int NG>
+__global__ __launch_bounds__(256) void k_bsgs_acc_dense(const u64* __restrict__ X, const u64* __restrict__ ROT, const u64* __restrict__ diag,
+                                                         u64* __restrict__ inner, const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 n,
+                                                         u32 nrot, u32 rows_per_rot, u32 ngiant1) {
+    const u32 row = blockIdx.x, j = row % (u32)sel.n;
+    const ntt_limb_t L = LT[sel.idx[j]];
+    const size_t base = (size_t)row * n, rstride = (size_t)rows_per_rot * n, dstride = (size_t)sel.n * n, jstride = (size_t)(nrot + 1u) * dstride;
+    const u64* dj = diag + (size_t)j * n;
+    const u32 chunk = bsgs_lazy_chunk(L.q);
+    for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
+        for (u32 j0 = 0; j0 < ngiant1; j0 += NG) {
+            const u64* dg[NG];
+#pragma unroll
+            for (int o = 0; o < NG; o++) dg[o] = dj + (size_t)bsgs_tile_step(j0, (u32)o, ngiant1) * jstride + i;
+            bsgs_sums<NG> s;
+            s.clear();
+            u32 pend = 0;
+            for (u32 k = 0; k <= nrot; k++) {
+                const u64 x = k == 0 ? X[base + i] : ROT[(size_t)(k - 1) * rstride + base + i];
+                u64 d[NG];
+#pragma unroll
+                for (int o = 0; o < NG; o++) d[o] = dg[o][(size_t)k * dstride];
+                if (bsgs_fold_due(pend, chunk)) s.fold(L.br);
+                s.mac(x, d);
+                pend++;
+            }
+#pragma unroll
+            for (int o = 0; o < NG; o++)
+                if (j0 + (u32)o < ngiant1) inner[(size_t)(j0 + (u32)o) * rstride + base + i] = s.word(o, L.br);
+        }
+    }
+}
+// first, out: [rows][N]; rest: [nrest][rows][N] (rstride words apart)
+__global__ __launch_bounds__(256) void k_bsgs_sum(const u64* __restrict__ first, const u64* __restrict__ rest, u64* __restrict__ out,
+                                                   const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 n, u32 nrest, size_t rstride) {
+    const u32 row = blockIdx.x, j = row % (u32)sel.n;
+    const u64 q = LT[sel.idx[j]].q;
+    const size_t base = (size_t)row * n;
+    for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
+        u64 r = first[base + i];
+        for (u32 t = 0; t < nrest; t++) r = addmod(r, rest[(size_t)t * rstride + base + i], q);
+        out[base + i] = r;
     }
 }
 

@@ -512,6 +512,21 @@ int tfhe_galois_key_prepare(tfhe_ctx* c, int Lk, int n_digits, uint64_t g, const
     return launch(c, k_ntt_perm, row_grid((unsigned)(n_digits * 2 * Lk), (size_t)c->N), dim3(256), 0, evk, evk_out, ginv, (u32)c->N);
 }
 
+// the workspace of the hoisted rotations for a call of `batch` ciphertexts (also read by whoever nests such a call in a workspace of
+// its own, tfhe_matmul_bsgs): per ciphertext S (2 nw rows) + digits (level nw) + T (2 nw) + rotated input (2 level); then one
+// prepared key where the caller's are plain
+struct rotate_many_ws_t {
+    size_t per_ct, ntt_tmp;
+    int64_t chunk;
+    size_t bytes() const { return ntt_tmp + (size_t)chunk * per_ct; }
+};
+static rotate_many_ws_t rotate_many_ws(const tfhe_ctx* c, int level, int nw, int64_t batch) {
+    rotate_many_ws_t W{};
+    W.per_ct = ((size_t)4 * nw + (size_t)level * nw + (size_t)2 * level) * (size_t)c->N * 8;
+    W.chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, W.per_ct);
+    W.ntt_tmp = c->logN > 14 ? (size_t)W.chunk * std::max(2, level) * nw * (size_t)c->N * 8 : 0;
+    return W;
+}
 int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, int prepared,
                      const uint64_t* galois, int n_rot, const uint64_t* ct, uint64_t* out, int64_t batch) {
     if (!evks || !galois || n_rot < 0) return fail(TFHE_E_BADARG, "null argument");
@@ -533,10 +548,9 @@ int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
         return TFHE_OK;
     }
     const ks_arg_t A = make_ks_arg(Lk, level, special, polys);
-    // workspace per ciphertext: S (2 nw rows) + digits (level nw) + T (2 nw) + rotated input (2 level); + one prepared key
-    const size_t per_ct = ((size_t)4 * nw + (size_t)level * nw + (size_t)polys * level) * N * 8;
-    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
-    const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * std::max(2, level) * nw * N * 8 : 0;
+    const rotate_many_ws_t W = rotate_many_ws(c, level, nw, batch);
+    const size_t per_ct = W.per_ct, ntt_tmp = W.ntt_tmp;
+    const int64_t chunk = W.chunk;
     const size_t key_bytes = prepared ? 0 : (size_t)n_digits * 2 * Lk * N * 8;
     void* ws = nullptr;
     int rc = ensure_ws(c, ntt_tmp + chunk * per_ct + key_bytes, &ws);
@@ -601,48 +615,8 @@ int tfhe_rotate_prepared(tfhe_ctx* c, int Lk, int level, int special, const uint
     return keyswitch_impl(c, Lk, level, special, evk_prepared, ct, 2, out, batch, g, true, false, true);
 }
 
-// ---- diagonal matrix-vector product (infer.jl:140-149, test/ckks_matmul.jl:33-41) in one call ---------------------------
-// out = diag_0 (.) c + sum_r diag_{r+1} (.) rotate(gk_r, c): the hoisted rotations of tfhe_rotate_many (one digit decomposition
-// of c) with every step -- key sums, inverse transforms, automorphism + tail, forward transforms, accumulation -- run over ALL
-// rotations at once instead of rotation by rotation (R x more rows per launch: about 15 launches per product instead of
-// about 8 R + 2 R + 2), and the rotated ciphertexts never return to the caller.  Same arithmetic, term by term, as
-// rotate_many -> nntt -> dot: bit-identical results.
-int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, const uint64_t* galois,
-                     int n_rot, const uint64_t* diags, const uint64_t* ct, uint64_t* out, int64_t batch) {
-    if (!evks || !galois || !diags || n_rot < 0) return fail(TFHE_E_BADARG, "null argument");
-    if (n_rot > TFHE_DOT_MAX) return fail(TFHE_E_UNSUPPORTED, "tfhe_matmul_diag takes at most %d rotations per call", TFHE_DOT_MAX);
-    for (int r = 0; r < n_rot; r++) {
-        int rc = ks_check(c, Lk, level, special, evks[r], n_digits, ct, 2, out, batch);
-        if (!rc) rc = galois_check(c, galois[r]);
-        if (rc) return rc;
-    }
-    if (n_rot == 0) {
-        int rc = ks_check(c, Lk, level, special, diags, n_digits, ct, 2, out, batch);
-        if (rc) return rc;
-    }
-    if (batch == 0) return TFHE_OK;
-    const int nw = special ? level + 1 : level, polys = 2, R = n_rot;
-    const size_t N = (size_t)c->N;
-    const u32 n = (u32)c->N;
-    ks_arg_t A = make_ks_arg(Lk, level, special, polys);
-    const limb_sel_t sl = first_limbs(level);
-    rescale_arg_t ra{};
-    if (special) {
-        special_inv_table(c, Lk, level, ra.qlinv);
-        std::copy(ra.qlinv, ra.qlinv + level, A.pinv);
-    }
-    rot_tail_arg_t G{};
-    for (int r = 0; r < R; r++) G.g[r] = galois[r];
-    // With a special prime the rotations are finished in the evaluation domain (k_md_*: only the special limb of every key sum is
-    // inverse-transformed); TFHE_MD_COEFF=1 keeps the coefficient-domain tail (k_ks_rot_tail) for comparisons.
-    static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
-    const bool eval_form = special && R > 0 && !md_coeff;
-    // workspace per ciphertext: digits (level nw rows) + S / T (R 2 nw) + rotated ciphertexts (R 2 level) + the ciphertext's own transform (2 level)
-    // (+ evaluation-domain form: the lifted special limbs before their transforms (R 2 level) and the special limbs themselves (R 2))
-    // (the untransformed lifts only where the lift is not fused into the transforms' loads)
-    const bool need_lf = eval_form && !(md_lift_is_fused(c, A, sl) && (size_t)R * 2 * level * 4 * 512 <= 0x7fffffffull);
-    const size_t per_ct = ((size_t)level * nw + (size_t)R * 2 * nw + (size_t)R * 2 * level + (size_t)2 * level +
-                           (eval_form ? (need_lf ? (size_t)R * 2 * level : 0) + (size_t)R * 2 : 0)) * N * 8;
+// the bound on the per-call workspace of the diagonal products (tfhe_matmul_diag, tfhe_matmul_bsgs)
+static size_t md_ws_cap(const tfhe_ctx* c) {
     // The keys of all R rotations are read once per chunk (2.8 GB at N = 2^16, 6 limbs + special prime, 63 rotations): a chunk as
     // large as the memory allows (32 GiB of workspace unless TFHE_MD_WS_GIB says otherwise; halved while the allocation fails)
     static const size_t ws_cap_env = env_gib("TFHE_MD_WS_GIB", 32);
@@ -679,14 +653,128 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
             ws_cap = std::min(ws_cap, std::max<size_t>((fr + c->ws_bytes + cached) / 2, (size_t)1 << 30));
         }
     }
+    return ws_cap;
+}
+
+// The rotation phase of a diagonal product -- everything up to the accumulation -- is shared by tfhe_matmul_diag and
+// tfhe_matmul_bsgs: what it consists of is decided once per call (md_plan), its buffers are laid out per chunk (md_bufs), and
+// md_rotations runs it over one chunk.
+struct md_plan_t {
+    ks_arg_t A; limb_sel_t sl; rescale_arg_t ra; rot_tail_arg_t G;
+    int Lk, level, nw, R;
+    // With a special prime the rotations are finished in the evaluation domain (k_md_*: only the special limb of every key sum is
+    // inverse-transformed); TFHE_MD_COEFF=1 keeps the coefficient-domain tail (k_ks_rot_tail) for comparisons.
+    bool eval_form;
+    bool need_lf;        // the untransformed lifts: only where the lift is not fused into the transforms' loads
+    // workspace rows (N words) per ciphertext: digits (level nw) + S / T (R 2 nw) + rotated ciphertexts (R 2 level) + the ciphertext's
+    // own transform (2 level) (+ evaluation-domain form: the lifted special limbs before their transforms (R 2 level) and the
+    // special limbs themselves (R 2))
+    size_t rows;
+    size_t ntt_rows;     // rows of the largest stand-alone transform, per ciphertext
+};
+static md_plan_t md_plan(const tfhe_ctx* c, int Lk, int level, int special, const uint64_t* galois, int R) {
+    md_plan_t P{};
+    const int nw = special ? level + 1 : level;
+    P.Lk = Lk; P.level = level; P.nw = nw; P.R = R;
+    P.A = make_ks_arg(Lk, level, special, 2);
+    P.sl = first_limbs(level);
+    if (special) {
+        special_inv_table(c, Lk, level, P.ra.qlinv);
+        std::copy(P.ra.qlinv, P.ra.qlinv + level, P.A.pinv);
+    }
+    for (int r = 0; r < R; r++) P.G.g[r] = galois[r];
+    static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
+    P.eval_form = special && R > 0 && !md_coeff;
+    P.need_lf = P.eval_form && !(md_lift_is_fused(c, P.A, P.sl) && (size_t)R * 2 * level * 4 * 512 <= 0x7fffffffull);
+    P.rows = (size_t)level * nw + (size_t)R * 2 * nw + (size_t)R * 2 * level + (size_t)2 * level +
+             (P.eval_form ? (P.need_lf ? (size_t)R * 2 * level : 0) + (size_t)R * 2 : 0);
+    P.ntt_rows = std::max<size_t>({(size_t)level * nw, (size_t)R * 2 * nw, (size_t)2 * level});
+    return P;
+}
+// ROT: the transformed rotated ciphertexts [R][nb][2][level][N], in the evaluation-domain form the lifts U of the same shape
+struct md_bufs_t { u64 *dig, *S, *ROT, *X, *LF, *PB, *end; };
+static md_bufs_t md_bufs(const md_plan_t& P, u64* base, int64_t chunk, size_t N) {
+    md_bufs_t B{};
+    const size_t R = (size_t)P.R, level = (size_t)P.level, nw = (size_t)P.nw;
+    B.dig = base;
+    B.S = B.dig + (size_t)chunk * level * nw * N;
+    B.ROT = B.S + (size_t)chunk * R * 2 * nw * N;
+    B.X = B.ROT + (size_t)chunk * R * 2 * level * N;
+    B.LF = P.need_lf ? B.X + (size_t)chunk * 2 * level * N : nullptr;   // lifted special limbs, untransformed (same shape as U)
+    B.PB = B.X + (size_t)chunk * 2 * level * N + (P.need_lf ? (size_t)chunk * R * 2 * level * N : 0);   // [R][nb][2][N]
+    B.end = base + (size_t)chunk * P.rows * N;
+    return B;
+}
+// X = NTT(cin) and, per rotation r: evaluation-domain form -- V in S (k_ks_inner<.., EPI>) and the lifts U in ROT, *scaled telling
+// whether U carries the factor P^-1 already (md_lift_fwd); otherwise NTT(rotate(gk_r, cin)) in ROT
+static int md_rotations(tfhe_ctx* c, const md_plan_t& P, const uint64_t* const* evks, const u64* cin, int64_t nb, const md_bufs_t& B, bool* scaled) {
+    const int Lk = P.Lk, level = P.level, nw = P.nw, R = P.R;
+    const u32 n = (u32)c->N;
+    int rc;
+    if (P.eval_form) {
+        const u32 groups = (u32)((int64_t)R * nb * 2);
+        rc = run_ntt(c, false, cin, B.X, nb * 2 * level, P.sl);
+        if (rc) return rc;
+        rc = ks_digits_fwd(c, P.A, cin, B.dig, nb);
+        if (rc) return rc;
+        rc = ks_inner_launch(c, P.A, Lk, nullptr, B.dig, B.S, nb, evks, R, B.X);   // limbs j < level leave as V = S' P^-1 + X0 [s = 0]
+        if (rc) return rc;
+        rc = launch(c, k_md_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, B.S, B.PB, P.G, n, (u32)nw, (u32)level, (u32)nb, groups);
+        if (rc) return rc;
+        limb_sel_t sp{};
+        sp.n = 1;
+        sp.idx[0] = Lk - 1;
+        rc = run_ntt(c, true, B.PB, B.PB, (int64_t)groups, sp);
+        if (rc) return rc;
+        return md_lift_fwd(c, P.A, P.sl, P.ra, B.PB, B.LF, B.ROT, (int64_t)groups, scaled);
+    }
+    if (R) {
+        rc = ks_digits_fwd(c, P.A, cin, B.dig, nb);
+        if (rc) return rc;
+        rc = ks_inner_launch(c, P.A, Lk, nullptr, B.dig, B.S, nb, evks, R);   // key sums of the unrotated digits against every prepared key
+        if (rc) return rc;
+        rc = run_ntt(c, true, B.S, B.S, (int64_t)R * nb * 2 * nw, P.A.w);
+        if (rc) return rc;
+        rc = launch(c, k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, B.S, cin, B.ROT, c->limbs_dev, P.A, P.ra, P.G, n, (u32)nb,
+                    (u32)((int64_t)R * nb * 2));
+        if (rc) return rc;
+        rc = run_ntt(c, false, B.ROT, B.ROT, (int64_t)R * nb * 2 * level, P.sl);
+        if (rc) return rc;
+    }
+    return run_ntt(c, false, cin, B.X, nb * 2 * level, P.sl);
+}
+
+// ---- diagonal matrix-vector product (infer.jl:140-149, test/ckks_matmul.jl:33-41) in one call ---------------------------
+// out = diag_0 (.) c + sum_r diag_{r+1} (.) rotate(gk_r, c): the hoisted rotations of tfhe_rotate_many (one digit decomposition
+// of c) with every step -- key sums, inverse transforms, automorphism + tail, forward transforms, accumulation -- run over ALL
+// rotations at once instead of rotation by rotation (R x more rows per launch: about 15 launches per product instead of
+// about 8 R + 2 R + 2), and the rotated ciphertexts never return to the caller.  Same arithmetic, term by term, as
+// rotate_many -> nntt -> dot: bit-identical results.
+int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, const uint64_t* galois,
+                     int n_rot, const uint64_t* diags, const uint64_t* ct, uint64_t* out, int64_t batch) {
+    if (!evks || !galois || !diags || n_rot < 0) return fail(TFHE_E_BADARG, "null argument");
+    if (n_rot > TFHE_DOT_MAX) return fail(TFHE_E_UNSUPPORTED, "tfhe_matmul_diag takes at most %d rotations per call", TFHE_DOT_MAX);
+    for (int r = 0; r < n_rot; r++) {
+        int rc = ks_check(c, Lk, level, special, evks[r], n_digits, ct, 2, out, batch);
+        if (!rc) rc = galois_check(c, galois[r]);
+        if (rc) return rc;
+    }
+    if (n_rot == 0) {
+        int rc = ks_check(c, Lk, level, special, diags, n_digits, ct, 2, out, batch);
+        if (rc) return rc;
+    }
+    if (batch == 0) return TFHE_OK;
+    const size_t N = (size_t)c->N;
+    const md_plan_t P = md_plan(c, Lk, level, special, galois, n_rot);
+    const size_t per_ct = P.rows * N * 8;
+    const size_t ws_cap = md_ws_cap(c);
     int64_t chunk = chunk_of(c, batch, 512, ws_cap, per_ct);
     size_t ntt_tmp = 0;
     void* ws = nullptr;
     int rc;
     ws_borrow_t borrow(c);    // a workspace above ws_keep_bytes() is this call's: back to the allocator on every return path
     for (bool first_try = true;; first_try = false) {
-        const size_t ntt_rows = (size_t)chunk * std::max<size_t>({(size_t)level * nw, (size_t)R * 2 * nw, (size_t)2 * level});
-        ntt_tmp = c->logN > 14 ? ntt_rows * N * 8 : 0;
+        ntt_tmp = c->logN > 14 ? (size_t)chunk * P.ntt_rows * N * 8 : 0;
         const size_t need = ntt_tmp + chunk * per_ct;
         if (first_try && need > ws_keep_bytes() && need > c->ws_bytes) borrow.begin();
         rc = ensure_ws(c, need, &ws, borrow.active);
@@ -694,57 +782,132 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
         chunk = (chunk + 1) / 2;
     }
     if (rc) return rc;
-    u64* dig = (u64*)((char*)ws + ntt_tmp);
-    u64* S = dig + (size_t)chunk * level * nw * N;
-    u64* ROT = S + (size_t)chunk * R * 2 * nw * N;
-    u64* X = ROT + (size_t)chunk * R * 2 * level * N;
+    const md_bufs_t B = md_bufs(P, (u64*)((char*)ws + ntt_tmp), chunk, N);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
-        const u64* cin = ct + (size_t)b0 * polys * level * N;
-        if (eval_form) {
-            u64* const U = ROT;                                  // [R][nb][2][level][N]
-            u64* const LF = need_lf ? X + (size_t)chunk * 2 * level * N : nullptr;   // lifted special limbs, untransformed (same shape)
-            u64* const PB = X + (size_t)chunk * 2 * level * N + (need_lf ? (size_t)chunk * R * 2 * level * N : 0);   // [R][nb][2][N]
-            const u32 groups = (u32)((int64_t)R * nb * 2);
-            rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
-            if (rc) return rc;
-            rc = ks_digits_fwd(c, A, cin, dig, nb);
-            if (rc) return rc;
-            rc = ks_inner_launch(c, A, Lk, nullptr, dig, S, nb, evks, R, X);   // limbs j < level leave as V = S' P^-1 + X0 [s = 0]
-            if (rc) return rc;
-            rc = launch(c, k_md_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, S, PB, G, n, (u32)nw, (u32)level, (u32)nb, groups);
-            if (rc) return rc;
-            limb_sel_t sp{};
-            sp.n = 1;
-            sp.idx[0] = Lk - 1;
-            rc = run_ntt(c, true, PB, PB, (int64_t)groups, sp);
-            if (rc) return rc;
-            bool scaled = true;
-            rc = md_lift_fwd(c, A, sl, ra, PB, LF, U, (int64_t)groups, &scaled);
-            if (rc) return rc;
-            auto acc = scaled ? k_md_acc<false> : k_md_acc<true>;
-            rc = launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, X, S, U, diags, out + (size_t)b0 * 2 * level * N, c->limbs_dev, sl,
-                        G, ra, n, (u32)nw, (u32)R, (u32)nb);
-            if (rc) return rc;
-            continue;
-        }
-        if (R) {
-            rc = ks_digits_fwd(c, A, cin, dig, nb);
-            if (rc) return rc;
-            rc = ks_inner_launch(c, A, Lk, nullptr, dig, S, nb, evks, R);   // key sums of the unrotated digits against every prepared key
-            if (rc) return rc;
-            rc = run_ntt(c, true, S, S, (int64_t)R * nb * 2 * nw, A.w);
-            if (rc) return rc;
-            rc = launch(c, k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, S, cin, ROT, c->limbs_dev, A, ra, G, n, (u32)nb,
-                        (u32)((int64_t)R * nb * 2));
-            if (rc) return rc;
-            rc = run_ntt(c, false, ROT, ROT, (int64_t)R * nb * 2 * level, sl);
-            if (rc) return rc;
-        }
-        rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
+        bool scaled = true;
+        rc = md_rotations(c, P, evks, ct + (size_t)b0 * 2 * level * N, nb, B, &scaled);
         if (rc) return rc;
-        rc = launch(c, k_matmul_acc, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, X, ROT, diags, out + (size_t)b0 * 2 * level * N,
-                    c->limbs_dev, sl, n, (u32)R, (u32)(nb * 2 * level));
+        u64* const o = out + (size_t)b0 * 2 * level * N;
+        if (P.eval_form) {
+            auto acc = scaled ? k_md_acc<false> : k_md_acc<true>;
+            rc = launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, B.X, B.S, B.ROT, diags, o, c->limbs_dev, P.sl, P.G, P.ra, (u32)N, (u32)P.nw,
+                        (u32)P.R, (u32)nb);
+        } else {
+            rc = launch(c, k_matmul_acc, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, B.X, B.ROT, diags, o, c->limbs_dev, P.sl, (u32)N,
+                        (u32)P.R, (u32)(nb * 2 * level));
+        }
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
+
+// ---- the same product by baby and giant steps ------------------------------------------------------------------------------
+// With the rotation index written k = j n1 + i,  sum_k d_k (.) rho^k(x) = sum_j rho^(j n1)( sum_i rho^(-j n1)(d_k) (.) rho^i(x) ):
+// n_baby + n_giant keys and key sums instead of one per diagonal; the plaintext diagonals arrive pre-rotated.
+//     inner_j = sum_{i = 0 .. n_baby} diags[j][i] (.) NTT(r_i(ct))       (r_0 = identity, r_i = rotate(baby key i - 1, .))
+//     out     = INTT(inner_0) + sum_{j = 1 .. n_giant} rotate(giant key j - 1, INTT(inner_j))
+// The baby phase is tfhe_matmul_diag's up to its accumulation (md_rotations); the accumulations with n_giant + 1 outputs are
+// k_bsgs_acc / k_bsgs_acc_dense; one batched inverse transform covers all inner sums; the giant rotations go through the
+// prepared-key key switch (keyswitch_impl), one per giant step over the chunk; k_bsgs_sum adds up.  Exact arithmetic on canonical
+// residues throughout: the words of tfhe_rotate_many -> tfhe_nntt -> tfhe_dot -> tfhe_inntt -> tfhe_rotate_prepared -> tfhe_add.
+//
+// The workspace the giant rotations' key switch asks for at the start of the context workspace, for `batch` ciphertexts: either
+// route a prepared-key rotation can take (ks_plan decides by the operands' addresses, which are ours and always disjoint)
+static size_t bsgs_nested_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t batch) {
+    const int nw = special ? level + 1 : level;
+    const u64* const in = (const u64*)(uintptr_t)4096;   // two disjoint, aligned ranges: never dereferenced by the plan
+    const ks_plan_t P = ks_plan(c, Lk, level, special, 2, batch, in, in + (size_t)batch * 2 * level * (size_t)c->N, 1, true, false, true);
+    const size_t tail = P.rot == KS_ROT_HOISTED ? 0 : P.bytes();
+    return std::max(tail, rotate_many_ws(c, level, nw, batch).bytes());
+}
+// the output tile: 4 giant steps per pass, fewer where there are fewer sums (log2)
+static int bsgs_log_tile(int ngiant1) { return ngiant1 >= 3 ? 2 : ngiant1 - 1; }
+int tfhe_matmul_bsgs(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby,
+                     const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant, int n_digits, const uint64_t* diags,
+                     const uint64_t* ct, uint64_t* out, int64_t batch) {
+    // host checks that need no ring first, then the context, then the ring's
+    if (!baby_evks || !baby_galois || !giant_evks || !giant_galois || !diags || !ct || !out) return fail(TFHE_E_BADARG, "null argument");
+    if (n_baby < 0 || n_baby > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_baby=%d outside [0,%d]", n_baby, TFHE_DOT_MAX);
+    if (n_giant < 0 || n_giant > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_giant=%d outside [0,%d]", n_giant, TFHE_DOT_MAX);
+    for (int r = 0; r < n_baby; r++)
+        if (!baby_evks[r]) return fail(TFHE_E_BADARG, "null baby key %d", r);
+    for (int r = 0; r < n_giant; r++)
+        if (!giant_evks[r]) return fail(TFHE_E_BADARG, "null giant key %d", r);
+    for (int r = 0; r < n_baby + n_giant; r++)
+        if (((r < n_baby ? baby_galois[r] : giant_galois[r - n_baby]) & 1) == 0) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
+    if ((const void*)out == (const void*)ct || (const void*)out == (const void*)diags) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (!c) return fail(TFHE_E_BADARG, "null context");
+    int rc = ks_check(c, Lk, level, special, diags, n_digits, ct, 2, out, batch);
+    if (rc) return rc;
+    for (int r = 0; r < n_baby + n_giant; r++)
+        if ((rc = galois_check(c, r < n_baby ? baby_galois[r] : giant_galois[r - n_baby]))) return rc;
+    const size_t N = (size_t)c->N;
+    const int ng1 = n_giant + 1;
+    const size_t ct_bytes = (size_t)batch * 2 * level * N * 8;
+    if (ranges_overlap(out, ct_bytes, ct, ct_bytes) || ranges_overlap(out, ct_bytes, diags, (size_t)ng1 * (n_baby + 1) * level * N * 8))
+        return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (batch == 0) return TFHE_OK;
+    const md_plan_t P = md_plan(c, Lk, level, special, baby_galois, n_baby);
+    // One allocation: [ region 0 | the baby phase (md_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ].
+    // Region 0 is the start of the context workspace, which the stand-alone transforms of N > 2^14 and the nested key switch
+    // take for themselves (ensure_ws hands out the start of whatever is allocated): sized for the larger of the two, so that a
+    // nested ensure_ws neither grows -- moves -- the workspace nor reaches our buffers.
+    const size_t rows = P.rows + (size_t)(ng1 + n_giant) * 2 * level, per_ct = rows * N * 8;
+    const size_t ntt_rows = std::max(P.ntt_rows, (size_t)ng1 * 2 * level);
+    int64_t chunk = chunk_of(c, batch, 512, md_ws_cap(c), per_ct);
+    size_t region0 = 0;
+    void* ws = nullptr;
+    ws_borrow_t borrow(c);    // a workspace above ws_keep_bytes() is this call's: back to the allocator on every return path
+    for (bool first_try = true;; first_try = false) {
+        region0 = c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : 0;
+        if (n_giant) region0 = std::max(region0, bsgs_nested_bytes(c, Lk, level, special, chunk));
+        region0 = (region0 + 255) & ~(size_t)255;
+        const size_t need = region0 + chunk * per_ct;
+        if (first_try && need > ws_keep_bytes() && need > c->ws_bytes) borrow.begin();
+        rc = ensure_ws(c, need, &ws, borrow.active);
+        if (rc != TFHE_E_NOMEM || chunk == 1) break;
+        chunk = (chunk + 1) / 2;
+    }
+    if (rc) return rc;
+    const md_bufs_t B = md_bufs(P, (u64*)((char*)ws + region0), chunk, N);
+    u64* const INNER = B.end;
+    u64* const GOUT = INNER + (size_t)chunk * ng1 * 2 * level * N;
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const size_t ct_words = (size_t)nb * 2 * level * N;   // one inner sum / one giant result of this chunk
+        bool scaled = true;
+        rc = md_rotations(c, P, baby_evks, ct + (size_t)b0 * 2 * level * N, nb, B, &scaled);
+        if (rc) return rc;
+        rc = dispatch_int<0, 2>(bsgs_log_tile(ng1), [&](auto lg) {
+            constexpr int NG = 1 << decltype(lg)::value;
+            if (P.eval_form) {
+                auto acc = scaled ? k_bsgs_acc<false, NG> : k_bsgs_acc<true, NG>;
+                return launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, B.X, B.S, B.ROT, diags, INNER, c->limbs_dev, P.sl, P.G, P.ra, (u32)N,
+                              (u32)P.nw, (u32)P.R, (u32)nb, (u32)ng1);
+            }
+            return launch(c, k_bsgs_acc_dense<NG>, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, B.X, B.ROT, diags, INNER, c->limbs_dev,
+                          P.sl, (u32)N, (u32)P.R, (u32)(nb * 2 * level), (u32)ng1);
+        });
+        if (rc) return rc;
+        rc = run_ntt(c, true, INNER, INNER, (int64_t)ng1 * nb * 2 * level, P.sl);
+        if (rc) return rc;
+        // What the nested key switch will ask for, from its own plan on the real operands: it must stay inside region 0.  The plan of
+        // the first giant step stands for all of them: it depends on the operands only through their disjointness and 16-byte
+        // alignment, and step j reads INNER + j ct_words and writes GOUT + (j - 1) ct_words -- disjoint ranges of one allocation, every
+        // offset a multiple of 8 N bytes from a 256-byte aligned base -- and on the Galois element only for what it writes into the plan.
+        if (n_giant) {
+            const ks_plan_t Q = ks_plan(c, Lk, level, special, 2, nb, INNER + ct_words, GOUT, giant_galois[0], true, false, true);
+            const size_t nested = Q.rot == KS_ROT_HOISTED ? rotate_many_ws(c, level, P.nw, nb).bytes() : Q.bytes();
+            if (nested > region0) return fail(TFHE_E_UNSUPPORTED, "internal: the nested key switch needs %zu bytes, region 0 holds %zu", nested, region0);
+        }
+        for (int j = 1; j <= n_giant; j++) {   // (the nested call finds the workspace large enough: same block, region 0)
+            rc = keyswitch_impl(c, Lk, level, special, giant_evks[j - 1], INNER + (size_t)j * ct_words, 2, GOUT + (size_t)(j - 1) * ct_words, nb,
+                                giant_galois[j - 1], true, false, true);
+            if (rc) return rc;
+        }
+        rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)INNER, (const u64*)GOUT,
+                    out + (size_t)b0 * 2 * level * N, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words);
         if (rc) return rc;
     }
     return TFHE_OK;

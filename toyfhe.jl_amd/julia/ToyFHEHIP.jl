@@ -561,6 +561,37 @@ function matmul_diag(gks::Vector{<:ToyFHE.GaloisKey}, diags::Vector{<:RingElemen
     # (ckksencoding.jl:106-111: CipherText{CKKSEncoding{Tscale^2}}); other encodings carry no scale
     CipherText{squared_encoding(Enc)}(c.params, unpack(ctx, out, ℛ, 2; dual=true))
 end
+# The same product by baby and giant steps in one device call (tfhe_matmul_bsgs): inner_j = sum_i diags[j][i] .* r_i(c) over the
+# baby keys (r_1 = identity), result = inner_1 + sum_{j > 1} rotate(giant[j-1], inner_j); length(baby) + length(giant) keys instead
+# of one per diagonal.  diags: length(giant) + 1 rows of length(baby) + 1 plaintext elements, pre-rotated by the caller.  The
+# result is in the coefficient domain.  (Not executed anywhere yet: the tests check the ccall against the header.)
+function matmul_bsgs(baby::Vector{<:ToyFHE.GaloisKey}, giant::Vector{<:ToyFHE.GaloisKey}, diags::Vector{<:Vector{<:RingElement{ℛ,T,<:HipVector}}},
+                     c::CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}) where {Enc,P,ℛ,T}
+    @assert length(c.cs) == 2 && length(diags) == length(giant) + 1 && all(r -> length(r) == length(baby) + 1, diags)
+    max(length(baby), length(giant)) <= 64 || throw(ToyFHE.UsageError("matmul_bsgs: at most 64 baby and 64 giant steps per call (TFHE_DOT_MAX)"))
+    # either key set may be empty (n_baby = 0: plain products, rotated and added; n_giant = 0: matmul_diag in the coefficient domain);
+    # the key ring, the special prime and the digit count are read from the first key there is
+    isempty(baby) && isempty(giant) && throw(ToyFHE.UsageError("matmul_bsgs: no Galois key at all -- that is a plain product, use .*"))
+    ek1 = (isempty(baby) ? giant[1] : baby[1]).key; keyring = NTT.ring(ek1.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T); cnt = batchsize(c)
+    ctx = hipring(keyring); ct = pack(ctx, c); n = degree(ℛ); nb = length(baby); ng = length(giant)
+    pb = HipVector[prepared(gk) for gk in baby]; pg = HipVector[prepared(gk) for gk in giant]     # PREPARED keys only
+    dparts = HipVector[coeffs_dual(d).parent for row in diags for d in row]
+    all(d -> d.count == 1, dparts) || throw(ToyFHE.UsageError("matmul_bsgs: one polynomial per diagonal"))
+    dg = HipVector{T}(level, n, (ng + 1) * (nb + 1)); on(ctx, (dg,), (dparts...,))
+    GC.@preserve dparts dg for (k, d) in enumerate(dparts)                    # dg: [ng + 1][nb + 1][level][N]
+        check(ccall((:tfhe_memcpy_d2d, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t),
+              ctx.handle, dg.ptr + 8 * (k - 1) * level * n, d.ptr, 8 * level * n))
+    end
+    out = HipVector{T}(2 * level, n, cnt); on(ctx, (out,), (ct, dg, pb..., pg...))
+    bkeys = Ptr{UInt64}[k.ptr for k in pb]; bgs = UInt64[gk.galois_element for gk in baby]
+    gkeys = Ptr{UInt64}[k.ptr for k in pg]; ggs = UInt64[gk.galois_element for gk in giant]
+    GC.@preserve pb pg ct dg out check(ccall((:tfhe_matmul_bsgs, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Cint, Cint,
+                 Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, ek1.params isa ModulusRaised ? 1 : 0, bkeys, bgs, nb, gkeys, ggs, ng, length(ek1.key),
+                dg.ptr, ct.ptr, out.ptr, cnt))
+    CipherText{squared_encoding(Enc)}(c.params, unpack(ctx, out, ℛ, 2))
+end
 squared_encoding(::Type{CKKSEncoding{Tscale}}) where {Tscale} = CKKSEncoding{Tscale^2}
 squared_encoding(::Type{E}) where {E} = E
 

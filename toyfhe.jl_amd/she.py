@@ -1569,6 +1569,87 @@ def matmul_diag(gks, diags, c: CipherText) -> CipherText:
     return CipherText(c.params, res, Fraction(c.scale) ** 2)
 
 
+def bsgs_diagonals(dv, n1: int, block: int = 1):
+    """The baby-step/giant-step regrouping of a diagonal product.  `dv[k]`, k < n, are slot vectors: diagonal k multiplies the
+    rotation of the input by k * block slots (rotation by s steps acts on the slots as np.roll(x, s)).  With k = j n1 + i,
+        sum_k dv[k] * roll(x, k block) = sum_j roll( sum_i D[j][i] * roll(x, i block), j n1 block ),
+        D[j][i] = np.roll(dv[j n1 + i], -j n1 block)        (rows with j n1 + i >= n are zero).
+    Returns (D, baby_steps, giant_steps): D of shape [n2][n1'][slots] with n2 = ceil(n / n1) and n1' = min(n1, n), and the rotation
+    steps the two key sets are made for (keygen_galois_many): [i block for 0 < i < n1'], [j n1 block for 0 < j < n2].  Encode
+    D.reshape(n2 * n1', slots) for `matmul_bsgs`."""
+    dv = np.asarray(dv)
+    if dv.ndim != 2 or n1 < 1 or block < 1:
+        raise AssertionError("bsgs_diagonals: dv is [n][slots], n1 >= 1, block >= 1")
+    n = dv.shape[0]
+    n1 = min(int(n1), n)
+    n2 = -(-n // n1)
+    D = np.zeros((n2, n1) + dv.shape[1:], dtype=dv.dtype)
+    for k in range(n):
+        j, i = divmod(k, n1)
+        D[j, i] = np.roll(dv[k], -j * n1 * block, axis=-1)
+    return D, [i * block for i in range(1, n1)], [j * n1 * block for j in range(1, n2)]
+
+
+def matmul_bsgs(baby_gks, giant_gks, diags, c: CipherText) -> CipherText:
+    """The diagonal product by baby and giant steps in ONE device call (tfhe_matmul_bsgs):
+        inner_j = sum_i diags[j][i] .* NTT(r_i(c)),   r_0 = identity, r_i = rotate(baby_gks[i - 1], .)
+        result  = inner_0 + sum_{j >= 1} rotate(giant_gks[j - 1], inner_j)
+    `diags`: len(giant_gks) + 1 lists of len(baby_gks) + 1 plaintext elements of c's ring at c's scale (one polynomial each, shared
+    by the batch), or ONE stacked element holding the (len(giant_gks) + 1)(len(baby_gks) + 1) diagonals back to back, giant step
+    major (what ckks_encode returns for bsgs_diagonals(..)[0].reshape(-1, slots)).  Pre-rotating them is the caller's business
+    (bsgs_diagonals).  Word for word rotate_many -> dot_plain per giant step -> rotate -> +; the result is in the coefficient
+    domain, at the squared scale."""
+    baby_gks, giant_gks = list(baby_gks), list(giant_gks)
+    if len(c) != 2:
+        raise AssertionError("rotate takes a 2-element ciphertext")
+    c._need_scale()
+    if len(baby_gks) > DOT_MAX or len(giant_gks) > DOT_MAX:
+        raise UsageError(f"matmul_bsgs: at most {DOT_MAX} baby and {DOT_MAX} giant steps per call")
+    ring, n, batch = c[0].ring, c[0].count, c[0].batch
+    level = ring.L
+    nb1, ng1 = len(baby_gks) + 1, len(giant_gks) + 1
+    stacked = isinstance(diags, RingElement)
+    if stacked:
+        if diags.ring != ring or diags.count != ng1 * nb1:
+            raise UsageError("matmul_bsgs: a stacked plaintext element must hold (giant steps + 1) x (baby steps + 1) diagonals")
+    else:
+        diags = [list(row) for row in diags]
+        if len(diags) != ng1 or any(len(row) != nb1 for row in diags):
+            raise AssertionError("matmul_bsgs: one row of diagonals per giant step plus one, one diagonal per baby step plus one in each")
+        diags = [d for row in diags for d in row]
+        for d in diags:
+            if not isinstance(d, RingElement) or d.ring != ring or d.count != 1:
+                raise UsageError("matmul_bsgs: the diagonals are single plaintext elements of the ciphertext's ring")
+    gks = baby_gks + giant_gks
+    if gks:
+        params = gks[0].key.params
+        if any(g.key.params is not params for g in gks) or params.relin_window != 0:
+            raise UsageError("hoisted rotations need Galois keys of one parameter set with RNS digits")
+        keyring = gks[0].key.key[0].mask.ring
+        special = isinstance(params, ModulusRaised)
+    else:
+        keyring, special = ring, False
+    if keyring.idx != list(range(keyring.L)) or ring.idx != list(range(level)):
+        raise UsageError("ciphertext ring is not a prefix of the key ring")
+    prim = [x.coeffs_primal() for x in c.cs]               # both before the hand-over (see keyswitch)
+    duals = [diags.coeffs_dual()] if stacked else [d.coeffs_dual() for d in diags]
+    if ring.ctx is not keyring.ctx:
+        if ring.N != keyring.N or ring.moduli != keyring.moduli[:level] or ring.psi != keyring.psi[:level]:
+            raise UsageError("ciphertext and key belong to different rings")
+        keyring.ctx.wait_for(ring.ctx)
+    sz = level * ring.N
+    dg = duals[0] if stacked else _pack(duals, ring, 1, ctx=keyring.ctx)   # [ng1][nb1][level][N]
+    ct = _pack(prim, ring, n, ctx=keyring.ctx)
+    out = DeviceBuffer(n * 2 * sz)
+    keyring.ctx.matmul_bsgs(keyring.L, level, special, [g.prepared().ptr for g in baby_gks], [g.galois_element for g in baby_gks],
+                            [g.prepared().ptr for g in giant_gks], [g.galois_element for g in giant_gks],
+                            len(gks[0].key.key) if gks else level, dg.ptr, ct.ptr, out.ptr, n)
+    res = _unpack(out, ring, n, 2, batch, primal=True, ctx=keyring.ctx)
+    if ring.ctx is not keyring.ctx:
+        ring.ctx.wait_for(keyring.ctx)
+    return CipherText(c.params, res, Fraction(c.scale) ** 2)
+
+
 class _View:
     """a window into a DeviceBuffer (keeps the parent alive)"""
 
