@@ -1,30 +1,30 @@
-// tests/bsgs_emul/bsgs_emul.cpp -- CPU emulation of the multi-output accumulations of tfhe_matmul_bsgs: the bodies of
-// toyfhe.jl_amd/csrc/bsgs_core.h strung together in the order of k_bsgs_acc (gather form) and k_bsgs_acc_dense (kernels.h), one
-// "thread" per coefficient, one limb.  TEST INFRASTRUCTURE ONLY.
+// tests/bsgs_emul/bsgs_emul.cpp -- CPU emulation of the accumulations of tfhe_matmul_diag (one output) and tfhe_matmul_bsgs (a tile
+// of outputs): the bodies of toyfhe.jl_amd/csrc/lazy_sum.h strung together in the order of k_md_acc (gather form) and
+// k_md_acc_dense (kernels.h), one "thread" per coefficient, one limb.  TEST INFRASTRUCTURE ONLY.
 #include <cstddef>
 #include <cstdint>
 #include "../../toyfhe.jl_amd/csrc/host_math.h"
-#include "../../toyfhe.jl_amd/csrc/bsgs_core.h"
+#include "../../toyfhe.jl_amd/csrc/lazy_sum.h"
 
 namespace {
 
-// k_bsgs_acc_dense: x [n], rot [nrot][n], diag [ngiant1][nrot + 1][n] -> inner [ngiant1][n]
+// k_md_acc_dense: x [n], rot [nrot][n], diag [ngiant1][nrot + 1][n] -> inner [ngiant1][n]
 template <int NG>
 void dense(const barrett_t& br, u32 n, u32 nrot, u32 ngiant1, const u64* x, const u64* rot, const u64* diag, u64* inner) {
     const size_t dstride = n, jstride = (size_t)(nrot + 1u) * dstride;
-    const u32 chunk = bsgs_lazy_chunk(br.q);
+    const u32 chunk = lazy_chunk(br.q);
     for (u32 i = 0; i < n; i++) {
         for (u32 j0 = 0; j0 < ngiant1; j0 += NG) {
             const u64* dg[NG];
             for (int o = 0; o < NG; o++) dg[o] = diag + (size_t)bsgs_tile_step(j0, (u32)o, ngiant1) * jstride + i;
-            bsgs_sums<NG> s;
+            lazy_sums<NG> s;
             s.clear();
             u32 pend = 0;
             for (u32 k = 0; k <= nrot; k++) {
                 const u64 v = k == 0 ? x[i] : rot[(size_t)(k - 1) * n + i];
                 u64 d[NG];
                 for (int o = 0; o < NG; o++) d[o] = dg[o][(size_t)k * dstride];
-                if (bsgs_fold_due(pend, chunk)) s.fold(br);
+                if (lazy_fold_due(pend, chunk)) s.fold(br);
                 s.mac(v, d);
                 pend++;
             }
@@ -33,18 +33,18 @@ void dense(const barrett_t& br, u32 n, u32 nrot, u32 ngiant1, const u64* x, cons
         }
     }
 }
-// k_bsgs_acc, one row pair: x0, x1 [n]; v [nrot][n][2] (both components of a position side by side, epi_pair); u0, u1 [nrot][n];
+// k_md_acc, one row pair: x0, x1 [n]; v [nrot][n][2] (both components of a position side by side, epi_pair); u0, u1 [nrot][n];
 // g [nrot]; diag as above -> inner0, inner1 [ngiant1][n]
 template <bool USCALE, int NG>
 void gather(const barrett_t& br, tw_t pinv, u32 n, u32 nrot, u32 ngiant1, const u64* x0, const u64* x1, const u64* v, const u64* u0, const u64* u1,
             const u64* g, const u64* diag, u64* inner0, u64* inner1) {
     const size_t dstride = n, jstride = (size_t)(nrot + 1u) * dstride;
-    const u32 chunk = bsgs_lazy_chunk(br.q);
+    const u32 chunk = lazy_chunk(br.q);
     for (u32 k = 0; k < n; k++) {
         for (u32 j0 = 0; j0 < ngiant1; j0 += NG) {
             const u64* dg[NG];
             for (int o = 0; o < NG; o++) dg[o] = diag + (size_t)bsgs_tile_step(j0, (u32)o, ngiant1) * jstride;
-            bsgs_sums<NG> a0, a1;
+            lazy_sums<NG> a0, a1;
             u64 d[NG];
             for (int o = 0; o < NG; o++) d[o] = dg[o][k];
             a0.clear(); a1.clear();
@@ -55,9 +55,9 @@ void gather(const barrett_t& br, tw_t pinv, u32 n, u32 nrot, u32 ngiant1, const 
                 const u32 kk = galois_ntt_pos(k, g[t], n);
                 const u64* vv = v + ((size_t)t * n + kk) * 2;
                 for (int o = 0; o < NG; o++) d[o] = dg[o][(size_t)(t + 1) * dstride + k];
-                if (bsgs_fold_due(pend, chunk)) { a0.fold(br); a1.fold(br); }
-                a0.mac(bsgs_gather_term<USCALE>(vv[0], u0[(size_t)t * n + k], pinv, br.q), d);
-                a1.mac(bsgs_gather_term<USCALE>(vv[1], u1[(size_t)t * n + k], pinv, br.q), d);
+                if (lazy_fold_due(pend, chunk)) { a0.fold(br); a1.fold(br); }
+                a0.mac(gather_term<USCALE>(vv[0], u0[(size_t)t * n + k], pinv, br.q), d);
+                a1.mac(gather_term<USCALE>(vv[1], u1[(size_t)t * n + k], pinv, br.q), d);
                 pend++;
             }
             for (int o = 0; o < NG; o++) {
@@ -75,7 +75,7 @@ void gather(const barrett_t& br, tw_t pinv, u32 n, u32 nrot, u32 ngiant1, const 
 extern "C" {
 
 // the lazy-reduction chunk of a modulus
-unsigned bsgs_emul_chunk(uint64_t q) { return bsgs_lazy_chunk(q); }
+unsigned bsgs_emul_chunk(uint64_t q) { return lazy_chunk(q); }
 
 // 0, or -1 for a tile the kernels are not built for
 int bsgs_emul_dense(uint64_t q, int tile, uint32_t n, uint32_t nrot, uint32_t ngiant1, const uint64_t* x, const uint64_t* rot, const uint64_t* diag,

@@ -62,7 +62,7 @@ MIXED_MIN_WORDS = 1 << 20          # toyfhe_hip.hip TFHE_MIXED_MIN_WORDS: words 
 
 
 def sum_chunk(bits):
-    """kernels.h k_dot / k_lincomb / k_lincomb_many / k_matmul_acc / k_md_acc: products summed between two Barrett
+    """lazy_sum.h lazy_chunk (k_dot / k_lincomb / k_lincomb_many / k_dot_view / k_md_acc / k_md_acc_dense): products summed between two Barrett
     reductions, 2^(62 - bits(q)) capped at 64 (chunk (q - 1)^2 < 2^(bits + 62), the Barrett window)"""
     return 1 if bits >= 62 else min(64, 1 << (62 - bits))
 

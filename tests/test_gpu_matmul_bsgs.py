@@ -74,7 +74,7 @@ CASES = [(6, [40, 40, 40, 40], 3, 2, None, True), (12, [60, 40, 40, 60], 2, 2, 3
 @pytest.mark.parametrize("logn,bits,n_baby,n_giant,batch,raised", CASES)
 def test_matmul_bsgs_is_word_for_word_the_composition(logn, bits, n_baby, n_giant, batch, raised):
     """uniform rings, the mixed 60/40-bit CKKS rings (two lanes) and the sub-block transforms of N = 2^15 / 2^16; with the special
-    prime the baby phase ends in the evaluation domain (k_bsgs_acc), without it in the coefficient tail (k_bsgs_acc_dense); the
+    prime the baby phase ends in the evaluation domain (k_md_acc), without it in the coefficient tail (k_md_acc_dense); the
     diagonals as lists and as one stacked element; once more a level down, on the same keys"""
     N = 1 << logn
     kp, c, baby, giant, dv = _setup(N, _ring(N, bits), raised, n_baby, n_giant, batch, 2000 + logn)

@@ -145,7 +145,8 @@ def test_limbwise_operations_on_the_operand_edge_cross_product(name):
 
 
 # ---------------------------------------------------------------------------------------------------
-# sums in the Barrett window (k_dot, k_lincomb, k_lincomb_many): chunk = 2^(62 - bits) products between two reductions
+# sums in the Barrett window (k_dot, k_lincomb, k_lincomb_many, k_md_acc, k_md_acc_dense): chunk = 2^(62 - bits) products between two
+# reductions (csrc/lazy_sum.h lazy_chunk)
 # ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["top56", "top57", "top58", "top59", "top60", "top61", "top62", "fold61", "fold62", "top52",
                                   "fp-top", "u64-bottom"])
@@ -188,13 +189,18 @@ def test_sums_with_every_operand_q_minus_1(name):
         assert np.array_equal(out2.to_numpy((2, L, N)), want2.astype(np.uint64)), ("lincomb_many 1", terms)
 
 
+@pytest.mark.parametrize("raised", [True, False])
 @pytest.mark.parametrize("name,n_rot", [("top61", 3), ("top60", 5), ("fold62", 2)])
-def test_matmul_diag_at_the_top_of_the_bit_lengths(name, n_rot):
-    """tfhe_matmul_diag (k_matmul_acc / k_md_acc: n_rot + 1 products per chunk of 2^(62 - bits)) against rotate_many and
-    dot_plain, word for word, on a ring of the largest primes below 2^61 / 2^60 and the fold primes, diagonals of q - 1"""
+def test_matmul_diag_at_the_top_of_the_bit_lengths(name, n_rot, raised):
+    """tfhe_matmul_diag (one sum of k_md_acc with a special prime, of k_md_acc_dense without: n_rot + 1 products, more than the chunk
+    of 2^(62 - bits)) against rotate_many and dot_plain, word for word, on a ring of the largest primes below 2^61 / 2^60 and the
+    fold primes, diagonals of q - 1"""
     N = 1 << 10
     R = tf.NegacyclicRing(N, edge(name, 3, N))
-    params = tf.ModulusRaised(tf.CKKSParams(R, 0, 3.2))
+    assert n_rot + 1 > H.sum_chunk(min(q.bit_length() for q in R.moduli))      # every limb folds at least once
+    params = tf.CKKSParams(R, 0, 3.2)
+    if raised:
+        params = tf.ModulusRaised(params)
     rng = tf.DeviceRng(77)
     kp = tf.keygen(rng, params)
     c = tf.encrypt(rng, kp, tf.ckks_encode(np.ones(N // 2, dtype=complex), params.R_cipher(), 2**30), scale=2**30)

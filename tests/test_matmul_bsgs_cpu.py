@@ -1,7 +1,7 @@
 """No-GPU checks of tfhe_matmul_bsgs (the diagonal matrix product by baby and giant steps, one device call): the symbol is declared,
 exported, bound by ctypes and by the Julia shim with one signature; every argument check that does not need the ring runs on the
-host before any device use; she.bsgs_diagonals regroups a diagonal sum exactly; the accumulation bodies of the new kernels
-(csrc/bsgs_core.h) run on the CPU (tests/bsgs_emul/) give exact big-integer sums at 61- and 62-bit moduli with more terms than the
+host before any device use; she.bsgs_diagonals regroups a diagonal sum exactly; the accumulation bodies of the k_md_acc kernels
+(csrc/lazy_sum.h) run on the CPU (tests/bsgs_emul/) give exact big-integer sums at 61- and 62-bit moduli with more terms than the
 lazy-reduction chunk; and the gfx950 code objects of the accumulation kernels use no scratch memory."""
 import ctypes as C
 import os
@@ -158,9 +158,9 @@ def test_bsgs_diagonals_on_the_example_layout_give_the_matrix_product(n1):
 
 # ---- the accumulation bodies on the CPU --------------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bsgs_emul") / "libbsgs_emul.so")
+def load_emul(tmpdir):
+    """tests/bsgs_emul/bsgs_emul.cpp compiled for the host into `tmpdir` and bound"""
+    so = str(tmpdir / "libbsgs_emul.so")
     src = os.path.join(ROOT, "tests", "bsgs_emul", "bsgs_emul.cpp")
     subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
                            "-shared", "-o", so, src])
@@ -170,6 +170,11 @@ def emul(tmp_path_factory):
     L.bsgs_emul_dense.argtypes, L.bsgs_emul_dense.restype = [u64, C.c_int, u32, u32, u32, vp, vp, vp, vp], C.c_int
     L.bsgs_emul_gather.argtypes, L.bsgs_emul_gather.restype = [u64, C.c_int, C.c_int, u64, u32, u32, u32] + [vp] * 9, C.c_int
     return L
+
+
+@pytest.fixture(scope="module")
+def emul(tmp_path_factory):
+    return load_emul(tmp_path_factory.mktemp("bsgs_emul"))
 
 
 def _moduli():
@@ -238,7 +243,8 @@ def test_accumulation_bodies_match_exact_sums(emul, q, chunk, edge):
 
 @pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc is not installed")
 def test_accumulation_kernels_use_no_scratch(tmp_path):
-    """compiler-reported scratch is 0 for every instantiation the entry point launches: the accumulators stay in registers"""
+    """compiler-reported scratch is 0 for every instantiation tfhe_matmul_diag and tfhe_matmul_bsgs launch: the accumulators stay in
+    registers"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     src = os.path.join(ROOT, "tests", "bsgs_emul", "resource_probe.hip")
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "--cuda-device-only", "-c", src,
@@ -246,8 +252,8 @@ def test_accumulation_kernels_use_no_scratch(tmp_path):
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout[-4000:]
     blocks = re.split(r"remark: [^\n]*Function Name: ", r.stdout)[1:]
-    mine = [b for b in blocks if re.match(r"_Z\d+k_bsgs_", b)]
-    assert len(mine) == 10, [b.split()[0] for b in mine]   # 6 x k_bsgs_acc, 3 x k_bsgs_acc_dense, k_bsgs_sum
+    mine = [b for b in blocks if re.match(r"_Z\d+(k_md_acc|k_md_acc_dense|k_bsgs_sum)[IP]", b)]   # (template arguments / first parameter)
+    assert len(mine) == 10, [b.split()[0] for b in mine]   # 6 x k_md_acc, 3 x k_md_acc_dense, k_bsgs_sum
     for b in mine:
         name = b.split()[0]
         scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))

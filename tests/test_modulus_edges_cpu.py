@@ -11,6 +11,7 @@ import pytest
 import toyfhe_jl_amd as tf
 from oracle import ref_cpu, spec
 from tests import helpers as H
+from tests import test_matmul_bsgs_cpu as bsgs
 from tests.emul import emul
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "toyfhe.jl_amd", "csrc")
@@ -21,7 +22,7 @@ def _src(name):
         return f.read()
 
 
-def test_class_thresholds_match_the_engine_sources():
+def test_class_thresholds_match_the_engine_sources(tmp_path):
     fp = _src("fp64arith.h")
     assert int(re.search(r"#define TFHE_FP_QMAX (\d+)ull", fp).group(1)) == H.FP_QMAX
     assert (1 << int(re.search(r"#define TFHE_FPS_QMAX \(1ull << (\d+)\)", fp).group(1))) == H.FPS_QMAX
@@ -31,15 +32,23 @@ def test_class_thresholds_match_the_engine_sources():
     assert int(re.search(r"const int lazy = fold \? \(qbits <= 61 \? DCH : (\d+)\)", k).group(1)) == H.KS_FOLD_LAZY_62
     assert re.search(r'static_assert\(DCH <= 15, "fold budget at 61 bits"\)', k)
     assert re.search(r'static_assert\(DCH \+ 1 <= 16, "acc52 term budget"\)', k)
-    # the chunk of every Barrett-window sum kernel (k_dot, k_lincomb, k_lincomb_many, k_matmul_acc, k_md_acc)
-    chunks = re.findall(r"chunk = bits >= (\d+) \? 1u? : \((\d+) - bits >= (\d+) \? (\d+)u? : \(1u? << \((\d+) - bits\)\)\)", k)
-    assert len(chunks) == 5 and len(re.findall(r"\bchunk = bits\b", k)) == 5, chunks
-    for top, room, capexp, cap, room2 in chunks:
-        room, room2 = int(room), int(room2)
-        assert room == room2
-        for bits in range(2, 63):
-            got = 1 if bits >= int(top) else (int(cap) if room - bits >= int(capexp) else 1 << (room - bits))
-            assert got == H.sum_chunk(bits), (bits, got)
+    # the chunk of every Barrett-window sum kernel: the rule is written in ONE function (lazy_sum.h lazy_chunk) over all of csrc/
+    # (bfv_tables.h's `room = 62 - bits` is the conversions' own rule, below), every such kernel calls it, and compiled for the host
+    # (tests/bsgs_emul/) it gives H.sum_chunk at the smallest and the largest modulus of every bit length
+    code = {f: re.sub(r"//[^\n]*", "", _src(f)) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc", ".hip"))}
+    rule = r"(?<!room = )62 - bits"
+    assert [f for f, text in code.items() if re.search(rule, text)] == ["lazy_sum.h"]
+    body = re.search(r"\nTFHE_HD u32 lazy_chunk\(u64 q\) \{\n(.*?)\n\}\n", code["lazy_sum.h"], re.S).group(1)
+    assert len(re.findall(rule, body)) == len(re.findall(rule, code["lazy_sum.h"])) >= 1
+    assert not any(re.search(r"\bchunk = bits\b", text) for text in code.values())
+    for f, kernel in (("kernels.h", "k_dot"), ("kernels.h", "k_lincomb"), ("kernels.h", "k_lincomb_many"), ("dot_core.h", "k_dot_view"),
+                      ("kernels.h", "k_md_acc"), ("kernels.h", "k_md_acc_dense")):
+        bodies = re.findall(r"\bvoid %s\(.*?\n\}\n" % kernel, code[f], re.S)
+        assert len(bodies) == 1 and len(re.findall(r"\bchunk = (?:\(int\))?lazy_chunk\(L\.q\);", bodies[0])) == 1, kernel
+    lazy_chunk = bsgs.load_emul(tmp_path).bsgs_emul_chunk
+    for bits in range(2, 63):
+        for q in ((1 << bits) - 1, 1 << (bits - 1)):
+            assert lazy_chunk(q) == H.sum_chunk(bits), (bits, q)
     b = _src("bfv_tables.h")
     rooms = re.findall(r"room = (\d+) - (?:max)?bits;", b)
     assert rooms == ["62", "62"], rooms

@@ -21,6 +21,7 @@
 // The words are those of tfhe_nntt followed by tfhe_mad term by term.
 #pragma once
 #include <algorithm>
+#include "lazy_sum.h"
 #include "row_core.h"
 
 // How a fused pass of n terms over `rows` (item, limb) rows is split over its terms: *tps terms per split, the number of splits
@@ -157,9 +158,7 @@ __global__ __launch_bounds__(256) void k_dot_view(dot_view_arg_t D, const u64* a
     const u32 row = blockIdx.x, j = row % (u32)sel.n;
     const size_t item = row / (u32)sel.n, off = (size_t)j * n;
     const ntt_limb_t L = LT[sel.idx[j]];
-    int bits = 0;
-    while ((L.q >> bits) != 0) bits++;
-    const int chunk = bits >= 62 ? 1 : (62 - bits >= 6 ? 64 : (1 << (62 - bits)));   // products summed between two reductions
+    const int chunk = (int)lazy_chunk(L.q);   // products summed between two reductions
     const u64* const arow = acc ? acc + item * acc_stride + off : nullptr;
     u64* const drow = dst + item * dst_stride + off;
     for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {

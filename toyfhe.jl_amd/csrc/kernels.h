@@ -6,7 +6,7 @@
 #include <type_traits>
 #include "bfv_core.h"
 #include "bfv_fast.h"
-#include "bsgs_core.h"
+#include "lazy_sum.h"
 #include "ntt_core.h"
 
 typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
@@ -1097,9 +1097,7 @@ __global__ __launch_bounds__(256) void k_dot(dot_arg_t D, const u64* __restrict_
     const u32 row = blockIdx.x, j = row % (u32)sel.n;
     const ntt_limb_t L = LT[sel.idx[j]];
     const size_t base = (size_t)row * n;
-    int bits = 0;
-    while ((L.q >> bits) != 0) bits++;
-    const int chunk = bits >= 62 ? 1 : (62 - bits >= 6 ? 64 : (1 << (62 - bits)));   // products summed between two reductions
+    const int chunk = (int)lazy_chunk(L.q);   // products summed between two reductions
     for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
         u64 r = acc ? acc[base + i] : 0;
         for (int k0 = 0; k0 < D.n; k0 += chunk) {
@@ -1120,9 +1118,7 @@ __global__ __launch_bounds__(256) void k_lincomb(dot_arg_t D, const u64* __restr
     const u32 row = blockIdx.x, j = row % (u32)sel.n;
     const ntt_limb_t L = LT[sel.idx[j]];
     const size_t base = (size_t)row * n;
-    int bits = 0;
-    while ((L.q >> bits) != 0) bits++;
-    const int chunk = bits >= 62 ? 1 : (62 - bits >= 6 ? 64 : (1 << (62 - bits)));   // products summed between two reductions
+    const int chunk = (int)lazy_chunk(L.q);   // products summed between two reductions
     for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
         u64 r = 0;
         for (int k0 = 0; k0 < D.n; k0 += chunk) {
@@ -1146,9 +1142,7 @@ __global__ __launch_bounds__(256) void k_lincomb_many(dot_arg_t D, const u64* __
     const u32 row = blockIdx.x, j = row % (u32)sel.n;
     const ntt_limb_t L = LT[sel.idx[j]];
     const size_t base = (size_t)row * n, ostride = (size_t)D.n * sel.n;
-    int bits = 0;
-    while ((L.q >> bits) != 0) bits++;
-    const int chunk = bits >= 62 ? 1 : (62 - bits >= 6 ? 64 : (1 << (62 - bits)));   // products summed between two reductions
+    const int chunk = (int)lazy_chunk(L.q);   // products summed between two reductions
     for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
         u64 r[NO];
 #pragma unroll
@@ -1168,34 +1162,6 @@ __global__ __launch_bounds__(256) void k_lincomb_many(dot_arg_t D, const u64* __
         }
 #pragma unroll
         for (int o = 0; o < NO; o++) O.dst[o][base + i] = r[o];
-    }
-}
-
-// Diagonal matrix-vector product, accumulation step: out[b][s][j] = diag[0][j] (.) X[b][s][j] + sum_r diag[r+1][j] (.) ROT[r][b][s][j]
-// (NTT domain; the loop `result += rotated_k * diagonal_k` of infer.jl:140-149 / test/ckks_matmul.jl:33-41 over all terms in
-// one pass: the canonical residues of the term-by-term sum).  diag: [R+1][limbs][N], shared by the batch.
-__global__ __launch_bounds__(256) void k_matmul_acc(const u64* __restrict__ X, const u64* __restrict__ ROT, const u64* __restrict__ diag,
-                                                     u64* __restrict__ out, const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 n,
-                                                     u32 nrot, u32 rows_per_rot) {
-    const u32 row = blockIdx.x, j = row % (u32)sel.n;   // row = (b * 2 + s) * limbs + j
-    const ntt_limb_t L = LT[sel.idx[j]];
-    const size_t base = (size_t)row * n, rstride = (size_t)rows_per_rot * n, dstride = (size_t)sel.n * n;
-    const u64* dj = diag + (size_t)j * n;
-    int bits = 0;
-    while ((L.q >> bits) != 0) bits++;
-    const u32 chunk = bits >= 62 ? 1u : (62 - bits >= 6 ? 64u : (1u << (62 - bits)));
-    for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
-        u64 r = 0;
-        for (u32 k0 = 0; k0 <= nrot; k0 += chunk) {
-            acc128 s{r, 0};
-            const u32 k1 = k0 + chunk <= nrot ? k0 + chunk : nrot + 1;
-            for (u32 k = k0; k < k1; k++) {
-                const u64 x = k == 0 ? X[base + i] : ROT[(size_t)(k - 1) * rstride + base + i];
-                acc_mac(s, x, dj[(size_t)k * dstride + i]);
-            }
-            r = barrett_reduce128(s.lo, s.hi, L.br);
-        }
-        out[base + i] = r;
     }
 }
 
@@ -2426,125 +2392,44 @@ __global__ __launch_bounds__(256) void k_md_lift(const u64* __restrict__ P, u64*
     for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x)
         d[i] = shoup_full(barrett_reduce128(s[i], 0, L.br), ra.qlinv[j], L.q);
 }
-// out rows (b, s, j) = (b * 2 + s) * level + j; diag: [R+1][level][N].  One XCD takes the two rows (b, 0, j), (b, 1, j) at a time:
-// they share the diagonal words and the permuted positions, and the V windows in flight are the two rows of ONE rotation (a
-// version that requested four rotations at a time per coefficient ran slower than the plain loop: eight windows are the whole
-// L2).  The memory parallelism comes from KB coefficients per thread instead, with rotation t + 1 requested before rotation t
-// is accumulated.
+// ------------------------------------------------------------------------------------------------
+// The accumulations of tfhe_matmul_diag and tfhe_matmul_bsgs: one family, ngiant1 sums of the same rotated values.  With
+// k = j n1 + i the diagonal product regroups into
+//     sum_j rho^(j n1)( inner_j ),   inner_j = sum_{i = 0 .. nrot} diag[j][i] (.) NTT(r_i(c))      (r_0 = identity),
+// so the rotations r_i of the baby phase feed ngiant1 = n_giant + 1 sums; tfhe_matmul_diag is ngiant1 = 1 with `inner` its output.
+// Each rotated value of a coefficient is formed once per tile of NG <= 4 giant steps and multiplied into the tile's NG sums
+// (lazy_sum.h); within a tile only the diagonal words differ.  With more than four sums the gathers, the U loads and the
+// USCALE product are repeated once per tile, out of the L2.
+//   rows (b, s, j) = (b * 2 + s) * level + j      diag: [ngiant1][nrot + 1][level][N]      inner: [ngiant1][batch][2][level][N], NTT domain
+// The outputs are tiled NG giant steps per pass with the coefficients per thread reduced to match (KB NG = TFHE_MD_KB: 2 KB NG
+// accumulators at every NG, in registers, no scratch); a ragged last tile repeats its last step unstored.
+//   k_md_acc         the evaluation-domain form, rotated value V[pi_r k] - U[k].  One XCD takes the two rows (b, 0, j), (b, 1, j) at
+//                    a time: they share the diagonal words and the permuted positions, and the V windows in flight are the two rows
+//                    of ONE rotation (a version that requested four rotations at a time per coefficient ran slower than the plain
+//                    loop: eight windows are the whole L2).  The memory parallelism comes from KB coefficients per thread instead,
+//                    with rotation t + 1 requested before rotation t is accumulated.  The tiles of a coefficient block run back to
+//                    back, so the V windows of the row pair are still in the XCD's L2 when the next tile gathers them again
+//   k_md_acc_dense   the coefficient tail (no special prime, TFHE_MD_COEFF=1): dense ROT rows, the loop
+//                    `result += rotated_k * diagonal_k` of infer.jl:140-149 / test/ckks_matmul.jl:33-41 over all terms in one pass
+//   k_bsgs_sum       out = first + sum_t rest[t], limb-wise: INTT(inner_0) and the n_giant rotated inner sums
+// ------------------------------------------------------------------------------------------------
 #ifndef TFHE_MD_KB
 #define TFHE_MD_KB 8
 #endif
 #ifndef TFHE_MD_SLOTS
 #define TFHE_MD_SLOTS 32   // workgroups per XCD (KB x SLOTS x 256 = 2^16: measured 63.7 k / 65.9 k / 66.9 k images/s at KB = 2 / 4 / 8)
 #endif
-template <bool USCALE>
-__global__ __launch_bounds__(256) void k_md_acc(const u64* __restrict__ X, const u64* __restrict__ V, const u64* __restrict__ U,
-                                                 const u64* __restrict__ diag, u64* __restrict__ out, const ntt_limb_t* __restrict__ LT,
-                                                 limb_sel_t sel, rot_tail_arg_t G, rescale_arg_t ra, u32 n, u32 nw, u32 nrot, u32 batch) {
-    constexpr int KB = TFHE_MD_KB;
-    const u32 level = (u32)sel.n;
-    const u32 xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
-    // small rows: an XCD's workgroups split into teams of n / (256 KB) workgroups, a row pair each (at N = 2^13 one team per
-    // XCD had seven of its eight coefficient lanes clamped: half of the reference-size MNIST pass)
-    const u32 per = blockDim.x * KB, spt = n / per >= nslot ? nslot : (n / per ? n / per : 1u), teams = nslot / spt, team = slot / spt, ts = slot % spt;
-    if (team >= teams) return;
-    const u32 stride = spt * blockDim.x;
-    const size_t dstride = (size_t)level * n, gstride = (size_t)batch * 2;   // diagonal stride; groups per rotation
-    struct term_t { u64 v0[KB], v1[KB], u0[KB], u1[KB], d[KB]; };
-    for (u32 pr = team * 8u + xcd; pr < batch * level; pr += 8u * teams) {
-        const u32 j = pr % level, b = pr / level;
-        const ntt_limb_t L = LT[sel.idx[j]];
-        const tw_t pinv = ra.qlinv[j];
-        int bits = 0;
-        while ((L.q >> bits) != 0) bits++;
-        const u32 chunk = bits >= 62 ? 1u : (62 - bits >= 6 ? 64u : (1u << (62 - bits)));   // products summed between two reductions
-        const size_t row0 = ((size_t)b * 2 * level + j) * n, row1 = row0 + (size_t)level * n;
-        const u64* dj = diag + (size_t)j * n;
-        for (u32 kb = ts * blockDim.x + threadIdx.x; kb < n; kb += stride * KB) {
-            u32 k[KB];
-#pragma unroll
-            for (int i = 0; i < KB; i++) k[i] = kb + (u32)i * stride < n ? kb + (u32)i * stride : kb;   // (a clamped lane repeats kb; not stored)
-            auto fetch = [&](u32 t, term_t& T) {
-                const size_t g0 = (size_t)t * gstride + (size_t)b * 2;
-                const u64 g = G.g[t];
-                const u64x2_t* pv = (const u64x2_t*)(V + epi_pair((u32)(g0 >> 1), j, 0u, nw, n));   // both components of a position: one gather
-                const u64 *pu0 = U + (g0 * level + j) * n, *pu1 = U + ((g0 + 1) * level + j) * n, *pd = dj + (size_t)(t + 1) * dstride;
-#pragma unroll
-                for (int i = 0; i < KB; i++) {
-                    const u32 kk = galois_ntt_pos(k[i], g, n);
-                    const u64x2_t vv = pv[kk];
-                    T.v0[i] = vv.x; T.v1[i] = vv.y; T.u0[i] = pu0[k[i]]; T.u1[i] = pu1[k[i]]; T.d[i] = pd[k[i]];
-                }
-            };
-            acc128 a0[KB], a1[KB];
-#pragma unroll
-            for (int i = 0; i < KB; i++) {
-                const u64 d0 = dj[k[i]];
-                a0[i] = acc128{0, 0}; a1[i] = acc128{0, 0};
-                acc_mac(a0[i], X[row0 + k[i]], d0);
-                acc_mac(a1[i], X[row1 + k[i]], d0);
-            }
-            u32 pend = 1;
-            term_t cur;
-            fetch(0, cur);
-            for (u32 t = 0; t < nrot; t++) {
-                term_t nxt;
-                fetch(t + 1 < nrot ? t + 1 : t, nxt);
-                if (pend == chunk) {
-#pragma unroll
-                    for (int i = 0; i < KB; i++) {
-                        a0[i] = acc128{barrett_reduce128(a0[i].lo, a0[i].hi, L.br), 0};
-                        a1[i] = acc128{barrett_reduce128(a1[i].lo, a1[i].hi, L.br), 0};
-                    }
-                    pend = 0;
-                }
-#pragma unroll
-                for (int i = 0; i < KB; i++) {
-                    u64 w0 = cur.u0[i], w1 = cur.u1[i];
-                    if constexpr (USCALE) { w0 = shoup_full(w0, pinv, L.q); w1 = shoup_full(w1, pinv, L.q); }
-                    acc_mac(a0[i], submod(cur.v0[i], w0, L.q), cur.d[i]);
-                    acc_mac(a1[i], submod(cur.v1[i], w1, L.q), cur.d[i]);
-                }
-                pend++;
-                cur = nxt;
-            }
-#pragma unroll
-            for (int i = 0; i < KB; i++) {
-                if (kb + (u32)i * stride < n) {
-                    out[row0 + k[i]] = barrett_reduce128(a0[i].lo, a0[i].hi, L.br);
-                    out[row1 + k[i]] = barrett_reduce128(a1[i].lo, a1[i].hi, L.br);
-                }
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// tfhe_matmul_bsgs: the accumulations with more than one output.  With k = j n1 + i the diagonal product regroups into
-//     sum_j rho^(j n1)( inner_j ),   inner_j = sum_{i = 0 .. nrot} diag[j][i] (.) NTT(r_i(c))      (r_0 = identity),
-// so the rotations r_i of the baby phase (tfhe_matmul_diag's, up to its accumulation) feed ngiant1 = n_giant + 1 sums.  Each
-// rotated value of a coefficient is formed once per tile of NG <= 4 giant steps and multiplied into the tile's NG sums
-// (bsgs_core.h); within a tile only the diagonal words differ.  With more than four sums the gathers, the U loads and the
-// USCALE product are repeated once per tile, out of the L2.
-//   diag: [ngiant1][nrot + 1][level][N]      inner: [ngiant1][batch][2][level][N], NTT domain
-// The outputs are tiled NG giant steps per pass with the coefficients per thread reduced to match (KB NG = TFHE_MD_KB: the
-// same 2 KB NG accumulators as k_md_acc, in registers, no scratch); a ragged last tile repeats its last step unstored.
-//   k_bsgs_acc         the evaluation-domain form: rotated value V[pi_r k] - U[k] as k_md_acc, same XCD-cooperative walk -- the
-//                      tiles of a coefficient block run back to back, so the V windows of the row pair are still in the XCD's L2
-//                      when the next tile gathers them again
-//   k_bsgs_acc_dense   the coefficient tail (no special prime, TFHE_MD_COEFF=1): dense ROT rows as k_matmul_acc
-//   k_bsgs_sum         out = first + sum_t rest[t], limb-wise: INTT(inner_0) and the n_giant rotated inner sums
-// ------------------------------------------------------------------------------------------------
 template <bool USCALE, int NG>
-__global__ __launch_bounds__(256) void k_bsgs_acc(const u64* __restrict__ X, const u64* __restrict__ V, const u64* __restrict__ U,
-                                                   const u64* __restrict__ diag, u64* __restrict__ inner, const ntt_limb_t* __restrict__ LT,
-                                                   limb_sel_t sel, rot_tail_arg_t G, rescale_arg_t ra, u32 n, u32 nw, u32 nrot, u32 batch,
-                                                   u32 ngiant1) {
+__global__ __launch_bounds__(256) void k_md_acc(const u64* __restrict__ X, const u64* __restrict__ V, const u64* __restrict__ U,
+                                                 const u64* __restrict__ diag, u64* __restrict__ inner, const ntt_limb_t* __restrict__ LT,
+                                                 limb_sel_t sel, rot_tail_arg_t G, rescale_arg_t ra, u32 n, u32 nw, u32 nrot, u32 batch,
+                                                 u32 ngiant1) {
     constexpr int KB = TFHE_MD_KB / NG;
     static_assert(KB >= 1 && KB * NG == TFHE_MD_KB, "the output tile divides the coefficient block");
     const u32 level = (u32)sel.n;
     const u32 xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
-    // (teams for small rows: as k_md_acc)
+    // small rows: an XCD's workgroups split into teams of n / (256 KB) workgroups, a row pair each (at N = 2^13 one team per
+    // XCD had seven of its eight coefficient lanes clamped: half of the reference-size MNIST pass)
     const u32 per = blockDim.x * KB, spt = n / per >= nslot ? nslot : (n / per ? n / per : 1u), teams = nslot / spt, team = slot / spt, ts = slot % spt;
     if (team >= teams) return;
     const u32 stride = spt * blockDim.x;
@@ -2555,7 +2440,7 @@ __global__ __launch_bounds__(256) void k_bsgs_acc(const u64* __restrict__ X, con
         const u32 j = pr % level, b = pr / level;
         const ntt_limb_t L = LT[sel.idx[j]];
         const tw_t pinv = ra.qlinv[j];
-        const u32 chunk = bsgs_lazy_chunk(L.q);
+        const u32 chunk = lazy_chunk(L.q);
         const size_t row0 = ((size_t)b * 2 * level + j) * n, row1 = row0 + (size_t)level * n;
         const u64* dj = diag + (size_t)j * n;
         for (u32 kb = ts * blockDim.x + threadIdx.x; kb < n; kb += stride * KB) {
@@ -2580,7 +2465,7 @@ __global__ __launch_bounds__(256) void k_bsgs_acc(const u64* __restrict__ X, con
                         for (int o = 0; o < NG; o++) T.d[i][o] = dg[o][dt + k[i]];
                     }
                 };
-                bsgs_sums<NG> a0[KB], a1[KB];
+                lazy_sums<NG> a0[KB], a1[KB];
 #pragma unroll
                 for (int i = 0; i < KB; i++) {
                     u64 d0[NG];
@@ -2596,14 +2481,14 @@ __global__ __launch_bounds__(256) void k_bsgs_acc(const u64* __restrict__ X, con
                 for (u32 t = 0; t < nrot; t++) {
                     term_t nxt;
                     fetch(t + 1 < nrot ? t + 1 : t, nxt);
-                    if (bsgs_fold_due(pend, chunk)) {
+                    if (lazy_fold_due(pend, chunk)) {
 #pragma unroll
                         for (int i = 0; i < KB; i++) { a0[i].fold(L.br); a1[i].fold(L.br); }
                     }
 #pragma unroll
                     for (int i = 0; i < KB; i++) {
-                        a0[i].mac(bsgs_gather_term<USCALE>(cur.v0[i], cur.u0[i], pinv, L.q), cur.d[i]);
-                        a1[i].mac(bsgs_gather_term<USCALE>(cur.v1[i], cur.u1[i], pinv, L.q), cur.d[i]);
+                        a0[i].mac(gather_term<USCALE>(cur.v0[i], cur.u0[i], pinv, L.q), cur.d[i]);
+                        a1[i].mac(gather_term<USCALE>(cur.v1[i], cur.u1[i], pinv, L.q), cur.d[i]);
                     }
                     pend++;
                     cur = nxt;
@@ -2627,20 +2512,20 @@ __global__ __launch_bounds__(256) void k_bsgs_acc(const u64* __restrict__ X, con
 }
 // rows = batch * 2 * level, row = (b * 2 + s) * level + j; ROT: [nrot][rows][N] (rows_per_rot = rows)
 template <int NG>
-__global__ __launch_bounds__(256) void k_bsgs_acc_dense(const u64* __restrict__ X, const u64* __restrict__ ROT, const u64* __restrict__ diag,
-                                                         u64* __restrict__ inner, const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 n,
-                                                         u32 nrot, u32 rows_per_rot, u32 ngiant1) {
+__global__ __launch_bounds__(256) void k_md_acc_dense(const u64* __restrict__ X, const u64* __restrict__ ROT, const u64* __restrict__ diag,
+                                                       u64* __restrict__ inner, const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 n,
+                                                       u32 nrot, u32 rows_per_rot, u32 ngiant1) {
     const u32 row = blockIdx.x, j = row % (u32)sel.n;
     const ntt_limb_t L = LT[sel.idx[j]];
     const size_t base = (size_t)row * n, rstride = (size_t)rows_per_rot * n, dstride = (size_t)sel.n * n, jstride = (size_t)(nrot + 1u) * dstride;
     const u64* dj = diag + (size_t)j * n;
-    const u32 chunk = bsgs_lazy_chunk(L.q);
+    const u32 chunk = lazy_chunk(L.q);
     for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
         for (u32 j0 = 0; j0 < ngiant1; j0 += NG) {
             const u64* dg[NG];
 #pragma unroll
             for (int o = 0; o < NG; o++) dg[o] = dj + (size_t)bsgs_tile_step(j0, (u32)o, ngiant1) * jstride + i;
-            bsgs_sums<NG> s;
+            lazy_sums<NG> s;
             s.clear();
             u32 pend = 0;
             for (u32 k = 0; k <= nrot; k++) {
@@ -2648,7 +2533,7 @@ __global__ __launch_bounds__(256) void k_bsgs_acc_dense(const u64* __restrict__ 
                 u64 d[NG];
 #pragma unroll
                 for (int o = 0; o < NG; o++) d[o] = dg[o][(size_t)k * dstride];
-                if (bsgs_fold_due(pend, chunk)) s.fold(L.br);
+                if (lazy_fold_due(pend, chunk)) s.fold(L.br);
                 s.mac(x, d);
                 pend++;
             }

@@ -1,0 +1,369 @@
+// md_api.inc -- the diagonal matrix products tfhe_matmul_diag and tfhe_matmul_bsgs: the shared rotation phase (md_plan, md_bufs,
+// md_rotations), its workspace, and the two entry points; included by toyfhe_hip.hip after ks_api.inc, whose key-sum, digit and
+// rotation helpers (ks_digits_fwd, ks_inner_launch, keyswitch_impl, ks_plan, rotate_many_ws) it calls.  Kernels: kernels.h k_md_*.
+
+// tfhe_matmul_diag, evaluation-domain form: U[grp][j] = NTT_j( [P[grp]] mod q_j ) (x P^-1 unless *scaled comes back false) for
+// the `groups` special-limb rows P (coefficient domain, canonical) and the limbs j of `sl`.  At N = 2^16 the lift rides on the
+// forward transforms' loads (ntt_io_t::lift_unsigned: k_ntt_fwd_quad for the fp64-size limbs, k_ntt_fwd_top_lift + the u64 block
+// kernels for the others) and the factor P^-1 is left to k_md_acc; otherwise k_md_lift writes the scaled lifts to `LF` and plain
+// transforms follow.
+// Whether the unsigned lift can ride on the forward transforms' loads (ntt_io_t::lift_unsigned) for these target limbs and this
+// special prime: N = 2^15 / 2^16 through the pair / quad kernels (+ top-stage lift for the u64 limbs); N <= 2^14 through
+// run_ntt's digit-lift mode -- except when every target limb is fp64-size and the special prime is not (the uniform fp64 policy
+// reads its source as one double).
+static bool md_lift_is_fused(const tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl) {
+    const int level = A.level;
+    if (level > 32 || c->logN > 16) return false;
+    if (c->logN >= 15) return c->variant == 0;
+    const bool special_fp = c->limbs_host[A.w.idx[level]].Wd != nullptr;
+    return special_fp || !sel_fp(c, sl, 0);
+}
+static int md_lift_fwd(tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl, const rescale_arg_t& ra, const u64* P, u64* LF, u64* U,
+                       int64_t groups, bool* scaled) {
+    const int level = A.level;
+    const u32 n = (u32)c->N;
+    const int64_t rows = groups * level;
+    if (LF == nullptr) {   // the caller sized the workspace for the fused form (md_lift_is_fused)
+        ntt_io_t io = io_plain();
+        io.mode = 1; io.level = 1; io.nw = (u32)level; io.polys = 1; io.lift_unsigned = 1;
+        *scaled = false;
+        if (c->logN <= 14) return run_ntt(c, false, P, U, rows, sl, &io);
+        const int x = c->logN - 14;
+        const policy_split_t ps = policy_split(c, sl);
+        const u32 tmask = ps.fpmask, tall = ps.all;   // fp64-size target limbs
+        const bool special_fp = c->limbs_host[A.w.idx[level]].Wd != nullptr;
+        if ((rows << x) > 0x7fffffffll || (((uintptr_t)P | (uintptr_t)U) & 15u) != 0) return fail(TFHE_E_BADARG, "md_lift_fwd: row count / alignment");
+        int rc;
+        void* tmp = nullptr;
+        if (tmask != tall) {   // (before the fork: growing the workspace synchronises)
+            rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
+            if (rc) return rc;
+        }
+        lanes_t lanes(c, tmask != 0 && tmask != tall);   // both kinds of limbs: side by side
+        if (tmask) {   // the fp64-size limbs: one kernel per row (pair) (ArithFpWide reads a source above 2^52 in two halves)
+            ntt_io_t a = io;
+            a.limb_mask = tmask == tall ? 0u : tmask;
+            lanes.use(1);
+            rc = run_ntt_large(c, false, P, U, rows, sl, a, &a, true, !special_fp);
+            if (rc) return rc;
+            lanes.use(0);
+        }
+        if (tmask != tall) {   // the larger limbs: lift fused into the top stages (into the transform scratch), then the u64 block kernels
+            ntt_io_t w = io;
+            w.limb_mask = tmask ? (tall & ~tmask) : 0u;
+            rc = launch_top_lift(c, P, (u64*)tmp, rows, sl, w);
+            if (rc) return rc;
+            ntt_io_t ib = io_plain();
+            ib.limb_mask = w.limb_mask;
+            rc = launch_block_fwd<ArithInt, 14>(c, (const u64*)tmp, U, rows, sl, x, ib);
+            if (rc) return rc;
+        }
+        return TFHE_OK;
+    }
+    const int rc = launch(c, k_md_lift, row_grid((unsigned)rows, (size_t)c->N), dim3(256), 0, P, LF, c->limbs_dev, sl, ra, n);
+    if (rc) return rc;
+    *scaled = true;
+    return run_ntt(c, false, LF, U, rows, sl);
+}
+
+// the bound on the per-call workspace of the diagonal products (tfhe_matmul_diag, tfhe_matmul_bsgs)
+static size_t md_ws_cap(const tfhe_ctx* c) {
+    // The keys of all R rotations are read once per chunk (2.8 GB at N = 2^16, 6 limbs + special prime, 63 rotations): a chunk as
+    // large as the memory allows (32 GiB of workspace unless TFHE_MD_WS_GIB says otherwise; halved while the allocation fails)
+    static const size_t ws_cap_env = env_gib("TFHE_MD_WS_GIB", 32);
+    // ... and never more than half of what the device has free right now (counting what this context and the allocator's cache
+    // already hold, both of which the allocation below can reuse): other contexts, BFV plans and processes keep their room
+    size_t ws_cap = ws_cap_env;
+    {
+        // (hipMemGetInfo is a driver round trip -- milliseconds in a process with many allocations -- and this call sits in the
+        // launch path of a host-bound circuit: the reading is kept for two seconds)
+        // (r05, ADVICE r04: the reading and the allocator's cached bytes are those of THIS context's device -- a process driving
+        // several GPUs computed the cap from whichever device had asked last and from the cache summed over all of them)
+        struct mi_t { size_t free_bytes = 0; std::chrono::steady_clock::time_point at{}; };
+        static std::mutex mi_mu;
+        static std::map<int, mi_t> mi_dev;
+        size_t fr = 0, tot = 0;
+        bool have = false;
+        const int cur_dev = devalloc::current_device();          // what hipMemGetInfo reads and where the workspace will be allocated
+        {
+            std::lock_guard<std::mutex> g(mi_mu);
+            mi_t& mi = mi_dev[cur_dev];
+            const auto now = std::chrono::steady_clock::now();
+            if (mi.free_bytes && now - mi.at < std::chrono::seconds(2)) { fr = mi.free_bytes; have = true; }
+            else if (hipMemGetInfo(&fr, &tot) == hipSuccess) { mi.free_bytes = fr; mi.at = now; have = true; }
+            else (void)hipGetLastError();
+        }
+        if (have) {
+            size_t cached = 0;
+            {
+                devalloc::state_t& as = devalloc::S();
+                std::lock_guard<std::mutex> g(as.mu);
+                auto it = as.devs.find(cur_dev);
+                if (it != as.devs.end()) cached = it->second.cached_bytes;
+            }
+            ws_cap = std::min(ws_cap, std::max<size_t>((fr + c->ws_bytes + cached) / 2, (size_t)1 << 30));
+        }
+    }
+    return ws_cap;
+}
+
+// The workspace of one call, [ region 0 | chunk x per_ct bytes ]: the largest chunk of the batch that md_ws_cap admits, halved
+// while the allocation fails.  region0_of(chunk) gives the bytes at the start of the context workspace that the stand-alone
+// transforms of N > 2^14 and nested calls take for themselves (ensure_ws hands out the start of whatever is allocated).
+struct md_ws_t {
+    ws_borrow_t borrow;   // a workspace above ws_keep_bytes() is this call's: back to the allocator on every return path
+    int rc = TFHE_OK;
+    int64_t chunk;
+    size_t region0 = 0;
+    void* ws = nullptr;
+    md_ws_t(tfhe_ctx* c, int64_t batch, size_t per_ct, const std::function<size_t(int64_t)>& region0_of)
+        : borrow(c), chunk(chunk_of(c, batch, 512, md_ws_cap(c), per_ct)) {
+        for (bool first_try = true;; first_try = false) {
+            region0 = region0_of(chunk);
+            const size_t need = region0 + chunk * per_ct;
+            if (first_try && need > ws_keep_bytes() && need > c->ws_bytes) borrow.begin();
+            rc = ensure_ws(c, need, &ws, borrow.active);
+            if (rc != TFHE_E_NOMEM || chunk == 1) break;
+            chunk = (chunk + 1) / 2;
+        }
+    }
+    u64* base() const { return (u64*)((char*)ws + region0); }   // the first word after region 0
+};
+
+// The rotation phase of a diagonal product -- everything up to the accumulation -- is shared by tfhe_matmul_diag and
+// tfhe_matmul_bsgs: what it consists of is decided once per call (md_plan), its buffers are laid out per chunk (md_bufs), and
+// md_rotations runs it over one chunk.
+struct md_plan_t {
+    ks_arg_t A; limb_sel_t sl; rescale_arg_t ra; rot_tail_arg_t G;
+    int Lk, level, nw, R;
+    // With a special prime the rotations are finished in the evaluation domain (k_md_*: only the special limb of every key sum is
+    // inverse-transformed); TFHE_MD_COEFF=1 keeps the coefficient-domain tail (k_ks_rot_tail) for comparisons.
+    bool eval_form;
+    bool need_lf;        // the untransformed lifts: only where the lift is not fused into the transforms' loads
+    // workspace rows (N words) per ciphertext: digits (level nw) + S / T (R 2 nw) + rotated ciphertexts (R 2 level) + the ciphertext's
+    // own transform (2 level) (+ evaluation-domain form: the lifted special limbs before their transforms (R 2 level) and the
+    // special limbs themselves (R 2))
+    size_t rows;
+    size_t ntt_rows;     // rows of the largest stand-alone transform, per ciphertext
+};
+static md_plan_t md_plan(const tfhe_ctx* c, int Lk, int level, int special, const uint64_t* galois, int R) {
+    md_plan_t P{};
+    const int nw = special ? level + 1 : level;
+    P.Lk = Lk; P.level = level; P.nw = nw; P.R = R;
+    P.A = make_ks_arg(Lk, level, special, 2);
+    P.sl = first_limbs(level);
+    if (special) {
+        special_inv_table(c, Lk, level, P.ra.qlinv);
+        std::copy(P.ra.qlinv, P.ra.qlinv + level, P.A.pinv);
+    }
+    for (int r = 0; r < R; r++) P.G.g[r] = galois[r];
+    static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
+    P.eval_form = special && R > 0 && !md_coeff;
+    P.need_lf = P.eval_form && !(md_lift_is_fused(c, P.A, P.sl) && (size_t)R * 2 * level * 4 * 512 <= 0x7fffffffull);
+    P.rows = (size_t)level * nw + (size_t)R * 2 * nw + (size_t)R * 2 * level + (size_t)2 * level +
+             (P.eval_form ? (P.need_lf ? (size_t)R * 2 * level : 0) + (size_t)R * 2 : 0);
+    P.ntt_rows = std::max<size_t>({(size_t)level * nw, (size_t)R * 2 * nw, (size_t)2 * level});
+    return P;
+}
+// ROT: the transformed rotated ciphertexts [R][nb][2][level][N], in the evaluation-domain form the lifts U of the same shape
+struct md_bufs_t { u64 *dig, *S, *ROT, *X, *LF, *PB, *end; };
+static md_bufs_t md_bufs(const md_plan_t& P, u64* base, int64_t chunk, size_t N) {
+    md_bufs_t B{};
+    const size_t R = (size_t)P.R, level = (size_t)P.level, nw = (size_t)P.nw;
+    B.dig = base;
+    B.S = B.dig + (size_t)chunk * level * nw * N;
+    B.ROT = B.S + (size_t)chunk * R * 2 * nw * N;
+    B.X = B.ROT + (size_t)chunk * R * 2 * level * N;
+    B.LF = P.need_lf ? B.X + (size_t)chunk * 2 * level * N : nullptr;   // lifted special limbs, untransformed (same shape as U)
+    B.PB = B.X + (size_t)chunk * 2 * level * N + (P.need_lf ? (size_t)chunk * R * 2 * level * N : 0);   // [R][nb][2][N]
+    B.end = base + (size_t)chunk * P.rows * N;
+    return B;
+}
+// X = NTT(cin) and, per rotation r: evaluation-domain form -- V in S (k_ks_inner<.., EPI>) and the lifts U in ROT, *scaled telling
+// whether U carries the factor P^-1 already (md_lift_fwd); otherwise NTT(rotate(gk_r, cin)) in ROT
+static int md_rotations(tfhe_ctx* c, const md_plan_t& P, const uint64_t* const* evks, const u64* cin, int64_t nb, const md_bufs_t& B, bool* scaled) {
+    const int Lk = P.Lk, level = P.level, nw = P.nw, R = P.R;
+    const u32 n = (u32)c->N;
+    int rc;
+    if (P.eval_form) {
+        const u32 groups = (u32)((int64_t)R * nb * 2);
+        rc = run_ntt(c, false, cin, B.X, nb * 2 * level, P.sl);
+        if (rc) return rc;
+        rc = ks_digits_fwd(c, P.A, cin, B.dig, nb);
+        if (rc) return rc;
+        rc = ks_inner_launch(c, P.A, Lk, nullptr, B.dig, B.S, nb, evks, R, B.X);   // limbs j < level leave as V = S' P^-1 + X0 [s = 0]
+        if (rc) return rc;
+        rc = launch(c, k_md_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, B.S, B.PB, P.G, n, (u32)nw, (u32)level, (u32)nb, groups);
+        if (rc) return rc;
+        limb_sel_t sp{};
+        sp.n = 1;
+        sp.idx[0] = Lk - 1;
+        rc = run_ntt(c, true, B.PB, B.PB, (int64_t)groups, sp);
+        if (rc) return rc;
+        return md_lift_fwd(c, P.A, P.sl, P.ra, B.PB, B.LF, B.ROT, (int64_t)groups, scaled);
+    }
+    if (R) {
+        rc = ks_digits_fwd(c, P.A, cin, B.dig, nb);
+        if (rc) return rc;
+        rc = ks_inner_launch(c, P.A, Lk, nullptr, B.dig, B.S, nb, evks, R);   // key sums of the unrotated digits against every prepared key
+        if (rc) return rc;
+        rc = run_ntt(c, true, B.S, B.S, (int64_t)R * nb * 2 * nw, P.A.w);
+        if (rc) return rc;
+        rc = launch(c, k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, B.S, cin, B.ROT, c->limbs_dev, P.A, P.ra, P.G, n, (u32)nb,
+                    (u32)((int64_t)R * nb * 2));
+        if (rc) return rc;
+        rc = run_ntt(c, false, B.ROT, B.ROT, (int64_t)R * nb * 2 * level, P.sl);
+        if (rc) return rc;
+    }
+    return run_ntt(c, false, cin, B.X, nb * 2 * level, P.sl);
+}
+
+// ---- diagonal matrix-vector product (infer.jl:140-149, test/ckks_matmul.jl:33-41) in one call ---------------------------
+// out = diag_0 (.) c + sum_r diag_{r+1} (.) rotate(gk_r, c): the hoisted rotations of tfhe_rotate_many (one digit decomposition
+// of c) with every step -- key sums, inverse transforms, automorphism + tail, forward transforms, accumulation -- run over ALL
+// rotations at once instead of rotation by rotation (R x more rows per launch: about 15 launches per product instead of
+// about 8 R + 2 R + 2), and the rotated ciphertexts never return to the caller.  Same arithmetic, term by term, as
+// rotate_many -> nntt -> dot: bit-identical results.
+int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, const uint64_t* galois,
+                     int n_rot, const uint64_t* diags, const uint64_t* ct, uint64_t* out, int64_t batch) {
+    if (!evks || !galois || !diags || n_rot < 0) return fail(TFHE_E_BADARG, "null argument");
+    if (n_rot > TFHE_DOT_MAX) return fail(TFHE_E_UNSUPPORTED, "tfhe_matmul_diag takes at most %d rotations per call", TFHE_DOT_MAX);
+    for (int r = 0; r < n_rot; r++) {
+        int rc = ks_check(c, Lk, level, special, evks[r], n_digits, ct, 2, out, batch);
+        if (!rc) rc = galois_check(c, galois[r]);
+        if (rc) return rc;
+    }
+    if (n_rot == 0) {
+        int rc = ks_check(c, Lk, level, special, diags, n_digits, ct, 2, out, batch);
+        if (rc) return rc;
+    }
+    if (batch == 0) return TFHE_OK;
+    const size_t N = (size_t)c->N;
+    const md_plan_t P = md_plan(c, Lk, level, special, galois, n_rot);
+    // region 0: the scratch of the stand-alone transforms of N > 2^14
+    const md_ws_t W(c, batch, P.rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * P.ntt_rows * N * 8 : (size_t)0; });
+    if (W.rc) return W.rc;
+    const int64_t chunk = W.chunk;
+    const md_bufs_t B = md_bufs(P, W.base(), chunk, N);
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        bool scaled = true;
+        int rc = md_rotations(c, P, evks, ct + (size_t)b0 * 2 * level * N, nb, B, &scaled);
+        if (rc) return rc;
+        u64* const o = out + (size_t)b0 * 2 * level * N;   // one sum (ngiant1 = 1), written where it belongs
+        if (P.eval_form) {
+            auto acc = scaled ? k_md_acc<false, 1> : k_md_acc<true, 1>;
+            rc = launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, B.X, B.S, B.ROT, diags, o, c->limbs_dev, P.sl, P.G, P.ra, (u32)N, (u32)P.nw,
+                        (u32)P.R, (u32)nb, 1u);
+        } else {
+            rc = launch(c, k_md_acc_dense<1>, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, B.X, B.ROT, diags, o, c->limbs_dev, P.sl,
+                        (u32)N, (u32)P.R, (u32)(nb * 2 * level), 1u);
+        }
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
+
+// ---- the same product by baby and giant steps ------------------------------------------------------------------------------
+// With the rotation index written k = j n1 + i,  sum_k d_k (.) rho^k(x) = sum_j rho^(j n1)( sum_i rho^(-j n1)(d_k) (.) rho^i(x) ):
+// n_baby + n_giant keys and key sums instead of one per diagonal; the plaintext diagonals arrive pre-rotated.
+//     inner_j = sum_{i = 0 .. n_baby} diags[j][i] (.) NTT(r_i(ct))       (r_0 = identity, r_i = rotate(baby key i - 1, .))
+//     out     = INTT(inner_0) + sum_{j = 1 .. n_giant} rotate(giant key j - 1, INTT(inner_j))
+// The baby phase is tfhe_matmul_diag's up to its accumulation (md_rotations); the accumulations with n_giant + 1 outputs are
+// k_md_acc / k_md_acc_dense, tiled; one batched inverse transform covers all inner sums; the giant rotations go through the
+// prepared-key key switch (keyswitch_impl), one per giant step over the chunk; k_bsgs_sum adds up.  Exact arithmetic on canonical
+// residues throughout: the words of tfhe_rotate_many -> tfhe_nntt -> tfhe_dot -> tfhe_inntt -> tfhe_rotate_prepared -> tfhe_add.
+//
+// The workspace the giant rotations' key switch asks for at the start of the context workspace, for `batch` ciphertexts: either
+// route a prepared-key rotation can take (ks_plan decides by the operands' addresses, which are ours and always disjoint)
+static size_t bsgs_nested_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t batch) {
+    const int nw = special ? level + 1 : level;
+    const u64* const in = (const u64*)(uintptr_t)4096;   // two disjoint, aligned ranges: never dereferenced by the plan
+    const ks_plan_t P = ks_plan(c, Lk, level, special, 2, batch, in, in + (size_t)batch * 2 * level * (size_t)c->N, 1, true, false, true);
+    const size_t tail = P.rot == KS_ROT_HOISTED ? 0 : P.bytes();
+    return std::max(tail, rotate_many_ws(c, level, nw, batch).bytes());
+}
+// the output tile: 4 giant steps per pass, fewer where there are fewer sums (log2)
+static int bsgs_log_tile(int ngiant1) { return ngiant1 >= 3 ? 2 : ngiant1 - 1; }
+int tfhe_matmul_bsgs(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby,
+                     const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant, int n_digits, const uint64_t* diags,
+                     const uint64_t* ct, uint64_t* out, int64_t batch) {
+    // host checks that need no ring first, then the context, then the ring's
+    if (!baby_evks || !baby_galois || !giant_evks || !giant_galois || !diags || !ct || !out) return fail(TFHE_E_BADARG, "null argument");
+    if (n_baby < 0 || n_baby > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_baby=%d outside [0,%d]", n_baby, TFHE_DOT_MAX);
+    if (n_giant < 0 || n_giant > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_giant=%d outside [0,%d]", n_giant, TFHE_DOT_MAX);
+    for (int r = 0; r < n_baby; r++)
+        if (!baby_evks[r]) return fail(TFHE_E_BADARG, "null baby key %d", r);
+    for (int r = 0; r < n_giant; r++)
+        if (!giant_evks[r]) return fail(TFHE_E_BADARG, "null giant key %d", r);
+    for (int r = 0; r < n_baby + n_giant; r++)
+        if (((r < n_baby ? baby_galois[r] : giant_galois[r - n_baby]) & 1) == 0) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
+    if ((const void*)out == (const void*)ct || (const void*)out == (const void*)diags) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (!c) return fail(TFHE_E_BADARG, "null context");
+    int rc = ks_check(c, Lk, level, special, diags, n_digits, ct, 2, out, batch);
+    if (rc) return rc;
+    for (int r = 0; r < n_baby + n_giant; r++)
+        if ((rc = galois_check(c, r < n_baby ? baby_galois[r] : giant_galois[r - n_baby]))) return rc;
+    const size_t N = (size_t)c->N;
+    const int ng1 = n_giant + 1;
+    const size_t ct_bytes = (size_t)batch * 2 * level * N * 8;
+    if (ranges_overlap(out, ct_bytes, ct, ct_bytes) || ranges_overlap(out, ct_bytes, diags, (size_t)ng1 * (n_baby + 1) * level * N * 8))
+        return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (batch == 0) return TFHE_OK;
+    const md_plan_t P = md_plan(c, Lk, level, special, baby_galois, n_baby);
+    // One allocation: [ region 0 | the baby phase (md_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ].
+    // Region 0 is the start of the context workspace, which the stand-alone transforms of N > 2^14 and the nested key switch
+    // take for themselves (ensure_ws hands out the start of whatever is allocated): sized for the larger of the two, so that a
+    // nested ensure_ws neither grows -- moves -- the workspace nor reaches our buffers.
+    const size_t rows = P.rows + (size_t)(ng1 + n_giant) * 2 * level, per_ct = rows * N * 8;
+    const size_t ntt_rows = std::max(P.ntt_rows, (size_t)ng1 * 2 * level);
+    const md_ws_t W(c, batch, per_ct, [&](int64_t chunk) {
+        size_t r0 = c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : 0;
+        if (n_giant) r0 = std::max(r0, bsgs_nested_bytes(c, Lk, level, special, chunk));
+        return (r0 + 255) & ~(size_t)255;
+    });
+    if (W.rc) return W.rc;
+    const int64_t chunk = W.chunk;
+    const size_t region0 = W.region0;
+    const md_bufs_t B = md_bufs(P, W.base(), chunk, N);
+    u64* const INNER = B.end;
+    u64* const GOUT = INNER + (size_t)chunk * ng1 * 2 * level * N;
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const size_t ct_words = (size_t)nb * 2 * level * N;   // one inner sum / one giant result of this chunk
+        bool scaled = true;
+        rc = md_rotations(c, P, baby_evks, ct + (size_t)b0 * 2 * level * N, nb, B, &scaled);
+        if (rc) return rc;
+        rc = dispatch_int<0, 2>(bsgs_log_tile(ng1), [&](auto lg) {
+            constexpr int NG = 1 << decltype(lg)::value;
+            if (P.eval_form) {
+                auto acc = scaled ? k_md_acc<false, NG> : k_md_acc<true, NG>;
+                return launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, B.X, B.S, B.ROT, diags, INNER, c->limbs_dev, P.sl, P.G, P.ra, (u32)N,
+                              (u32)P.nw, (u32)P.R, (u32)nb, (u32)ng1);
+            }
+            return launch(c, k_md_acc_dense<NG>, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, B.X, B.ROT, diags, INNER, c->limbs_dev,
+                          P.sl, (u32)N, (u32)P.R, (u32)(nb * 2 * level), (u32)ng1);
+        });
+        if (rc) return rc;
+        rc = run_ntt(c, true, INNER, INNER, (int64_t)ng1 * nb * 2 * level, P.sl);
+        if (rc) return rc;
+        // What the nested key switch will ask for, from its own plan on the real operands: it must stay inside region 0.  The plan of
+        // the first giant step stands for all of them: it depends on the operands only through their disjointness and 16-byte
+        // alignment, and step j reads INNER + j ct_words and writes GOUT + (j - 1) ct_words -- disjoint ranges of one allocation, every
+        // offset a multiple of 8 N bytes from a 256-byte aligned base -- and on the Galois element only for what it writes into the plan.
+        if (n_giant) {
+            const ks_plan_t Q = ks_plan(c, Lk, level, special, 2, nb, INNER + ct_words, GOUT, giant_galois[0], true, false, true);
+            const size_t nested = Q.rot == KS_ROT_HOISTED ? rotate_many_ws(c, level, P.nw, nb).bytes() : Q.bytes();
+            if (nested > region0) return fail(TFHE_E_UNSUPPORTED, "internal: the nested key switch needs %zu bytes, region 0 holds %zu", nested, region0);
+        }
+        for (int j = 1; j <= n_giant; j++) {   // (the nested call finds the workspace large enough: same block, region 0)
+            rc = keyswitch_impl(c, Lk, level, special, giant_evks[j - 1], INNER + (size_t)j * ct_words, 2, GOUT + (size_t)(j - 1) * ct_words, nb,
+                                giant_galois[j - 1], true, false, true);
+            if (rc) return rc;
+        }
+        rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)INNER, (const u64*)GOUT,
+                    out + (size_t)b0 * 2 * level * N, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}

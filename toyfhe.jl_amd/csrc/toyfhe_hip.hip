@@ -8,6 +8,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -1022,6 +1023,7 @@ int tfhe_galois(tfhe_ctx* c, const uint64_t* src, uint64_t* dst, uint64_t g, int
 }
 
 #include "ks_api.inc"
+#include "md_api.inc"
 
 // ---- CKKS encode / decode (float; ckksencoding.jl:56-97, ckks.jl:35-59) -------------------------------------------
 static int ckks_tables(tfhe_ctx* c) {
