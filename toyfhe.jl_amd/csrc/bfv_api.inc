@@ -15,6 +15,10 @@ struct tfhe_bfv_plan {
     int fast_ns = 0, fast_np = 0;
     bool fast_narrow = false;  // all moduli below TFHE_FP_QMAX: the 26-bit-split / fp64 bodies (kernels specialised on it)
     bool use_fast = true;
+    // narrow fast path: ℛbig's limb table with the contraction's per-limb input constants folded into the closing scaling of the
+    // inverse transform (bfv_fold_kappa, bfv_tables.h).  Read by k_bfv_core_fused<.., OUTD> of this plan's multiplications only,
+    // whose rows go to k_bfv_contract_fast<.., FOLDED>; the context's own table is never changed.
+    ntt_limb_t* fold_dev = nullptr;
     hipEvent_t order_ev = nullptr;  // cross-stream ordering when ℛ and ℛbig live in contexts with different streams
 };
 
@@ -76,13 +80,14 @@ bool fast_has(int ns, int np) {
 }
 // lift_c2 (contraction of products, count = 3 * ciphertexts): c2 leaves as centred doubles for the fused key switch
 // t_double (contraction, narrow bodies): the input rows are reduced doubles (k_bfv_core_fused<.., OUTD>)
+// folded (with t_double): the rows also carry the per-limb input constants (k_bfv_core_fused run on the plan's folded limb table)
 int launch_fast(tfhe_bfv_plan* p, bool contract, const u64* src, u64* dst, int64_t count, bool copy_shared = true, bool lift_c2 = false,
-                bool t_double = false) {
+                bool t_double = false, bool folded = false) {
     const u32 n = (u32)p->big->N;
     const unsigned gx = (n + 255) / 256;
     const dim3 grid(gx * (unsigned)count);
     const bool lift3 = contract && lift_c2 && p->fast_narrow && count % 3 == 0;
-    if (t_double && !(contract && p->fast_narrow)) return fail(TFHE_E_UNSUPPORTED, "internal: double-valued tensor rows need the narrow contraction");
+    if ((t_double && !(contract && p->fast_narrow)) || (folded && !t_double)) return fail(TFHE_E_UNSUPPORTED, "internal: double-valued tensor rows need the narrow contraction");
     tfhe_ctx* const c = p->big;   // the conversions run on the stream of the big ring's context
 #define X(S, P_)                                                                                                          \
     if (p->fast_ns == S && p->fast_np == P_) {                                                                            \
@@ -90,7 +95,9 @@ int launch_fast(tfhe_bfv_plan* p, bool contract, const u64* src, u64* dst, int64
             auto ek = p->fast_narrow ? k_bfv_expand_fast<S, P_, true> : k_bfv_expand_fast<S, P_, false>;                  \
             return launch(c, ek, grid, dim3(256), 0, src, dst, p->fast_dev, n, gx, copy_shared ? 1 : 0);                  \
         }                                                                                                                 \
-        auto ck = lift3 && t_double ? k_bfv_contract_fast<S, P_, true, true, true>                                        \
+        auto ck = lift3 && folded   ? k_bfv_contract_fast<S, P_, true, true, true, true>                                  \
+                  : folded          ? k_bfv_contract_fast<S, P_, true, false, true, true>                                 \
+                  : lift3 && t_double ? k_bfv_contract_fast<S, P_, true, true, true>                                      \
                   : t_double        ? k_bfv_contract_fast<S, P_, true, false, true>                                       \
                   : lift3           ? k_bfv_contract_fast<S, P_, true, true>                                              \
                   : p->fast_narrow  ? k_bfv_contract_fast<S, P_, true>                                                    \
@@ -110,9 +117,9 @@ int launch_expand(tfhe_bfv_plan* p, const u64* src, u64* dst, int64_t count) {
     const size_t lds = (size_t)std::max(p->tab.nb, p->tab.ns) * BFV_BS * 8;
     return launch(p->big, k_bfv_expand, dim3(gx * (unsigned)count), dim3(BFV_BS), lds, src, dst, p->tab_dev, n, gx);
 }
-int launch_contract(tfhe_bfv_plan* p, const u64* src, u64* dst, int64_t count, bool lift_c2 = false, bool t_double = false) {
+int launch_contract(tfhe_bfv_plan* p, const u64* src, u64* dst, int64_t count, bool lift_c2 = false, bool t_double = false, bool folded = false) {
     if (count == 0) return TFHE_OK;
-    if (p->fast_dev && p->use_fast) return launch_fast(p, true, src, dst, count, true, lift_c2, t_double);
+    if (p->fast_dev && p->use_fast) return launch_fast(p, true, src, dst, count, true, lift_c2, t_double, folded);
     if (t_double) return fail(TFHE_E_UNSUPPORTED, "internal: double-valued tensor rows need the narrow contraction");
     if (lift_c2) return fail(TFHE_E_UNSUPPORTED, "internal: lifted output needs the narrow fast path");
     const u32 n = (u32)p->big->N;
@@ -129,7 +136,7 @@ int bfv_mul_chunk(tfhe_bfv_plan* p, const u64* c1, const u64* c2, u64* out3, int
     u64* E2 = E + (size_t)nct * 2 * nb * N;
     int rc;
     bool fused = false;  // transforms + tensor in one kernel (one scratch row per workgroup)
-    bool t_double = false;
+    bool t_double = false, folded = false;
     if (p->fast_dev && p->use_fast && bfv_core_fusable(p->big, p->sel_b)) {
         // the limbs ℛbig shares with ℛ are not copied by the expansion: the fused core reads them from the inputs
         core_alt_t alt{};
@@ -140,9 +147,11 @@ int bfv_mul_chunk(tfhe_bfv_plan* p, const u64* c1, const u64* c2, u64* out3, int
         if (!rc) rc = launch_fast(p, false, c2, E2, nct * 2, false);
         if (rc) return rc;
         t_double = p->fast_narrow;   // the narrow contraction takes the tensor rows as reduced doubles (6 instructions fewer per word)
-        rc = launch_bfv_core_fused(p->big, E1, E2, T, scratch, nct, p->sel_b, &fused, &alt, t_double);
+        // ... and, through the plan's limb table, already multiplied by the contraction's per-limb input constants
+        folded = t_double && p->fold_dev != nullptr;
+        rc = launch_bfv_core_fused(p->big, E1, E2, T, scratch, nct, p->sel_b, &fused, &alt, t_double, folded ? p->fold_dev : nullptr);
         if (rc) return rc;
-        if (!fused) t_double = false;
+        if (!fused) t_double = folded = false;   // (nothing was launched: the unfused route below runs on the context's table)
     } else {
         rc = launch_expand(p, c1, E1, nct * 2);            // mul_expand, bfv.jl:34
         if (rc) return rc;
@@ -159,7 +168,7 @@ int bfv_mul_chunk(tfhe_bfv_plan* p, const u64* c1, const u64* c2, u64* out3, int
         rc = run_ntt(p->big, true, T, T, nct * 3 * nb, p->sel_b);
         if (rc) return rc;
     }
-    return launch_contract(p, T, out3, nct * 3, lift_c2, t_double);  // mul_contract, bfv.jl:35-40 (c2 as centred doubles when relinearised next)
+    return launch_contract(p, T, out3, nct * 3, lift_c2, t_double, folded);  // mul_contract, bfv.jl:35-40 (c2 as centred doubles when relinearised next)
 }
 
 }  // namespace
@@ -206,6 +215,14 @@ int tfhe_bfv_plan_create(tfhe_ctx* small, const int32_t* idx_s, int ns, tfhe_ctx
                 hipMemcpy(p->fast_dev, &T, sizeof T, hipMemcpyHostToDevice);
                 p->fast_ns = T.ns; p->fast_np = T.np; p->fast_narrow = T.narrow != 0;
             }
+            if (!rc && p->fast_narrow) {
+                std::vector<ntt_limb_t> LT = big->limbs_host;   // (device pointers inside: the transform tables are the context's)
+                u64 kappa[TFHE_FAST_MAX * 2];
+                bfv_fold_kappa(T, kappa);
+                for (int l = 0; l < nb; l++) bfv_fold_limb(&LT[p->sel_b.idx[l]], kappa[l]);
+                if (devalloc::malloc_retry(&p->fold_dev, LT.size() * sizeof(ntt_limb_t)) != hipSuccess) rc = fail(TFHE_E_HIP, "hipMalloc failed");
+                else hipMemcpy(p->fold_dev, LT.data(), LT.size() * sizeof(ntt_limb_t), hipMemcpyHostToDevice);
+            }
         }
         delete F;
         if (rc) { tfhe_bfv_plan_destroy(p); return rc; }
@@ -224,6 +241,7 @@ int tfhe_bfv_plan_destroy(tfhe_bfv_plan* p) {
     for (void* d : p->allocs) hipFree(d);
     if (p->tab_dev) hipFree(p->tab_dev);
     if (p->fast_dev) hipFree(p->fast_dev);
+    if (p->fold_dev) hipFree(p->fold_dev);
     if (p->ws) hipFree(p->ws);
     delete p;
     return TFHE_OK;
@@ -280,6 +298,17 @@ static int bfv_mul_impl(tfhe_bfv_plan* p, const u64* evk, int n_digits, const u6
     u64* T = E + (size_t)chunk * 4 * nb * N;
     u64* R = T + (size_t)chunk * 3 * nb * N;
     u64* SCR = R + (relin ? (size_t)chunk * 3 * ns * N : 0);
+    // keyswitch(evk, c) on ℛ with RNS digits, rlwe_she.jl:315-347 (relin_window == 0).  The key is an argument of the call: it is
+    // prepared (converted to doubles on the fused paths) once, for the largest chunk, and every chunk runs on that preparation --
+    // where ℛ's context workspace, which holds the prepared key, is nobody else's between the chunks.  The plan's own workspace
+    // (plan_ws) shares nothing with it; what does take it is a stand-alone transform of N > 2^14 (run_ntt_large) in
+    // bfv_mul_chunk's unfused route when ℛbig lives in ℛ's context: there every chunk prepares for itself, as before.
+    const bool key_once = p->small != p->big || p->big->logN <= 14;
+    ks_prepared_t K;
+    if (relin && key_once && batch > 0) {
+        rc = ks_prepare(p->small, ns, ns, 0, evk, R, 3, out, chunk, 0, false, prelift, false, &K);
+        if (rc) return rc;
+    }
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nct = std::min(chunk, batch - b0);
         const u64* a = c1 + (size_t)b0 * 2 * ns * N;
@@ -293,8 +322,9 @@ static int bfv_mul_impl(tfhe_bfv_plan* p, const u64* evk, int n_digits, const u6
             rc = bfv_mul_chunk(p, a, b, R, nct, E, T, SCR, prelift);
             if (!rc) rc = stream_order(p, p->big, p->small);
             if (rc) return rc;
-            // keyswitch(evk, c) on ℛ with RNS digits, rlwe_she.jl:315-347 (relin_window == 0)
-            rc = keyswitch_impl(p->small, ns, ns, 0, evk, R, 3, out + (size_t)b0 * 2 * ns * N, nct, 0, false, prelift);
+            u64* const o = out + (size_t)b0 * 2 * ns * N;
+            if (!key_once) rc = ks_prepare(p->small, ns, ns, 0, evk, R, 3, o, nct, 0, false, prelift, false, &K);
+            if (!rc) rc = ks_run(p->small, K, R, o, nct);
             if (rc) return rc;
         }
     }

@@ -155,6 +155,9 @@ struct bfv_fast_tab_t {
     // exact-alpha tables (word arrays in global memory)
     const u64 *Mq, *Aq, *Mp, *Ap;
     int nwq, nwp;
+    // FOLDED contraction (bfv_contract_narrow): the tensor rows arrive multiplied by kappa -- c_a1[i] on an ℛ-limb, c_a2[j] 2^78 on a
+    // P-limb -- through the plan's copy of the transform's limb table (bfv_fold_kappa, bfv_tables.h)
+    double f_pcb[TFHE_FAST_MAX];                        // p_j + n_cB2[j]: the P-limb input y'' enters lane s0 as y'' + p_j + n_cB2[j]
 };
 
 template <int K, bool NARROW>
@@ -264,16 +267,63 @@ TFHE_HD double fp_affine(u64 x, double a, double b, double p, double pinv) {
 // v_mad_u64_u32 in the contraction's second conversion)
 struct split26 {
     u32 lo, hi;
+    u32 sum;  // lo + hi, formed once per operand: the multiplier of the middle lane of every three-product sum the operand enters (0 where
+              // the sums take four products)
 };
+template <bool K3 = true>
 TFHE_HD split26 split_of(u64 x) {
-    split26 r{(u32)x & 0x3ffffffu, (u32)(x >> 26)};
+    split26 r{(u32)x & 0x3ffffffu, (u32)(x >> 26), 0};
+    if constexpr (K3) r.sum = r.lo + r.hi;
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm("" : "+v"(r.lo), "+v"(r.hi));  // opaque (NOT volatile: a volatile asm orders every load around it and serialises the kernel): the halves are what the products see, not the 64-bit word
+    // opaque (NOT volatile: a volatile asm orders every load around it and serialises the kernel): the halves are what the products see, not the 64-bit word
+    if constexpr (K3) asm("" : "+v"(r.lo), "+v"(r.hi), "+v"(r.sum));
+    else asm("" : "+v"(r.lo), "+v"(r.hi));
 #endif
     return r;
 }
 TFHE_HD u64 join_of(split26 x) { return ((u64)x.hi << 26) | x.lo; }
-TFHE_HD void acc52_macs(acc52& a, split26 x, u64 cpacked) { acc52_mac(a, x.lo, x.hi, (u32)cpacked, (u32)(cpacked >> 32)); }
+// The product sums of the narrow bodies.  K3: THREE products per term instead of acc52_mac's four -- the lanes s0 = Σ x0 c0 and
+// s2 = Σ x1 c1 as before, and m = Σ (x0 + x1)(c0 + c1), from which the middle lane of the WHOLE sum follows once per output,
+// s1 = m - s0 - s2 (psum_close).  x0 + x1 comes with the operand (split26::sum); c0 + c1 is formed from the packed constant --
+// workgroup-uniform, so one scalar add -- and needs no table.  s0 and m both start from the plain addend `init` of the sum, which
+// cancels in the difference.  Ranges: operands are residues below TFHE_FP_QMAX, x0 + x1 < 2^26 + 2^24 + 2^14, and so are the
+// constants; a product is below 2^52.7 and init (< 2^52) + 16 of them below 2^57: no lane wraps, the difference is the exact
+// middle lane, and the three lanes handed to acc52_redc are the integers acc52_mac would have left (its bounds, modarith.h, stand
+// as they are).  !K3: m is acc52's s1 and a term is acc52_mac -- the form of the contraction on UNfolded rows (the public
+// tfhe_bfv_contract, the unfused route), where a third register per operand costs two resident waves per SIMD (70 -> 84-88
+// VGPRs), and of the expansion, which runs at the copy rate with either form.
+template <bool K3>
+struct psum {
+    u64 s0, m, s2;
+};
+template <bool K3>
+TFHE_HD psum<K3> psum_init(u64 init) { return psum<K3>{init, K3 ? init : 0, 0}; }
+template <bool K3>
+TFHE_HD void psum_mac(psum<K3>& a, split26 x, u64 cpacked) {
+    const u32 c0 = (u32)cpacked, c1 = (u32)(cpacked >> 32);
+    if constexpr (K3) {
+        a.s0 += (u64)x.lo * c0;
+        a.s2 += (u64)x.hi * c1;
+        a.m += (u64)x.sum * (c0 + c1);
+    } else {   // acc52_mac
+        a.s0 += (u64)x.lo * c0;
+        a.m += (u64)x.lo * c1;
+        a.m += (u64)x.hi * c0;
+        a.s2 += (u64)x.hi * c1;
+    }
+}
+template <bool K3>
+TFHE_HD acc52 psum_close(const psum<K3>& a) { return acc52{a.s0, K3 ? a.m - a.s0 - a.s2 : a.m, a.s2}; }
+#if defined(TFHE_EMUL_TRACK_NARROW) && !defined(__HIP_DEVICE_COMPILE__)
+// CPU emulation only: the largest value of each lane (s0, s1, s2, and psum's m) that ever reached acc52_redc, and how often a
+// conversion out of K limbs took the exact-alpha decision (the including file defines g_narrow_lane_max[4] and
+// g_narrow_exact_hits[TFHE_FAST_MAX + 1])
+#define TFHE_NARROW_LANES(a, kk) do { const u64 l_[4] = {(a).s0, (a).s1, (a).s2, (kk)}; for (int t_ = 0; t_ < 4; t_++) if (l_[t_] > g_narrow_lane_max[t_]) g_narrow_lane_max[t_] = l_[t_]; } while (0)
+#define TFHE_NARROW_EXACT_HIT(K) ((void)g_narrow_exact_hits[K]++)
+#else
+#define TFHE_NARROW_LANES(a, kk) ((void)0)
+#define TFHE_NARROW_EXACT_HIT(K) ((void)0)
+#endif
 // small multiplier (the alpha counts, < 2^26): two partial products
 TFHE_HD void acc52_mac_small(acc52& a, u32 x, u64 cpacked) {
     a.s0 += (u64)x * (u32)cpacked;
@@ -292,6 +342,7 @@ TFHE_HD u32 conv_alpha_fp(const double (&xd)[K], const split26 (&xs)[K], const d
     const double fl = __builtin_floor(s), f = s - fl;
     u32 n = (u32)fl;
     if (!(f > 0x1p-40 && f < 1.0 - 0x1p-40)) {  // rare: the words go through the scratch column to the rolled exact decision
+        TFHE_NARROW_EXACT_HIT(K);
 #pragma unroll
         for (int j = 0; j < K; j++) col[(size_t)j * cstride] = join_of(xs[j]);
         if (f <= 0x1p-40) n = n == 0 ? 0u : conv_alpha_exact_col(K, col, cstride, M, Aw, nwords, n - 1);
@@ -304,6 +355,8 @@ template <int NS, int NP>
 TFHE_HD void bfv_expand_narrow(const bfv_fast_tab_t& B, const u64* src, size_t ls, u64* dst, size_t ld, u64* col, int cstride,
                                bool copy_shared = true) {
     static_assert(NS + 2 <= 16 && NP + 2 <= 16, "acc52 term budget");
+    // (four-product sums: the three-product form took 6.5 % of this kernel's instructions and none of its time -- it runs at the
+    // copy rate, profiles/LOG.md)
     u64 x[NS];
     split26 xs[NS];
     double xd[NS];
@@ -311,7 +364,7 @@ TFHE_HD void bfv_expand_narrow(const bfv_fast_tab_t& B, const u64* src, size_t l
     for (int i = 0; i < NS; i++) {
         x[i] = src[(size_t)i * ls];
         xd[i] = fp_affine(x[i], B.f_ea[i], B.f_eb[i], B.f_q[i], B.f_qinv[i]);
-        xs[i] = split_of(fp_to_u64(xd[i]));
+        xs[i] = split_of<false>(fp_to_u64(xd[i]));
     }
     const u32 alpha = conv_alpha_fp<NS>(xd, xs, B.f_qinv, B.Mq, B.Aq, B.nwq, col, cstride);
     if (copy_shared) {
@@ -320,10 +373,12 @@ TFHE_HD void bfv_expand_narrow(const bfv_fast_tab_t& B, const u64* src, size_t l
     }
 #pragma unroll
     for (int j = 0; j < NP; j++) {  // output-major: the constants of output j are one contiguous row
-        acc52 a{B.n_eNegHalf[j], 0, 0};
+        psum<false> ak = psum_init<false>(B.n_eNegHalf[j]);
 #pragma unroll
-        for (int i = 0; i < NS; i++) acc52_macs(a, xs[i], B.t_eC[j][i]);
+        for (int i = 0; i < NS; i++) psum_mac(ak, xs[i], B.t_eC[j][i]);
+        acc52 a = psum_close(ak);
         acc52_mac_small(a, alpha, B.n_eNegA[j]);
+        TFHE_NARROW_LANES(a, ak.m);
         dst[(size_t)B.pos_p[j] * ld] = acc52_redc(a, B.mp[j]);
     }
 }
@@ -351,22 +406,37 @@ TFHE_HD double fp_affine_d(double y, double a, double b, double p, double pinv) 
 // TD: the inputs are reduced doubles y (bit patterns, |y| <= p/2 + 1) instead of canonical words -- the form
 // k_bfv_core_fused<.., OUTD> leaves its result rows in.  ℛ-limbs go straight into the fp64 affine map; a P-limb enters its
 // product sum as the non-negative integer y + p (< 1.5 p + 1: within the 26-bit-split budget, and congruent).
-template <int NS, int NP, bool TD = false>
+// FOLDED (implies TD): the producer has already multiplied every row by its per-limb input constant -- the transform's closing
+// scaling by N^-1 went through the plan's copy of the limb table, whose constants carry kappa (bfv_fold_kappa, bfv_tables.h):
+//   ℛ-limb i: y' = y c_a1[i] mod q_i, so ξ_i = y' + c_b1[i] reduced to [0, q_i): no product.  Range: the last-stage product of
+//             the transform reduces whatever its constant, |y'| <= q_i/2 + 1; with 0 <= c_b1 < q_i, |v| < 1.5 q_i + 1, which
+//             fp_reduce takes (exact far beyond it: |v| < 2^53), leaving |r| <= q_i/2 and r + q_i < q_i for r < 0.
+//   P-limb j: y'' = y c_a2[j] 2^78 mod p_j, so y'' + p_j (>= p_j/2 - 1 > 0) is a non-negative integer congruent to the old term
+//             (y + p_j) n_cA2[j]; it enters lane s0 as it is, together with n_cB2[j] (f_pcb = p_j + n_cB2[j]: the sum is an exact
+//             integer below 2.5 p_j + 1 < 2^52), with no split and no n_cA2 term.  acc52_redc divides the 2^78 out.
+template <int NS, int NP, bool TD = false, bool FOLDED = false>
 TFHE_HD void bfv_contract_narrow(const bfv_fast_tab_t& B, const u64* src, size_t ls, u64* dst, size_t ld, u64* col, int cstride,
                                  bool lifted_out = false) {
+    static_assert(TD || !FOLDED, "the folded rows are reduced doubles");
+    constexpr bool K3 = FOLDED;   // three-product sums (psum) on the folded route; the unfolded forms keep their four products and registers
     split26 xs[NS];
     double xd[NS];
 #pragma unroll
     for (int i = 0; i < NS; i++) {  // ξ_i of r = (t y + h) mod q
         const u64 w = src[(size_t)B.pos_s[i] * ls];
-        if constexpr (TD) {
+        if constexpr (FOLDED) {
+            double y;
+            __builtin_memcpy(&y, &w, 8);
+            const double r = fp_reduce(y + B.f_cb[i], B.f_q[i], B.f_qinv[i]);
+            xd[i] = r < 0.0 ? r + B.f_q[i] : r;
+        } else if constexpr (TD) {
             double y;
             __builtin_memcpy(&y, &w, 8);
             xd[i] = fp_affine_d(y, B.f_ca[i], B.f_cb[i], B.f_q[i], B.f_qinv[i]);
         } else {
             xd[i] = fp_affine(w, B.f_ca[i], B.f_cb[i], B.f_q[i], B.f_qinv[i]);
         }
-        xs[i] = split_of(fp_to_u64(xd[i]));
+        xs[i] = split_of<K3>(fp_to_u64(xd[i]));
     }
     const u32 a1 = conv_alpha_fp<NS>(xd, xs, B.f_qinv, B.Mq, B.Aq, B.nwq, col, cstride);
     split26 xps[NP];
@@ -374,28 +444,39 @@ TFHE_HD void bfv_contract_narrow(const bfv_fast_tab_t& B, const u64* src, size_t
     // ξ'_j of w + floor(P/2) in basis P: one product-sum and one reduction per limb, output-major
 #pragma unroll
     for (int j = 0; j < NP; j++) {
-        acc52 a{B.n_cB2[j], 0, 0};
+        psum<K3> ak;
         u64 yp = src[(size_t)B.pos_p[j] * ls];
-        if constexpr (TD) {
+        if constexpr (FOLDED) {
             double y;
             __builtin_memcpy(&y, &yp, 8);
-            yp = fp_to_u64(y + B.f_p[j]);
+            ak = psum_init<K3>(fp_to_u64(y + B.f_pcb[j]));
+        } else {
+            if constexpr (TD) {
+                double y;
+                __builtin_memcpy(&y, &yp, 8);
+                yp = fp_to_u64(y + B.f_p[j]);
+            }
+            ak = psum_init<K3>(B.n_cB2[j]);
+            psum_mac(ak, split_of<K3>(yp), B.n_cA2[j]);
         }
-        acc52_macs(a, split_of(yp), B.n_cA2[j]);
 #pragma unroll
-        for (int i = 0; i < NS; i++) acc52_macs(a, xs[i], B.t_cNegC1[j][i]);
+        for (int i = 0; i < NS; i++) psum_mac(ak, xs[i], B.t_cNegC1[j][i]);
+        acc52 a = psum_close(ak);
         acc52_mac_small(a, a1, B.n_cA1[j]);
+        TFHE_NARROW_LANES(a, ak.m);
         const u64 xpj = acc52_redc(a, B.mp[j]);
-        xps[j] = split_of(xpj);
+        xps[j] = split_of<K3>(xpj);
         xpd[j] = fp_from_u64(xpj);
     }
     const u32 a2 = conv_alpha_fp<NP>(xpd, xps, B.f_pinv, B.Mp, B.Ap, B.nwp, col, cstride);
 #pragma unroll
     for (int i = 0; i < NS; i++) {
-        acc52 a{B.n_cNegHalf[i], 0, 0};
+        psum<K3> ak = psum_init<K3>(B.n_cNegHalf[i]);
 #pragma unroll
-        for (int j = 0; j < NP; j++) acc52_macs(a, xps[j], B.t_cC2[i][j]);
+        for (int j = 0; j < NP; j++) psum_mac(ak, xps[j], B.t_cC2[i][j]);
+        acc52 a = psum_close(ak);
         acc52_mac_small(a, a2, B.n_cNegA2[i]);
+        TFHE_NARROW_LANES(a, ak.m);
         const u64 r = acc52_redc(a, B.mq[i]);
         dst[(size_t)i * ld] = lifted_out ? centred_double_bits(r, join_of(split26{B.mq[i].pl, B.mq[i].ph})) : r;
     }

@@ -217,6 +217,7 @@ inline bool build_bfv_fast_host(const std::vector<u64>& qs, const std::vector<u6
             B.n_cA2[j] = pack26(fold(B.c_a2[j].w, pj));
             B.n_cA1[j] = pack26(fold(B.c_A1[j], pj));
             B.n_cB2[j] = fold(B.c_b2[j], pj);
+            B.f_pcb[j] = (double)(pj + B.n_cB2[j]);   // < 2 p < 2^52: exact
             for (int i = 0; i < ns; i++) {
                 B.n_eC[i][j] = pack26(fold(B.e_C[i][j], pj));
                 B.n_cNegC1[i][j] = pack26(fold(neg(B.c_C1[i][j], pj), pj));
@@ -243,4 +244,20 @@ inline bool build_bfv_fast_host(const std::vector<u64>& qs, const std::vector<u6
     H->Ap.assign(Pb.begin(), Pb.end());
     B.Mq = H->Mq.data(); B.Aq = H->Aq.data(); B.Mp = H->Mp.data(); B.Ap = H->Ap.data();
     return true;
+}
+// The folded contraction (bfv_contract_narrow<.., FOLDED>) takes rows that their producer has multiplied by kappa[l], l a limb of
+// ℛbig in buffer order: c_a1[i] = t (q/q_i)^-1 mod q_i on ℛ-limb i, c_a2[j] 2^78 mod p_j on P-limb j (the 2^78 is what acc52_redc
+// divides out again).  The producer is the last stage of the inverse transform, which multiplies every output by N^-1 (or
+// Winv[1] N^-1) anyway: `fold` scales those two constants of a limb's table entry -- the fp64 pair, the only ones the fp64 kernels
+// read (ArithFp::make); the u64 twins stay.  Narrow tables only.
+inline void bfv_fold_kappa(const bfv_fast_tab_t& B, u64* kappa) {
+    using namespace hostmath;
+    for (int i = 0; i < B.ns; i++) kappa[B.pos_s[i]] = B.c_a1[i].w;
+    for (int j = 0; j < B.np; j++) kappa[B.pos_p[j]] = mulmod_slow(B.c_a2[j].w, powmod(2, TFHE_MONT26_RBITS, B.pb[j].q), B.pb[j].q);
+}
+template <class LIMB>
+inline void bfv_fold_limb(LIMB* L, u64 kappa) {
+    using namespace hostmath;
+    L->ninv_d.w = (double)mulmod_slow(L->ninv.w, kappa, L->q);
+    L->w1inv_ninv_d.w = (double)mulmod_slow(L->w1inv_ninv.w, kappa, L->q);
 }

@@ -2733,7 +2733,8 @@ __global__ __launch_bounds__(256) void k_bfv_expand_fast(const u64* __restrict__
 // LIFT3 (narrow bodies, products: three polynomials per ciphertext): every third polynomial (c2) leaves as centred doubles
 // for the fused key switch (bfv_contract_narrow, lifted_out: workgroup-uniform).
 // TD (narrow bodies): the input rows are reduced doubles (k_bfv_core_fused<.., OUTD>) instead of canonical words
-template <int NS, int NP, bool NARROW, bool LIFT3 = false, bool TD = false>
+// FOLDED (implies TD): the rows also carry the contraction's per-limb input constants (the plan's folded limb table, bfv_api.inc)
+template <int NS, int NP, bool NARROW, bool LIFT3 = false, bool TD = false, bool FOLDED = false>
 __global__ __launch_bounds__(256) void k_bfv_contract_fast(const u64* __restrict__ src, u64* __restrict__ dst,
                                                             const bfv_fast_tab_t* __restrict__ Bt, u32 n, u32 gx) {
     const u32 k = (blockIdx.x % gx) * 256 + threadIdx.x;
@@ -2742,7 +2743,7 @@ __global__ __launch_bounds__(256) void k_bfv_contract_fast(const u64* __restrict
     if (k >= n) return;
     if constexpr (NARROW) {
         __shared__ u64 col[(NS > NP ? NS : NP) * 256];  // scratch column of the rare exact-alpha decision (bfv_fast.h conv_alpha_fp)
-        bfv_contract_narrow<NS, NP, TD>(*Bt, src + p * (NS + NP) * n + k, n, dst + p * NS * n + k, n, col + threadIdx.x, 256, LIFT3 && b % 3u == 2u);
+        bfv_contract_narrow<NS, NP, TD, FOLDED>(*Bt, src + p * (NS + NP) * n + k, n, dst + p * NS * n + k, n, col + threadIdx.x, 256, LIFT3 && b % 3u == 2u);
     } else {
         bfv_contract_fast<NS, NP, false>(*Bt, src + p * (NS + NP) * n + k, n, dst + p * NS * n + k, n);
     }

@@ -390,21 +390,33 @@ static u64 inv_mod_2n(u64 g, u64 twoN) {  // g odd, twoN a power of two: Newton 
     for (int i = 0; i < 6; i++) x *= 2 - g * x;
     return x & (twoN - 1);
 }
-static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, u64* out, int64_t batch,
-                          u64 galois, bool rotate, bool prelifted = false, bool key_prepared = false) {
+// A key switch in two steps.  ks_prepare: the plan, the workspace and what is done to the KEY (k_evk_to_f64 on the fused paths,
+// k_ntt_perm for a rotation finished in the tail) -- everything that depends on the key and the shape only.  ks_run: the ciphertexts.
+// One preparation serves any number of runs of at most the prepared `batch` each with the same key (tfhe_bfv_mul_relin: one per
+// chunk of its own pipeline), PROVIDED nobody else takes the context's workspace in between: ensure_ws hands the start of the one
+// block to every caller and frees it when a larger one is asked for, so the regions below -- the key among them -- are only ours
+// from the preparation to the last run if no other entry point of this context runs between them.
+struct ks_prepared_t {
+    ks_plan_t P;
+    const u64* key;      // the caller's key, or the workspace copy
+    u64 *S, *dig, *rot;
+    u64 galois;
+    int polys;
+};
+static int ks_prepare(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, const u64* out, int64_t batch,
+                      u64 galois, bool rotate, bool prelifted, bool key_prepared, ks_prepared_t* K) {
     if (prelifted && (rotate || special || !ks_prelift_ok(c, level))) return fail(TFHE_E_UNSUPPORTED, "internal: pre-lifted rows need the fused key switch");
-    ks_plan_t P = ks_plan(c, Lk, level, special, polys, batch, ct, out, galois, rotate, prelifted, key_prepared);
-    if (P.rot == KS_ROT_HOISTED) {
-        const uint64_t* one[1] = {evk};
-        return tfhe_rotate_many(c, Lk, level, special, one, level, 1, &galois, 1, ct, out, batch);
-    }
+    K->P = ks_plan(c, Lk, level, special, polys, batch, ct, out, galois, rotate, prelifted, key_prepared);
+    ks_plan_t& P = K->P;
+    K->key = evk; K->galois = galois; K->polys = polys;
+    if (P.rot == KS_ROT_HOISTED) return TFHE_OK;   // the caller hands the call to tfhe_rotate_many
     if (special) special_inv_table(c, Lk, level, P.ra.qlinv);
     const size_t N = P.N;
     void* ws = nullptr;
     int rc = ensure_ws(c, P.bytes(), &ws);
     if (rc) return rc;
-    u64 *const S = P.region(ws, 0), *const dig = P.region(ws, P.S_rows), *const rot = P.region(ws, P.S_rows + P.dig_rows),
-        *const kw = P.region(ws, P.S_rows + P.dig_rows + P.rot_rows);
+    K->S = P.region(ws, 0); K->dig = P.region(ws, P.S_rows); K->rot = P.region(ws, P.S_rows + P.dig_rows);
+    u64* const kw = P.region(ws, P.S_rows + P.dig_rows + P.rot_rows);
     const u64 ginv = P.key_perm ? inv_mod_2n(galois, 2 * (u64)c->N) : (u64)0;
     if (P.path != KS_THREE) {
         rc = launch(c, k_evk_to_f64, row_grid((unsigned)(level * 2 * P.A.nw), N), dim3(256), 0, evk, kw, c->limbs_dev, P.A, Lk, (u32)N, c->logN <= 14 ? 1 : 0,
@@ -413,19 +425,37 @@ static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64
         rc = launch(c, k_ntt_perm, row_grid((unsigned)(level * 2 * Lk), N), dim3(256), 0, evk, kw, ginv, (u32)N);
     }
     if (rc) return rc;
-    if (P.path != KS_THREE || P.key_perm) evk = kw;
+    if (P.path != KS_THREE || P.key_perm) K->key = kw;
+    return TFHE_OK;
+}
+// `batch` ciphertexts (at most the prepared batch) by a prepared key switch
+static int ks_run(tfhe_ctx* c, const ks_prepared_t& K, const u64* ct, u64* out, int64_t batch) {
+    const ks_plan_t& P = K.P;
+    const int level = P.A.level, polys = K.polys;
+    const size_t N = P.N;
     for (int64_t b0 = 0; b0 < batch; b0 += P.chunk) {
         const int64_t nb = std::min(P.chunk, batch - b0);
         const u64* cin = ct + (size_t)b0 * polys * level * N;
         if (P.rot == KS_ROT_COPY) {
-            rc = do_galois(c, cin, rot, galois, nb * polys * level, first_limbs(level));
+            const int rc = do_galois(c, cin, K.rot, K.galois, nb * polys * level, first_limbs(level));
             if (rc) return rc;
-            cin = rot;
+            cin = K.rot;
         }
-        rc = ks_chunk(c, P, evk, cin, out + (size_t)b0 * 2 * level * N, nb, S, dig);
+        const int rc = ks_chunk(c, P, K.key, cin, out + (size_t)b0 * 2 * level * N, nb, K.S, K.dig);
         if (rc) return rc;
     }
     return TFHE_OK;
+}
+static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, u64* out, int64_t batch,
+                          u64 galois, bool rotate, bool prelifted = false, bool key_prepared = false) {
+    ks_prepared_t K;
+    const int rc = ks_prepare(c, Lk, level, special, evk, ct, polys, out, batch, galois, rotate, prelifted, key_prepared, &K);
+    if (rc) return rc;
+    if (K.P.rot == KS_ROT_HOISTED) {
+        const uint64_t* one[1] = {evk};
+        return tfhe_rotate_many(c, Lk, level, special, one, level, 1, &galois, 1, ct, out, batch);
+    }
+    return ks_run(c, K, ct, out, batch);
 }
 
 int tfhe_keyswitch(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk, int n_digits, const uint64_t* ct, int polys, uint64_t* out, int64_t batch) {

@@ -161,7 +161,9 @@ TFHE_HD u64 acc52_redc(acc52 a, const mont26_t& M) {
     // and r = (z + M p) 2^-78 < z 2^-78 + p.  Each of the at most 16 terms of z is a source operand below 2^51 (a residue, the
     // alpha count or 1) times a constant reduced mod the target p, so z < 16 2^51 p = 2^55 p, z 2^-78 < 2^-23 p and r < 2 p for
     // every p: one conditional subtraction makes it canonical.  Every lane stays below 2^57 (s0 < 2^56 + 2^52, s1 and s2 less),
-    // so every carry (lane >> 26) fits 31 bits.  (An unmasked 32-bit m in rounds one and two carried up to 2^32.3 out of s0 / s1
+    // so every carry (lane >> 26) fits 31 bits.  The folded contraction (bfv_fast.h, FOLDED) starts lane s0 of a P-limb's sum from
+    // y'' + p + n_cB2 < 2.5 p + 1 < 2^52 instead of from n_cB2 plus one product: one more plain addend below 2^51 in the place of a
+    // term (s0 < 2^52 + 15 2^52 = 2^56, z < 2^52 + 15 2^51 p: both inside the bounds above).  (An unmasked 32-bit m in rounds one and two carried up to 2^32.3 out of s0 / s1
     // -- truncated -- at primes whose low 26 bits are large, such as the top of the fp64 class, and left r up to 64 p at primes
     // below 2^31.)
     u32 m = ((u32)a.s0 * M.pp) & 0x3ffffffu;

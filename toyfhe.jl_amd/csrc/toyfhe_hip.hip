@@ -560,9 +560,10 @@ int run_ntt(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, c
 bool bfv_core_fusable(const tfhe_ctx* c, const limb_sel_t& sel) { return c->variant == 0 && c->logN >= 12 && c->logN <= 14 && sel_fp(c, sel, 0); }
 // forward transforms + tensor + inverse transforms of one BFV multiplication chunk in one kernel (fp64 policy, N = 2^12 .. 2^14:
 // the reference's own BFV tests run at 2^11 - 2^12, test/bfv_crt.jl:8, and its MNIST parameters at 2^13, infer.jl:97);
-// *done = false when the configuration is not covered.  scratch: one row per workgroup.
+// *done = false when the configuration is not covered.  scratch: one row per workgroup.  limbs: the limb table the kernel reads
+// (nullptr: the context's; the BFV plan passes its copy with the contraction's input constants folded in, bfv_api.inc).
 int launch_bfv_core_fused(tfhe_ctx* c, const u64* Ea, const u64* Eb, u64* T, u64* scratch, int64_t nct, const limb_sel_t& sel, bool* done,
-                          const core_alt_t* altp = nullptr, bool out_double = false) {
+                          const core_alt_t* altp = nullptr, bool out_double = false, const ntt_limb_t* limbs = nullptr) {
     *done = false;
     if (!bfv_core_fusable(c, sel) || nct * sel.n > 0x7fffffffll) return TFHE_OK;
     core_alt_t alt{};
@@ -575,7 +576,7 @@ int launch_bfv_core_fused(tfhe_ctx* c, const u64* Ea, const u64* Eb, u64* T, u64
         const unsigned grid = cu_grid(c, items, LOGB == 14 ? 1u : 2u);
         // limb transforms inside this launch: 4 forward + 3 inverse per item
         return launch_prof(c, (int64_t)items * 7, kern, dim3(grid), dim3(1 << LOGT), fused_lds_bytes<LOGB, LOGT>(), Ea, Eb, T, scratch,
-                           c->limbs_dev, sel, items, alt);
+                           limbs ? limbs : c->limbs_dev, sel, items, alt);
     });
     if (rc) return rc;
     *done = true;
