@@ -89,16 +89,7 @@ def encrypted_matmul(gk, W, x, B, cache=None, fused=False):
     if isinstance(gk, BsgsKeys):
         # the whole product in one device call by baby and giant steps (tfhe_matmul_bsgs): n1 + 64 / n1 - 2 keys instead of 63; the
         # diagonals are pre-rotated on the host (bsgs_diagonals) and encoded once per (matrix, level, scale)
-        key = (id(W), "bsgs", gk.n1, x.ring().L, x.scale)
-        if cache is None or key not in cache:
-            vs = np.stack([np.repeat(np.array([W[i, (i - k) % n] for i in range(n)]), B) for k in range(n)])
-            D = tf.bsgs_diagonals(vs, gk.n1, block=B)[0]
-            enc = tf.ckks_encode(D.reshape(-1, D.shape[-1]).astype(np.complex128), x.ring(), x.scale)
-            enc.coeffs_dual()
-            if cache is None:
-                return tf.matmul_bsgs(gk.baby, gk.giant, enc, x)
-            cache[key] = enc
-        return tf.matmul_bsgs(gk.baby, gk.giant, cache[key], x)
+        return tf.matmul_bsgs(gk.baby, gk.giant, bsgs_encoded(gk, W, x, B, cache), x)
     if isinstance(gk, (list, tuple)) and cache is not None and fused:
         # the whole product in one device call (tfhe_matmul_diag): the diagonals are single plaintexts shared by the batch
         key = (id(W), "fused", x.ring().L, x.scale)
@@ -120,6 +111,38 @@ def encrypted_matmul(gk, W, x, B, cache=None, fused=False):
     for k in range(1, n):
         result = result + rots[k].mul_plain(diag(k))
     return result
+
+
+def bsgs_encoded(gk, W, x, B, cache=None):
+    """the pre-rotated diagonals of W for the baby/giant split of `gk` as one stacked plaintext at x's level and scale, encoded once
+    per (matrix, split, level, scale) when a cache is given"""
+    n = 64
+    key = (id(W), "bsgs", gk.n1, x.ring().L, x.scale)
+    if cache is not None and key in cache:
+        return cache[key]
+    vs = np.stack([np.repeat(np.array([W[i, (i - k) % n] for i in range(n)]), B) for k in range(n)])
+    D = tf.bsgs_diagonals(vs, gk.n1, block=B)[0]
+    enc = tf.ckks_encode(D.reshape(-1, D.shape[-1]).astype(np.complex128), x.ring(), x.scale)
+    enc.coeffs_dual()
+    if cache is not None:
+        cache[key] = enc
+    return enc
+
+
+def encrypted_matmul_blocks(gk, Ws, xs, B, b, cache=None, name=None):
+    """infer.jl:158-163 in one device call (tfhe_matmul_bsgs_blocks): sum_m Ws[m] @ xs[m] .+ b with the inner sums of all inputs added
+    before the giant rotations -- len(gk.giant) giant key switches instead of len(xs) times as many; the bias, encoded at the result's
+    scale (once per (layer, level, scale) with a cache, under add_bias's key), rides on the closing sum"""
+    x = xs[0]
+    scale2 = x.scale ** 2
+    key = ("bias", name, x.ring().L, scale2)
+    if cache is not None and key in cache:
+        bias = cache[key]
+    else:
+        bias = tf.ckks_encode(np.asarray(b, dtype=np.complex128), x.ring(), scale2)
+        if cache is not None:
+            cache[key] = bias
+    return tf.matmul_bsgs_blocks(gk.baby, gk.giant, [bsgs_encoded(gk, W, x, B, cache) for W in Ws], xs, bias)
 
 
 def add_bias(ct, x, cache=None, name=None):
@@ -148,13 +171,17 @@ def load_model(path=GOLDEN_MODEL):
 
 
 def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None,
-        mul_relin=False, bsgs=0):
-    """`bsgs` = n1 > 0: every matrix product as one tfhe_matmul_bsgs call with n1 - 1 baby and ceil(64 / n1) - 1 giant keys (a third
+        mul_relin=False, bsgs=0, blocks=False):
+    """`blocks` (with `bsgs`): the first dense layer -- a 64 x 256 matrix over the four squares, .+ b -- as ONE tfhe_matmul_bsgs_blocks
+    call instead of four tfhe_matmul_bsgs calls, three ciphertext additions and a plaintext addition.
+    `bsgs` = n1 > 0: every matrix product as one tfhe_matmul_bsgs call with n1 - 1 baby and ceil(64 / n1) - 1 giant keys (a third
     circuit shape beside the chained loop and the 63 hoisted keys; the other layers as chosen by the remaining switches).
     `mul_relin`: the two square layers as one device call each (she.mul_relin = tfhe_mul_relin) instead of
     modswitch(keyswitch(ek, c * c)); same logits, bit for bit.
     `batches` = K ciphertext sets evaluated together (K * B images): every ring element carries a leading batch dimension
     of K, so each device call covers K ciphertexts (the batch the engine shards across GPUs)."""
+    if blocks and not bsgs:
+        raise ValueError("blocks needs bsgs = n1 > 0")
     N = 1 << logn
     B = N // 128                                                   # images per ciphertext
     K = int(batches)
@@ -224,11 +251,14 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
           sq1 = [tf.she.mul_relin(ek, c, c, rescale=True) for c in conved]
       else:
           sq1 = [tf.modswitch(tf.keyswitch(ek, c * c)) for c in conved]
-      fq1 = None
-      for i in range(4):
-          part = encrypted_matmul(gk, fq1_blocks[i], sq1[i], B, cache, fused)
-          fq1 = part if fq1 is None else fq1 + part
-      fq1 = tf.modswitch(add_bias(fq1, np.repeat(model["fq1_b"], B), cache, "fq1"))
+      if blocks:
+          fq1 = tf.modswitch(encrypted_matmul_blocks(gk, fq1_blocks, list(sq1), B, np.repeat(model["fq1_b"], B), cache, "fq1"))
+      else:
+          fq1 = None
+          for i in range(4):
+              part = encrypted_matmul(gk, fq1_blocks[i], sq1[i], B, cache, fused)
+              fq1 = part if fq1 is None else fq1 + part
+          fq1 = tf.modswitch(add_bias(fq1, np.repeat(model["fq1_b"], B), cache, "fq1"))
       sq2 = tf.she.mul_relin(ek, fq1, fq1, rescale=True) if mul_relin else tf.modswitch(tf.keyswitch(ek, fq1 * fq1))
       res = add_bias(encrypted_matmul(gk, W2, sq2, B, cache, fused), np.repeat(np.concatenate([model["fq2_b"], np.zeros(54)]), B), cache, "fq2")
       ev1.record(res[0].ring.ctx)
@@ -265,5 +295,10 @@ if __name__ == "__main__":
                     help="the two square layers through she.mul_relin (one tfhe_mul_relin call each) instead of modswitch(keyswitch(ek, c * c))")
     ap.add_argument("--bsgs", type=int, default=0, metavar="N1",
                     help="each matrix product as one tfhe_matmul_bsgs call: N1 - 1 baby and ceil(64 / N1) - 1 giant Galois keys instead of 63")
+    ap.add_argument("--blocks", action="store_true",
+                    help="with --bsgs N1: the first dense layer (64 x 256 over the four squares, + bias) as one tfhe_matmul_bsgs_blocks call")
     a = ap.parse_args()
-    run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin, bsgs=a.bsgs)
+    if a.blocks and not a.bsgs:
+        ap.error("--blocks needs --bsgs N1")
+    run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin, bsgs=a.bsgs,
+        blocks=a.blocks)

@@ -215,6 +215,34 @@ int tfhe_matmul_bsgs(tfhe_ctx *ctx, int key_limbs, int level, int special,
                      const uint64_t *const *baby_evks, const uint64_t *baby_galois, int n_baby,
                      const uint64_t *const *giant_evks, const uint64_t *giant_galois, int n_giant,
                      int n_digits, const uint64_t *diags, const uint64_t *ct, uint64_t *out, int64_t batch);
+/* The block-row product by baby and giant steps, in one call: n_in ciphertext inputs, each with its own diagonals, over ONE key set
+ * (examples/encrypted_mnist/infer.jl:158-163: a 64 x 256 matrix applied to four ciphertexts, .+ b).  The rotation is linear, so the
+ * inner sums of all inputs are added before they are rotated: n_giant giant key switches instead of n_in n_giant.
+ *     inner_j = sum_{m < n_in} sum_{i = 0 .. n_baby} diags[m][j][i] .* NTT(r_i(cts[m]))      j = 0 .. n_giant
+ *     out     = INTT(inner_0) + sum_{j = 1 .. n_giant} rotate(giant key j - 1, INTT(inner_j))   (+ bias on component 0)
+ *   baby_evks / giant_evks, baby_galois / giant_galois, n_baby, n_giant in [0, 64], n_digits: as for tfhe_matmul_bsgs (PREPARED keys,
+ *   HOST arrays);
+ *   diags: HOST array of n_in device pointers, each [n_giant + 1][n_baby + 1][level][N], NTT domain, shared by the batch (the layout
+ *   tfhe_matmul_bsgs takes, one per input);  cts: HOST array of n_in device pointers, each [batch][2][level][N], coefficient domain
+ *   (the same pointer may appear more than once);  n_in in [1, 64];
+ *   bias: NULL, or device [level][N], coefficient domain, canonical residues, shared by the batch: added limb-wise to component 0 of
+ *   every output ciphertext;  out: [batch][2][level][N], coefficient domain.
+ * The result equals, word for word, per input tfhe_rotate_many over the baby keys -> tfhe_nntt; per giant step ONE sum over all
+ * n_in (n_baby + 1) terms, tfhe_dot (chained through its acc above 64 terms); -> tfhe_inntt -> tfhe_rotate_prepared per giant step
+ * j >= 1 -> tfhe_add -> tfhe_add of the bias onto component 0: exact arithmetic on canonical residues, so every path
+ * (evaluation-domain or coefficient tail, every route of the nested key switch) and every tfhe_ctx_set_chunk gives the same bits.
+ * It is NOT the sum of n_in calls of tfhe_matmul_bsgs: the contraction by the special prime rounds, and here it rounds
+ * once per giant step, not once per input and giant step.  With n_in = 1 and bias = NULL the words are those of tfhe_matmul_bsgs.
+ * Checked on the host before any device use, in this order: null arrays, a null key among the first n_baby / n_giant, a null
+ * diags[m] or cts[m] among the first n_in; n_baby / n_giant outside [0, 64], n_in outside [1, 64]; an even Galois element; out
+ * starting where any cts[m], diags[m] or bias starts (all TFHE_E_BADARG); then the context; then the level / key-limb rules of
+ * tfhe_keyswitch, Galois elements not below 2N and out overlapping any operand anywhere (TFHE_E_BADARG).  batch == 0 does nothing,
+ * but still needs a context. */
+int tfhe_matmul_bsgs_blocks(tfhe_ctx *ctx, int key_limbs, int level, int special,
+                            const uint64_t *const *baby_evks, const uint64_t *baby_galois, int n_baby,
+                            const uint64_t *const *giant_evks, const uint64_t *giant_galois, int n_giant, int n_digits,
+                            const uint64_t *const *diags, const uint64_t *const *cts, int n_in,
+                            const uint64_t *bias, uint64_t *out, int64_t batch);
 /* the one-time key preparation of the hoisted rotations: evk_out = the Galois key of x -> x^g (layout of tfhe_keyswitch,
  * n_digits components over key_limbs moduli) with every NTT-domain row permuted by g^-1, so that the key products run on the
  * transformed digits of the unrotated ciphertext.  prepared = 0 above takes plain keys and prepares them per call. */

@@ -2403,6 +2403,8 @@ __global__ __launch_bounds__(256) void k_md_lift(const u64* __restrict__ P, u64*
 //   rows (b, s, j) = (b * 2 + s) * level + j      diag: [ngiant1][nrot + 1][level][N]      inner: [ngiant1][batch][2][level][N], NTT domain
 // The outputs are tiled NG giant steps per pass with the coefficients per thread reduced to match (KB NG = TFHE_MD_KB: 2 KB NG
 // accumulators at every NG, in registers, no scratch); a ragged last tile repeats its last step unstored.
+// SEED (tfhe_matmul_bsgs_blocks, the inputs after the first of a chunk): every sum starts from the reduced word already in `inner`
+// instead of from zero (lazy_sums::seed), so the sums over several inputs never take a pass of their own.
 //   k_md_acc         the evaluation-domain form, rotated value V[pi_r k] - U[k].  One XCD takes the two rows (b, 0, j), (b, 1, j) at
 //                    a time: they share the diagonal words and the permuted positions, and the V windows in flight are the two rows
 //                    of ONE rotation (a version that requested four rotations at a time per coefficient ran slower than the plain
@@ -2419,7 +2421,7 @@ __global__ __launch_bounds__(256) void k_md_lift(const u64* __restrict__ P, u64*
 #ifndef TFHE_MD_SLOTS
 #define TFHE_MD_SLOTS 32   // workgroups per XCD (KB x SLOTS x 256 = 2^16: measured 63.7 k / 65.9 k / 66.9 k images/s at KB = 2 / 4 / 8)
 #endif
-template <bool USCALE, int NG>
+template <bool USCALE, int NG, bool SEED = false>
 __global__ __launch_bounds__(256) void k_md_acc(const u64* __restrict__ X, const u64* __restrict__ V, const u64* __restrict__ U,
                                                  const u64* __restrict__ diag, u64* __restrict__ inner, const ntt_limb_t* __restrict__ LT,
                                                  limb_sel_t sel, rot_tail_arg_t G, rescale_arg_t ra, u32 n, u32 nw, u32 nrot, u32 batch,
@@ -2471,11 +2473,23 @@ __global__ __launch_bounds__(256) void k_md_acc(const u64* __restrict__ X, const
                     u64 d0[NG];
 #pragma unroll
                     for (int o = 0; o < NG; o++) d0[o] = dg[o][k[i]];
-                    a0[i].clear(); a1[i].clear();
+                    if (SEED) {   // the sums so far of this chunk's earlier inputs (a repeated lane of a ragged tile has none)
+                        u64 s0[NG], s1[NG];
+#pragma unroll
+                        for (int o = 0; o < NG; o++) {
+                            const bool live = j0 + (u32)o < ngiant1;
+                            const u64* oj = inner + (size_t)(live ? j0 + (u32)o : j0) * ostride;
+                            s0[o] = live ? oj[row0 + k[i]] : 0;
+                            s1[o] = live ? oj[row1 + k[i]] : 0;
+                        }
+                        a0[i].seed(s0); a1[i].seed(s1);
+                    } else {
+                        a0[i].clear(); a1[i].clear();
+                    }
                     a0[i].mac(X[row0 + k[i]], d0);
                     a1[i].mac(X[row1 + k[i]], d0);
                 }
-                u32 pend = 1;
+                u32 pend = 1;   // the X term (a seed is the reduced word under the products, not one of them)
                 term_t cur;
                 fetch(0, cur);
                 for (u32 t = 0; t < nrot; t++) {
@@ -2511,7 +2525,7 @@ __global__ __launch_bounds__(256) void k_md_acc(const u64* __restrict__ X, const
     }
 }
 // rows = batch * 2 * level, row = (b * 2 + s) * level + j; ROT: [nrot][rows][N] (rows_per_rot = rows)
-template <int NG>
+template <int NG, bool SEED = false>
 __global__ __launch_bounds__(256) void k_md_acc_dense(const u64* __restrict__ X, const u64* __restrict__ ROT, const u64* __restrict__ diag,
                                                        u64* __restrict__ inner, const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 n,
                                                        u32 nrot, u32 rows_per_rot, u32 ngiant1) {
@@ -2526,7 +2540,14 @@ __global__ __launch_bounds__(256) void k_md_acc_dense(const u64* __restrict__ X,
 #pragma unroll
             for (int o = 0; o < NG; o++) dg[o] = dj + (size_t)bsgs_tile_step(j0, (u32)o, ngiant1) * jstride + i;
             lazy_sums<NG> s;
-            s.clear();
+            if (SEED) {
+                u64 w[NG];
+#pragma unroll
+                for (int o = 0; o < NG; o++) w[o] = j0 + (u32)o < ngiant1 ? inner[(size_t)(j0 + (u32)o) * rstride + base + i] : 0;
+                s.seed(w);
+            } else {
+                s.clear();
+            }
             u32 pend = 0;
             for (u32 k = 0; k <= nrot; k++) {
                 const u64 x = k == 0 ? X[base + i] : ROT[(size_t)(k - 1) * rstride + base + i];
@@ -2543,15 +2564,19 @@ __global__ __launch_bounds__(256) void k_md_acc_dense(const u64* __restrict__ X,
         }
     }
 }
-// first, out: [rows][N]; rest: [nrest][rows][N] (rstride words apart)
+// first, out: [rows][N], row = (b * 2 + s) * level + j; rest: [nrest][rows][N] (rstride words apart); bias: null, or [level][N]
+// added to the component-0 rows (s = 0) after the giant sums
 __global__ __launch_bounds__(256) void k_bsgs_sum(const u64* __restrict__ first, const u64* __restrict__ rest, u64* __restrict__ out,
-                                                   const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 n, u32 nrest, size_t rstride) {
+                                                   const ntt_limb_t* __restrict__ LT, limb_sel_t sel, u32 n, u32 nrest, size_t rstride,
+                                                   const u64* __restrict__ bias) {
     const u32 row = blockIdx.x, j = row % (u32)sel.n;
     const u64 q = LT[sel.idx[j]].q;
     const size_t base = (size_t)row * n;
+    const u64* bj = bias != nullptr && ((row / (u32)sel.n) & 1u) == 0 ? bias + (size_t)j * n : nullptr;
     for (u32 i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
         u64 r = first[base + i];
         for (u32 t = 0; t < nrest; t++) r = addmod(r, rest[(size_t)t * rstride + base + i], q);
+        if (bj) r = addmod(r, bj[i], q);
         out[base + i] = r;
     }
 }

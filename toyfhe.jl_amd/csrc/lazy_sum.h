@@ -1,8 +1,9 @@
 // lazy_sum.h -- sums of 128-bit products under the Barrett window: how many products fit between two reductions (lazy_chunk, the
 // one place in csrc/ where that rule is written: k_dot, k_lincomb, k_lincomb_many and k_dot_view take their chunk from it), and the
 // accumulation bodies of the diagonal products -- NO running sums of ONE value each, tfhe_matmul_diag with NO = 1, tfhe_matmul_bsgs
-// with a tile of up to four giant steps.  Plain host / device functions: the kernels (kernels.h: k_md_acc, k_md_acc_dense) string
-// them together with their loads, tests/bsgs_emul/ runs them on the CPU against exact sums.
+// with a tile of up to four giant steps, tfhe_matmul_bsgs_blocks the same seeded with the sums of its earlier inputs.  Plain host /
+// device functions: the kernels (kernels.h: k_md_acc, k_md_acc_dense) string them together with their loads, tests/bsgs_emul/ and
+// tests/bsgs_blocks_emul/ run them on the CPU against exact sums.
 //
 // inner_j[k] = sum_{i = 0 .. n_baby} diag[j][i][k] * r_i[k] for the giant steps j of one tile: every r_i[k] is formed once and
 // multiplied into the tile's NO sums; only the diagonal words differ between them.
@@ -25,6 +26,12 @@ struct lazy_sums {
     TFHE_HD void clear() {
 #pragma unroll
         for (int o = 0; o < NO; o++) a[o] = acc128{0, 0};
+    }
+    // the seeded start (tfhe_matmul_bsgs_blocks, inputs m >= 1): every sum continues from a reduced word w[o] < q instead of from
+    // zero.  That word is the "reduced word" of lazy_chunk's window, not one of its products: `pend` starts where it starts after clear()
+    TFHE_HD void seed(const u64* w) {
+#pragma unroll
+        for (int o = 0; o < NO; o++) a[o] = acc128{w[o], 0};
     }
     // x into every sum, each against its own diagonal word
     TFHE_HD void mac(u64 x, const u64* d) {

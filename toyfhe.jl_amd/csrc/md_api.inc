@@ -1,5 +1,5 @@
-// md_api.inc -- the diagonal matrix products tfhe_matmul_diag and tfhe_matmul_bsgs: the shared rotation phase (md_plan, md_bufs,
-// md_rotations), its workspace, and the two entry points; included by toyfhe_hip.hip after ks_api.inc, whose key-sum, digit and
+// md_api.inc -- the diagonal matrix products tfhe_matmul_diag, tfhe_matmul_bsgs and tfhe_matmul_bsgs_blocks: the shared rotation phase
+// (md_plan, md_bufs, md_rotations), its workspace, and the three entry points; included by toyfhe_hip.hip after ks_api.inc, whose key-sum, digit and
 // rotation helpers (ks_digits_fwd, ks_inner_launch, keyswitch_impl, ks_plan, rotate_many_ws) it calls.  Kernels: kernels.h k_md_*.
 
 // tfhe_matmul_diag, evaluation-domain form: U[grp][j] = NTT_j( [P[grp]] mod q_j ) (x P^-1 unless *scaled comes back false) for
@@ -285,6 +285,79 @@ static size_t bsgs_nested_bytes(const tfhe_ctx* c, int Lk, int level, int specia
 }
 // the output tile: 4 giant steps per pass, fewer where there are fewer sums (log2)
 static int bsgs_log_tile(int ngiant1) { return ngiant1 >= 3 ? 2 : ngiant1 - 1; }
+// The device side of both entry points, after their host checks: n_in inputs, each with its own diagonals, feed ONE set of inner
+// sums per chunk.  Input 0 of every chunk runs the unseeded accumulation (INNER still holds the previous chunk's sums), the others the
+// seeded form, which continues from the reduced words in INNER; the baby-phase buffers are reused input after input (one stream, in
+// order: md_lift_fwd's side lane has joined when md_rotations returns).  The giant rotations, the inverse transform and the closing
+// sum (+ bias on component 0) then run once per chunk, whatever n_in.
+static int matmul_bsgs_run(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby,
+                           const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant, const uint64_t* const* diags,
+                           const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out, int64_t batch) {
+    const size_t N = (size_t)c->N;
+    const int ng1 = n_giant + 1;
+    const md_plan_t P = md_plan(c, Lk, level, special, baby_galois, n_baby);
+    // One allocation: [ region 0 | the baby phase (md_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ].
+    // Region 0 is the start of the context workspace, which the stand-alone transforms of N > 2^14 and the nested key switch
+    // take for themselves (ensure_ws hands out the start of whatever is allocated): sized for the larger of the two, so that a
+    // nested ensure_ws neither grows -- moves -- the workspace nor reaches our buffers.  Nothing scales with n_in.
+    const size_t rows = P.rows + (size_t)(ng1 + n_giant) * 2 * level, per_ct = rows * N * 8;
+    const size_t ntt_rows = std::max(P.ntt_rows, (size_t)ng1 * 2 * level);
+    const md_ws_t W(c, batch, per_ct, [&](int64_t chunk) {
+        size_t r0 = c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : 0;
+        if (n_giant) r0 = std::max(r0, bsgs_nested_bytes(c, Lk, level, special, chunk));
+        return (r0 + 255) & ~(size_t)255;
+    });
+    if (W.rc) return W.rc;
+    const int64_t chunk = W.chunk;
+    const size_t region0 = W.region0;
+    const md_bufs_t B = md_bufs(P, W.base(), chunk, N);
+    u64* const INNER = B.end;
+    u64* const GOUT = INNER + (size_t)chunk * ng1 * 2 * level * N;
+    int rc;
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const size_t ct_words = (size_t)nb * 2 * level * N;   // one inner sum / one giant result of this chunk
+        for (int m = 0; m < n_in; m++) {
+            bool scaled = true;
+            rc = md_rotations(c, P, baby_evks, cts[m] + (size_t)b0 * 2 * level * N, nb, B, &scaled);
+            if (rc) return rc;
+            const u64* const dm = diags[m];
+            rc = dispatch_int<0, 2>(bsgs_log_tile(ng1), [&](auto lg) {
+                constexpr int NG = 1 << decltype(lg)::value;
+                if (P.eval_form) {
+                    auto acc = m == 0 ? (scaled ? k_md_acc<false, NG> : k_md_acc<true, NG>)
+                                      : (scaled ? k_md_acc<false, NG, true> : k_md_acc<true, NG, true>);
+                    return launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, B.X, B.S, B.ROT, dm, INNER, c->limbs_dev, P.sl, P.G, P.ra, (u32)N,
+                                  (u32)P.nw, (u32)P.R, (u32)nb, (u32)ng1);
+                }
+                auto acc = m == 0 ? k_md_acc_dense<NG> : k_md_acc_dense<NG, true>;
+                return launch(c, acc, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, B.X, B.ROT, dm, INNER, c->limbs_dev, P.sl, (u32)N,
+                              (u32)P.R, (u32)(nb * 2 * level), (u32)ng1);
+            });
+            if (rc) return rc;
+        }
+        rc = run_ntt(c, true, INNER, INNER, (int64_t)ng1 * nb * 2 * level, P.sl);
+        if (rc) return rc;
+        // What the nested key switch will ask for, from its own plan on the real operands: it must stay inside region 0.  The plan of
+        // the first giant step stands for all of them: it depends on the operands only through their disjointness and 16-byte
+        // alignment, and step j reads INNER + j ct_words and writes GOUT + (j - 1) ct_words -- disjoint ranges of one allocation, every
+        // offset a multiple of 8 N bytes from a 256-byte aligned base -- and on the Galois element only for what it writes into the plan.
+        if (n_giant) {
+            const ks_plan_t Q = ks_plan(c, Lk, level, special, 2, nb, INNER + ct_words, GOUT, giant_galois[0], true, false, true);
+            const size_t nested = Q.rot == KS_ROT_HOISTED ? rotate_many_ws(c, level, P.nw, nb).bytes() : Q.bytes();
+            if (nested > region0) return fail(TFHE_E_UNSUPPORTED, "internal: the nested key switch needs %zu bytes, region 0 holds %zu", nested, region0);
+        }
+        for (int j = 1; j <= n_giant; j++) {   // (the nested call finds the workspace large enough: same block, region 0)
+            rc = keyswitch_impl(c, Lk, level, special, giant_evks[j - 1], INNER + (size_t)j * ct_words, 2, GOUT + (size_t)(j - 1) * ct_words, nb,
+                                giant_galois[j - 1], true, false, true);
+            if (rc) return rc;
+        }
+        rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)INNER, (const u64*)GOUT,
+                    out + (size_t)b0 * 2 * level * N, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words, (const u64*)bias);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
 int tfhe_matmul_bsgs(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby,
                      const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant, int n_digits, const uint64_t* diags,
                      const uint64_t* ct, uint64_t* out, int64_t batch) {
@@ -305,65 +378,53 @@ int tfhe_matmul_bsgs(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
     for (int r = 0; r < n_baby + n_giant; r++)
         if ((rc = galois_check(c, r < n_baby ? baby_galois[r] : giant_galois[r - n_baby]))) return rc;
     const size_t N = (size_t)c->N;
-    const int ng1 = n_giant + 1;
     const size_t ct_bytes = (size_t)batch * 2 * level * N * 8;
-    if (ranges_overlap(out, ct_bytes, ct, ct_bytes) || ranges_overlap(out, ct_bytes, diags, (size_t)ng1 * (n_baby + 1) * level * N * 8))
+    if (ranges_overlap(out, ct_bytes, ct, ct_bytes) || ranges_overlap(out, ct_bytes, diags, (size_t)(n_giant + 1) * (n_baby + 1) * level * N * 8))
         return fail(TFHE_E_BADARG, "out overlaps an operand");
     if (batch == 0) return TFHE_OK;
-    const md_plan_t P = md_plan(c, Lk, level, special, baby_galois, n_baby);
-    // One allocation: [ region 0 | the baby phase (md_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ].
-    // Region 0 is the start of the context workspace, which the stand-alone transforms of N > 2^14 and the nested key switch
-    // take for themselves (ensure_ws hands out the start of whatever is allocated): sized for the larger of the two, so that a
-    // nested ensure_ws neither grows -- moves -- the workspace nor reaches our buffers.
-    const size_t rows = P.rows + (size_t)(ng1 + n_giant) * 2 * level, per_ct = rows * N * 8;
-    const size_t ntt_rows = std::max(P.ntt_rows, (size_t)ng1 * 2 * level);
-    const md_ws_t W(c, batch, per_ct, [&](int64_t chunk) {
-        size_t r0 = c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : 0;
-        if (n_giant) r0 = std::max(r0, bsgs_nested_bytes(c, Lk, level, special, chunk));
-        return (r0 + 255) & ~(size_t)255;
-    });
-    if (W.rc) return W.rc;
-    const int64_t chunk = W.chunk;
-    const size_t region0 = W.region0;
-    const md_bufs_t B = md_bufs(P, W.base(), chunk, N);
-    u64* const INNER = B.end;
-    u64* const GOUT = INNER + (size_t)chunk * ng1 * 2 * level * N;
-    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-        const int64_t nb = std::min(chunk, batch - b0);
-        const size_t ct_words = (size_t)nb * 2 * level * N;   // one inner sum / one giant result of this chunk
-        bool scaled = true;
-        rc = md_rotations(c, P, baby_evks, ct + (size_t)b0 * 2 * level * N, nb, B, &scaled);
-        if (rc) return rc;
-        rc = dispatch_int<0, 2>(bsgs_log_tile(ng1), [&](auto lg) {
-            constexpr int NG = 1 << decltype(lg)::value;
-            if (P.eval_form) {
-                auto acc = scaled ? k_md_acc<false, NG> : k_md_acc<true, NG>;
-                return launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, B.X, B.S, B.ROT, diags, INNER, c->limbs_dev, P.sl, P.G, P.ra, (u32)N,
-                              (u32)P.nw, (u32)P.R, (u32)nb, (u32)ng1);
-            }
-            return launch(c, k_md_acc_dense<NG>, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, B.X, B.ROT, diags, INNER, c->limbs_dev,
-                          P.sl, (u32)N, (u32)P.R, (u32)(nb * 2 * level), (u32)ng1);
-        });
-        if (rc) return rc;
-        rc = run_ntt(c, true, INNER, INNER, (int64_t)ng1 * nb * 2 * level, P.sl);
-        if (rc) return rc;
-        // What the nested key switch will ask for, from its own plan on the real operands: it must stay inside region 0.  The plan of
-        // the first giant step stands for all of them: it depends on the operands only through their disjointness and 16-byte
-        // alignment, and step j reads INNER + j ct_words and writes GOUT + (j - 1) ct_words -- disjoint ranges of one allocation, every
-        // offset a multiple of 8 N bytes from a 256-byte aligned base -- and on the Galois element only for what it writes into the plan.
-        if (n_giant) {
-            const ks_plan_t Q = ks_plan(c, Lk, level, special, 2, nb, INNER + ct_words, GOUT, giant_galois[0], true, false, true);
-            const size_t nested = Q.rot == KS_ROT_HOISTED ? rotate_many_ws(c, level, P.nw, nb).bytes() : Q.bytes();
-            if (nested > region0) return fail(TFHE_E_UNSUPPORTED, "internal: the nested key switch needs %zu bytes, region 0 holds %zu", nested, region0);
-        }
-        for (int j = 1; j <= n_giant; j++) {   // (the nested call finds the workspace large enough: same block, region 0)
-            rc = keyswitch_impl(c, Lk, level, special, giant_evks[j - 1], INNER + (size_t)j * ct_words, 2, GOUT + (size_t)(j - 1) * ct_words, nb,
-                                giant_galois[j - 1], true, false, true);
-            if (rc) return rc;
-        }
-        rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)INNER, (const u64*)GOUT,
-                    out + (size_t)b0 * 2 * level * N, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words);
-        if (rc) return rc;
+    return matmul_bsgs_run(c, Lk, level, special, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, &diags, &ct, 1, nullptr, out, batch);
+}
+
+// ---- the block-row product: several inputs, one set of giant rotations -------------------------------------------------------
+// out = sum_m M_m x_m (+ bias) for n_in ciphertext inputs, each with its own diagonals, over ONE key set.  The rotation is linear:
+//     sum_m sum_j rho^(j n1)( inner_{m,j} ) = sum_j rho^(j n1)( sum_m inner_{m,j} ),
+// so the inner sums of all inputs are added -- in the accumulation itself, seeded -- before they are inverse-transformed and rotated:
+// n_giant giant key switches and n_giant + 1 inverse-transformed sums instead of n_in times as many, one pass over the output.
+// The words are those of ONE tfhe_dot over all n_in (n_baby + 1) terms per giant step, not those of n_in calls of
+// tfhe_matmul_bsgs added up: the contraction by the special prime rounds once per giant step here.
+int tfhe_matmul_bsgs_blocks(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby,
+                            const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant, int n_digits,
+                            const uint64_t* const* diags, const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out, int64_t batch) {
+    // host checks that need no ring first (nulls, counts, parity, equal starts), then the context, then the ring's
+    if (!baby_evks || !baby_galois || !giant_evks || !giant_galois || !diags || !cts || !out) return fail(TFHE_E_BADARG, "null argument");
+    const auto within = [](int n) { return n < 0 ? 0 : (n > TFHE_DOT_MAX ? TFHE_DOT_MAX : n); };   // (an array is read no further than a valid count reaches)
+    for (int r = 0; r < within(n_baby); r++)
+        if (!baby_evks[r]) return fail(TFHE_E_BADARG, "null baby key %d", r);
+    for (int r = 0; r < within(n_giant); r++)
+        if (!giant_evks[r]) return fail(TFHE_E_BADARG, "null giant key %d", r);
+    for (int m = 0; m < within(n_in); m++) {
+        if (!diags[m]) return fail(TFHE_E_BADARG, "null diagonals of input %d", m);
+        if (!cts[m]) return fail(TFHE_E_BADARG, "null ciphertext of input %d", m);
     }
-    return TFHE_OK;
+    if (n_baby < 0 || n_baby > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_baby=%d outside [0,%d]", n_baby, TFHE_DOT_MAX);
+    if (n_giant < 0 || n_giant > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_giant=%d outside [0,%d]", n_giant, TFHE_DOT_MAX);
+    if (n_in < 1 || n_in > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_in=%d outside [1,%d]", n_in, TFHE_DOT_MAX);
+    for (int r = 0; r < n_baby + n_giant; r++)
+        if (((r < n_baby ? baby_galois[r] : giant_galois[r - n_baby]) & 1) == 0) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
+    if ((const void*)out == (const void*)bias) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    for (int m = 0; m < n_in; m++)
+        if ((const void*)out == (const void*)cts[m] || (const void*)out == (const void*)diags[m]) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (!c) return fail(TFHE_E_BADARG, "null context");
+    int rc = ks_check(c, Lk, level, special, diags[0], n_digits, cts[0], 2, out, batch);
+    if (rc) return rc;
+    for (int r = 0; r < n_baby + n_giant; r++)
+        if ((rc = galois_check(c, r < n_baby ? baby_galois[r] : giant_galois[r - n_baby]))) return rc;
+    const size_t N = (size_t)c->N;
+    const size_t ct_bytes = (size_t)batch * 2 * level * N * 8, diag_bytes = (size_t)(n_giant + 1) * (n_baby + 1) * level * N * 8;
+    if (bias && ranges_overlap(out, ct_bytes, bias, (size_t)level * N * 8)) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    for (int m = 0; m < n_in; m++)
+        if (ranges_overlap(out, ct_bytes, cts[m], ct_bytes) || ranges_overlap(out, ct_bytes, diags[m], diag_bytes))
+            return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (batch == 0) return TFHE_OK;
+    return matmul_bsgs_run(c, Lk, level, special, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags, cts, n_in, bias, out, batch);
 }

@@ -592,6 +592,46 @@ function matmul_bsgs(baby::Vector{<:ToyFHE.GaloisKey}, giant::Vector{<:ToyFHE.Ga
                 dg.ptr, ct.ptr, out.ptr, cnt))
     CipherText{squared_encoding(Enc)}(c.params, unpack(ctx, out, ℛ, 2))
 end
+# The block-row product in one device call (tfhe_matmul_bsgs_blocks): length(cs) inputs, each with its own rows of diagonals, over one
+# key set; the inner sums of all inputs are added before the giant rotations.  bias: nothing, or one plaintext element at the result's
+# scale, added to component 1.  (Not executed anywhere yet: the tests check the ccall against the header.)
+function matmul_bsgs_blocks(baby::Vector{<:ToyFHE.GaloisKey}, giant::Vector{<:ToyFHE.GaloisKey},
+                            diags::Vector{<:Vector{<:Vector{<:RingElement{ℛ,T,<:HipVector}}}},
+                            cs::Vector{<:CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}}, bias=nothing) where {Enc,P,ℛ,T}
+    nin = length(cs); nb = length(baby); ng = length(giant)
+    @assert 1 <= nin <= 64 && length(diags) == nin && all(c -> length(c.cs) == 2, cs)
+    @assert all(m -> length(m) == ng + 1 && all(r -> length(r) == nb + 1, m), diags)
+    max(nb, ng) <= 64 || throw(ToyFHE.UsageError("matmul_bsgs_blocks: at most 64 baby and 64 giant steps per call (TFHE_DOT_MAX)"))
+    isempty(baby) && isempty(giant) && throw(ToyFHE.UsageError("matmul_bsgs_blocks: no Galois key at all -- plain products, use .* and +"))
+    ek1 = (isempty(baby) ? giant[1] : baby[1]).key; keyring = NTT.ring(ek1.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T)
+    cnt = batchsize(cs[1]); ctx = hipring(keyring); n = degree(ℛ)
+    cts = HipVector[pack(ctx, c) for c in cs]
+    pb = HipVector[prepared(gk) for gk in baby]; pg = HipVector[prepared(gk) for gk in giant]     # PREPARED keys only
+    dgs = HipVector[]
+    for m in diags                                                              # one [ng + 1][nb + 1][level][N] per input
+        dparts = HipVector[coeffs_dual(d).parent for row in m for d in row]
+        all(d -> d.count == 1, dparts) || throw(ToyFHE.UsageError("matmul_bsgs_blocks: one polynomial per diagonal"))
+        dg = HipVector{T}(level, n, (ng + 1) * (nb + 1)); on(ctx, (dg,), (dparts...,))
+        GC.@preserve dparts dg for (k, d) in enumerate(dparts)
+            check(ccall((:tfhe_memcpy_d2d, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t),
+                  ctx.handle, dg.ptr + 8 * (k - 1) * level * n, d.ptr, 8 * level * n))
+        end
+        push!(dgs, dg)
+    end
+    bv = bias === nothing ? nothing : coeffs_primal(bias).parent
+    out = HipVector{T}(2 * level, n, cnt)
+    on(ctx, (out,), bv === nothing ? (cts..., dgs..., pb..., pg...) : (cts..., dgs..., pb..., pg..., bv))
+    bkeys = Ptr{UInt64}[k.ptr for k in pb]; bgs = UInt64[gk.galois_element for gk in baby]
+    gkeys = Ptr{UInt64}[k.ptr for k in pg]; ggs = UInt64[gk.galois_element for gk in giant]
+    dptrs = Ptr{UInt64}[d.ptr for d in dgs]; cptrs = Ptr{UInt64}[c.ptr for c in cts]
+    bptr = bv === nothing ? Ptr{UInt64}(0) : bv.ptr
+    GC.@preserve pb pg cts dgs bv out check(ccall((:tfhe_matmul_bsgs_blocks, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Cint, Cint,
+                 Ptr{Ptr{UInt64}}, Ptr{Ptr{UInt64}}, Cint, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, ek1.params isa ModulusRaised ? 1 : 0, bkeys, bgs, nb, gkeys, ggs, ng, length(ek1.key),
+                dptrs, cptrs, nin, bptr, out.ptr, cnt))
+    CipherText{squared_encoding(Enc)}(cs[1].params, unpack(ctx, out, ℛ, 2))
+end
 squared_encoding(::Type{CKKSEncoding{Tscale}}) where {Tscale} = CKKSEncoding{Tscale^2}
 squared_encoding(::Type{E}) where {E} = E
 

@@ -1650,6 +1650,84 @@ def matmul_bsgs(baby_gks, giant_gks, diags, c: CipherText) -> CipherText:
     return CipherText(c.params, res, Fraction(c.scale) ** 2)
 
 
+def matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias=None) -> CipherText:
+    """The block-row product by baby and giant steps in ONE device call (tfhe_matmul_bsgs_blocks): the sum over the inputs cs[m] of
+    matmul_bsgs(baby_gks, giant_gks, diags[m], cs[m]) as a circuit, but with the inner sums of all inputs added BEFORE the giant
+    rotations (len(giant_gks) key switches instead of len(cs) times as many):
+        inner_j = sum_m sum_i diags[m][j][i] .* NTT(r_i(cs[m])),   result = inner_0 + sum_{j >= 1} rotate(giant_gks[j - 1], inner_j) (+ bias)
+    `diags`: one entry per input, each in either form `matmul_bsgs` takes; `cs`: two-element ciphertexts of one ring, level, scale and
+    batch; `bias`: None, or a single plaintext element of that ring encoded at the RESULT's scale (c.scale ** 2), added to component
+    0.  Word for word rotate_many per input -> ONE dot_plain per giant step over all terms -> rotate -> + (-> + bias); not the words
+    of the per-input calls added up (the key switch's contraction rounds once per giant step here).  The result is in the
+    coefficient domain, at the squared scale."""
+    baby_gks, giant_gks, cs, diags = list(baby_gks), list(giant_gks), list(cs), list(diags)
+    if len(diags) != len(cs) or not cs:
+        raise UsageError("matmul_bsgs_blocks: one set of diagonals per input ciphertext, at least one input")
+    if len(cs) > DOT_MAX:
+        raise UsageError(f"matmul_bsgs_blocks: at most {DOT_MAX} inputs per call")
+    c = cs[0]
+    for x in cs:
+        if len(x) != 2:
+            raise AssertionError("rotate takes a 2-element ciphertext")
+        x._need_scale()
+    if len(baby_gks) > DOT_MAX or len(giant_gks) > DOT_MAX:
+        raise UsageError(f"matmul_bsgs: at most {DOT_MAX} baby and {DOT_MAX} giant steps per call")
+    ring, n, batch = c[0].ring, c[0].count, c[0].batch
+    for x in cs[1:]:
+        if x[0].ring != ring or x[1].ring != ring or x.scale != c.scale or x[0].count != n or x[0].batch != batch or x.params is not c.params:
+            raise UsageError("matmul_bsgs_blocks: the inputs are ciphertexts of one ring, level, scale and batch")
+    level = ring.L
+    nb1, ng1 = len(baby_gks) + 1, len(giant_gks) + 1
+    forms = []                                             # per input: (stacked, element(s))
+    for dm in diags:
+        if isinstance(dm, RingElement):
+            if dm.ring != ring or dm.count != ng1 * nb1:
+                raise UsageError("matmul_bsgs: a stacked plaintext element must hold (giant steps + 1) x (baby steps + 1) diagonals")
+            forms.append((True, dm))
+        else:
+            dm = [list(row) for row in dm]
+            if len(dm) != ng1 or any(len(row) != nb1 for row in dm):
+                raise AssertionError("matmul_bsgs: one row of diagonals per giant step plus one, one diagonal per baby step plus one in each")
+            dm = [d for row in dm for d in row]
+            for d in dm:
+                if not isinstance(d, RingElement) or d.ring != ring or d.count != 1:
+                    raise UsageError("matmul_bsgs: the diagonals are single plaintext elements of the ciphertext's ring")
+            forms.append((False, dm))
+    if bias is not None and (not isinstance(bias, RingElement) or bias.ring != ring or bias.count != 1):
+        raise UsageError("matmul_bsgs_blocks: the bias is a single plaintext element of the ciphertexts' ring")
+    gks = baby_gks + giant_gks
+    if gks:
+        params = gks[0].key.params
+        if any(g.key.params is not params for g in gks) or params.relin_window != 0:
+            raise UsageError("hoisted rotations need Galois keys of one parameter set with RNS digits")
+        keyring = gks[0].key.key[0].mask.ring
+        special = isinstance(params, ModulusRaised)
+    else:
+        keyring, special = ring, False
+    if keyring.idx != list(range(keyring.L)) or ring.idx != list(range(level)):
+        raise UsageError("ciphertext ring is not a prefix of the key ring")
+    prims = [[e.coeffs_primal() for e in x.cs] for x in cs]   # all before the hand-over (see keyswitch)
+    duals = [[d.coeffs_dual()] if stacked else [e.coeffs_dual() for e in d] for stacked, d in forms]
+    bprim = None if bias is None else bias.coeffs_primal()
+    if ring.ctx is not keyring.ctx:
+        if ring.N != keyring.N or ring.moduli != keyring.moduli[:level] or ring.psi != keyring.psi[:level]:
+            raise UsageError("ciphertext and key belong to different rings")
+        keyring.ctx.wait_for(ring.ctx)
+    sz = level * ring.N
+    dgs = [du[0] if stacked else _pack(du, ring, 1, ctx=keyring.ctx) for (stacked, _), du in zip(forms, duals)]   # each [ng1][nb1][level][N]
+    packed = {}                                            # (a ciphertext given twice is packed once: the call takes repeated pointers)
+    cts = [packed[id(x)] if id(x) in packed else packed.setdefault(id(x), _pack(p, ring, n, ctx=keyring.ctx)) for x, p in zip(cs, prims)]
+    out = DeviceBuffer(n * 2 * sz)
+    keyring.ctx.matmul_bsgs_blocks(keyring.L, level, special, [g.prepared().ptr for g in baby_gks], [g.galois_element for g in baby_gks],
+                                   [g.prepared().ptr for g in giant_gks], [g.galois_element for g in giant_gks],
+                                   len(gks[0].key.key) if gks else level, [d.ptr for d in dgs], [t.ptr for t in cts],
+                                   None if bprim is None else bprim.ptr, out.ptr, n)
+    res = _unpack(out, ring, n, 2, batch, primal=True, ctx=keyring.ctx)
+    if ring.ctx is not keyring.ctx:
+        ring.ctx.wait_for(keyring.ctx)
+    return CipherText(c.params, res, Fraction(c.scale) ** 2)
+
+
 class _View:
     """a window into a DeviceBuffer (keeps the parent alive)"""
 
