@@ -17,6 +17,7 @@ import toyfhe_jl_amd as tf
 from oracle import ref_cpu, spec
 from tests import enc_oracle as EO
 from tests import helpers as H
+from tests.matmul_oracle import rotate as ref_rotate
 from tests.test_gpu_encrypt import check_decrypt, check_encrypt, context as enc_context, dev_i32, rand_ints
 from tests.test_gpu_mul_relin import oracle as mul_relin_oracle
 
@@ -73,10 +74,6 @@ def sizes(N):
 
 def galois_elements(N):
     return [pow(3, N // 2 + 3, 2 * N), 2 * N - 1, 3]   # many sign wraps, the conjugation, one step
-
-
-def ref_rotate(ref, level, special, evk, g, ct):
-    return ref.keyswitch(level, special, evk, ref.galois(g, ct.reshape(-1, level, ref.N), idx=range(level)).reshape(ct.shape))
 
 
 # every route of keyswitch_impl / tfhe_rotate_many: generic, k_ks_fused<13>, the two-launch fused form at 2^14, the sub-block fused

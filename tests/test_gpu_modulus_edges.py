@@ -190,11 +190,11 @@ def test_sums_with_every_operand_q_minus_1(name):
 
 
 @pytest.mark.parametrize("raised", [True, False])
-@pytest.mark.parametrize("name,n_rot", [("top61", 3), ("top60", 5), ("fold62", 2)])
+@pytest.mark.parametrize("name,n_rot", [("top61", 3), ("top60", 5), ("fold62", 2), ("top62", 2)])
 def test_matmul_diag_at_the_top_of_the_bit_lengths(name, n_rot, raised):
     """tfhe_matmul_diag (one sum of k_md_acc with a special prime, of k_md_acc_dense without: n_rot + 1 products, more than the chunk
-    of 2^(62 - bits)) against rotate_many and dot_plain, word for word, on a ring of the largest primes below 2^61 / 2^60 and the
-    fold primes, diagonals of q - 1"""
+    of 2^(62 - bits)) against rotate_many and dot_plain, word for word, on a ring of the largest primes below 2^62 (chunk 1: a fold
+    before every rotated term) / 2^61 / 2^60 and the fold primes, diagonals of q - 1"""
     N = 1 << 10
     R = tf.NegacyclicRing(N, edge(name, 3, N))
     assert n_rot + 1 > H.sum_chunk(min(q.bit_length() for q in R.moduli))      # every limb folds at least once
