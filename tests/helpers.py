@@ -96,6 +96,30 @@ def primes_above(bound, n, N):
     return out
 
 
+def row_policy_cases():
+    """(logn, q, fp) of the fused row kernels' body tests: the u64 policy at the largest prime below 2^62 and at a 53-bit prime,
+    N = 2^12 and 2^14; the fp64 policy at the top of its class (the largest prime below TFHE_FP_QMAX), N = 2^12, 2^13, 2^14"""
+    out = []
+    for logn in (12, 14):
+        N = 1 << logn
+        out += [(logn, primes_below(Q_LIMIT, 1, N)[0], 0), (logn, primes_above(1 << 52, 1, N)[0], 0)]
+    out += [(logn, primes_below(FP_QMAX, 1, 1 << logn)[0], 1) for logn in (12, 13, 14)]
+    return out
+
+
+def words_mod(rng, q, shape, edge):
+    """random residues, or (edge) every word q - 1"""
+    if edge:
+        return np.full(shape, q - 1, dtype=np.uint64)
+    return (rng.integers(0, 1 << 62, shape, dtype=np.uint64) % np.uint64(q)).astype(np.uint64)
+
+
+def galois_pos(n, g):
+    """the evaluation-domain gather of x -> x^g (modarith.h galois_ntt_pos): the position output k reads, for k < n"""
+    k = np.arange(n, dtype=object)
+    return np.array([int(((g * (2 * int(x) + 1) - 1) >> 1) & (n - 1)) for x in k])
+
+
 def primes_above_ratio(k, bits, n, N):
     """the n smallest NTT-friendly primes above 2^64 / k, all of `bits` bits: there 2^64 mod q = 2^64 - (k - 1) q is
     close to q, the worst case of the high-word fold in k_ks_inner (z' = hi (2^64 mod q) + lo)"""

@@ -77,11 +77,4 @@ int keygen_core_emul_item_stream(int logn, uint64_t q, int fp, const uint64_t* s
     });
 }
 
-// the dynamic LDS bytes the launch of k_evalkey_fused asks for at this size (launch_fused_rows: lds_words<LOGB, LOGT>() * 8); -2 unsupported
-long keygen_core_emul_lds_bytes(int logn) {
-    long bytes = 0;
-    const int rc = by_size<emul>(logn, false, [&](auto& e) { bytes = (long)e.lds.size() * 8; });
-    return rc ? rc : bytes;
-}
-
 }  // extern "C"

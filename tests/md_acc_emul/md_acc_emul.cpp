@@ -1,7 +1,8 @@
-// tests/bsgs_blocks_emul/bsgs_blocks_emul.cpp -- CPU emulation of the accumulations of tfhe_matmul_bsgs_blocks: several inputs chained
-// through the seed.  The bodies of toyfhe.jl_amd/csrc/lazy_sum.h strung together in the order of k_md_acc (gather form) and
-// k_md_acc_dense (kernels.h), one "thread" per coefficient, one limb; input 0 runs the unseeded form over whatever `inner` holds, every
-// later input the seeded form (csrc/md_api.inc: matmul_bsgs_run).  TEST INFRASTRUCTURE ONLY.
+// tests/md_acc_emul/md_acc_emul.cpp -- CPU emulation of the accumulations of tfhe_matmul_diag (one output), tfhe_matmul_bsgs (a tile of
+// outputs; both nin = 1) and tfhe_matmul_bsgs_blocks (several inputs chained through the seed).  The bodies of
+// toyfhe.jl_amd/csrc/lazy_sum.h strung together in the order of k_md_acc (gather form) and k_md_acc_dense (kernels.h), one "thread"
+// per coefficient, one limb; input 0 runs the unseeded form over whatever `inner` holds, every later input the seeded form
+// (csrc/md_api.inc: matmul_bsgs_run).  TEST INFRASTRUCTURE ONLY.
 #include <cstddef>
 #include <cstdint>
 #include "../../toyfhe.jl_amd/csrc/host_math.h"
@@ -111,11 +112,11 @@ void gather_inputs(const barrett_t& br, tw_t pinv, u32 n, u32 nrot, u32 ngiant1,
 extern "C" {
 
 // the lazy-reduction chunk of a modulus
-unsigned bsgs_blocks_emul_chunk(uint64_t q) { return lazy_chunk(q); }
+unsigned md_acc_emul_chunk(uint64_t q) { return lazy_chunk(q); }
 
 // x [nin][n], rot [nin][max(nrot, 1)][n], diag [nin][ngiant1][nrot + 1][n] -> inner [ngiant1][n] (whatever it holds on entry is
 // overwritten by input 0).  0, or -1 for a tile the kernels are not built for
-int bsgs_blocks_emul_dense(uint64_t q, int tile, uint32_t n, uint32_t nrot, uint32_t ngiant1, uint32_t nin, const uint64_t* x, const uint64_t* rot,
+int md_acc_emul_dense(uint64_t q, int tile, uint32_t n, uint32_t nrot, uint32_t ngiant1, uint32_t nin, const uint64_t* x, const uint64_t* rot,
                            const uint64_t* diag, uint64_t* inner) {
     const barrett_t br = hostmath::make_barrett(q);
     switch (tile) {
@@ -127,7 +128,7 @@ int bsgs_blocks_emul_dense(uint64_t q, int tile, uint32_t n, uint32_t nrot, uint
 }
 // x [nin][2][n], v [nin][nrot][n][2], u [nin][2][nrot][n], g [nrot] (one key set for every input), diag as above -> inner0, inner1
 // [ngiant1][n].  uscale != 0: the lifts arrive without the factor pinv (a residue below q), which the term applies itself
-int bsgs_blocks_emul_gather(uint64_t q, int tile, int uscale, uint64_t pinv, uint32_t n, uint32_t nrot, uint32_t ngiant1, uint32_t nin,
+int md_acc_emul_gather(uint64_t q, int tile, int uscale, uint64_t pinv, uint32_t n, uint32_t nrot, uint32_t ngiant1, uint32_t nin,
                             const uint64_t* x, const uint64_t* v, const uint64_t* u, const uint64_t* g, const uint64_t* diag, uint64_t* inner0,
                             uint64_t* inner1) {
     const barrett_t br = hostmath::make_barrett(q);

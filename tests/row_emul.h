@@ -72,6 +72,13 @@ int by_size(int logn, bool fp, F&& f) {
     }
     return -2;
 }
+// the dynamic LDS bytes the launch of a fused row kernel asks for at this size (launch_fused_rows: lds_words<LOGB, LOGT>() * 8); -2
+// unsupported.  Every library built on this header exports it (tests/kernel_harness.py lds_bytes).
+extern "C" long row_emul_lds_bytes(int logn) {
+    long bytes = 0;
+    const int rc = by_size<row_emul>(logn, false, [&](auto& e) { bytes = (long)e.lds.size() * 8; });
+    return rc ? rc : bytes;
+}
 // The preamble of an extern "C" emulation function: the tables of the one limb (psi = 0: the minimal root), the tracker reset,
 // f(e) with e.limb() set, the tracker's reading to *max_ratio (0 for the u64 policy).  Returns 0, -1 bad psi, -2 unsupported size,
 // -3 fp64 policy asked for a modulus above TFHE_FP_QMAX.

@@ -5,17 +5,15 @@ accumulator type and keeps four products as well.  Inputs: all 0, all
 p - 1, the centred extremes a transform output may take, rows that force the exact-alpha decision in each conversion, and a few
 thousand random coefficients.  The lanes that reached acc52_redc are checked against the limits its proof states (modarith.h)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import ref_cpu
 from tests import helpers as H
+from tests import kernel_harness as KH
 from tests.emul import emul
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, T = 4096, 65537
 u64p = C.POINTER(C.c_uint64)
 
@@ -26,11 +24,7 @@ LANE_LIMITS = ((1 << 56) + (1 << 52), 1 << 57, 1 << 53, 1 << 57)
 
 @pytest.fixture(scope="module")
 def bodies(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bfv_folded_emul") / "libbfv_folded_emul.so")
-    src = os.path.join(ROOT, "tests", "bfv_folded_emul", "bfv_folded_emul.cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-shared", "-o", so, src])
-    L = C.CDLL(so)
+    L = KH.build_emul("bfv_folded_emul/bfv_folded_emul.cpp", tmp_path_factory.mktemp("bfv_folded_emul"))
     L.bfvf_run.argtypes = [u64p, C.c_int, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int64, u64p, u64p, u64p, C.POINTER(C.c_int64)]
     L.bfvf_run.restype = C.c_int
     L.bfvf_kappa.argtypes = [u64p, C.c_int, u64p, C.c_int, C.c_uint64, u64p, u64p, C.POINTER(C.c_double)]

@@ -7,9 +7,6 @@ kernel the entry points launch use no scratch memory and fit the LDS."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
@@ -17,6 +14,7 @@ import pytest
 from oracle import ref_cpu
 from tests import enc_oracle as EO
 from tests import helpers as H
+from tests import kernel_harness as KH
 from tests import test_julia_shim_cpu as shim
 from toyfhe_jl_amd import native
 
@@ -125,17 +123,15 @@ def test_decrypt_argument_validation_precedes_device_use():
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("enc_core_emul") / "libenc_core_emul.so")
-    src = os.path.join(ROOT, "tests", "enc_core_emul", "enc_core_emul.cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-shared", "-o", so, src])
-    L = C.CDLL(so)
+    L = KH.build_emul("enc_core_emul/enc_core_emul.cpp", tmp_path_factory.mktemp("enc_core_emul"))
     vp, dp = C.c_void_p, C.POINTER(C.c_double)
     L.enc_core_emul_encrypt.argtypes = [C.c_int, C.c_uint64, C.c_int, vp, vp, C.c_uint64, vp, vp, dp]
     L.enc_core_emul_decrypt.argtypes = [C.c_int, C.c_uint64, C.c_int, vp, vp, C.c_int, C.c_int, vp, dp]
     L.enc_core_emul_encrypt.restype = L.enc_core_emul_decrypt.restype = C.c_int
 
     class E:
+        lib = L
+
         @staticmethod
         def encrypt(logn, q, fp, pk, rand, mult_e, msg):
             pk, rand = np.ascontiguousarray(pk, dtype=np.uint64), np.ascontiguousarray(rand, dtype=np.int32)
@@ -156,17 +152,6 @@ def emul(tmp_path_factory):
     return E
 
 
-def _cases():
-    """(logn, q, fp): the u64 policy at the largest prime below 2^62 and at a 53-bit prime, N = 2^12 and 2^14; the fp64 policy at
-    the top of its class (the largest prime below TFHE_FP_QMAX), N = 2^12, 2^13, 2^14"""
-    out = []
-    for logn in (12, 14):
-        N = 1 << logn
-        out += [(logn, H.primes_below(H.Q_LIMIT, 1, N)[0], 0), (logn, H.primes_above(1 << 52, 1, N)[0], 0)]
-    out += [(logn, H.primes_below(H.FP_QMAX, 1, 1 << logn)[0], 1) for logn in (12, 13, 14)]
-    return out
-
-
 FP_LIMIT = 7.9      # fp64arith.h TFHE_FP_LIMIT: |operand| / p admitted into an fp64 product or reduction
 
 
@@ -177,7 +162,7 @@ def _extreme_rand(rng, N):
     return r
 
 
-@pytest.mark.parametrize("logn,q,fp", _cases())
+@pytest.mark.parametrize("logn,q,fp", H.row_policy_cases())
 def test_fused_encrypt_body_matches_the_oracle(emul, logn, q, fp):
     N = 1 << logn
     assert (q < H.FP_QMAX) if fp else (q.bit_length() in (53, 62))
@@ -198,7 +183,7 @@ def test_fused_encrypt_body_matches_the_oracle(emul, logn, q, fp):
 
 @pytest.mark.parametrize("ntt_in", [False, True])
 @pytest.mark.parametrize("polys", [2, 3])
-@pytest.mark.parametrize("logn,q,fp", _cases())
+@pytest.mark.parametrize("logn,q,fp", H.row_policy_cases())
 def test_fused_decrypt_body_matches_the_oracle(emul, logn, q, fp, polys, ntt_in):
     N = 1 << logn
     rng = np.random.default_rng(1000 * logn + 10 * polys + ntt_in + fp)
@@ -217,44 +202,19 @@ def test_fused_decrypt_body_matches_the_oracle(emul, logn, q, fp, polys, ntt_in)
 
 # ---- resources of the gfx950 code objects ------------------------------------------------------------------------------------
 
-LDS_LIMIT = 163840   # bytes of LDS a workgroup may use on gfx950 (160 KiB)
-
-
-def _probe(lb, fp, outdir):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "tests", "enc_core_emul", "resource_probe.hip")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "--cuda-device-only", "-c", src,
-           f"-DPROBE_LB={lb}", f"-DPROBE_FP={fp}", "-o", os.path.join(outdir, f"probe_{lb}_{fp}.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return r.stdout
-
-
-def _dynamic_lds(lb):
-    """what the launch asks for (enc_api.inc): the padded row image lds_words<LOGB, LOGT>() * 8 (ntt_core.h)"""
-    m = (1 << lb) - 1
-    words = (m + 2 * (m >> 6) + (m >> 10) + 1) if lb >= 13 else (m + 4 * (m >> 6) + (m >> 9) + 1)
-    return words * 8
-
-
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc is not installed")
-def test_fused_kernels_use_no_scratch_and_fit_the_lds(tmp_path):
+@KH.needs_hipcc
+def test_fused_kernels_use_no_scratch_and_fit_the_lds(tmp_path, emul):
     """compiler-reported scratch is 0 and static + dynamic LDS <= 163 840 B for every instantiation the two entry points launch"""
     jobs = [(lb, fp) for lb in (12, 13, 14) for fp in (0, 1)]
-    with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
-        logs = list(ex.map(lambda j: _probe(j[0], j[1], str(tmp_path)), jobs))
+    found = KH.probe_all("enc_core_emul/resource_probe.hip", tmp_path, [(f"PROBE_LB={lb}", f"PROBE_FP={fp}") for lb, fp in jobs])
     seen = 0
-    for (lb, fp), log in zip(jobs, logs):
-        blocks = re.split(r"remark: [^\n]*Function Name: ", log)[1:]
-        mine = [b for b in blocks if b.startswith("_Z15k_encrypt_fused") or b.startswith("_Z15k_decrypt_fused")]
-        assert len(mine) == (6 if lb < 14 else 5), (lb, fp, [b.split()[0] for b in mine])   # (2^14: no fused form for 3 NTT-domain components)
-        for b in mine:
-            name = b.split()[0]
-            scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-            static_lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-            vgprs = int(re.search(r" VGPRs: (\d+)", b).group(1))
-            print(f"{name}: {vgprs} VGPRs, scratch {scratch}, static LDS {static_lds}, dynamic LDS {_dynamic_lds(lb)}")
-            assert scratch == 0, (name, scratch)
-            assert static_lds + _dynamic_lds(lb) <= LDS_LIMIT, (name, static_lds, _dynamic_lds(lb))
+    for (lb, fp), kernels in zip(jobs, found):
+        dynamic = KH.lds_bytes(emul.lib, lb)              # what the launch asks for (enc_api.inc)
+        mine = [k for k in kernels if k["name"].startswith(("_Z15k_encrypt_fused", "_Z15k_decrypt_fused"))]
+        assert len(mine) == (6 if lb < 14 else 5), (lb, fp, [k["name"] for k in mine])   # (2^14: no fused form for 3 NTT-domain components)
+        for k in mine:
+            print(f"{k['name']}: {k['vgprs']} VGPRs, scratch {k['scratch']}, static LDS {k['static_lds']}, dynamic LDS {dynamic}")
+            assert k["scratch"] == 0, (k["name"], k["scratch"])
+            assert k["static_lds"] + dynamic <= KH.LDS_LIMIT, (k["name"], k["static_lds"], dynamic)
             seen += 1
     assert seen == 34

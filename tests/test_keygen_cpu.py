@@ -7,15 +7,13 @@ the gfx950 code objects of every fused kernel the entry point launches use no sc
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 from oracle import ref_cpu, spec
 from tests import helpers as H
+from tests import kernel_harness as KH
 from tests import keygen_oracle as KO
 from tests import test_julia_shim_cpu as shim
 from toyfhe_jl_amd import native
@@ -27,7 +25,6 @@ KEY = ("tfhe_evalkey_gen", ["ptr", "int", "ptr", "ptr", "ptr", "int", "ptr", "in
                             "ptr", "ptr", "ptr"])
 I32_BOUND = 2**31 - 1
 FP_LIMIT = 7.9      # fp64arith.h TFHE_FP_LIMIT: |operand| / p admitted into an fp64 product or reduction
-LDS_LIMIT = 163840  # bytes of LDS a workgroup may use on gfx950 (160 KiB)
 
 
 def _err():
@@ -139,11 +136,7 @@ def test_argument_validation_precedes_device_use_in_the_stated_order():
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("keygen_core_emul") / "libkeygen_core_emul.so")
-    src = os.path.join(ROOT, "tests", "keygen_core_emul", "keygen_core_emul.cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-shared", "-o", so, src])
-    L = C.CDLL(so)
+    L = KH.build_emul("keygen_core_emul/keygen_core_emul.cpp", tmp_path_factory.mktemp("keygen_core_emul"))
     vp = C.c_void_p
     L.keygen_core_emul_item.argtypes = [C.c_int, C.c_uint64, C.c_int, vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_double)]
     L.keygen_core_emul_item.restype = C.c_int
@@ -161,7 +154,6 @@ def emul(tmp_path_factory):
                                                C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                                vp, vp, C.POINTER(C.c_double)]
     L.keygen_core_emul_item_stream.restype = C.c_int
-    L.keygen_core_emul_lds_bytes.argtypes, L.keygen_core_emul_lds_bytes.restype = [C.c_int], C.c_long
 
     def stream(logn, q, fp, s, gamma, gel, sigma, mult_e, seed, stream_mask, stream_noise, mask_poly, noise_poly, stride, m, j, key_limbs):
         s = np.ascontiguousarray(s, dtype=np.uint64)
@@ -170,7 +162,7 @@ def emul(tmp_path_factory):
                                             mask_poly, noise_poly, stride, m, j, key_limbs, out.ctypes.data, noise.ctypes.data, C.byref(ratio))
         assert rc == 0, rc
         return out, noise, ratio.value
-    item.stream, item.lds_bytes = stream, L.keygen_core_emul_lds_bytes
+    item.stream, item.lib = stream, L
     return item
 
 
@@ -292,38 +284,20 @@ def test_the_gadget_tables_of_the_mirror_are_the_oracles():
 
 # ---- resources of the gfx950 code objects ------------------------------------------------------------------------------------
 
-def _probe(lb, fp, outdir):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "tests", "keygen_core_emul", "resource_probe.hip")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "--cuda-device-only", "-c", src,
-           f"-DPROBE_LB={lb}", f"-DPROBE_FP={fp}", "-o", os.path.join(outdir, f"probe_{lb}_{fp}.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return r.stdout
-
-
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc is not installed")
+@KH.needs_hipcc
 def test_fused_kernels_use_no_scratch_and_fit_the_lds(tmp_path, emul):
     """compiler-reported scratch is 0 and static + dynamic LDS <= 163 840 B for every instantiation the entry point launches.
     Resource figures only: nothing here looks at a kernel's instructions."""
     jobs = [(lb, fp) for lb in (12, 13, 14) for fp in (0, 1)]
-    with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
-        logs = list(ex.map(lambda j: _probe(j[0], j[1], str(tmp_path)), jobs))
+    found = KH.probe_all("keygen_core_emul/resource_probe.hip", tmp_path, [(f"PROBE_LB={lb}", f"PROBE_FP={fp}") for lb, fp in jobs])
     seen = 0
-    # what the launch asks for (keygen_api.inc): lds_words<LOGB, LOGT>() * 8, evaluated from ntt_core.h by the compiled emulation
-    dynamic = {lb: emul.lds_bytes(lb) for lb in (12, 13, 14)}
-    assert all(v > (8 << lb) for lb, v in dynamic.items())
-    for (lb, fp), log in zip(jobs, logs):
-        blocks = re.split(r"remark: [^\n]*Function Name: ", log)[1:]
-        mine = [b for b in blocks if b.startswith("_Z15k_evalkey_fused")]
-        assert len(mine) == 2, (lb, fp, [b.split()[0] for b in mine])            # device randomness and given randomness
-        for b in mine:
-            name = b.split()[0]
-            scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-            static_lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-            vgprs = int(re.search(r" VGPRs: (\d+)", b).group(1))
-            print(f"{name}: {vgprs} VGPRs, scratch {scratch}, static LDS {static_lds}, dynamic LDS {dynamic[lb]}")
-            assert scratch == 0, (name, scratch)
-            assert static_lds + dynamic[lb] <= LDS_LIMIT, (name, static_lds, dynamic[lb])
+    for (lb, fp), kernels in zip(jobs, found):
+        dynamic = KH.lds_bytes(emul.lib, lb)              # what the launch asks for (keygen_api.inc)
+        mine = [k for k in kernels if k["name"].startswith("_Z15k_evalkey_fused")]
+        assert len(mine) == 2, (lb, fp, [k["name"] for k in mine])            # device randomness and given randomness
+        for k in mine:
+            print(f"{k['name']}: {k['vgprs']} VGPRs, scratch {k['scratch']}, static LDS {k['static_lds']}, dynamic LDS {dynamic}")
+            assert k["scratch"] == 0, (k["name"], k["scratch"])
+            assert k["static_lds"] + dynamic <= KH.LDS_LIMIT, (k["name"], k["static_lds"], dynamic)
             seen += 1
     assert seen == 12

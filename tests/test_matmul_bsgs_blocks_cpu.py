@@ -1,18 +1,17 @@
 """No-GPU checks of tfhe_matmul_bsgs_blocks (the block-row matrix product by baby and giant steps, several inputs in one device
 call): the symbol is declared, exported, bound by ctypes and by the Julia shim with one signature; every argument check that does not
 need the ring runs on the host before any device use, in the order the header states; the SEEDED accumulation bodies of the k_md_acc
-kernels (csrc/lazy_sum.h), run on the CPU (tests/bsgs_blocks_emul/), chain three inputs into exact big-integer sums at 60-, 61- and
+kernels (csrc/lazy_sum.h), run on the CPU (tests/md_acc_emul/), chain three inputs into exact big-integer sums at 60-, 61- and
 62-bit moduli; the gfx950 code objects of the seeded kernels use no scratch memory; and the mirror's usage errors."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import helpers as H
+from tests import kernel_harness as KH
 from tests import test_julia_shim_cpu as shim
 from toyfhe_jl_amd import native, she
 
@@ -133,23 +132,9 @@ def test_argument_validation_precedes_device_use():
 
 # ---- the seeded accumulation bodies on the CPU -------------------------------------------------------------------------------
 
-def load_emul(tmpdir):
-    """tests/bsgs_blocks_emul/bsgs_blocks_emul.cpp compiled for the host into `tmpdir` and bound"""
-    so = str(tmpdir / "libbsgs_blocks_emul.so")
-    src = os.path.join(ROOT, "tests", "bsgs_blocks_emul", "bsgs_blocks_emul.cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-shared", "-o", so, src])
-    L = C.CDLL(so)
-    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-    L.bsgs_blocks_emul_chunk.argtypes, L.bsgs_blocks_emul_chunk.restype = [u64], C.c_uint
-    L.bsgs_blocks_emul_dense.argtypes, L.bsgs_blocks_emul_dense.restype = [u64, C.c_int, u32, u32, u32, u32, vp, vp, vp, vp], C.c_int
-    L.bsgs_blocks_emul_gather.argtypes, L.bsgs_blocks_emul_gather.restype = [u64, C.c_int, C.c_int, u64, u32, u32, u32, u32] + [vp] * 7, C.c_int
-    return L
-
-
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    return load_emul(tmp_path_factory.mktemp("bsgs_blocks_emul"))
+    return KH.md_acc_emul(tmp_path_factory.mktemp("md_acc_emul"))
 
 
 def _moduli():
@@ -159,17 +144,6 @@ def _moduli():
     return out
 
 
-def _words(rng, q, shape, edge):
-    """random residues, or (edge) every word q - 1"""
-    if edge:
-        return np.full(shape, q - 1, dtype=np.uint64)
-    return (rng.integers(0, 1 << 62, shape, dtype=np.uint64) % np.uint64(q)).astype(np.uint64)
-
-
-def _galois_pos(n, g):
-    return np.array([int(((g * (2 * k + 1) - 1) >> 1) & (n - 1)) for k in range(n)])
-
-
 @pytest.mark.parametrize("q,chunk", _moduli())
 @pytest.mark.parametrize("edge", [False, True])
 def test_seeded_accumulation_bodies_match_exact_sums(emul, q, chunk, edge):
@@ -177,19 +151,19 @@ def test_seeded_accumulation_bodies_match_exact_sums(emul, q, chunk, edge):
     both forms, every output tile (1, 2, 4 giant steps per pass) at whole and ragged tile counts, with random words and with every
     word q - 1 (the seed q - 1 under `chunk` products of (q - 1)^2: the top of the Barrett window).  `inner` arrives full of q - 1:
     input 0 must not read it."""
-    assert emul.bsgs_blocks_emul_chunk(q) == chunk
+    assert emul.md_acc_emul_chunk(q) == chunk
     n, nin = 64, 3
     rng = np.random.default_rng(q % 1000 + edge)
     pinv = int(rng.integers(1, 1 << 29)) % q or 1
     for nrot, ngiant1, tile in ((5, 1, 1), (5, 2, 2), (8, 3, 4), (5, 4, 4), (8, 5, 4), (5, 2, 4), (5, 3, 2), (8, 2, 1)):
         assert nrot + 1 > chunk
-        x = _words(rng, q, (nin, 2, n), edge)
-        diag = _words(rng, q, (nin, ngiant1, nrot + 1, n), edge)
+        x = H.words_mod(rng, q, (nin, 2, n), edge)
+        diag = H.words_mod(rng, q, (nin, ngiant1, nrot + 1, n), edge)
         # the dense form: ROT rows as they are (component 0 of x)
-        rot = _words(rng, q, (nin, nrot, n), edge)
+        rot = H.words_mod(rng, q, (nin, nrot, n), edge)
         x0 = np.ascontiguousarray(x[:, 0])
         inner = np.full((ngiant1, n), q - 1, dtype=np.uint64)
-        assert emul.bsgs_blocks_emul_dense(q, tile, n, nrot, ngiant1, nin, x0.ctypes.data, rot.ctypes.data, diag.ctypes.data, inner.ctypes.data) == 0
+        assert emul.md_acc_emul_dense(q, tile, n, nrot, ngiant1, nin, x0.ctypes.data, rot.ctypes.data, diag.ctypes.data, inner.ctypes.data) == 0
         for j in range(ngiant1):
             want = 0
             for m in range(nin):
@@ -198,11 +172,11 @@ def test_seeded_accumulation_bodies_match_exact_sums(emul, q, chunk, edge):
             assert np.array_equal(inner[j].astype(object), want % q), ("dense", q, nrot, ngiant1, tile, j)
         # the gather form: rotated value V[pi_r k] - U[k] (U scaled by P^-1 in the term where uscale is set)
         gs = np.array([int(g) for g in rng.choice(np.arange(3, 2 * n, 2), nrot, replace=False)], dtype=np.uint64)
-        v = _words(rng, q, (nin, nrot, n, 2), False)
-        u = _words(rng, q, (nin, 2, nrot, n), edge)
+        v = H.words_mod(rng, q, (nin, nrot, n, 2), False)
+        u = H.words_mod(rng, q, (nin, 2, nrot, n), edge)
         for uscale in (0, 1):
             i0, i1 = np.full((ngiant1, n), q - 1, dtype=np.uint64), np.full((ngiant1, n), q - 1, dtype=np.uint64)
-            assert emul.bsgs_blocks_emul_gather(q, tile, uscale, pinv, n, nrot, ngiant1, nin, x.ctypes.data, v.ctypes.data, u.ctypes.data,
+            assert emul.md_acc_emul_gather(q, tile, uscale, pinv, n, nrot, ngiant1, nin, x.ctypes.data, v.ctypes.data, u.ctypes.data,
                                                 gs.ctypes.data, diag.ctypes.data, i0.ctypes.data, i1.ctypes.data) == 0
             for s, got in ((0, i0), (1, i1)):
                 want = [0] * ngiant1
@@ -210,35 +184,26 @@ def test_seeded_accumulation_bodies_match_exact_sums(emul, q, chunk, edge):
                     terms = [x[m][s].astype(object)]
                     for t in range(nrot):
                         uu = u[m][s][t].astype(object) * (pinv if uscale else 1) % q
-                        terms.append((v[m][t][_galois_pos(n, int(gs[t])), s].astype(object) - uu) % q)
+                        terms.append((v[m][t][H.galois_pos(n, int(gs[t])), s].astype(object) - uu) % q)
                     for j in range(ngiant1):
                         want[j] = want[j] + sum(diag[m][j][i].astype(object) * terms[i] for i in range(nrot + 1))
                 for j in range(ngiant1):
                     assert np.array_equal(got[j].astype(object), want[j] % q), ("gather", q, nrot, ngiant1, tile, uscale, s, j)
-    assert emul.bsgs_blocks_emul_dense(q, 3, n, 0, 1, 1, None, None, None, None) == -1
+    assert emul.md_acc_emul_dense(q, 3, n, 0, 1, 1, None, None, None, None) == -1
 
 
 # ---- resources of the gfx950 code objects ------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc is not installed")
+@KH.needs_hipcc
 def test_seeded_accumulation_kernels_use_no_scratch(tmp_path):
     """compiler-reported scratch is 0 for every seeded instantiation tfhe_matmul_bsgs_blocks launches (k_md_acc<., 1, true> holds 16
     accumulators and their seeds next to the gathers of the next rotation: the tightest of them)"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "tests", "bsgs_blocks_emul", "resource_probe.hip")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "--cuda-device-only", "-c", src,
-           "-o", str(tmp_path / "probe.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stdout)[1:]
-    seeded = [b for b in blocks if re.match(r"_Z\d+k_md_acc(ILb[01]ELi[124]ELb1EE|_denseILi[124]ELb1EE)", b)]   # <USCALE, NG, true> / <NG, true>
-    assert len(seeded) == 9, [b.split()[0] for b in blocks]   # 6 x k_md_acc, 3 x k_md_acc_dense
-    for b in seeded:
-        name = b.split()[0]
-        scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-        vgprs, agprs = int(re.search(r" VGPRs: (\d+)", b).group(1)), int(re.search(r"AGPRs: (\d+)", b).group(1))
-        print(f"{name}: {vgprs} VGPRs, {agprs} AGPRs, scratch {scratch}")
-        assert scratch == 0, (name, scratch)
+    kernels = KH.kernel_resources("md_acc_emul/resource_probe.hip", tmp_path, ["PROBE_SEED=1"])
+    seeded = [k for k in kernels if re.match(r"_Z\d+k_md_acc(ILb[01]ELi[124]ELb1EE|_denseILi[124]ELb1EE)", k["name"])]   # <USCALE, NG, true> / <NG, true>
+    assert len(seeded) == 9, [k["name"] for k in kernels]   # 6 x k_md_acc, 3 x k_md_acc_dense
+    for k in seeded:
+        print(f"{k['name']}: {k['vgprs']} VGPRs, {k['agprs']} AGPRs, scratch {k['scratch']}")
+        assert k["scratch"] == 0, (k["name"], k["scratch"])
 
 
 def test_dispatch_launches_exactly_the_probed_forms():

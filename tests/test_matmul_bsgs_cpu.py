@@ -1,18 +1,17 @@
 """No-GPU checks of tfhe_matmul_bsgs (the diagonal matrix product by baby and giant steps, one device call): the symbol is declared,
 exported, bound by ctypes and by the Julia shim with one signature; every argument check that does not need the ring runs on the
 host before any device use; she.bsgs_diagonals regroups a diagonal sum exactly; the accumulation bodies of the k_md_acc kernels
-(csrc/lazy_sum.h) run on the CPU (tests/bsgs_emul/) give exact big-integer sums at 61- and 62-bit moduli with more terms than the
+(csrc/lazy_sum.h) run on the CPU (tests/md_acc_emul/, one input) give exact big-integer sums at 61- and 62-bit moduli with more terms than the
 lazy-reduction chunk; and the gfx950 code objects of the accumulation kernels use no scratch memory."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import helpers as H
+from tests import kernel_harness as KH
 from tests import test_julia_shim_cpu as shim
 from toyfhe_jl_amd import native, she
 
@@ -158,23 +157,9 @@ def test_bsgs_diagonals_on_the_example_layout_give_the_matrix_product(n1):
 
 # ---- the accumulation bodies on the CPU --------------------------------------------------------------------------------------
 
-def load_emul(tmpdir):
-    """tests/bsgs_emul/bsgs_emul.cpp compiled for the host into `tmpdir` and bound"""
-    so = str(tmpdir / "libbsgs_emul.so")
-    src = os.path.join(ROOT, "tests", "bsgs_emul", "bsgs_emul.cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-shared", "-o", so, src])
-    L = C.CDLL(so)
-    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-    L.bsgs_emul_chunk.argtypes, L.bsgs_emul_chunk.restype = [u64], C.c_uint
-    L.bsgs_emul_dense.argtypes, L.bsgs_emul_dense.restype = [u64, C.c_int, u32, u32, u32, vp, vp, vp, vp], C.c_int
-    L.bsgs_emul_gather.argtypes, L.bsgs_emul_gather.restype = [u64, C.c_int, C.c_int, u64, u32, u32, u32] + [vp] * 9, C.c_int
-    return L
-
-
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    return load_emul(tmp_path_factory.mktemp("bsgs_emul"))
+    return KH.md_acc_emul(tmp_path_factory.mktemp("md_acc_emul"))      # (nin inputs chained: nin = 1 here)
 
 
 def _moduli():
@@ -185,35 +170,23 @@ def _moduli():
     return out
 
 
-def _words(rng, q, shape, edge):
-    """random residues, or (edge) every word q - 1"""
-    if edge:
-        return np.full(shape, q - 1, dtype=np.uint64)
-    return (rng.integers(0, 1 << 62, shape, dtype=np.uint64) % np.uint64(q)).astype(np.uint64)
-
-
-def _galois_pos(n, g):
-    k = np.arange(n, dtype=object)
-    return np.array([int(((g * (2 * int(x) + 1) - 1) >> 1) & (n - 1)) for x in k])
-
-
 @pytest.mark.parametrize("q,chunk", _moduli())
 @pytest.mark.parametrize("edge", [False, True])
 def test_accumulation_bodies_match_exact_sums(emul, q, chunk, edge):
     """both forms, every output tile (1, 2, 4 giant steps per pass) at whole and ragged tile counts, n_baby + 1 = 6 and 9 terms: above
     the chunk of the 60-, 61- and 62-bit moduli (4, 2, 1), with random words and with every word q - 1"""
-    assert emul.bsgs_emul_chunk(q) == chunk
+    assert emul.md_acc_emul_chunk(q) == chunk
     n = 64
     rng = np.random.default_rng(q % 1000 + edge)
     pinv = int(rng.integers(1, 1 << 29)) % q or 1
     for nrot, ngiant1, tile in ((5, 1, 1), (5, 2, 2), (8, 3, 4), (5, 4, 4), (8, 5, 4), (0, 3, 4), (5, 2, 4), (5, 3, 2)):
         assert nrot == 0 or nrot + 1 > chunk or chunk == 64
-        x = _words(rng, q, (2, n), edge)
-        diag = _words(rng, q, (ngiant1, nrot + 1, n), edge)
+        x = H.words_mod(rng, q, (2, n), edge)
+        diag = H.words_mod(rng, q, (ngiant1, nrot + 1, n), edge)
         # the dense form: ROT rows as they are
-        rot = _words(rng, q, (max(nrot, 1), n), edge)
+        rot = H.words_mod(rng, q, (max(nrot, 1), n), edge)
         inner = np.zeros((ngiant1, n), dtype=np.uint64)
-        assert emul.bsgs_emul_dense(q, tile, n, nrot, ngiant1, x[0].ctypes.data, rot.ctypes.data, diag.ctypes.data, inner.ctypes.data) == 0
+        assert emul.md_acc_emul_dense(q, tile, n, nrot, ngiant1, 1, x[0].ctypes.data, rot.ctypes.data, diag.ctypes.data, inner.ctypes.data) == 0
         terms = [x[0].astype(object)] + [rot[t].astype(object) for t in range(nrot)]
         for j in range(ngiant1):
             want = sum(diag[j][i].astype(object) * terms[i] for i in range(nrot + 1)) % q
@@ -222,41 +195,33 @@ def test_accumulation_bodies_match_exact_sums(emul, q, chunk, edge):
             continue                                       # (the evaluation-domain form needs a rotation)
         # the gather form: rotated value V[pi_r k] - U[k] (U scaled by P^-1 in the term where uscale is set)
         gs = np.array([int(g) for g in rng.choice(np.arange(3, 2 * n, 2), nrot, replace=False)], dtype=np.uint64)
-        v = _words(rng, q, (nrot, n, 2), False)
-        u = _words(rng, q, (2, nrot, n), edge)
+        v = H.words_mod(rng, q, (nrot, n, 2), False)
+        u = H.words_mod(rng, q, (2, nrot, n), edge)
         for uscale in (0, 1):
             i0, i1 = np.zeros((ngiant1, n), dtype=np.uint64), np.zeros((ngiant1, n), dtype=np.uint64)
-            assert emul.bsgs_emul_gather(q, tile, uscale, pinv, n, nrot, ngiant1, x[0].ctypes.data, x[1].ctypes.data, v.ctypes.data, u[0].ctypes.data,
-                                         u[1].ctypes.data, gs.ctypes.data, diag.ctypes.data, i0.ctypes.data, i1.ctypes.data) == 0
+            assert emul.md_acc_emul_gather(q, tile, uscale, pinv, n, nrot, ngiant1, 1, x.ctypes.data, v.ctypes.data, u.ctypes.data, gs.ctypes.data,
+                                           diag.ctypes.data, i0.ctypes.data, i1.ctypes.data) == 0      # (x [2][n], u [2][nrot][n]: one input's layout)
             for s, got in ((0, i0), (1, i1)):
                 terms = [x[s].astype(object)]
                 for t in range(nrot):
                     uu = u[s][t].astype(object) * (pinv if uscale else 1) % q
-                    terms.append((v[t][_galois_pos(n, int(gs[t])), s].astype(object) - uu) % q)
+                    terms.append((v[t][H.galois_pos(n, int(gs[t])), s].astype(object) - uu) % q)
                 for j in range(ngiant1):
                     want = sum(diag[j][i].astype(object) * terms[i] for i in range(nrot + 1)) % q
                     assert np.array_equal(got[j].astype(object), want), ("gather", q, nrot, ngiant1, tile, uscale, s, j)
-    assert emul.bsgs_emul_dense(q, 3, n, 0, 1, None, None, None, None) == -1
+    assert emul.md_acc_emul_dense(q, 3, n, 0, 1, 1, None, None, None, None) == -1
 
 
 # ---- resources of the gfx950 code objects ------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc is not installed")
+@KH.needs_hipcc
 def test_accumulation_kernels_use_no_scratch(tmp_path):
     """compiler-reported scratch is 0 for every instantiation tfhe_matmul_diag and tfhe_matmul_bsgs launch: the accumulators stay in
     registers"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "tests", "bsgs_emul", "resource_probe.hip")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "--cuda-device-only", "-c", src,
-           "-o", str(tmp_path / "probe.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stdout)[1:]
-    mine = [b for b in blocks if re.match(r"_Z\d+(k_md_acc|k_md_acc_dense|k_bsgs_sum)[IP]", b)]   # (template arguments / first parameter)
-    assert len(mine) == 10, [b.split()[0] for b in mine]   # 6 x k_md_acc, 3 x k_md_acc_dense, k_bsgs_sum
-    for b in mine:
-        name = b.split()[0]
-        scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-        vgprs, agprs = int(re.search(r" VGPRs: (\d+)", b).group(1)), int(re.search(r"AGPRs: (\d+)", b).group(1))
-        print(f"{name}: {vgprs} VGPRs, {agprs} AGPRs, scratch {scratch}")
-        assert scratch == 0, (name, scratch)
+    kernels = KH.kernel_resources("md_acc_emul/resource_probe.hip", tmp_path, ["PROBE_SEED=0"])
+    # <USCALE, NG, false> / <NG, false> / k_bsgs_sum's first parameter
+    mine = [k for k in kernels if re.match(r"_Z\d+(k_md_acc(ILb[01]ELi[124]ELb0EE|_denseILi[124]ELb0EE)|k_bsgs_sumP)", k["name"])]
+    assert len(mine) == 10, [k["name"] for k in kernels]   # 6 x k_md_acc, 3 x k_md_acc_dense, k_bsgs_sum
+    for k in mine:
+        print(f"{k['name']}: {k['vgprs']} VGPRs, {k['agprs']} AGPRs, scratch {k['scratch']}")
+        assert k["scratch"] == 0, (k["name"], k["scratch"])

@@ -11,7 +11,7 @@ import pytest
 import toyfhe_jl_amd as tf
 from oracle import ref_cpu, spec
 from tests import helpers as H
-from tests import test_matmul_bsgs_cpu as bsgs
+from tests import kernel_harness as KH
 from tests.emul import emul
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "toyfhe.jl_amd", "csrc")
@@ -34,7 +34,7 @@ def test_class_thresholds_match_the_engine_sources(tmp_path):
     assert re.search(r'static_assert\(DCH \+ 1 <= 16, "acc52 term budget"\)', k)
     # the chunk of every Barrett-window sum kernel: the rule is written in ONE function (lazy_sum.h lazy_chunk) over all of csrc/
     # (bfv_tables.h's `room = 62 - bits` is the conversions' own rule, below), every such kernel calls it, and compiled for the host
-    # (tests/bsgs_emul/) it gives H.sum_chunk at the smallest and the largest modulus of every bit length
+    # (tests/md_acc_emul/) it gives H.sum_chunk at the smallest and the largest modulus of every bit length
     code = {f: re.sub(r"//[^\n]*", "", _src(f)) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc", ".hip"))}
     rule = r"(?<!room = )62 - bits"
     assert [f for f, text in code.items() if re.search(rule, text)] == ["lazy_sum.h"]
@@ -45,7 +45,7 @@ def test_class_thresholds_match_the_engine_sources(tmp_path):
                       ("kernels.h", "k_md_acc"), ("kernels.h", "k_md_acc_dense")):
         bodies = re.findall(r"\bvoid %s\(.*?\n\}\n" % kernel, code[f], re.S)
         assert len(bodies) == 1 and len(re.findall(r"\bchunk = (?:\(int\))?lazy_chunk\(L\.q\);", bodies[0])) == 1, kernel
-    lazy_chunk = bsgs.load_emul(tmp_path).bsgs_emul_chunk
+    lazy_chunk = KH.md_acc_emul(tmp_path).md_acc_emul_chunk
     for bits in range(2, 63):
         for q in ((1 << bits) - 1, 1 << (bits - 1)):
             assert lazy_chunk(q) == H.sum_chunk(bits), (bits, q)

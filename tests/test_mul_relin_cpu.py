@@ -6,15 +6,13 @@ kernel the entry point launches use no scratch memory and fit the LDS."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 from oracle import ref_cpu
 from tests import helpers as H
+from tests import kernel_harness as KH
 from tests import test_julia_shim_cpu as shim
 from toyfhe_jl_amd import native
 
@@ -98,11 +96,7 @@ def test_argument_validation_precedes_device_use():
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("mul_core_emul") / "libmul_core_emul.so")
-    src = os.path.join(ROOT, "tests", "mul_core_emul", "mul_core_emul.cpp")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-shared", "-o", so, src])
-    L = C.CDLL(so)
+    L = KH.build_emul("mul_core_emul/mul_core_emul.cpp", tmp_path_factory.mktemp("mul_core_emul"))
     u64p = C.POINTER(C.c_uint64)
     L.mul_core_emul.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p]
     L.mul_core_emul.restype = C.c_int
@@ -113,6 +107,7 @@ def emul(tmp_path_factory):
         rc = L.mul_core_emul(logn, q, 0, int(square), int(ntt_in), a.ctypes.data_as(u64p), b.ctypes.data_as(u64p), out.ctypes.data_as(u64p))
         assert rc == 0, rc
         return out
+    run.lib = L
     return run
 
 
@@ -156,44 +151,19 @@ def test_u64_core_body_two_parking_rows_at_2_14(emul):
 
 # ---- resources of the gfx950 code objects ------------------------------------------------------------------------------------
 
-LDS_LIMIT = 163840   # bytes of LDS a workgroup may use on gfx950 (160 KiB)
-
-
-def _probe(lb, fp, outdir):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "tests", "mul_core_emul", "resource_probe.hip")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "--cuda-device-only", "-c", src,
-           f"-DPROBE_LB={lb}", f"-DPROBE_FP={fp}", "-o", os.path.join(outdir, f"probe_{lb}_{fp}.o"), "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return r.stdout
-
-
-def _dynamic_lds(lb, fp):
-    """what the launch asks for (mul_api.inc): the padded row image lds_words<LOGB, LOGT>() * 8 (ntt_core.h)"""
-    m = (1 << lb) - 1
-    words = (m + 2 * (m >> 6) + (m >> 10) + 1) if lb - (lb - 5 if lb >= 13 else lb - 4) == 5 else (m + 4 * (m >> 6) + (m >> 9) + 1)
-    return words * 8
-
-
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc is not installed")
-def test_fused_kernels_use_no_scratch_and_fit_the_lds(tmp_path):
+@KH.needs_hipcc
+def test_fused_kernels_use_no_scratch_and_fit_the_lds(tmp_path, emul):
     """compiler-reported scratch is 0 and static + dynamic LDS <= 163 840 B for every instantiation tfhe_mul_relin launches"""
     jobs = [(lb, fp) for lb in (12, 13, 14) for fp in (0, 1)]
-    with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
-        logs = list(ex.map(lambda j: _probe(j[0], j[1], str(tmp_path)), jobs))
+    found = KH.probe_all("mul_core_emul/resource_probe.hip", tmp_path, [(f"PROBE_LB={lb}", f"PROBE_FP={fp}") for lb, fp in jobs])
     seen = 0
-    for (lb, fp), log in zip(jobs, logs):
-        blocks = re.split(r"remark: [^\n]*Function Name: ", log)[1:]
-        mine = [b for b in blocks if b.startswith("_Z14k_mul_core_int") or b.startswith("_Z16k_bfv_core_fused")]
-        assert len(mine) == (4 if (fp == 0 or lb < 14) else 3), (lb, fp, [b.split()[0] for b in mine])
-        for b in mine:
-            name = b.split()[0]
-            scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))
-            static_lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
-            vgprs = int(re.search(r" VGPRs: (\d+)", b).group(1))
-            print(f"{name}: {vgprs} VGPRs, scratch {scratch}, static LDS {static_lds}, dynamic LDS {_dynamic_lds(lb, fp)}")
-            assert scratch == 0, (name, scratch)
-            assert static_lds + _dynamic_lds(lb, fp) <= LDS_LIMIT, (name, static_lds, _dynamic_lds(lb, fp))
+    for (lb, fp), kernels in zip(jobs, found):
+        dynamic = KH.lds_bytes(emul.lib, lb)              # what the launch asks for (mul_api.inc)
+        mine = [k for k in kernels if k["name"].startswith(("_Z14k_mul_core_int", "_Z16k_bfv_core_fused"))]
+        assert len(mine) == (4 if (fp == 0 or lb < 14) else 3), (lb, fp, [k["name"] for k in mine])
+        for k in mine:
+            print(f"{k['name']}: {k['vgprs']} VGPRs, scratch {k['scratch']}, static LDS {k['static_lds']}, dynamic LDS {dynamic}")
+            assert k["scratch"] == 0, (k["name"], k["scratch"])
+            assert k["static_lds"] + dynamic <= KH.LDS_LIMIT, (k["name"], k["static_lds"], dynamic)
             seen += 1
     assert seen == 23

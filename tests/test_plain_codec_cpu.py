@@ -2,33 +2,23 @@
 tests/plain_emul/plain_emul.cpp runs the very per-coefficient code and host table of the device kernels against the oracle
 (spec.bfv_decode, spec.bgv_decode, spec.bfv_encode, and the noise remainder birem of she.invariant_noise_budget)."""
 import ctypes as C
-import os
 import random
-import re
-import shlex
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import spec
+from tests import kernel_harness as KH
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORDS = 40  # TFHE_MAX_LIMBS: words per noise remainder in the harness output
 u64p = C.POINTER(C.c_uint64)
 
 
-def _makefile_flags():
-    text = open(os.path.join(ROOT, "tests", "emul", "Makefile")).read()
-    return shlex.split(re.search(r"^CXXFLAGS\s*\?=\s*(.*)$", text, flags=re.M).group(1))
-
-
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("plain_emul") / "libplain_emul.so")
-    src = os.path.join(ROOT, "tests", "plain_emul", "plain_emul.cpp")
-    subprocess.check_call(["g++", *_makefile_flags(), "-shared", "-o", so, src])
-    L = C.CDLL(so)
+    # (the warnings and the range tracker tests/emul/Makefile builds the general bodies with)
+    L = KH.build_emul("plain_emul/plain_emul.cpp", tmp_path_factory.mktemp("plain_emul"),
+                      ("-Wall", "-Wno-unused-function", "-DTFHE_EMUL_TRACK_RANGE"))
     L.plain_emul_run.argtypes = [u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, u64p, u64p, C.c_long, C.POINTER(C.c_long)]
     L.plain_emul_km.argtypes = [C.c_int]
     return L

@@ -2,8 +2,8 @@
 // one place in csrc/ where that rule is written: k_dot, k_lincomb, k_lincomb_many and k_dot_view take their chunk from it), and the
 // accumulation bodies of the diagonal products -- NO running sums of ONE value each, tfhe_matmul_diag with NO = 1, tfhe_matmul_bsgs
 // with a tile of up to four giant steps, tfhe_matmul_bsgs_blocks the same seeded with the sums of its earlier inputs.  Plain host /
-// device functions: the kernels (kernels.h: k_md_acc, k_md_acc_dense) string them together with their loads, tests/bsgs_emul/ and
-// tests/bsgs_blocks_emul/ run them on the CPU against exact sums.
+// device functions: the kernels (kernels.h: k_md_acc, k_md_acc_dense) string them together with their loads, tests/md_acc_emul/
+// runs them on the CPU against exact sums.
 //
 // inner_j[k] = sum_{i = 0 .. n_baby} diag[j][i][k] * r_i[k] for the giant steps j of one tile: every r_i[k] is formed once and
 // multiplied into the tile's NO sums; only the diagonal words differ between them.
