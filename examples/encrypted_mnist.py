@@ -145,6 +145,34 @@ def encrypted_matmul_blocks(gk, Ws, xs, B, b, cache=None, name=None):
     return tf.matmul_bsgs_blocks(gk.baby, gk.giant, [bsgs_encoded(gk, W, x, B, cache) for W in Ws], xs, bias)
 
 
+class RectKeys:
+    """the key sets of a rectangular product by extended diagonals (tf.rect_diagonals): baby, giant, and one list of keys per fold step"""
+
+    def __init__(self, n1, baby, giant, folds):
+        self.n1, self.baby, self.giant, self.folds = n1, list(baby), list(giant), [list(g) for g in folds]
+
+
+def encrypted_matmul_rect(gk, W, x, B, b, cache=None, name=None):
+    """the last layer (infer.jl:169-173, a 10 x 64 matrix, .+ b) in one device call (tfhe_matmul_bsgs_fold): 16 extended diagonals and
+    the fold of the four partial sums (tf.rect_diagonals' default: one step of three rotations) instead of the 64 diagonals of the
+    matrix padded to 64 x 64.  Every row r of the result holds logit r mod 16; the
+    bias, replicated the same way and encoded at the result's scale, is added after the fold."""
+    scale2 = x.scale ** 2
+    key = (id(W), "rect", gk.n1, x.ring().L, x.scale)
+    if cache is not None and key in cache:
+        enc, bias = cache[key]
+    else:
+        D = tf.rect_diagonals(W, gk.n1, block=B)[0]
+        enc = tf.ckks_encode(D.reshape(-1, D.shape[-1]).astype(np.complex128), x.ring(), x.scale)
+        enc.coeffs_dual()
+        m = D.shape[0] * D.shape[1]                                 # the row count rounded up to a power of two
+        bp = np.concatenate([np.asarray(b, dtype=np.float64), np.zeros(m - len(b))])
+        bias = tf.ckks_encode(np.repeat(np.tile(bp, W.shape[1] // m), B).astype(np.complex128), x.ring(), scale2)
+        if cache is not None:
+            cache[key] = (enc, bias)
+    return tf.matmul_bsgs_fold(gk.baby, gk.giant, [enc], [x], gk.folds, bias)
+
+
 def add_bias(ct, x, cache=None, name=None):
     """ct .+ bias (infer.jl: the `.+ b` of every layer).  With a cache the bias is encoded once per (layer, level, scale) like the
     weight plaintexts -- each encoding is a host-to-device copy the pass would otherwise wait on -- and added to the first
@@ -171,8 +199,11 @@ def load_model(path=GOLDEN_MODEL):
 
 
 def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None,
-        mul_relin=False, bsgs=0, blocks=False):
-    """`blocks` (with `bsgs`): the first dense layer -- a 64 x 256 matrix over the four squares, .+ b -- as ONE tfhe_matmul_bsgs_blocks
+        mul_relin=False, bsgs=0, blocks=False, rect=False):
+    """`rect` (with `bsgs`): the last layer -- 10 x 64, .+ b -- as ONE tfhe_matmul_bsgs_fold call over 16 extended diagonals and the fold
+    of the four partial sums instead of the full product of the matrix padded to 64 x 64 (the key sets: the square product's baby and
+    giant keys where the steps coincide, new keys for the rest).
+    `blocks` (with `bsgs`): the first dense layer -- a 64 x 256 matrix over the four squares, .+ b -- as ONE tfhe_matmul_bsgs_blocks
     call instead of four tfhe_matmul_bsgs calls, three ciphertext additions and a plaintext addition.
     `bsgs` = n1 > 0: every matrix product as one tfhe_matmul_bsgs call with n1 - 1 baby and ceil(64 / n1) - 1 giant keys (a third
     circuit shape beside the chained loop and the 63 hoisted keys; the other layers as chosen by the remaining switches).
@@ -180,8 +211,8 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
     modswitch(keyswitch(ek, c * c)); same logits, bit for bit.
     `batches` = K ciphertext sets evaluated together (K * B images): every ring element carries a leading batch dimension
     of K, so each device call covers K ciphertexts (the batch the engine shards across GPUs)."""
-    if blocks and not bsgs:
-        raise ValueError("blocks needs bsgs = n1 > 0")
+    if (blocks or rect) and not bsgs:
+        raise ValueError("blocks and rect need bsgs = n1 > 0")
     N = 1 << logn
     B = N // 128                                                   # images per ciphertext
     K = int(batches)
@@ -211,6 +242,12 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
         _, bsteps, gsteps = tf.bsgs_diagonals(np.zeros((64, 1)), int(bsgs), block=B)
         keys = tf.keygen_galois_many(rng, kp.priv, steps=bsteps + gsteps)               # one device call for both key sets
         gk = BsgsKeys(int(bsgs), keys[:len(bsteps)], keys[len(bsteps):])
+        if rect:   # the last layer's own steps: the square product's keys where it has them, new keys for the rest (the fold's)
+            _, rb, rg, rf = tf.rect_diagonals(np.zeros((10, 64)), int(bsgs), block=B)
+            have = dict(zip(bsteps + gsteps, keys))
+            need = sorted({s for s in rb + rg + [s for g in rf for s in g]} - set(have))
+            have.update(zip(need, tf.keygen_galois_many(rng, kp.priv, steps=need)))
+            gk_rect = RectKeys(int(bsgs), [have[s] for s in rb], [have[s] for s in rg], [[have[s] for s in g] for g in rf])
     elif hoisted:
         gk = tf.keygen_galois_many(rng, kp.priv, steps=[k * B for k in range(1, 64)])   # one device call for the 63 keys
     else:
@@ -260,7 +297,10 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
               fq1 = part if fq1 is None else fq1 + part
           fq1 = tf.modswitch(add_bias(fq1, np.repeat(model["fq1_b"], B), cache, "fq1"))
       sq2 = tf.she.mul_relin(ek, fq1, fq1, rescale=True) if mul_relin else tf.modswitch(tf.keyswitch(ek, fq1 * fq1))
-      res = add_bias(encrypted_matmul(gk, W2, sq2, B, cache, fused), np.repeat(np.concatenate([model["fq2_b"], np.zeros(54)]), B), cache, "fq2")
+      if rect:
+          res = encrypted_matmul_rect(gk_rect, model["fq2_w"], sq2, B, model["fq2_b"], cache, "fq2")
+      else:
+          res = add_bias(encrypted_matmul(gk, W2, sq2, B, cache, fused), np.repeat(np.concatenate([model["fq2_b"], np.zeros(54)]), B), cache, "fq2")
       ev1.record(res[0].ring.ctx)
       t_enq = time.perf_counter() - t0                                # every launch of the circuit is enqueued; the device may still be running
       dec = tf.ckks_decode(tf.decrypt(kp, res), res.scale).real       # [K][N/2]
@@ -297,8 +337,10 @@ if __name__ == "__main__":
                     help="each matrix product as one tfhe_matmul_bsgs call: N1 - 1 baby and ceil(64 / N1) - 1 giant Galois keys instead of 63")
     ap.add_argument("--blocks", action="store_true",
                     help="with --bsgs N1: the first dense layer (64 x 256 over the four squares, + bias) as one tfhe_matmul_bsgs_blocks call")
+    ap.add_argument("--rect", action="store_true",
+                    help="with --bsgs N1: the last layer (10 x 64, + bias) as one tfhe_matmul_bsgs_fold call: 16 extended diagonals and a fold")
     a = ap.parse_args()
-    if a.blocks and not a.bsgs:
-        ap.error("--blocks needs --bsgs N1")
+    if (a.blocks or a.rect) and not a.bsgs:
+        ap.error("--blocks and --rect need --bsgs N1")
     run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin, bsgs=a.bsgs,
-        blocks=a.blocks)
+        blocks=a.blocks, rect=a.rect)

@@ -243,6 +243,44 @@ int tfhe_matmul_bsgs_blocks(tfhe_ctx *ctx, int key_limbs, int level, int special
                             const uint64_t *const *giant_evks, const uint64_t *giant_galois, int n_giant, int n_digits,
                             const uint64_t *const *diags, const uint64_t *const *cts, int n_in,
                             const uint64_t *bias, uint64_t *out, int64_t batch);
+/* Rotate and sum, in one call: the sum of a ciphertext with rotations of itself, step by step ("sum of slots"; the fold that closes
+ * the product of a rectangular matrix, below).
+ *     F_0 = ct;   F_{t+1} = F_t + sum_{u < group_sizes[t]} rotate(key_{t,u}, F_t);   out = F_{n_groups}
+ *   evks / galois_elements: HOST arrays over all groups back to back (group 0's keys first): device pointers to PREPARED Galois keys
+ *   (tfhe_galois_key_prepare) and their Galois elements;  group_sizes: HOST array [n_groups], every entry >= 1, their sum <= 64;
+ *   n_groups in [0, 64] (0: out = ct);  ct, out: [batch][2][level][N], coefficient domain; out overlaps nothing.
+ * The result equals, word for word, per group tfhe_rotate_many (prepared) over the group's keys on F_t -> tfhe_add of every result
+ * onto F_t: exact arithmetic on canonical residues, so every path (with a special prime the rotations are summed in the evaluation
+ * domain and inverse-transformed once per group; without one they are summed in the coefficient domain) and every
+ * tfhe_ctx_set_chunk gives the same bits.
+ * Checked on the host before any device use, in this order: null arrays (evks, galois_elements, group_sizes, ct, out); n_groups
+ * outside [0, 64]; a group size below 1; more than 64 keys in all; a null key; an even Galois element; out starting where ct starts
+ * (all TFHE_E_BADARG); then the context; then the level / key-limb rules of tfhe_keyswitch, Galois elements not below 2N and out
+ * overlapping ct anywhere (TFHE_E_BADARG).  batch == 0 does nothing, but still needs a context. */
+int tfhe_rotate_sum(tfhe_ctx *ctx, int key_limbs, int level, int special, const uint64_t *const *evks, const uint64_t *galois_elements,
+                    const int *group_sizes, int n_groups, int n_digits, const uint64_t *ct, uint64_t *out, int64_t batch);
+/* The product of a rectangular matrix, in one call: tfhe_matmul_bsgs_blocks without its bias -> the fold of tfhe_rotate_sum -> the
+ * bias onto component 0.  For an m x n matrix with m | n (m a power of two) the diagonals are the m EXTENDED ones,
+ * e_i[r] = W[r mod m][(r - i) mod n], and log2(n / m) fold steps add the n / m partial sums: m diagonals and log2(n / m) fold keys
+ * instead of n diagonals of the matrix padded to n x n.  Afterwards every row r holds out[r mod m].
+ *   baby_evks .. n_in: as for tfhe_matmul_bsgs_blocks;
+ *   fold_evks / fold_galois / fold_group_sizes / n_fold_groups: as evks / galois_elements / group_sizes / n_groups of tfhe_rotate_sum;
+ *   bias: NULL, or device [level][N], coefficient domain: added to component 0 AFTER the fold (before it, the fold would multiply it);
+ *   out: [batch][2][level][N], coefficient domain.
+ * The result equals, word for word, tfhe_matmul_bsgs_blocks (bias = NULL) -> tfhe_rotate_sum -> tfhe_add of the bias onto component 0,
+ * on every path and for every tfhe_ctx_set_chunk; with n_fold_groups = 0 the words are those of tfhe_matmul_bsgs_blocks.
+ * Checked on the host before any device use, in this order: null arrays (the fold's three among them), a null key among the first
+ * n_baby / n_giant, a null diags[m] or cts[m] among the first n_in; n_baby / n_giant outside [0, 64], n_in outside [1, 64];
+ * n_fold_groups outside [0, 64], a fold group size below 1, more than 64 fold keys in all, a null fold key; an even Galois element
+ * (baby, giant, fold); out starting where any cts[m], diags[m] or bias starts (all TFHE_E_BADARG); then the context; then the
+ * level / key-limb rules of tfhe_keyswitch, Galois elements not below 2N and out overlapping any operand anywhere (TFHE_E_BADARG).
+ * batch == 0 does nothing, but still needs a context. */
+int tfhe_matmul_bsgs_fold(tfhe_ctx *ctx, int key_limbs, int level, int special,
+                          const uint64_t *const *baby_evks, const uint64_t *baby_galois, int n_baby,
+                          const uint64_t *const *giant_evks, const uint64_t *giant_galois, int n_giant, int n_digits,
+                          const uint64_t *const *diags, const uint64_t *const *cts, int n_in,
+                          const uint64_t *const *fold_evks, const uint64_t *fold_galois, const int *fold_group_sizes, int n_fold_groups,
+                          const uint64_t *bias, uint64_t *out, int64_t batch);
 /* the one-time key preparation of the hoisted rotations: evk_out = the Galois key of x -> x^g (layout of tfhe_keyswitch,
  * n_digits components over key_limbs moduli) with every NTT-domain row permuted by g^-1, so that the key products run on the
  * transformed digits of the unrotated ciphertext.  prepared = 0 above takes plain keys and prepares them per call. */

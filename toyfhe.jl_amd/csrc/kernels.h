@@ -2524,6 +2524,70 @@ __global__ __launch_bounds__(256) void k_md_acc(const u64* __restrict__ X, const
         }
     }
 }
+// One step of the rotate-and-sum fold (tfhe_rotate_sum, tfhe_matmul_bsgs_fold) in the evaluation-domain form: the value itself plus
+// its nrot >= 1 rotations, no plaintext factor,
+//     S[b][s][j][k] = X[b][s][j][k] + sum_r ( V[grp_r][j][pi_r k] - U[grp_r][j][k] (x P^-1 if USCALE) ),
+// with X, V, U what md_rotations leaves for k_md_acc.  k_md_acc's walk, for its reasons: one XCD takes the row pair (b, 0, j),
+// (b, 1, j) at a time, so that the two V windows of one rotation stay in one L2; teams for small rows; TFHE_MD_KB coefficients per
+// thread; rotation t + 1 requested before rotation t is added.  Plain modular additions (fold_term): no 128-bit sums, no diagonal
+// words.  One inverse transform of S follows instead of one per rotation.  S: [batch][2][level][N], NTT domain; it may not be X.
+template <bool USCALE>
+__global__ __launch_bounds__(256) void k_md_fold(const u64* __restrict__ X, const u64* __restrict__ V, const u64* __restrict__ U,
+                                                  u64* __restrict__ S, const ntt_limb_t* __restrict__ LT, limb_sel_t sel, rot_tail_arg_t G,
+                                                  rescale_arg_t ra, u32 n, u32 nw, u32 nrot, u32 batch) {
+    constexpr int KB = TFHE_MD_KB;
+    const u32 level = (u32)sel.n;
+    const u32 xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
+    const u32 per = blockDim.x * KB, spt = n / per >= nslot ? nslot : (n / per ? n / per : 1u), teams = nslot / spt, team = slot / spt, ts = slot % spt;
+    if (team >= teams) return;
+    const u32 stride = spt * blockDim.x;
+    const size_t gstride = (size_t)batch * 2;   // groups per rotation
+    struct term_t { u64 v0[KB], v1[KB], u0[KB], u1[KB]; };
+    for (u32 pr = team * 8u + xcd; pr < batch * level; pr += 8u * teams) {
+        const u32 j = pr % level, b = pr / level;
+        const u64 q = LT[sel.idx[j]].q;
+        const tw_t pinv = ra.qlinv[j];
+        const size_t row0 = ((size_t)b * 2 * level + j) * n, row1 = row0 + (size_t)level * n;
+        for (u32 kb = ts * blockDim.x + threadIdx.x; kb < n; kb += stride * KB) {
+            u32 k[KB];
+#pragma unroll
+            for (int i = 0; i < KB; i++) k[i] = kb + (u32)i * stride < n ? kb + (u32)i * stride : kb;   // (a clamped lane repeats kb; not stored)
+            auto fetch = [&](u32 t, term_t& T) {
+                const size_t g0 = (size_t)t * gstride + (size_t)b * 2;
+                const u64 g = G.g[t];
+                const u64x2_t* pv = (const u64x2_t*)(V + epi_pair((u32)(g0 >> 1), j, 0u, nw, n));   // both components of a position: one gather
+                const u64 *pu0 = U + (g0 * level + j) * n, *pu1 = U + ((g0 + 1) * level + j) * n;
+#pragma unroll
+                for (int i = 0; i < KB; i++) {
+                    const u64x2_t vv = pv[galois_ntt_pos(k[i], g, n)];
+                    T.v0[i] = vv.x; T.v1[i] = vv.y; T.u0[i] = pu0[k[i]]; T.u1[i] = pu1[k[i]];
+                }
+            };
+            u64 a0[KB], a1[KB];
+#pragma unroll
+            for (int i = 0; i < KB; i++) { a0[i] = X[row0 + k[i]]; a1[i] = X[row1 + k[i]]; }
+            term_t cur;
+            fetch(0, cur);
+            for (u32 t = 0; t < nrot; t++) {
+                term_t nxt;
+                fetch(t + 1 < nrot ? t + 1 : t, nxt);
+#pragma unroll
+                for (int i = 0; i < KB; i++) {
+                    a0[i] = fold_term<USCALE>(a0[i], cur.v0[i], cur.u0[i], pinv, q);
+                    a1[i] = fold_term<USCALE>(a1[i], cur.v1[i], cur.u1[i], pinv, q);
+                }
+                cur = nxt;
+            }
+#pragma unroll
+            for (int i = 0; i < KB; i++) {
+                if (kb + (u32)i * stride < n) {
+                    S[row0 + k[i]] = a0[i];
+                    S[row1 + k[i]] = a1[i];
+                }
+            }
+        }
+    }
+}
 // rows = batch * 2 * level, row = (b * 2 + s) * level + j; ROT: [nrot][rows][N] (rows_per_rot = rows)
 template <int NG, bool SEED = false>
 __global__ __launch_bounds__(256) void k_md_acc_dense(const u64* __restrict__ X, const u64* __restrict__ ROT, const u64* __restrict__ diag,

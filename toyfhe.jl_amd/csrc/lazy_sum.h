@@ -56,3 +56,9 @@ TFHE_HD u64 gather_term(u64 v, u64 u, tw_t pinv, u64 q) {
     if (USCALE) u = shoup_full(u, pinv, q);
     return submod(v, u, q);
 }
+// one step of the rotate-and-sum fold (k_md_fold): the running sum of a coefficient plus the rotated value of one rotation.  Plain
+// modular additions on canonical residues -- there is no plaintext factor, so nothing is summed lazily
+template <bool USCALE>
+TFHE_HD u64 fold_term(u64 acc, u64 v, u64 u, tw_t pinv, u64 q) {
+    return addmod(acc, gather_term<USCALE>(v, u, pinv, q), q);
+}

@@ -1,5 +1,6 @@
-// md_api.inc -- the diagonal matrix products tfhe_matmul_diag, tfhe_matmul_bsgs and tfhe_matmul_bsgs_blocks: the shared rotation phase
-// (md_plan, md_bufs, md_rotations), its workspace, and the three entry points; included by toyfhe_hip.hip after ks_api.inc, whose key-sum, digit and
+// md_api.inc -- the diagonal matrix products tfhe_matmul_diag, tfhe_matmul_bsgs and tfhe_matmul_bsgs_blocks, the rotate-and-sum fold
+// tfhe_rotate_sum and the rectangular product tfhe_matmul_bsgs_fold: the shared rotation phase (md_plan, md_bufs, md_rotations), its
+// workspace, the fold (md_fold_plan, md_fold_run) and the five entry points; included by toyfhe_hip.hip after ks_api.inc, whose key-sum, digit and
 // rotation helpers (ks_digits_fwd, ks_inner_launch, keyswitch_impl, ks_plan, rotate_many_ws) it calls.  Kernels: kernels.h k_md_*.
 
 // tfhe_matmul_diag, evaluation-domain form: U[grp][j] = NTT_j( [P[grp]] mod q_j ) (x P^-1 unless *scaled comes back false) for
@@ -179,6 +180,19 @@ static md_bufs_t md_bufs(const md_plan_t& P, u64* base, int64_t chunk, size_t N)
     B.end = base + (size_t)chunk * P.rows * N;
     return B;
 }
+// The coefficient tail of the rotation phase (no special prime, or TFHE_MD_COEFF=1; R >= 1): ROT = rotate(gk_r, cin) for every r, in the
+// COEFFICIENT domain, [R][nb][2][level][N] -- where the products transform them next (md_rotations) and the fold adds them as they are
+static int md_rotations_coeff(tfhe_ctx* c, const md_plan_t& P, const uint64_t* const* evks, const u64* cin, int64_t nb, const md_bufs_t& B) {
+    const int R = P.R;
+    int rc = ks_digits_fwd(c, P.A, cin, B.dig, nb);
+    if (rc) return rc;
+    rc = ks_inner_launch(c, P.A, P.Lk, nullptr, B.dig, B.S, nb, evks, R);   // key sums of the unrotated digits against every prepared key
+    if (rc) return rc;
+    rc = run_ntt(c, true, B.S, B.S, (int64_t)R * nb * 2 * P.nw, P.A.w);
+    if (rc) return rc;
+    return launch(c, k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, B.S, cin, B.ROT, c->limbs_dev, P.A, P.ra, P.G, (u32)c->N, (u32)nb,
+                  (u32)((int64_t)R * nb * 2));
+}
 // X = NTT(cin) and, per rotation r: evaluation-domain form -- V in S (k_ks_inner<.., EPI>) and the lifts U in ROT, *scaled telling
 // whether U carries the factor P^-1 already (md_lift_fwd); otherwise NTT(rotate(gk_r, cin)) in ROT
 static int md_rotations(tfhe_ctx* c, const md_plan_t& P, const uint64_t* const* evks, const u64* cin, int64_t nb, const md_bufs_t& B, bool* scaled) {
@@ -203,14 +217,7 @@ static int md_rotations(tfhe_ctx* c, const md_plan_t& P, const uint64_t* const* 
         return md_lift_fwd(c, P.A, P.sl, P.ra, B.PB, B.LF, B.ROT, (int64_t)groups, scaled);
     }
     if (R) {
-        rc = ks_digits_fwd(c, P.A, cin, B.dig, nb);
-        if (rc) return rc;
-        rc = ks_inner_launch(c, P.A, Lk, nullptr, B.dig, B.S, nb, evks, R);   // key sums of the unrotated digits against every prepared key
-        if (rc) return rc;
-        rc = run_ntt(c, true, B.S, B.S, (int64_t)R * nb * 2 * nw, P.A.w);
-        if (rc) return rc;
-        rc = launch(c, k_ks_rot_tail, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, B.S, cin, B.ROT, c->limbs_dev, P.A, P.ra, P.G, n, (u32)nb,
-                    (u32)((int64_t)R * nb * 2));
+        rc = md_rotations_coeff(c, P, evks, cin, nb, B);
         if (rc) return rc;
         rc = run_ntt(c, false, B.ROT, B.ROT, (int64_t)R * nb * 2 * level, P.sl);
         if (rc) return rc;
@@ -283,6 +290,76 @@ static size_t bsgs_nested_bytes(const tfhe_ctx* c, int Lk, int level, int specia
     const size_t tail = P.rot == KS_ROT_HOISTED ? 0 : P.bytes();
     return std::max(tail, rotate_many_ws(c, level, nw, batch).bytes());
 }
+// ---- the rotate-and-sum fold ---------------------------------------------------------------------------------------------------
+// F_0 = the input;  F_{t+1} = F_t + sum_{u < sizes[t]} rotate(key_{t,u}, F_t): log2(n / m) steps of it add up the n / m partial sums a
+// product by m extended diagonals leaves (tfhe_matmul_bsgs_fold), and by itself it is the sum of slots (tfhe_rotate_sum).  One step over
+// a chunk is the rotation phase of a diagonal product over the group's keys (md_rotations) followed by
+//   with a special prime   k_md_fold (the value and its rotations added in the evaluation domain) and ONE inverse transform of the
+//                          sum, 2 level rows per ciphertext instead of 2 level per rotation;
+//   without one            k_bsgs_sum over the rows k_ks_rot_tail left in the coefficient domain (md_rotations_coeff): no transform.
+// Every group goes this way, a group of one included: its other route, the giant steps' prepared-key key switch followed by k_bsgs_sum,
+// is the same key sums and tail plus a pass over the ciphertext, and has not been measured against this one.
+// Exact arithmetic on canonical residues: the words of tfhe_rotate_many(prepared) over the group's keys -> tfhe_add, group by group.
+struct md_fold_t {
+    const uint64_t* const* evks;   // all groups back to back
+    const uint64_t* galois;
+    const int* sizes;
+    int n_groups;
+    std::vector<md_plan_t> plans;  // one per group
+    size_t rows = 0, ntt_rows = 0; // the largest group's (md_plan_t)
+};
+static md_fold_t md_fold_plan(const tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, const uint64_t* galois,
+                              const int* sizes, int n_groups) {
+    md_fold_t F{evks, galois, sizes, n_groups, {}, 0, 0};
+    F.plans.reserve((size_t)n_groups);
+    for (int t = 0, off = 0; t < n_groups; off += sizes[t], t++) {
+        F.plans.push_back(md_plan(c, Lk, level, special, galois + off, sizes[t]));
+        F.rows = std::max(F.rows, F.plans.back().rows);
+        F.ntt_rows = std::max(F.ntt_rows, F.plans.back().ntt_rows);
+    }
+    return F;
+}
+// All steps over one chunk.  `in`: F_0, [nb][2][level][N]; it may be FB[1] (step t reads FB[(t - 1) & 1] and writes FB[t & 1]), the
+// last step writes `out` (+ bias on component 0).  `base`: F.rows rows per ciphertext of the chunk, laid out per group (md_bufs).
+static int md_fold_run(tfhe_ctx* c, const md_fold_t& F, u64* base, int64_t chunk, u64* const FB[2], const u64* in, int64_t nb, const u64* bias,
+                       u64* out) {
+    const size_t N = (size_t)c->N;
+    const u64* src = in;
+    for (int t = 0, off = 0; t < F.n_groups; off += F.sizes[t], t++) {
+        const md_plan_t& P = F.plans[(size_t)t];
+        const md_bufs_t B = md_bufs(P, base, chunk, N);
+        const bool last = t + 1 == F.n_groups;
+        const size_t ct_words = (size_t)nb * 2 * P.level * N;
+        const dim3 rows = row_grid((unsigned)(nb * 2 * P.level), N);
+        u64* dst = last ? out : FB[t & 1];
+        int rc;
+        if (P.eval_form) {
+            bool scaled = true;
+            rc = md_rotations(c, P, F.evks + off, src, nb, B, &scaled);
+            if (rc) return rc;
+            u64* const sum = last && bias ? FB[t & 1] : dst;   // (the bias is a coefficient-domain row: added after the inverse transform)
+            auto fold = scaled ? k_md_fold<false> : k_md_fold<true>;
+            rc = launch(c, fold, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, (const u64*)B.X, (const u64*)B.S, (const u64*)B.ROT, sum, c->limbs_dev, P.sl,
+                        P.G, P.ra, (u32)N, (u32)P.nw, (u32)P.R, (u32)nb);
+            if (rc) return rc;
+            rc = run_ntt(c, true, sum, sum, nb * 2 * P.level, P.sl);
+            if (rc) return rc;
+            if (sum != dst) {
+                rc = launch(c, k_bsgs_sum, rows, dim3(256), 0, (const u64*)sum, (const u64*)sum, dst, c->limbs_dev, P.sl, (u32)N, 0u, ct_words, bias);
+                if (rc) return rc;
+            }
+        } else {
+            rc = md_rotations_coeff(c, P, F.evks + off, src, nb, B);
+            if (rc) return rc;
+            rc = launch(c, k_bsgs_sum, rows, dim3(256), 0, src, (const u64*)B.ROT, dst, c->limbs_dev, P.sl, (u32)N, (u32)P.R, ct_words,
+                        last ? bias : (const u64*)nullptr);
+            if (rc) return rc;
+        }
+        src = dst;
+    }
+    return TFHE_OK;
+}
+
 // the output tile: 4 giant steps per pass, fewer where there are fewer sums (log2)
 static int bsgs_log_tile(int ngiant1) { return ngiant1 >= 3 ? 2 : ngiant1 - 1; }
 // The device side of both entry points, after their host checks: n_in inputs, each with its own diagonals, feed ONE set of inner
@@ -292,16 +369,21 @@ static int bsgs_log_tile(int ngiant1) { return ngiant1 >= 3 ? 2 : ngiant1 - 1; }
 // sum (+ bias on component 0) then run once per chunk, whatever n_in.
 static int matmul_bsgs_run(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby,
                            const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant, const uint64_t* const* diags,
-                           const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out, int64_t batch) {
+                           const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out, int64_t batch, const md_fold_t* fold = nullptr) {
     const size_t N = (size_t)c->N;
     const int ng1 = n_giant + 1;
     const md_plan_t P = md_plan(c, Lk, level, special, baby_galois, n_baby);
-    // One allocation: [ region 0 | the baby phase (md_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ].
+    // One allocation: [ region 0 | the baby phase (md_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N]
+    // (| F [2][chunk][2][level][N] with fold steps) ].
     // Region 0 is the start of the context workspace, which the stand-alone transforms of N > 2^14 and the nested key switch
     // take for themselves (ensure_ws hands out the start of whatever is allocated): sized for the larger of the two, so that a
     // nested ensure_ws neither grows -- moves -- the workspace nor reaches our buffers.  Nothing scales with n_in.
-    const size_t rows = P.rows + (size_t)(ng1 + n_giant) * 2 * level, per_ct = rows * N * 8;
-    const size_t ntt_rows = std::max(P.ntt_rows, (size_t)ng1 * 2 * level);
+    // With fold steps (tfhe_matmul_bsgs_fold) the baby-phase region is as large as the largest fold group needs -- the fold runs when the
+    // baby phase of the chunk is over -- and two ping-pong ciphertext buffers F follow the giant results: the closing sum writes F_0 into
+    // FB[1] instead of `out`, and the last fold step writes `out`, with the bias.
+    const size_t phase_rows = std::max(P.rows, fold ? fold->rows : (size_t)0);
+    const size_t rows = phase_rows + (size_t)(ng1 + n_giant + (fold ? 2 : 0)) * 2 * level, per_ct = rows * N * 8;
+    const size_t ntt_rows = std::max({P.ntt_rows, (size_t)ng1 * 2 * level, fold ? fold->ntt_rows : (size_t)0});
     const md_ws_t W(c, batch, per_ct, [&](int64_t chunk) {
         size_t r0 = c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : 0;
         if (n_giant) r0 = std::max(r0, bsgs_nested_bytes(c, Lk, level, special, chunk));
@@ -311,8 +393,9 @@ static int matmul_bsgs_run(tfhe_ctx* c, int Lk, int level, int special, const ui
     const int64_t chunk = W.chunk;
     const size_t region0 = W.region0;
     const md_bufs_t B = md_bufs(P, W.base(), chunk, N);
-    u64* const INNER = B.end;
+    u64* const INNER = W.base() + (size_t)chunk * phase_rows * N;   // (= B.end without fold steps)
     u64* const GOUT = INNER + (size_t)chunk * ng1 * 2 * level * N;
+    u64* const FB[2] = {GOUT + (size_t)chunk * n_giant * 2 * level * N, GOUT + (size_t)chunk * (n_giant + 1) * 2 * level * N};
     int rc;
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
@@ -352,9 +435,14 @@ static int matmul_bsgs_run(tfhe_ctx* c, int Lk, int level, int special, const ui
                                 giant_galois[j - 1], true, false, true);
             if (rc) return rc;
         }
+        u64* const o = out + (size_t)b0 * 2 * level * N;
         rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)INNER, (const u64*)GOUT,
-                    out + (size_t)b0 * 2 * level * N, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words, (const u64*)bias);
+                    fold ? FB[1] : o, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words, fold ? (const u64*)nullptr : (const u64*)bias);
         if (rc) return rc;
+        if (fold) {
+            rc = md_fold_run(c, *fold, W.base(), chunk, FB, FB[1], nb, bias, o);
+            if (rc) return rc;
+        }
     }
     return TFHE_OK;
 }
@@ -427,4 +515,118 @@ int tfhe_matmul_bsgs_blocks(tfhe_ctx* c, int Lk, int level, int special, const u
             return fail(TFHE_E_BADARG, "out overlaps an operand");
     if (batch == 0) return TFHE_OK;
     return matmul_bsgs_run(c, Lk, level, special, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags, cts, n_in, bias, out, batch);
+}
+
+// ---- rotate-and-sum, and the product of a rectangular matrix ------------------------------------------------------------------------
+// the checks of a fold's host arrays that need no ring, after the null arrays: the group count, the group sizes, their sum, the keys
+static int fold_check_host(const uint64_t* const* evks, const int* sizes, int n_groups) {
+    if (n_groups < 0 || n_groups > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_fold_groups=%d outside [0,%d]", n_groups, TFHE_DOT_MAX);
+    int total = 0;
+    for (int t = 0; t < n_groups; t++) {
+        if (sizes[t] < 1) return fail(TFHE_E_BADARG, "fold group %d has size %d, below 1", t, sizes[t]);
+        if (sizes[t] > TFHE_DOT_MAX || (total += sizes[t]) > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "more than %d fold keys", TFHE_DOT_MAX);
+    }
+    for (int r = 0; r < total; r++)
+        if (!evks[r]) return fail(TFHE_E_BADARG, "null fold key %d", r);
+    return TFHE_OK;
+}
+static int fold_total(const int* sizes, int n_groups) {
+    int total = 0;
+    for (int t = 0; t < n_groups; t++) total += sizes[t];
+    return total;
+}
+int tfhe_rotate_sum(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, const uint64_t* galois, const int* group_sizes,
+                    int n_groups, int n_digits, const uint64_t* ct, uint64_t* out, int64_t batch) {
+    // host checks that need no ring first (nulls, counts, parity, equal starts), then the context, then the ring's
+    if (!evks || !galois || !group_sizes || !ct || !out) return fail(TFHE_E_BADARG, "null argument");
+    int rc = fold_check_host(evks, group_sizes, n_groups);
+    if (rc) return rc;
+    const int total = fold_total(group_sizes, n_groups);
+    for (int r = 0; r < total; r++)
+        if ((galois[r] & 1) == 0) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
+    if ((const void*)out == (const void*)ct) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (!c) return fail(TFHE_E_BADARG, "null context");
+    rc = ks_check(c, Lk, level, special, ct, n_digits, ct, 2, out, batch);
+    if (rc) return rc;
+    for (int r = 0; r < total; r++)
+        if ((rc = galois_check(c, galois[r]))) return rc;
+    const size_t N = (size_t)c->N;
+    const size_t ct_bytes = (size_t)batch * 2 * level * N * 8;
+    if (ranges_overlap(out, ct_bytes, ct, ct_bytes)) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (batch == 0) return TFHE_OK;
+    if (n_groups == 0) {   // out = ct
+        const limb_sel_t sl = first_limbs(level);
+        for (int64_t b0 = 0; b0 < batch; b0 += 0x10000) {   // (the row count of one launch stays far below 2^31)
+            const int64_t nb = std::min<int64_t>(0x10000, batch - b0);
+            const u64* s = ct + (size_t)b0 * 2 * level * N;
+            rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, s, s, out + (size_t)b0 * 2 * level * N, c->limbs_dev,
+                        sl, (u32)N, 0u, (size_t)0, (const u64*)nullptr);
+            if (rc) return rc;
+        }
+        return TFHE_OK;
+    }
+    const md_fold_t F = md_fold_plan(c, Lk, level, special, evks, galois, group_sizes, n_groups);
+    // One allocation: [ region 0 | the rotation phase of the largest group (md_bufs) | two ping-pong ciphertext buffers F ].
+    const size_t rows = F.rows + (size_t)2 * 2 * level;
+    const md_ws_t W(c, batch, rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * F.ntt_rows * N * 8 : (size_t)0; });
+    if (W.rc) return W.rc;
+    const int64_t chunk = W.chunk;
+    u64* const F0 = W.base() + (size_t)chunk * F.rows * N;
+    u64* const FB[2] = {F0, F0 + (size_t)chunk * 2 * level * N};
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        rc = md_fold_run(c, F, W.base(), chunk, FB, ct + (size_t)b0 * 2 * level * N, nb, nullptr, out + (size_t)b0 * 2 * level * N);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
+
+// out = fold( sum_m M_m x_m ) + bias: tfhe_matmul_bsgs_blocks without its bias, the fold steps over the chunk's result while it is
+// still in the workspace, and the bias -- AFTER the fold, which would multiply it -- with the last step's store.  For an m x n matrix,
+// m | n, the diagonals are the m extended ones and the fold's log2(n / m) steps add up the n / m partial sums (she.rect_diagonals).
+int tfhe_matmul_bsgs_fold(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby,
+                          const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant, int n_digits,
+                          const uint64_t* const* diags, const uint64_t* const* cts, int n_in, const uint64_t* const* fold_evks,
+                          const uint64_t* fold_galois, const int* fold_group_sizes, int n_fold_groups, const uint64_t* bias, uint64_t* out,
+                          int64_t batch) {
+    // the checks of tfhe_matmul_bsgs_blocks, in its order, with the fold's among them
+    if (!baby_evks || !baby_galois || !giant_evks || !giant_galois || !diags || !cts || !fold_evks || !fold_galois || !fold_group_sizes || !out)
+        return fail(TFHE_E_BADARG, "null argument");
+    const auto within = [](int n) { return n < 0 ? 0 : (n > TFHE_DOT_MAX ? TFHE_DOT_MAX : n); };   // (an array is read no further than a valid count reaches)
+    for (int r = 0; r < within(n_baby); r++)
+        if (!baby_evks[r]) return fail(TFHE_E_BADARG, "null baby key %d", r);
+    for (int r = 0; r < within(n_giant); r++)
+        if (!giant_evks[r]) return fail(TFHE_E_BADARG, "null giant key %d", r);
+    for (int m = 0; m < within(n_in); m++) {
+        if (!diags[m]) return fail(TFHE_E_BADARG, "null diagonals of input %d", m);
+        if (!cts[m]) return fail(TFHE_E_BADARG, "null ciphertext of input %d", m);
+    }
+    if (n_baby < 0 || n_baby > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_baby=%d outside [0,%d]", n_baby, TFHE_DOT_MAX);
+    if (n_giant < 0 || n_giant > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_giant=%d outside [0,%d]", n_giant, TFHE_DOT_MAX);
+    if (n_in < 1 || n_in > TFHE_DOT_MAX) return fail(TFHE_E_BADARG, "n_in=%d outside [1,%d]", n_in, TFHE_DOT_MAX);
+    int rc = fold_check_host(fold_evks, fold_group_sizes, n_fold_groups);
+    if (rc) return rc;
+    const int n_fold = fold_total(fold_group_sizes, n_fold_groups);
+    const auto element = [&](int r) { return r < n_baby ? baby_galois[r] : (r < n_baby + n_giant ? giant_galois[r - n_baby] : fold_galois[r - n_baby - n_giant]); };
+    for (int r = 0; r < n_baby + n_giant + n_fold; r++)
+        if ((element(r) & 1) == 0) return fail(TFHE_E_BADARG, "galois element must be odd and below 2N");
+    if ((const void*)out == (const void*)bias) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    for (int m = 0; m < n_in; m++)
+        if ((const void*)out == (const void*)cts[m] || (const void*)out == (const void*)diags[m]) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (!c) return fail(TFHE_E_BADARG, "null context");
+    rc = ks_check(c, Lk, level, special, diags[0], n_digits, cts[0], 2, out, batch);
+    if (rc) return rc;
+    for (int r = 0; r < n_baby + n_giant + n_fold; r++)
+        if ((rc = galois_check(c, element(r)))) return rc;
+    const size_t N = (size_t)c->N;
+    const size_t ct_bytes = (size_t)batch * 2 * level * N * 8, diag_bytes = (size_t)(n_giant + 1) * (n_baby + 1) * level * N * 8;
+    if (bias && ranges_overlap(out, ct_bytes, bias, (size_t)level * N * 8)) return fail(TFHE_E_BADARG, "out overlaps an operand");
+    for (int m = 0; m < n_in; m++)
+        if (ranges_overlap(out, ct_bytes, cts[m], ct_bytes) || ranges_overlap(out, ct_bytes, diags[m], diag_bytes))
+            return fail(TFHE_E_BADARG, "out overlaps an operand");
+    if (batch == 0) return TFHE_OK;
+    if (n_fold_groups == 0)
+        return matmul_bsgs_run(c, Lk, level, special, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags, cts, n_in, bias, out, batch);
+    const md_fold_t F = md_fold_plan(c, Lk, level, special, fold_evks, fold_galois, fold_group_sizes, n_fold_groups);
+    return matmul_bsgs_run(c, Lk, level, special, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags, cts, n_in, bias, out, batch, &F);
 }

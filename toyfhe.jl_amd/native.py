@@ -129,6 +129,9 @@ def lib():
         "tfhe_matmul_bsgs": [vp, i32, i32, i32, C.POINTER(vp), u64p, i32, C.POINTER(vp), u64p, i32, i32, vp, vp, vp, i64],
         "tfhe_matmul_bsgs_blocks": [vp, i32, i32, i32, C.POINTER(vp), u64p, i32, C.POINTER(vp), u64p, i32, i32, C.POINTER(vp), C.POINTER(vp), i32,
                                     vp, vp, i64],
+        "tfhe_rotate_sum": [vp, i32, i32, i32, C.POINTER(vp), u64p, C.POINTER(i32), i32, i32, vp, vp, i64],
+        "tfhe_matmul_bsgs_fold": [vp, i32, i32, i32, C.POINTER(vp), u64p, i32, C.POINTER(vp), u64p, i32, i32, C.POINTER(vp), C.POINTER(vp), i32,
+                                  C.POINTER(vp), u64p, C.POINTER(i32), i32, vp, vp, i64],
         "tfhe_lincomb_many": [vp, u64p, C.POINTER(vp), i32, C.POINTER(vp), i32, i64, i32, i32p],
         "tfhe_sample_uniform": [vp, i32, u64, C.c_uint32, u64, vp, i64],
         "tfhe_sample_gaussian": [vp, i32, C.c_double, u64, u64, C.c_uint32, u64, vp, i64],
@@ -173,7 +176,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_ctx_set_stream", "tfhe_ctx_sync", "tfhe_ctx_wait_for", "tfhe_ctx_set_ntt_variant", "tfhe_ctx_set_chunk", "tfhe_malloc", "tfhe_free", "tfhe_memcpy_h2d",
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
-    "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
+    "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
     "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
@@ -387,6 +390,32 @@ class Context:
         bg, gg = arr(C.c_uint64, baby_gs), arr(C.c_uint64, giant_gs)
         check(lib().tfhe_matmul_bsgs_blocks(self.h, key_limbs, level, int(bool(special)), bp, bg, len(baby_evks), gp, gg, len(giant_evks), n_digits,
                                             arr(C.c_void_p, diags), arr(C.c_void_p, cts), len(cts), bias, out, batch))
+
+    def rotate_sum(self, key_limbs, level, special, evk_groups, g_groups, n_digits, ct, out, batch):
+        """tfhe_rotate_sum: `evk_groups` / `g_groups` lists of lists -- per fold step the device pointers of its PREPARED Galois keys and
+        their Galois elements; ct, out [batch][2][level][N] (coefficient domain)"""
+        if [len(x) for x in evk_groups] != [len(x) for x in g_groups]:
+            raise AssertionError("tfhe_rotate_sum: one Galois element per key")
+        arr = lambda t, xs: (t * max(1, len(xs)))(*[int(x) for x in xs])     # (never a null array: no group is n = 0)
+        check(lib().tfhe_rotate_sum(self.h, key_limbs, level, int(bool(special)), arr(C.c_void_p, [p for grp in evk_groups for p in grp]),
+                                    arr(C.c_uint64, [g for grp in g_groups for g in grp]), arr(C.c_int, [len(grp) for grp in evk_groups]),
+                                    len(evk_groups), n_digits, ct, out, batch))
+
+    def matmul_bsgs_fold(self, key_limbs, level, special, baby_evks, baby_gs, giant_evks, giant_gs, n_digits, diags, cts, fold_evk_groups,
+                         fold_g_groups, bias, out, batch):
+        """tfhe_matmul_bsgs_fold: matmul_bsgs_blocks' operands, then the fold steps as for rotate_sum; the bias is added after the fold"""
+        if len(diags) != len(cts):
+            raise AssertionError("tfhe_matmul_bsgs_fold: one set of diagonals per input")
+        if [len(x) for x in fold_evk_groups] != [len(x) for x in fold_g_groups]:
+            raise AssertionError("tfhe_matmul_bsgs_fold: one Galois element per key")
+        arr = lambda t, xs: (t * max(1, len(xs)))(*[int(x) for x in xs])     # (never a null array: an empty key set is n = 0)
+        bp, gp = arr(C.c_void_p, baby_evks), arr(C.c_void_p, giant_evks)
+        bg, gg = arr(C.c_uint64, baby_gs), arr(C.c_uint64, giant_gs)
+        fp, fg = arr(C.c_void_p, [p for grp in fold_evk_groups for p in grp]), arr(C.c_uint64, [g for grp in fold_g_groups for g in grp])
+        fs = arr(C.c_int, [len(grp) for grp in fold_evk_groups])
+        check(lib().tfhe_matmul_bsgs_fold(self.h, key_limbs, level, int(bool(special)), bp, bg, len(baby_evks), gp, gg, len(giant_evks), n_digits,
+                                          arr(C.c_void_p, diags), arr(C.c_void_p, cts), len(cts), fp, fg, fs, len(fold_evk_groups), bias, out,
+                                          batch))
 
     def scalar_mul(self, scal, a, dst, count, limbs, idx=None):
         s = (C.c_uint64 * limbs)(*[int(x) for x in scal])

@@ -1660,6 +1660,108 @@ def matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias=None) -> CipherText:
     0.  Word for word rotate_many per input -> ONE dot_plain per giant step over all terms -> rotate -> + (-> + bias); not the words
     of the per-input calls added up (the key switch's contraction rounds once per giant step here).  The result is in the
     coefficient domain, at the squared scale."""
+    return _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, None)
+
+
+def _fold_groups(fold_gk_groups):
+    """the fold steps as a list of non-empty lists of Galois keys, 64 keys at the most"""
+    groups = [list(grp) for grp in fold_gk_groups]
+    if len(groups) > DOT_MAX or sum(len(grp) for grp in groups) > DOT_MAX:
+        raise UsageError(f"rotate_sum: at most {DOT_MAX} fold steps and {DOT_MAX} fold keys per call")
+    if any(not grp for grp in groups):
+        raise UsageError("rotate_sum: a fold step without a key")
+    return groups
+
+
+def rotate_sum(gk_groups, c: CipherText) -> CipherText:
+    """Rotate and sum in ONE device call (tfhe_rotate_sum): F_0 = c, F_{t+1} = F_t + sum_{gk in gk_groups[t]} rotate(gk, F_t), the result
+    the last F.  `gk_groups`: a list of lists of Galois keys, one list per step.  With the keys of the steps s, 2 s, 4 s, ... one per
+    group, the result holds in every slot the sum of the slots s apart ("sum of slots"; the fold that closes a product by extended
+    diagonals, rect_diagonals).  Word for word rotate_many over a group's keys -> + per group; scale and domain are c's."""
+    groups = _fold_groups(gk_groups)
+    if len(c) != 2:
+        raise AssertionError("rotate takes a 2-element ciphertext")
+    gks = [g for grp in groups for g in grp]
+    if not gks:
+        return c
+    params = gks[0].key.params
+    if any(g.key.params is not params for g in gks) or params.relin_window != 0:
+        raise UsageError("hoisted rotations need Galois keys of one parameter set with RNS digits")
+    keyring = gks[0].key.key[0].mask.ring
+    ring, n, batch = c[0].ring, c[0].count, c[0].batch
+    level, special = ring.L, isinstance(params, ModulusRaised)
+    if keyring.idx != list(range(keyring.L)) or ring.idx != list(range(level)):
+        raise UsageError("ciphertext ring is not a prefix of the key ring")
+    prim = [x.coeffs_primal() for x in c.cs]               # before the hand-over (see keyswitch)
+    if ring.ctx is not keyring.ctx:
+        if ring.N != keyring.N or ring.moduli != keyring.moduli[:level] or ring.psi != keyring.psi[:level]:
+            raise UsageError("ciphertext and key belong to different rings")
+        keyring.ctx.wait_for(ring.ctx)
+    ct = _pack(prim, ring, n, ctx=keyring.ctx)
+    out = DeviceBuffer(n * 2 * level * ring.N)
+    keyring.ctx.rotate_sum(keyring.L, level, special, [[g.prepared().ptr for g in grp] for grp in groups],
+                           [[g.galois_element for g in grp] for grp in groups], len(gks[0].key.key), ct.ptr, out.ptr, n)
+    res = _unpack(out, ring, n, 2, batch, primal=True, ctx=keyring.ctx)
+    if ring.ctx is not keyring.ctx:
+        ring.ctx.wait_for(keyring.ctx)
+    return CipherText(c.params, res, c.scale)
+
+
+def matmul_bsgs_fold(baby_gks, giant_gks, diags, cs, fold_gk_groups, bias=None) -> CipherText:
+    """The product of a rectangular matrix in ONE device call (tfhe_matmul_bsgs_fold): matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs)
+    without a bias -> rotate_sum(fold_gk_groups, .) -> + bias, word for word.  With the extended diagonals and the fold steps of
+    rect_diagonals it is W @ x for an m x n matrix, m | n, by m diagonals instead of the n of the matrix padded to n x n; every row r
+    of the result holds (W @ x)[r mod m].  `bias` (at the RESULT's scale, c.scale ** 2) is added AFTER the fold, so it is the bias of
+    the layer as it stands, replicated like the result.  Usage errors as matmul_bsgs_blocks; the result is in the coefficient domain,
+    at the squared scale."""
+    return _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, _fold_groups(fold_gk_groups))
+
+
+def rect_diagonals(W, n1: int, block: int = 1, fold_radix: int = 4):
+    """The diagonals and rotation steps of a RECTANGULAR matrix product, for matmul_bsgs_fold.  W is m0 x n; the input vector has n rows
+    of `block` slots each (row r in slots r block .. r block + block - 1 of n block slots); rotation by s steps acts on the slots as
+    np.roll(x, s), as for bsgs_diagonals.  Returns (D, baby_steps, giant_steps, fold_steps): D, baby_steps and giant_steps as
+    bsgs_diagonals returns them, fold_steps a list of groups of slot steps, one group per fold step (keygen_galois_many makes the
+    keys of a group).
+
+    Wide (m0 <= n): W is padded with zero rows to m, the next power of two, and n / m must be a power of two.  The m EXTENDED
+    diagonals dv[i][r block + c] = Wp[r mod m][(r - i) mod n] leave n / m partial sums m rows apart, which log2(n / m) fold steps add:
+    radix 2 by one key per step, [[m block], [2 m block], ...]; radix 4 by three keys per step, [[s, 2 s, 3 s], [4 s, 8 s, 12 s], ...]
+    with s = m block and one radix-2 group last when log2(n / m) is odd (half the steps, three times the keys and key sums per step).
+    Radix 4 is the default: the fold steps depend on each other, and one step of three rotations measured faster than two steps of
+    one at every size (profiles/LOG.md, matmul_rect), at the price of one more key per pair of steps.
+    Afterwards row r holds (W @ x)[r mod m]: rows m0 <= r mod m < m read zero.  m = n is the square product: no fold step.
+
+    Tall (m0 > n, n | m0): the n extended diagonals dv[i][r block + c] = W[r][(r - i) mod n] over m0 rows, no fold.  The INPUT must
+    be periodic with period n block slots -- row r holding x[r mod n], which is what a wide product leaves behind."""
+    W = np.asarray(W)
+    if W.ndim != 2 or n1 < 1 or block < 1 or fold_radix not in (2, 4):
+        raise AssertionError("rect_diagonals: W is [m0][n], n1 >= 1, block >= 1, fold_radix 2 or 4")
+    m0, n = W.shape
+    if m0 > n:
+        if m0 % n:
+            raise UsageError("rect_diagonals: a tall matrix needs its row count to be a multiple of its column count")
+        r = np.arange(m0)
+        dv = np.stack([np.repeat(W[r, (r - i) % n], block) for i in range(n)])
+        return bsgs_diagonals(dv, n1, block) + ([],)
+    m = 1 << max(0, int(m0 - 1).bit_length())
+    if n % m or (n // m) & (n // m - 1):
+        raise UsageError("rect_diagonals: the column count must be a power of two times the row count rounded up to a power of two")
+    Wp = np.zeros((m, n), dtype=W.dtype)
+    Wp[:m0] = W
+    r = np.arange(n)
+    dv = np.stack([np.repeat(Wp[r % m, (r - i) % n], block) for i in range(m)])
+    folds, s, left = [], m * block, (n // m).bit_length() - 1
+    while left:
+        if fold_radix == 4 and left >= 2:
+            folds.append([s, 2 * s, 3 * s]); s *= 4; left -= 2
+        else:
+            folds.append([s]); s *= 2; left -= 1
+    return bsgs_diagonals(dv, n1, block) + (folds,)
+
+
+def _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, fold_groups):
+    """matmul_bsgs_blocks (fold_groups None) and matmul_bsgs_fold (a list of lists of Galois keys, possibly empty)"""
     baby_gks, giant_gks, cs, diags = list(baby_gks), list(giant_gks), list(cs), list(diags)
     if len(diags) != len(cs) or not cs:
         raise UsageError("matmul_bsgs_blocks: one set of diagonals per input ciphertext, at least one input")
@@ -1695,7 +1797,7 @@ def matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias=None) -> CipherText:
             forms.append((False, dm))
     if bias is not None and (not isinstance(bias, RingElement) or bias.ring != ring or bias.count != 1):
         raise UsageError("matmul_bsgs_blocks: the bias is a single plaintext element of the ciphertexts' ring")
-    gks = baby_gks + giant_gks
+    gks = baby_gks + giant_gks + [g for grp in fold_groups or [] for g in grp]
     if gks:
         params = gks[0].key.params
         if any(g.key.params is not params for g in gks) or params.relin_window != 0:
@@ -1718,10 +1820,14 @@ def matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias=None) -> CipherText:
     packed = {}                                            # (a ciphertext given twice is packed once: the call takes repeated pointers)
     cts = [packed[id(x)] if id(x) in packed else packed.setdefault(id(x), _pack(p, ring, n, ctx=keyring.ctx)) for x, p in zip(cs, prims)]
     out = DeviceBuffer(n * 2 * sz)
-    keyring.ctx.matmul_bsgs_blocks(keyring.L, level, special, [g.prepared().ptr for g in baby_gks], [g.galois_element for g in baby_gks],
-                                   [g.prepared().ptr for g in giant_gks], [g.galois_element for g in giant_gks],
-                                   len(gks[0].key.key) if gks else level, [d.ptr for d in dgs], [t.ptr for t in cts],
-                                   None if bprim is None else bprim.ptr, out.ptr, n)
+    keys = (keyring.L, level, special, [g.prepared().ptr for g in baby_gks], [g.galois_element for g in baby_gks],
+            [g.prepared().ptr for g in giant_gks], [g.galois_element for g in giant_gks], len(gks[0].key.key) if gks else level,
+            [d.ptr for d in dgs], [t.ptr for t in cts])
+    if fold_groups is None:
+        keyring.ctx.matmul_bsgs_blocks(*keys, None if bprim is None else bprim.ptr, out.ptr, n)
+    else:
+        keyring.ctx.matmul_bsgs_fold(*keys, [[g.prepared().ptr for g in grp] for grp in fold_groups],
+                                     [[g.galois_element for g in grp] for grp in fold_groups], None if bprim is None else bprim.ptr, out.ptr, n)
     res = _unpack(out, ring, n, 2, batch, primal=True, ctx=keyring.ctx)
     if ring.ctx is not keyring.ctx:
         ring.ctx.wait_for(keyring.ctx)
