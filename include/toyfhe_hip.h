@@ -85,6 +85,10 @@ int tfhe_ctx_set_ntt_variant(tfhe_ctx *ctx, int variant);
 /* upper bound on the ciphertexts (polynomials, for the samplers and codecs) per internal chunk of every chunked entry point
  * driven through this context; 0 = default.  Same words for every value -- a cross-check knob for tests. */
 int tfhe_ctx_set_chunk(tfhe_ctx *ctx, int chunk);
+/* the context's current long-lived workspace (device pointer and size; NULL / 0 before the first call that needs one).  Reports
+ * state and never allocates -- a diagnostic for tests, which fill the block between calls (tfhe_memset) to show that no entry
+ * point's words depend on what its scratch held.  The block moves when a later call needs a larger one. */
+int tfhe_ctx_workspace(const tfhe_ctx *ctx, void **ptr, size_t *bytes);
 
 /* ---- device memory helpers (for callers without a GPU array package) -------------------------
  * tfhe_malloc / tfhe_free are a size-bucketed recycling allocator (csrc/dev_alloc.h): the reference allocates a fresh array
@@ -341,6 +345,8 @@ int tfhe_bfv_mul_relin(tfhe_bfv_plan *plan, const uint64_t *evk, int n_digits, c
 int tfhe_bfv_plan_set_variant(tfhe_bfv_plan *plan, int variant);
 /* ciphertexts processed per internal chunk (workspace = chunk * (7 nb + 3 ns) * N * 8 bytes); 0 = default (256) */
 int tfhe_bfv_plan_set_chunk(tfhe_bfv_plan *plan, int chunk);
+/* the plan's own workspace, as tfhe_ctx_workspace (the transforms inside a BFV call also use the two contexts' workspaces) */
+int tfhe_bfv_plan_workspace(const tfhe_bfv_plan *plan, void **ptr, size_t *bytes);
 
 /* ---- CKKS / BGV: ciphertext product + relinearisation (+ modswitch) in one call ------------------------------------
  * c1*c2 (rlwe_she.jl:247-262, mul_expand/mul_contract = identity) -> keyswitch(evk, .) (rlwe_she.jl:315-347; ModulusRaised

@@ -81,3 +81,18 @@ def test_argument_validation_precedes_device_use():
     lib = tf.native.lib()
     assert lib.tfhe_ctx_set_chunk(None, 8) == tf.native.E_BADARG and b"null context" in lib.tfhe_last_error()
     assert lib.tfhe_ctx_set_chunk(None, -1) == tf.native.E_BADARG and b"chunk cap" in lib.tfhe_last_error()   # the sign first
+
+
+def test_workspace_accessors_reject_null_arguments():
+    """tfhe_ctx_workspace / tfhe_bfv_plan_workspace only report state: a null owner or a null out pointer is TFHE_E_BADARG, on the
+    host, and what the out pointers held is left alone."""
+    lib = tf.native.lib()
+    block = ctypes.create_string_buffer(8)                  # stands in for an owner; never dereferenced: an out pointer is null
+    owner = ctypes.c_void_p(ctypes.addressof(block))
+    for f in (lib.tfhe_ctx_workspace, lib.tfhe_bfv_plan_workspace):
+        ptr, n = ctypes.c_void_p(1234), ctypes.c_size_t(5678)
+        assert f(None, ctypes.byref(ptr), ctypes.byref(n)) == tf.native.E_BADARG and b"null" in lib.tfhe_last_error()
+        assert f(owner, None, ctypes.byref(n)) == tf.native.E_BADARG and b"null" in lib.tfhe_last_error()
+        assert f(owner, ctypes.byref(ptr), None) == tf.native.E_BADARG and b"null" in lib.tfhe_last_error()
+        assert f(None, None, None) == tf.native.E_BADARG
+        assert (ptr.value, n.value) == (1234, 5678)

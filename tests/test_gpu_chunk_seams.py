@@ -389,6 +389,28 @@ def test_decrypt_phase_across_chunks(logn, bits, combos):
 # ---------------------------------------------------------------------------------------------------
 # CKKS encode / decode, the plain codec, the samplers
 # ---------------------------------------------------------------------------------------------------
+def ckks_encoding_close(slot_row, words, ring, scale, what=None):
+    """one encoding [L][N] against spec.ckks_encode: integers equal up to the rounding of the float transform; -> the words as lists"""
+    N, eps = ring.N, 2.0 ** -53
+    want = spec.poly_to_ints(spec.ckks_encode(list(slot_row), ring, scale), ring)
+    enc = [list(map(int, l)) for l in words]
+    diff = [spec.centred(g - w_, ring.Q) for g, w_ in zip(spec.poly_to_ints(enc, ring), want)]
+    allowed = max(1, int(8 * np.log2(N) * eps * np.abs(slot_row).max() * float(scale)))
+    assert max(abs(d) for d in diff) <= allowed, (what, max(abs(d) for d in diff), allowed)
+    if allowed == 1:
+        assert sum(1 for d in diff if d) <= max(2, N // 20), what
+    return enc
+
+
+def ckks_decoding_close(slot_row, enc, dec_row, ring, scale, what=None):
+    """the device's decoding of `enc` against spec.ckks_decode of the same words, and against the slots that were encoded"""
+    N, eps = ring.N, 2.0 ** -53
+    ref = spec.ckks_decode(enc, ring, scale)
+    tol = 8 * np.log2(N) * eps * max(1.0, np.abs(ref).max()) * 4
+    assert np.abs(dec_row - ref).max() <= tol, (what, np.abs(dec_row - ref).max(), tol)
+    assert np.abs(dec_row - slot_row).max() <= N * 2.0 / float(scale) + tol, what
+
+
 @pytest.mark.parametrize("N", [64, 4096])
 def test_ckks_codec_across_chunks(N):
     """(a): the tolerances of test_ckks_encode_decode_match_oracle on the picks; (b): identical words, the slot doubles as uint64"""
@@ -410,19 +432,8 @@ def test_ckks_codec_across_chunks(N):
         return dslots.to_numpy((BATCH, N))
     res = same_at_every_cap(ctx, encode, denc)
     dec = same_at_every_cap(ctx, decode, dslots).view(np.complex128)            # of the device encoding (denc holds `res` again)
-    eps = 2.0 ** -53
     for b in PICKS:
-        want = spec.poly_to_ints(spec.ckks_encode(list(slots[b]), ring, scale), ring)
-        enc = [list(map(int, l)) for l in res[b]]
-        diff = [spec.centred(g - w_, ring.Q) for g, w_ in zip(spec.poly_to_ints(enc, ring), want)]
-        allowed = max(1, int(8 * np.log2(N) * eps * np.abs(slots[b]).max() * float(scale)))
-        assert max(abs(d) for d in diff) <= allowed, (b, max(abs(d) for d in diff), allowed)
-        if allowed == 1:
-            assert sum(1 for d in diff if d) <= max(2, N // 20), b
-        ref = spec.ckks_decode(enc, ring, scale)
-        tol = 8 * np.log2(N) * eps * max(1.0, np.abs(ref).max()) * 4
-        assert np.abs(dec[b] - ref).max() <= tol, (b, np.abs(dec[b] - ref).max(), tol)
-        assert np.abs(dec[b] - slots[b]).max() <= N * 2.0 / float(scale) + tol, b
+        ckks_decoding_close(slots[b], ckks_encoding_close(slots[b], res[b], ring, scale, b), dec[b], ring, scale, b)
 
 
 def test_plain_codec_across_chunks():

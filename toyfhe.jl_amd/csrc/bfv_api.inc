@@ -253,6 +253,13 @@ int tfhe_bfv_plan_set_chunk(tfhe_bfv_plan* p, int chunk) {
     return TFHE_OK;
 }
 
+int tfhe_bfv_plan_workspace(const tfhe_bfv_plan* p, void** ptr, size_t* bytes) {
+    if (!p || !ptr || !bytes) return fail(TFHE_E_BADARG, "null argument");
+    *ptr = p->ws;
+    *bytes = p->ws_bytes;
+    return TFHE_OK;
+}
+
 int tfhe_bfv_plan_set_variant(tfhe_bfv_plan* p, int variant) {
     if (!p || variant < 0 || variant > 1) return fail(TFHE_E_BADARG, "variant must be 0 (auto) or 1 (general kernels)");
     p->use_fast = (variant == 0);

@@ -743,6 +743,12 @@ int tfhe_ctx_set_chunk(tfhe_ctx* c, int chunk) {
     c->chunk_cap = chunk;
     return TFHE_OK;
 }
+int tfhe_ctx_workspace(const tfhe_ctx* c, void** ptr, size_t* bytes) {
+    if (!c || !ptr || !bytes) return fail(TFHE_E_BADARG, "null argument");
+    *ptr = c->ws;
+    *bytes = c->ws_bytes;
+    return TFHE_OK;
+}
 
 int tfhe_malloc(size_t bytes, void** p) {
     if (!p) return fail(TFHE_E_BADARG, "null out pointer");

@@ -90,6 +90,7 @@ def lib():
         "tfhe_ctx_wait_for": [vp, vp],
         "tfhe_ctx_set_ntt_variant": [vp, i32],
         "tfhe_ctx_set_chunk": [vp, i32],
+        "tfhe_ctx_workspace": [vp, C.POINTER(vp), C.POINTER(sz)],
         "tfhe_malloc": [sz, C.POINTER(vp)],
         "tfhe_free": [vp],
         "tfhe_memcpy_h2d": [vp, vp, sz],
@@ -141,6 +142,7 @@ def lib():
         "tfhe_bfv_plan_destroy": [vp],
         "tfhe_bfv_plan_set_chunk": [vp, i32],
         "tfhe_bfv_plan_set_variant": [vp, i32],
+        "tfhe_bfv_plan_workspace": [vp, C.POINTER(vp), C.POINTER(sz)],
         "tfhe_bfv_mul": [vp, vp, vp, vp, i64],
         "tfhe_bfv_expand": [vp, vp, vp, i64],
         "tfhe_bfv_contract": [vp, vp, vp, i64],
@@ -173,11 +175,11 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "tfhe_last_error", "tfhe_device_count", "tfhe_set_device", "tfhe_ctx_create", "tfhe_ctx_destroy", "tfhe_ctx_psi",
-    "tfhe_ctx_set_stream", "tfhe_ctx_sync", "tfhe_ctx_wait_for", "tfhe_ctx_set_ntt_variant", "tfhe_ctx_set_chunk", "tfhe_malloc", "tfhe_free", "tfhe_memcpy_h2d",
+    "tfhe_ctx_set_stream", "tfhe_ctx_sync", "tfhe_ctx_wait_for", "tfhe_ctx_set_ntt_variant", "tfhe_ctx_set_chunk", "tfhe_ctx_workspace", "tfhe_malloc", "tfhe_free", "tfhe_memcpy_h2d",
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
     "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
-    "tfhe_bfv_plan_set_variant", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
+    "tfhe_bfv_plan_set_variant", "tfhe_bfv_plan_workspace", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
 ]
@@ -296,6 +298,12 @@ class Context:
     def set_chunk(self, n):
         """cap every internal chunk of the chunked entry points at n ciphertexts / polynomials (0 = defaults); same words"""
         check(lib().tfhe_ctx_set_chunk(self.h, int(n)))
+
+    def workspace(self):
+        """(device pointer, bytes) of the context's long-lived workspace as it is now; (0, 0) before the first call that needs one"""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        check(lib().tfhe_ctx_workspace(self.h, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
 
     # ---- raw ops on device pointers (ints) ----
     def nntt(self, src, dst, count, limbs, idx=None):
@@ -544,6 +552,12 @@ class BfvPlan:
 
     def set_variant(self, v):
         check(lib().tfhe_bfv_plan_set_variant(self.h, int(v)))
+
+    def workspace(self):
+        """(device pointer, bytes) of the plan's own workspace as it is now; (0, 0) before the first call that needs one"""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        check(lib().tfhe_bfv_plan_workspace(self.h, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
 
     def mul(self, c1, c2, out, batch):
         check(lib().tfhe_bfv_mul(self.h, c1, c2, out, batch))
