@@ -29,6 +29,16 @@
  *     collector's finalizer thread): tfhe_free takes the allocator's lock and parks the block behind events recorded on every
  *     live context's stream -- it never waits and never touches a context's scratch; the destroy calls synchronise the
  *     object's own stream first and must only not race with a call that is still USING that object.
+ *     tfhe_ctx_destroy DRAINS the context's streams (main and side lane) BEFORE the allocator forgets them: a tfhe_free that arrives
+ *     from another thread while the destroy runs still parks its block behind the context's queued work.  tfhe_bfv_plan_destroy
+ *     drains the main stream and the side lane of both of its contexts.
+ *     Held by: contexts / plans on different threads, first use at once, the thread-local error text --
+ *     tests/test_gpu_threads.py test_four_rings_on_four_threads_first_use_at_once_and_error_text_per_thread; tfhe_free from any
+ *     thread -- test_frees_from_a_finaliser_thread_while_the_producer_keeps_enqueuing; a freed block is not handed out while
+ *     queued work of another stream can touch it -- test_hand_out_waits_for_work_queued_on_another_stream and (the next user a borrowed workspace)
+ *     test_workspace_borrower_takes_the_parked_block_behind_a_stream_wait; destroy drains first --
+ *     test_destroy_drains_before_the_allocator_forgets_the_stream; the allocator's lock, events and stream waits on threads, on
+ *     the CPU under sanitizers -- tests/test_alloc_model_cpu.py.
  *   - a BFV plan over two contexts runs the extension-basis work on ℛbig's stream and the key switch on ℛ's stream and
  *     orders the two with events; it never re-points a context's stream.  Results are ordered on ℛ's stream
  *     (tfhe_ctx_sync(small) waits for them).

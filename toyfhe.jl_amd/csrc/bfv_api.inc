@@ -235,8 +235,14 @@ int tfhe_bfv_plan_create(tfhe_ctx* small, const int32_t* idx_s, int ns, tfhe_ctx
 
 int tfhe_bfv_plan_destroy(tfhe_bfv_plan* p) {
     if (!p) return TFHE_OK;
-    if (p->big && p->big->stream) hipStreamSynchronize(p->big->stream);
-    if (p->small && p->small->stream && (!p->big || p->small->stream != p->big->stream)) hipStreamSynchronize(p->small->stream);
+    // main_stream and the side lane, as tfhe_ctx_destroy does: ctx->stream is the side lane while another thread is inside a forked
+    // call on that context (lanes_t), and the plan's own kernels were enqueued on main_stream
+    auto drain = [](tfhe_ctx* c) {
+        if (c->main_stream) hipStreamSynchronize(c->main_stream);
+        if (c->side_stream) hipStreamSynchronize(c->side_stream);
+    };
+    if (p->big) drain(p->big);
+    if (p->small && p->small != p->big) drain(p->small);
     if (p->order_ev) hipEventDestroy(p->order_ev);
     for (void* d : p->allocs) hipFree(d);
     if (p->tab_dev) hipFree(p->tab_dev);

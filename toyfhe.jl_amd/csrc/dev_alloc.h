@@ -140,21 +140,41 @@ inline void set_stream(hipStream_t* sp, hipStream_t v) {
 
 // move parked blocks whose events have all completed to the ready lists (front of the queue first; stop at the first busy one).
 // Only hipErrorNotReady means "busy": any other status is a device error (fault, reset, a destroyed stream) and comes back to the
-// caller -- a waiting alloc() must not spin on it (r06).
-inline hipError_t poll_locked(dev_state_t& d) {
+// caller -- a waiting alloc() must not spin on it (r06).  The block whose event failed is RETIRED: nothing can tell
+// any more when the work before its release ends, so it never becomes ready; it leaves the queue and the cache's count and goes
+// back to the driver (hipFree synchronises the device -- this is alloc()'s side, never release()'s), its failing event is dropped.
+// Left at the front it would hide every later block for good: no block released after it could ever be reused.
+inline hipError_t poll_locked(state_t& s, dev_state_t& d) {
+    hipError_t rc = hipSuccess;
     while (!d.parked.empty()) {
         parked_t& b = d.parked.front();
-        for (hipEvent_t ev : b.evs) {
-            const hipError_t q = hipEventQuery(ev);
+        hipError_t bad = hipSuccess;
+        size_t n_done = 0;
+        for (; n_done < b.evs.size(); n_done++) {
+            const hipError_t q = hipEventQuery(b.evs[n_done]);
             if (q == hipSuccess) continue;
             (void)hipGetLastError();
-            return q == hipErrorNotReady ? hipSuccess : q;
+            if (q == hipErrorNotReady) return rc;
+            bad = q;
+            break;
+        }
+        if (bad != hipSuccess) {
+            if (rc == hipSuccess) rc = bad;
+            for (size_t i = 0; i < b.evs.size(); i++)
+                if (i != n_done) d.ev_pool.push_back(b.evs[i]);       // (re-recorded before their next use)
+            if (b.p) {
+                d.cached_bytes -= b.bytes;
+                s.cached_bytes -= b.bytes;
+                if (hipFree(b.p) != hipSuccess) (void)hipGetLastError();
+            }
+            d.parked.pop_front();
+            continue;
         }
         for (hipEvent_t ev : b.evs) d.ev_pool.push_back(ev);
         if (b.p) d.ready[b.bytes].push_back(b.p);                // (p == nullptr: the events of a block alloc_ws took while parked)
         d.parked.pop_front();
     }
-    return hipSuccess;
+    return rc;
 }
 // the oldest parked block of exactly `bytes`, queried directly (a busy, unrelated block at the front of the queue does not hide it):
 // *found = one is parked; returns hipSuccess with *out set when its events have completed (the block leaves the queue, its
@@ -181,7 +201,7 @@ inline hipError_t take_parked_locked(dev_state_t& d, size_t bytes, void** out, b
 inline void trim_locked(state_t& s) {
     dev_state_t& d = dev_locked(s, current_device());
     (void)hipDeviceSynchronize();
-    (void)poll_locked(d);
+    (void)poll_locked(s, d);
     for (auto& kv : d.ready)
         for (void* p : kv.second) (void)hipFree(p);
     d.ready.clear();
@@ -244,7 +264,7 @@ inline hipError_t alloc(size_t bytes, void** out) {
             if (s.debug) s.t_trim += now_s() - t0;
         }
     }
-    (void)poll_locked(d);
+    (void)poll_locked(s, d);
     d.last_use[bytes] = ++d.seq;
     auto it = d.ready.find(bytes);
     if ((it == d.ready.end() || it->second.empty()) && d.cached_bytes > d.soft_cached) {
@@ -279,7 +299,7 @@ inline hipError_t alloc(size_t bytes, void** out) {
                 if (spin < 256) std::this_thread::yield();
                 else std::this_thread::sleep_for(std::chrono::microseconds(20));
                 g.lock();
-                if (poll_locked(d) != hipSuccess) break;
+                if (poll_locked(s, d) != hipSuccess) break;
             }
             if (s.debug) s.t_wait += now_s() - tw0;
         }
@@ -320,7 +340,7 @@ inline hipError_t alloc_ws(size_t bytes, hipStream_t stream, void** out, size_t*
         if (s.enabled) {
             const int dev = current_device();
             dev_state_t& d = dev_locked(s, dev);
-            (void)poll_locked(d);
+            (void)poll_locked(s, d);
             size_t best = 0;
             for (auto& kv : d.ready)
                 if (kv.first >= bytes && kv.first <= 2 * bytes && !kv.second.empty() && (best == 0 || kv.first < best)) best = kv.first;

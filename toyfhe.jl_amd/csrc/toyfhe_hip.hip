@@ -681,12 +681,16 @@ int tfhe_ctx_create(int64_t N, int L, const uint64_t* q, const uint64_t* psi, tf
 
 int tfhe_ctx_destroy(tfhe_ctx* c) {
     if (!c) return TFHE_OK;
+    // Drain BEFORE the allocator forgets the stream: while work is still queued here another thread may tfhe_free a buffer that
+    // work reads (its call has returned, so the free is legal), and only a release event recorded on this stream keeps the block
+    // from the next tfhe_malloc.  Once both streams are empty nothing of this context can touch a block any more.
+    if (c->main_stream) hipStreamSynchronize(c->main_stream);
+    if (c->side_stream) hipStreamSynchronize(c->side_stream);
     devalloc::unregister_stream(&c->main_stream);
-    if (c->side_stream) { hipStreamSynchronize(c->side_stream); hipStreamDestroy(c->side_stream); }
+    if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->ev_join) hipEventDestroy(c->ev_join);
     c->stream = c->main_stream;
-    if (c->stream) hipStreamSynchronize(c->stream);
     for (auto* t : c->tabs) hipFree(t);
     for (auto* t : c->ksw_allocs) hipFree(t);
     if (c->limbs_dev) hipFree(c->limbs_dev);
