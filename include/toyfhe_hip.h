@@ -314,6 +314,39 @@ int tfhe_galois_key_prepare(tfhe_ctx *ctx, int key_limbs, int n_digits, uint64_t
 int tfhe_keyswitch_window(tfhe_ctx *ctx, int key_limbs, int level, int special, int window_bits, const uint64_t *evk, int n_windows,
                           const uint64_t *ct, int polys, uint64_t *out, int64_t batch);
 
+/* ---- keyswitch with grouped RNS digits and several special primes (the "hybrid" gadget) ---------------------------------------
+ * tfhe_keyswitch takes one digit per ciphertext limb and at most one special prime: level * (level + 1) forward transforms and
+ * `level` key components of 2 (level + 1) rows.  Here a digit covers `group` limbs and the key ring ends in n_special = k special
+ * primes whose product P should be at least every group modulus: with d = ceil(level / group) digits, d * (level + k) forward
+ * transforms and d key components of 2 (level + k) rows.  Every step is exact arithmetic on canonical residues.
+ *   Key ring: limbs 0..key_limbs-1 of ctx, the last k of them the special primes.  Ciphertext ring: limbs 0..level-1,
+ *   level <= key_limbs - k.  Working limbs W = [0..level-1] + [key_limbs-k..key_limbs-1], nw = level + k.
+ *   Digit g covers limbs G_g = [g group, min((g + 1) group, level)), g < d: the last group may be ragged, and at a level below
+ *   the key's a group is cut at `level`.
+ *   1. digit_g = the centred representative of c[end] modulo Q_g = prod_{i in G_g} q_i -- the exact CRT value with the tie rule of
+ *      signedmod.jl:12-19 (n > Q_g ÷ 2 => n - Q_g) -- reduced into every limb of W: switch(ℛ_W, .) of bfv.jl:202-226 applied to
+ *      the sub-ring of the group; with group = 1 the digit of rlwe_she.jl:326-329.
+ *   2. S_s = P c_s (+ k zero limbs) + sum_g key_{g,s} * digit_g over W; s = 0 uses masked, s = 1 uses mask (rlwe_she.jl:340-344);
+ *      c_2 starts from zero for a 2-element input (rlwe_she.jl:324).
+ *   3. out_s = modswitch (crt.jl:215-228, unsigned c_last) applied k times to S_s, the last special prime first
+ *      = c_s + the k-step contraction of INTT(sum_g ...), which is what is computed.
+ *   evk: [n_digits][2][key_limbs][N], component 0 = mask, 1 = masked, NTT domain; n_digits >= d, the first d components are used.
+ *        Gadget row g holds P mod q_j at the limbs j of group g at the key's own top level and zero elsewhere (the special primes'
+ *        columns are zero): tfhe_evalkey_gen takes it as a table.
+ *   ct: [batch][polys][level][N], polys in {2,3};  out: [batch][2][level][N];  both in the coefficient domain, as for tfhe_keyswitch.
+ * (n_special, group) = (1, 1) gives the words of tfhe_keyswitch(special = 1), (0, 1) those of tfhe_keyswitch(special = 0).
+ * tfhe_rotate_grouped is apply_galois_element (pow2_cyc_rings.jl:321-329) into the workspace followed by the key switch of the copy
+ * (rlwe_she.jl:355-359), ct: [batch][2][level][N].
+ * Checked on the host before any device use, in this order: a null argument; polys outside {2,3}; key_limbs outside [1, L];
+ * n_special outside [0, min(4, key_limbs - 1)]; group < 1 (all TFHE_E_BADARG); level outside [1, key_limbs - n_special]
+ * (TFHE_E_LEVEL_MISMATCH); n_digits < ceil(level / group) (TFHE_E_PARAMS_MISMATCH); level + n_special > 40 (TFHE_E_UNSUPPORTED);
+ * a negative batch (TFHE_E_BADARG); a Galois element that is even or not below 2N (TFHE_E_BADARG).  `out` against `ct` and `evk`:
+ * the rule of tfhe_keyswitch -- none is checked.  batch == 0 does nothing. */
+int tfhe_keyswitch_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *evk, int n_digits,
+                           const uint64_t *ct, int polys, uint64_t *out, int64_t batch);
+int tfhe_rotate_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *evk, int n_digits,
+                        uint64_t galois_element, const uint64_t *ct, uint64_t *out, int64_t batch);
+
 /* ---- CKKS encode / decode (float; ckksencoding.jl:56-97, FixedRational ckks.jl:35-59) -- SURVEY §8(f) ----
  * The ring is limbs 0..level-1 of ctx.  scale = scale_mant * 2^scale_exp2 (2^40 = (1, 40); any positive scale to
  * 2^-63 relative).  slots: [batch][N/2] complex doubles (re, im interleaved), device memory.

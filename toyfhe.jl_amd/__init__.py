@@ -9,7 +9,7 @@ from .native import BfvPlan, Comm, PlainPlan, Context, DeviceBuffer, Event, HipE
 from . import ring, she  # noqa: F401,E402
 from .ring import NegacyclicRing, PlainElement, PlainRing, RingElement, nextprime, plaintext_space  # noqa: F401,E402
 from . import wire  # noqa: F401,E402
-from .she import (DeviceRng, BFVParams, BGVParams, CKKSParams, CipherText, ModulusRaised, apply_galois_element, bsgs_diagonals,  # noqa: F401,E402
+from .she import (DeviceRng, BFVParams, BGVParams, CKKSParams, CipherText, GroupedRaised, ModulusRaised, apply_galois_element, bsgs_diagonals,  # noqa: F401,E402
                   ckks_decode, ckks_encode, decrypt, decrypt_array, enc_mul, encrypt, invariant_noise_budget, keygen, keygen_evalmult, keygen_galois, keygen_galois_many,
                   keyswitch, make_eval_key, matmul_bsgs, matmul_bsgs_blocks, matmul_bsgs_fold, matmul_diag, modswitch, mul_relin, rect_diagonals,
                   rotate, rotate_many, rotate_sum)

@@ -42,11 +42,25 @@ struct conv_tab_t {
     const u64* Aw;
 };
 
+// KMAX != 0 (conv_prepare_n, conv_eval_n): a compile-time bound on the source limbs, T.k <= KMAX -- every loop over them is unrolled
+// and xi is indexed by constants only, so a caller's xi[KMAX] stays in registers (k_ks_group_digits).  KMAX = 0: the loops run to T.k
+// (conv_prepare, conv_eval).
+template <int KMAX, class F>
+TFHE_HD void conv_each_source(const conv_tab_t& T, F&& f) {
+    if constexpr (KMAX != 0) {
+#pragma unroll
+        for (int j = 0; j < KMAX; j++)
+            if (j < T.k) f(j);
+    } else {
+        for (int j = 0; j < T.k; j++) f(j);
+    }
+}
 // Step 1: xi[j*stride] holds residue x_j on entry and ξ_j on exit.  Returns α.
-TFHE_HD u32 conv_prepare(const conv_tab_t& T, u64* xi, int stride, bool centred) {
+template <int KMAX>
+TFHE_HD u32 conv_prepare_n(const conv_tab_t& T, u64* xi, int stride, bool centred) {
     u64 frac = 0;
     u32 carries = 0;
-    for (int j = 0; j < T.k; j++) {
+    conv_each_source<KMAX>(T, [&](int j) {
         u64 x = xi[(size_t)j * stride];
         const u64 aj = T.a[j];
         if (centred) x = addmod(x, T.half[j], aj);
@@ -58,7 +72,7 @@ TFHE_HD u32 conv_prepare(const conv_tab_t& T, u64* xi, int stride, bool centred)
         const u64 s = frac + f;
         carries += (s < f);
         frac = s;
-    }
+    });
     const u64 slack = 2ull * (u64)T.k;
     if (frac + slack >= frac) return carries;  // no wrap possible: α is certain
     // Exact decision: is X = Σ ξ_j (A/a_j) >= (carries+1) A ?  Word-serial subtract, keep the borrow.
@@ -71,7 +85,7 @@ TFHE_HD u32 conv_prepare(const conv_tab_t& T, u64* xi, int stride, bool centred)
     u64 borrow = 0;
     for (int w = 0; w <= T.nwords; w++) {
         if (w < T.nwords) {
-            for (int j = 0; j < T.k; j++) {
+            conv_each_source<KMAX>(T, [&](int j) {
                 const u64 xij = xi[(size_t)j * stride], mw = T.M[(size_t)j * T.nwords + w];
                 const u64 lo = xij * mw, hi = mulhi64(xij, mw);
                 u64 s = acc_lo + lo;
@@ -83,7 +97,7 @@ TFHE_HD u32 conv_prepare(const conv_tab_t& T, u64* xi, int stride, bool centred)
                 c2 += (s < c);
                 acc_hi = s;
                 acc_ex += c2;
-            }
+            });
         }
         const u64 xw = acc_lo;  // word w of X
         acc_lo = acc_hi; acc_hi = acc_ex; acc_ex = 0;
@@ -98,6 +112,7 @@ TFHE_HD u32 conv_prepare(const conv_tab_t& T, u64* xi, int stride, bool centred)
     }
     return carries + (borrow ? 0u : 1u);  // no final borrow  <=>  X >= (carries+1) A
 }
+TFHE_HD u32 conv_prepare(const conv_tab_t& T, u64* xi, int stride, bool centred) { return conv_prepare_n<0>(T, xi, stride, centred); }
 
 // The exact plain lift itself, X - alpha A in [0, A), as T.nwords little-endian 64-bit words (xi, alpha from
 // conv_prepare(…, centred = false)).  Used where the reference takes digits of convert(Integer, x)
@@ -161,30 +176,37 @@ TFHE_HD void window_digits_coeff(const conv_tab_t* T, const u64* c, size_t ls, i
 }
 
 // Step 2: the exact value (plain lift, or centred lift when `centred`) modulo target i.
-TFHE_HD u64 conv_eval(const conv_tab_t& T, const u64* xi, int stride, int i, u32 alpha, bool centred) {
+template <int KMAX>
+TFHE_HD u64 conv_eval_n(const conv_tab_t& T, const u64* xi, int stride, int i, u32 alpha, bool centred) {
     const barrett_t& bt = T.t[i];
     u64 r;
     const int cf = T.copy_from[i];
     if (cf >= 0) {
         // target equals a source modulus: x mod a_j is the stored residue; recover it from ξ_j
         // (ξ_j = x'_j inv_j  =>  x'_j = ξ_j (A/a_j) mod a_j = ξ_j C[j][i] mod t_i)
-        r = mulmod(xi[(size_t)cf * stride], T.C[(size_t)cf * T.m + i], bt);
+        u64 xc = KMAX ? 0 : xi[(size_t)cf * stride];
+#pragma unroll
+        for (int j = 0; j < KMAX; j++) xc |= xi[(size_t)j * stride] & (0 - (u64)(j == cf));   // (a mask, not an index: xi stays in registers)
+        r = mulmod(xc, T.C[(size_t)cf * T.m + i], bt);
         if (centred) r = submod(r, T.halfT[i], bt.q);
         return r;
     }
     acc128 acc{0, 0};
     u64 sum = 0;
     int pending = 0;
-    for (int j = 0; j < T.k; j++) {
+    conv_each_source<KMAX>(T, [&](int j) {
         acc_mac(acc, xi[(size_t)j * stride], T.C[(size_t)j * T.m + i]);
         if (++pending == T.lazy) {
             sum = addmod(sum, barrett_reduce128(acc.lo, acc.hi, bt), bt.q);
             acc = acc128{0, 0};
             pending = 0;
         }
-    }
+    });
     if (pending) sum = addmod(sum, barrett_reduce128(acc.lo, acc.hi, bt), bt.q);
     r = submod(sum, mulmod((u64)alpha, T.Amod[i], bt), bt.q);
     if (centred) r = submod(r, T.halfT[i], bt.q);
     return r;
+}
+TFHE_HD u64 conv_eval(const conv_tab_t& T, const u64* xi, int stride, int i, u32 alpha, bool centred) {
+    return conv_eval_n<0>(T, xi, stride, i, alpha, centred);
 }

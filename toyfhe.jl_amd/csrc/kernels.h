@@ -2837,3 +2837,6 @@ __global__ __launch_bounds__(256) void k_bfv_contract_fast(const u64* __restrict
         bfv_contract_fast<NS, NP, false>(*Bt, src + p * (NS + NP) * n + k, n, dst + p * NS * n + k, n);
     }
 }
+
+// the grouped key switch: its digit and tail kernels
+#include "ks_group_core.h"

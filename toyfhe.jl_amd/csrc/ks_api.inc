@@ -671,3 +671,160 @@ int tfhe_keyswitch_window(tfhe_ctx* c, int key_limbs, int level, int special, in
     }
     return TFHE_OK;
 }
+
+// ---- key switch with grouped RNS digits and several special primes ("hybrid" gadget) ---------------------------------------
+// Digit g = the centred representative of c[end] modulo Q_g = prod of the limbs [g group, min((g+1) group, level)) (signedmod.jl:12-19;
+// switch(ℛ_W, .) of bfv.jl:202-226 on the group's sub-ring; one limb per group: rlwe_she.jl:326-329), in every working limb
+// W = [0 .. level-1] ∪ [key_limbs - n_special .. key_limbs - 1];  S_s = P c_s ⊕ zeros + sum_g key_{g,s} digit_g over W;  out_s =
+// modswitch (crt.jl:215-228) applied n_special times, the last special prime first = c_s + the contraction of INTT(sum_g ...).
+//   k_ks_group_digits -> run_ntt over W -> ks_inner_launch (A.level = digits, A.w = W) -> run_ntt -> k_ks_group_tail
+// workspace: [ transform scratch | S: [chunk][2][nw][N] | digits: [chunk][d][nw][N] | rotated copy: [chunk][2][level][N] ]
+struct ksg_plan_t {
+    ks_group_arg_t G;
+    ks_arg_t A;          // the key sums: A.level = digits
+    ks_arg_t At;         // n_special == 0: the row bookkeeping of ks_plain_tail (level = ciphertext limbs)
+    int Lk;
+    const conv_tab_t* tabs;
+    int64_t chunk;
+    size_t N, S_rows, dig_rows, rot_rows, ntt_tmp;
+    size_t bytes() const { return ntt_tmp + (size_t)chunk * (S_rows + dig_rows + rot_rows) * N * 8; }
+    u64* region(void* ws, size_t before) const { return (u64*)((char*)ws + ntt_tmp) + (size_t)chunk * before * N; }
+};
+// one conv_tab_t per digit (source: the group cut at this level, targets: W), built on first use and kept with the context
+static int ksg_table(tfhe_ctx* c, int Lk, int level, int k, int group, const conv_tab_t** out) {
+    *out = nullptr;
+    std::lock_guard<std::mutex> g(c->ksw_mu);
+    const std::array<int, 4> key{Lk, level, k, group};
+    auto it = c->ksg_tabs.find(key);
+    if (it != c->ksg_tabs.end()) { *out = it->second; return TFHE_OK; }
+    const limb_sel_t w = working_limbs_k(Lk, level, k);
+    std::vector<u64> targets;
+    for (int j = 0; j < w.n; j++) targets.push_back(c->q[w.idx[j]]);
+    const int d = (level + group - 1) / group;
+    std::vector<conv_tab_t> tabs((size_t)d);
+    auto up = [&](const void* src, size_t bytes, const void** dev) -> bool {
+        void* p = nullptr;
+        if (devalloc::malloc_retry(&p, bytes) != hipSuccess) return false;
+        c->ksw_allocs.push_back(p);
+        if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
+        *dev = p;
+        return true;
+    };
+    for (int gi = 0; gi < d; gi++) {
+        const int lo = gi * group, hi = std::min(lo + group, level);
+        conv_host_t H;
+        build_conv_host(std::vector<u64>(c->q.begin() + lo, c->q.begin() + hi), targets, &H);
+        conv_tab_t T = H.tab;
+        if (!up(H.C.data(), H.C.size() * 8, (const void**)&T.C) || !up(H.M.data(), H.M.size() * 8, (const void**)&T.M) ||
+            !up(H.Aw.data(), H.Aw.size() * 8, (const void**)&T.Aw)) {
+            (void)hipGetLastError();
+            return fail(TFHE_E_NOMEM, "allocating the grouped-digit tables failed");
+        }
+        tabs[(size_t)gi] = T;
+    }
+    const void* dt = nullptr;
+    if (!up(tabs.data(), tabs.size() * sizeof(conv_tab_t), &dt)) {
+        (void)hipGetLastError();
+        return fail(TFHE_E_NOMEM, "allocating the grouped-digit tables failed");
+    }
+    c->ksg_tabs[key] = (conv_tab_t*)dt;
+    *out = (const conv_tab_t*)dt;
+    return TFHE_OK;
+}
+static int ksg_plan(tfhe_ctx* c, int Lk, int level, int k, int group, int polys, int64_t batch, bool rotate, ksg_plan_t* P) {
+    const int d = (level + group - 1) / group, nw = level + k;
+    P->Lk = Lk; P->N = (size_t)c->N;
+    ks_group_arg_t& G = P->G;
+    G = ks_group_arg_t{};
+    G.level = level; G.nw = nw; G.k = k; G.polys = polys; G.group = group; G.d = d;
+    G.w = working_limbs_k(Lk, level, k);
+    // inv[t][j] = p_t^-1 mod working limb j, for the limbs step t still holds (j < level + t)
+    for (int t = 0; t < k; t++) {
+        const u64 p = c->q[G.w.idx[level + t]];
+        for (int j = 0; j < level + t; j++) {
+            const u64 qj = c->q[G.w.idx[j]];
+            G.inv[t][j] = hostmath::make_tw(hostmath::invmod_prime(p % qj, qj), qj);
+        }
+    }
+    P->A = make_ks_arg_grouped(Lk, level, k, d, polys);
+    P->At = make_ks_arg(Lk, level, 0, polys);
+    P->S_rows = (size_t)2 * nw;
+    P->dig_rows = (size_t)d * nw;
+    P->rot_rows = rotate ? (size_t)2 * level : 0;
+    P->chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, (P->S_rows + P->dig_rows + P->rot_rows) * P->N * 8);
+    // transforms above N = 2^14 use the start of the context workspace: ours is kept apart from it (as ks_plan)
+    P->ntt_tmp = c->logN > 14 ? (size_t)P->chunk * std::max(2, d) * nw * P->N * 8 : 0;
+    return ksg_table(c, Lk, level, k, group, &P->tabs);
+}
+// one chunk of `batch` ciphertexts: `ct` the chunk's input (the rotated copy for a rotation)
+static int ksg_chunk(tfhe_ctx* c, const ksg_plan_t& P, const u64* evk, const u64* ct, u64* out, int64_t batch, u64* S, u64* dig) {
+    const ks_group_arg_t& G = P.G;
+    const u32 n = (u32)c->N;
+    // two coefficients per thread (16-byte loads and stores) where the rows allow it
+    const bool v2 = n % 2 == 0 && (((uintptr_t)ct | (uintptr_t)out) & 15u) == 0;
+    const u32 gx = v2 ? (n / 2 + 255) / 256 : (n + 255) / 256;
+    const dim3 dgrid((unsigned)(batch * G.d * gx)), tgrid((unsigned)(batch * 2 * gx));
+    int rc = dispatch_int<0, 4>(G.group <= 4 ? G.group : 0, [&](auto gc) {
+        constexpr int GG = decltype(gc)::value;
+        return v2 ? launch(c, k_ks_group_digits<GG, 2>, dgrid, dim3(256), 0, ct, dig, P.tabs, G, n, gx)
+                  : launch(c, k_ks_group_digits<GG, 1>, dgrid, dim3(256), 0, ct, dig, P.tabs, G, n, gx);
+    });
+    if (rc) return rc;
+    rc = run_ntt(c, false, dig, dig, batch * G.d * G.nw, P.A.w);
+    if (rc) return rc;
+    rc = ks_inner_launch(c, P.A, P.Lk, evk, dig, S, batch);
+    if (rc) return rc;
+    if (G.k == 0) return ks_plain_tail(c, P.At, rescale_arg_t{}, S, ct, out, batch);
+    rc = run_ntt(c, true, S, S, batch * 2 * G.nw, P.A.w);
+    if (rc) return rc;
+    const u32 add_s = G.polys == 3 ? 2u : 1u;   // c2 starts from zero for a 2-element input (rlwe_she.jl:324)
+    return dispatch_int<1, TFHE_KSG_MAX_SPECIAL>(G.k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        return v2 ? launch(c, k_ks_group_tail<K, 2>, tgrid, dim3(256), 0, (const u64*)S, ct, out, c->limbs_dev, G, n, gx, add_s)
+                  : launch(c, k_ks_group_tail<K, 1>, tgrid, dim3(256), 0, (const u64*)S, ct, out, c->limbs_dev, G, n, gx, add_s);
+    });
+}
+static int ksg_check(tfhe_ctx* c, int Lk, int level, int k, int group, const void* evk, int n_digits, const void* ct, int polys, const void* out,
+                     int64_t batch, bool rotate, u64 galois) {
+    char msg[160];
+    const int rc = ks_group_check(!c || !evk || !ct || !out, c ? c->L : 0, c ? c->N : 0, Lk, level, k, group, n_digits, polys, batch, rotate, galois,
+                                  msg, sizeof msg);
+    return rc ? fail(rc, "%s", msg) : TFHE_OK;
+}
+static int ksg_impl(tfhe_ctx* c, int Lk, int level, int k, int group, const u64* evk, const u64* ct, int polys, u64* out, int64_t batch, u64 galois,
+                    bool rotate) {
+    if (batch == 0) return TFHE_OK;
+    group = std::min(group, level);   // (one digit: every larger group is the whole ciphertext ring)
+    ksg_plan_t P;
+    int rc = ksg_plan(c, Lk, level, k, group, polys, batch, rotate, &P);
+    if (rc) return rc;
+    void* ws = nullptr;
+    rc = ensure_ws(c, P.bytes(), &ws);
+    if (rc) return rc;
+    u64 *S = P.region(ws, 0), *dig = P.region(ws, P.S_rows), *rot = P.region(ws, P.S_rows + P.dig_rows);
+    const size_t N = P.N;
+    for (int64_t b0 = 0; b0 < batch; b0 += P.chunk) {
+        const int64_t nb = std::min(P.chunk, batch - b0);
+        const u64* cin = ct + (size_t)b0 * polys * level * N;
+        if (rotate) {   // KS_ROT_COPY: apply_galois_element into the workspace, then the key switch of the copy
+            rc = do_galois(c, cin, rot, galois, nb * polys * level, first_limbs(level));
+            if (rc) return rc;
+            cin = rot;
+        }
+        rc = ksg_chunk(c, P, evk, cin, out + (size_t)b0 * 2 * level * N, nb, S, dig);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
+int tfhe_keyswitch_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* evk, int n_digits, const uint64_t* ct,
+                           int polys, uint64_t* out, int64_t batch) {
+    const int rc = ksg_check(c, key_limbs, level, n_special, group, evk, n_digits, ct, polys, out, batch, false, 0);
+    if (rc) return rc;
+    return ksg_impl(c, key_limbs, level, n_special, group, evk, ct, polys, out, batch, 0, false);
+}
+int tfhe_rotate_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* evk, int n_digits, uint64_t galois_element,
+                        const uint64_t* ct, uint64_t* out, int64_t batch) {
+    const int rc = ksg_check(c, key_limbs, level, n_special, group, evk, n_digits, ct, 2, out, batch, true, galois_element);
+    if (rc) return rc;
+    return ksg_impl(c, key_limbs, level, n_special, group, evk, ct, 2, out, batch, galois_element, true);
+}

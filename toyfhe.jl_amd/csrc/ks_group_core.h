@@ -1,0 +1,179 @@
+// ks_group_core.h -- the two kernels of the key switch with grouped RNS digits and several special primes
+// (tfhe_keyswitch_grouped, ks_api.inc), and their per-coefficient bodies.
+//
+// Digit g of c[end] is the centred representative of c[end] modulo Q_g = prod_{i in G_g} q_i (the exact CRT value with the tie
+// rule of signedmod.jl:12-19, n > Q_g ÷ 2 => n - Q_g; switch(ℛ_W, .) of bfv.jl:202-226 on the sub-ring of the group; with one limb
+// per group the digit of rlwe_she.jl:326-329), reduced into every working limb W = [0 .. level-1] ∪ [the k special primes].  The
+// key sums over W are contracted by modswitch (crt.jl:215-228, unsigned c_last) once per special prime, the last one first.
+// The bodies are TFHE_HD: tests/ks_group_emul runs them on the host.
+#pragma once
+#include <cstdio>
+
+#include "../../include/toyfhe_hip.h"
+#include "conv_core.h"
+
+#define TFHE_KSG_MAX_SPECIAL 4
+
+// The host checks of tfhe_keyswitch_grouped / tfhe_rotate_grouped in the order include/toyfhe_hip.h states, on plain numbers (L, N:
+// the context's ring; any_null: a null argument, the context among them), so that tests/ks_group_emul runs them without a device.
+// Returns TFHE_OK, or the status with its message in `msg`.
+inline int ks_group_check(bool any_null, int L, int64_t N, int Lk, int level, int k, int group, int n_digits, int polys, int64_t batch, bool rotate,
+                          uint64_t galois, char* msg, size_t cap) {
+    msg[0] = 0;
+    if (any_null) return snprintf(msg, cap, "null argument"), TFHE_E_BADARG;
+    if (polys != 2 && polys != 3) return snprintf(msg, cap, "keyswitch needs a 2- or 3-element ciphertext (rlwe_she.jl:318), got %d", polys), TFHE_E_BADARG;
+    if (Lk < 1 || Lk > L) return snprintf(msg, cap, "key_limbs=%d outside [1,%d]", Lk, L), TFHE_E_BADARG;
+    const int kmax = TFHE_KSG_MAX_SPECIAL < Lk - 1 ? TFHE_KSG_MAX_SPECIAL : Lk - 1;
+    if (k < 0 || k > kmax) return snprintf(msg, cap, "n_special=%d outside [0,%d]", k, kmax), TFHE_E_BADARG;
+    if (group < 1) return snprintf(msg, cap, "group=%d: a digit takes at least one limb", group), TFHE_E_BADARG;
+    if (level < 1 || level > Lk - k) return snprintf(msg, cap, "level=%d outside [1,%d]", level, Lk - k), TFHE_E_LEVEL_MISMATCH;
+    const int d = (int)(((int64_t)level + group - 1) / group);
+    if (n_digits < d)
+        return snprintf(msg, cap, "evaluation key has %d components, level %d in groups of %d needs %d", n_digits, level, group, d), TFHE_E_PARAMS_MISMATCH;
+    if (level + k > TFHE_MAX_LIMBS) return snprintf(msg, cap, "%d working limbs, at most %d are supported", level + k, TFHE_MAX_LIMBS), TFHE_E_UNSUPPORTED;
+    if (batch < 0) return snprintf(msg, cap, "negative batch"), TFHE_E_BADARG;
+    if (rotate && ((galois & 1) == 0 || galois >= 2 * (uint64_t)N)) return snprintf(msg, cap, "galois element must be odd and below 2N"), TFHE_E_BADARG;
+    return TFHE_OK;
+}
+
+// ---- digits: conv_prepare (centred) over the group's residues, conv_eval into each working limb ------------------------------
+// G: the residues a thread holds, at least the group's size T.k (a group cut short by the level has fewer); G = 0: any size
+template <int G>
+struct ks_group_digit_t {
+    u64 xi[G ? G : TFHE_MAX_LIMBS];   // the group's residues of one coefficient on entry, conv_prepare's xi afterwards
+    u32 alpha;
+};
+template <int G>
+TFHE_HD void ks_group_prepare(const conv_tab_t& T, ks_group_digit_t<G>& D) { D.alpha = conv_prepare_n<G>(T, D.xi, 1, true); }
+// the digit modulo working limb i (a limb of the group itself: the residue back, conv_eval's copy path)
+template <int G>
+TFHE_HD u64 ks_group_eval(const conv_tab_t& T, const ks_group_digit_t<G>& D, int i) { return conv_eval_n<G>(T, D.xi, 1, i, D.alpha, true); }
+
+// ---- tail: K modswitch steps, the last special prime first -------------------------------------------------------------------
+// inv[t][j] = p_t^-1 mod (working limb j), p_t the t-th special prime (working limb level + t); only j < level + t is read.
+// The steps on the special limbs themselves are triangular: step t takes y[t] as it stands -- the unsigned "last" of that step --
+// out of every y[u], u < t.  On return y[t] is the "last" of step t.
+template <int K>
+TFHE_HD void ks_group_tail_special(u64 (&y)[K], const barrett_t* pb, const tw_t (*inv)[TFHE_MAX_LIMBS], int level) {
+#pragma unroll
+    for (int t = K - 1; t >= 1; t--)
+#pragma unroll
+        for (int u = 0; u < t; u++)
+            y[u] = shoup_full(submod(y[u], barrett_reduce128(y[t], 0, pb[u]), pb[u].q), inv[t][level + u], pb[u].q);
+}
+// one ciphertext limb j through the K updates (x - last) p_t^-1;  K = 1: the words of k_ks_rescale_add
+template <int K>
+TFHE_HD u64 ks_group_tail_limb(u64 x, const u64 (&last)[K], const barrett_t& bj, const tw_t (*inv)[TFHE_MAX_LIMBS], int j) {
+#pragma unroll
+    for (int t = K - 1; t >= 0; t--) x = shoup_full(submod(x, barrett_reduce128(last[t], 0, bj), bj.q), inv[t][j], bj.q);
+    return x;
+}
+
+#if defined(__HIPCC__)
+struct ks_group_arg_t {
+    int level, nw, k, polys;   // ciphertext limbs, working limbs (level + k), special primes, elements of the input ciphertext
+    int group, d;              // limbs per digit, digits = ceil(level / group)
+    limb_sel_t w;              // the working limbs
+    tw_t inv[TFHE_KSG_MAX_SPECIAL][TFHE_MAX_LIMBS];
+};
+
+// dig [batch][d][nw][N] from c[end] of ct [batch][polys][level][N]; tabs: one conv_tab_t per group (source: the group cut at this
+// level, targets: W).  A thread takes V coefficients (V = 2: 16-byte loads and stores, as k_rescale_cm) of one (ciphertext, group):
+// it reads the group's rows once and writes nw rows -- the kernel is bound by its stores, `level` rows in and d nw rows out per
+// ciphertext.  grid: batch * d * gx workgroups, gx = ceil(N / (256 V)).
+template <int G, int V>
+__global__ __launch_bounds__(256) void k_ks_group_digits(const u64* __restrict__ ct, u64* __restrict__ dig,
+                                                          const conv_tab_t* __restrict__ tabs, ks_group_arg_t A, u32 n, u32 gx) {
+    const u32 i = ((blockIdx.x % gx) * 256 + threadIdx.x) * (u32)V;
+    const u32 g = (blockIdx.x / gx) % (u32)A.d;
+    const size_t b = blockIdx.x / (gx * (u32)A.d);
+    if (i >= n) return;
+    const conv_tab_t& T = tabs[g];
+    const u64* src = ct + ((b * A.polys + A.polys - 1) * A.level + (size_t)g * A.group) * n + i;
+    u64* dst = dig + ((b * A.d + g) * A.nw) * n + i;
+    ks_group_digit_t<G> D[V];
+    constexpr int GG = G ? G : TFHE_MAX_LIMBS;
+    if constexpr (G != 0) {
+#pragma unroll
+        for (int j = 0; j < GG; j++) {
+            const int jj = j < T.k ? j : T.k - 1;   // a group cut short: the spare registers repeat its last limb, unused
+            if constexpr (V == 2) {
+                const u64x2_t x = *(const u64x2_t*)(src + (size_t)jj * n);
+                D[0].xi[j] = x.x; D[1].xi[j] = x.y;
+            } else {
+                D[0].xi[j] = src[(size_t)jj * n];
+            }
+        }
+    } else {
+        for (int j = 0; j < T.k; j++) {
+            if constexpr (V == 2) {
+                const u64x2_t x = *(const u64x2_t*)(src + (size_t)j * n);
+                D[0].xi[j] = x.x; D[1].xi[j] = x.y;
+            } else {
+                D[0].xi[j] = src[(size_t)j * n];
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < V; v++) ks_group_prepare<G>(T, D[v]);
+    for (int j = 0; j < A.nw; j++) {
+        if constexpr (V == 2) {
+            u64x2_t o;
+            o.x = ks_group_eval<G>(T, D[0], j);
+            o.y = ks_group_eval<G>(T, D[1], j);
+            *(u64x2_t*)(dst + (size_t)j * n) = o;
+        } else {
+            dst[(size_t)j * n] = ks_group_eval<G>(T, D[0], j);
+        }
+    }
+}
+
+// out [batch][2][level][N] from T = INTT(S) [batch][2][nw][N]:  out_s = c_s + the K-step contraction of T_s (c_s for s < add_s).
+// A thread takes V coefficients of one (ciphertext, component): the K special words first -- the triangular steps stay in
+// registers and leave the unsigned "last" of every step -- then the ciphertext limbs stream through one at a time, so no thread
+// holds nw words.  2 nw (+ the addends) rows in, 2 level rows out per ciphertext.  grid: batch * 2 * gx workgroups.
+template <int K, int V>
+__global__ __launch_bounds__(256) void k_ks_group_tail(const u64* __restrict__ T, const u64* __restrict__ ct, u64* __restrict__ out,
+                                                        const ntt_limb_t* __restrict__ LT, ks_group_arg_t A, u32 n, u32 gx, u32 add_s) {
+    const u32 i = ((blockIdx.x % gx) * 256 + threadIdx.x) * (u32)V;
+    const u32 s = (blockIdx.x / gx) & 1u;
+    const size_t b = blockIdx.x / (gx * 2u);
+    if (i >= n) return;
+    const u64* t = T + ((b * 2 + s) * A.nw) * n + i;
+    const u64* c = s < add_s ? ct + ((b * A.polys + s) * A.level) * n + i : nullptr;
+    u64* o = out + ((b * 2 + s) * A.level) * n + i;
+    barrett_t pb[K];
+    u64 y[V][K];
+#pragma unroll
+    for (int u = 0; u < K; u++) {
+        pb[u] = LT[A.w.idx[A.level + u]].br;
+        if constexpr (V == 2) {
+            const u64x2_t x = *(const u64x2_t*)(t + (size_t)(A.level + u) * n);
+            y[0][u] = x.x; y[1][u] = x.y;
+        } else {
+            y[0][u] = t[(size_t)(A.level + u) * n];
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < V; v++) ks_group_tail_special<K>(y[v], pb, A.inv, A.level);
+    for (int j = 0; j < A.level; j++) {
+        const barrett_t bj = LT[A.w.idx[j]].br;
+        if constexpr (V == 2) {
+            const u64x2_t x = *(const u64x2_t*)(t + (size_t)j * n);
+            u64x2_t r;
+            r.x = ks_group_tail_limb<K>(x.x, y[0], bj, A.inv, j);
+            r.y = ks_group_tail_limb<K>(x.y, y[1], bj, A.inv, j);
+            if (c) {
+                const u64x2_t cc = *(const u64x2_t*)(c + (size_t)j * n);
+                r.x = addmod(r.x, cc.x, bj.q);
+                r.y = addmod(r.y, cc.y, bj.q);
+            }
+            *(u64x2_t*)(o + (size_t)j * n) = r;
+        } else {
+            u64 r = ks_group_tail_limb<K>(t[(size_t)j * n], y[0], bj, A.inv, j);
+            if (c) r = addmod(r, c[(size_t)j * n], bj.q);
+            o[(size_t)j * n] = r;
+        }
+    }
+}
+#endif  // __HIPCC__

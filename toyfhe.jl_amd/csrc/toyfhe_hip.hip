@@ -5,6 +5,7 @@
 #include <chrono>
 
 #include <algorithm>
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -103,6 +104,8 @@ struct tfhe_ctx {
     // exact-reconstruction tables of the window key switch, per level (built on first use)
     std::map<int, conv_tab_t*> ksw_tabs;
     std::vector<void*> ksw_allocs;
+    // the tables of the grouped key switch, one conv_tab_t per digit, per (key_limbs, level, n_special, group) (same lock, same frees)
+    std::map<std::array<int, 4>, conv_tab_t*> ksg_tabs;
     std::mutex ksw_mu;
     // N zero words (the "+ c" stream of the fused contraction for the component that has no addend), made on first use
     // (under zero_mu; a failed attempt is retried by the next call)
@@ -283,10 +286,24 @@ limb_sel_t working_limbs(int Lk, int level, int special) {
     if (special) w.idx[w.n++] = Lk - 1;
     return w;
 }
+// the same with the key's last `n_special` limbs as special primes (the grouped key switch)
+limb_sel_t working_limbs_k(int Lk, int level, int n_special) {
+    limb_sel_t w = first_limbs(level);
+    for (int t = 0; t < n_special; t++) w.idx[w.n++] = Lk - n_special + t;
+    return w;
+}
 ks_arg_t make_ks_arg(int Lk, int level, int special, int polys) {
     ks_arg_t A{};
     A.level = level; A.special = special; A.polys = polys;
     A.w = working_limbs(Lk, level, special);
+    A.nw = A.w.n;
+    return A;
+}
+// the row bookkeeping of the key sums of the grouped key switch: `digits` components over the working limbs with n_special special primes
+ks_arg_t make_ks_arg_grouped(int Lk, int level, int n_special, int digits, int polys) {
+    ks_arg_t A{};
+    A.level = digits; A.special = n_special ? 1 : 0; A.polys = polys;
+    A.w = working_limbs_k(Lk, level, n_special);
     A.nw = A.w.n;
     return A;
 }

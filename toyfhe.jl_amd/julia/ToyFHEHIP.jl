@@ -514,6 +514,31 @@ function ToyFHE.rotate(gk::ToyFHE.GaloisKey, c::CipherText{Enc,P,<:RingElement{â
     CipherText{Enc}(c.params, unpack(ctx, out, â„›, 2))
 end
 
+# key switch with grouped RNS digits and several special primes (tfhe_keyswitch_grouped): `ek` over a key ring whose last n_special
+# limbs are special primes, its gadget row g holding their product at the limbs of group g (`group` limbs per digit) and zero
+# elsewhere; c over the first limbs of that ring.  (n_special, group) = (1, 1) is ToyFHE.keyswitch under ModulusRaised, word for word.
+function keyswitch_grouped(ek::KeySwitchKey, c::CipherText{Enc,P,<:RingElement{â„›,T,<:HipVector}}, n_special::Integer, group::Integer) where {Enc,P,â„›,T}
+    @assert length(c.cs) in (2, 3)                                                    # rlwe_she.jl:318
+    keyring = NTT.ring(ek.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T); cnt = batchsize(c)
+    key = pack(ek); ctx = hipring(keyring)
+    ct = pack(ctx, c); out = HipVector{T}(2 * level, degree(â„›), cnt); on(ctx, (out,), (ct, key))
+    GC.@preserve key ct out check(ccall((:tfhe_keyswitch_grouped, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{UInt64}, Cint, Ptr{UInt64}, Cint, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, n_special, group, key.ptr, length(ek.key), ct.ptr, length(c.cs), out.ptr, cnt))
+    CipherText{Enc}(c.params, unpack(ctx, out, â„›, 2))
+end
+# the same after apply_galois_element (tfhe_rotate_grouped): rotate(gk, c) on such a key
+function rotate_grouped(gk::ToyFHE.GaloisKey, c::CipherText{Enc,P,<:RingElement{â„›,T,<:HipVector}}, n_special::Integer, group::Integer) where {Enc,P,â„›,T}
+    @assert length(c.cs) == 2
+    ek = gk.key; keyring = NTT.ring(ek.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T); cnt = batchsize(c)
+    key = pack(ek); ctx = hipring(keyring)
+    ct = pack(ctx, c); out = HipVector{T}(2 * level, degree(â„›), cnt); on(ctx, (out,), (ct, key))
+    GC.@preserve key ct out check(ccall((:tfhe_rotate_grouped, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{UInt64}, Cint, UInt64, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, n_special, group, key.ptr, length(ek.key), gk.galois_element, ct.ptr, out.ptr, cnt))
+    CipherText{Enc}(c.params, unpack(ctx, out, â„›, 2))
+end
+
 # hoisted rotations: [rotate(gk, c) for gk in gks] from one digit decomposition of c (tfhe_rotate_many)
 function rotate_many(gks::Vector{<:ToyFHE.GaloisKey}, c::CipherText{Enc,P,<:RingElement{â„›,T,<:HipVector}}) where {Enc,P,â„›,T}
     @assert length(c.cs) == 2

@@ -286,6 +286,61 @@ class ModulusRaised(SHESchemeParams):
         return self.params.decode_array(b)
 
 
+class GroupedRaised(SHESchemeParams):
+    """Keys with grouped RNS digits and several special primes (the "hybrid" gadget; tfhe_keyswitch_grouped): the last `n_special`
+    CRT primes of the key ring are reserved for keys, their product P pre-multiplies every key, and a digit of the key switch covers
+    `group` limbs of the ciphertext ring.  ModulusRaised is the case (1, 1) on the per-limb routes; this class is deliberately not one
+    of its subclasses: the fused routes test for ModulusRaised."""
+
+    def __init__(self, params: SHESchemeParams, n_special: int, group: int):
+        if params.relin_window != 0:
+            raise UsageError("GroupedRaised takes RNS digits (relin_window = 0)")
+        L = params.R_key().L
+        if not 0 <= int(n_special) <= min(4, L - 1) or int(group) < 1:
+            raise UsageError("GroupedRaised: n_special in [0, min(4, L - 1)] and group >= 1")
+        self.params, self.n_special, self.group = params, int(n_special), int(group)
+        self.sigma = params.sigma
+        self.scheme_name = params.scheme_name + f" (with {self.n_special} special primes, {self.group} limbs per digit)"
+
+    def R_cipher(self):
+        ring = self.params.R_cipher()
+        for _ in range(self.n_special):
+            ring = ring.drop_last()
+        return ring
+
+    def R_key(self):
+        return self.params.R_key()
+
+    def noise(self, rng, ring, batch=None):
+        return self.params.noise(rng, ring, batch)
+
+    def secret_dist(self, rng, ring, batch=None):
+        return self.params.secret_dist(rng, ring, batch)
+
+    def encode(self, plain):
+        return self.params.encode(plain)
+
+    def decode(self, b):
+        return self.params.decode(b)
+
+    def decode_array(self, b):
+        return self.params.decode_array(b)
+
+    def digit_groups(self, level: int):
+        """the limb ranges of the digits at `level`: groups of `group` limbs, the last one cut at the level"""
+        return [range(g * self.group, min((g + 1) * self.group, level)) for g in range(-(-level // self.group))]
+
+
+def _refuse_grouped(params, what: str):
+    if isinstance(params, GroupedRaised):
+        raise UsageError(f"{what} has no support for keys with grouped digits (GroupedRaised): keyswitch, rotate and modswitch take them")
+
+
+def _refuse_grouped_keys(gks, what: str):
+    for g in gks:     # (anything that is not a Galois key is the later checks' business)
+        _refuse_grouped(getattr(getattr(g, "key", None), "params", None), what)
+
+
 def _plain_plan(params, ring: NegacyclicRing):
     """the device codec of (ring, params.t), cached on the params object per ring; None when the device does not take it
     (t outside [2, 2^62) or not below the ring's modulus)"""
@@ -416,6 +471,7 @@ class GaloisKey:
     def prepared(self) -> DeviceBuffer:
         """the packed key with its NTT-domain rows permuted by g^-1 (tfhe_galois_key_prepare), once per key: what the hoisted
         rotations consume"""
+        _refuse_grouped(self.key.params, "GaloisKey.prepared (hoisted rotations)")
         if self._prepared is None:
             ring = self.key.key[0].mask.ring
             src = self.key.packed()
@@ -903,7 +959,7 @@ def _is_prefix(ring: NegacyclicRing) -> bool:
 
 def _noise_multiplier(params):
     """the multiplier of 𝒩 when the scheme draws 𝒢 and 𝒩 through the stock samplers (1; t for BGV, bgv.jl:27-34), else None"""
-    inner = params.params if isinstance(params, ModulusRaised) else params
+    inner = params.params if isinstance(params, (ModulusRaised, GroupedRaised)) else params
     if type(inner) in (BFVParams, CKKSParams):
         return 1
     return inner.t if type(inner) is BGVParams else None
@@ -970,6 +1026,9 @@ def _encrypt_zero_composed(rng, pub: PubKey, batch=None) -> CipherText:
     cs = (c1, c2)
     if isinstance(params, ModulusRaised):  # modulusraising.jl:23-26: drop the special limb
         cs = tuple(c.modswitch_drop() for c in cs)
+    if isinstance(params, GroupedRaised):  # the same for every special limb
+        for _ in range(params.n_special):
+            cs = tuple(c.modswitch_drop() for c in cs)
     return CipherText(params, cs)
 
 
@@ -1186,6 +1245,10 @@ def _gadget_table(params, ring: NegacyclicRing):
     """gamma[i][j]: the residue mod q_j that multiplies `old` in digit i of make_eval_key (rlwe_she.jl:281-287); ModulusRaised
     pre-multiplies by the special prime P (modulusraising.jl:28-32), whose own row and column are therefore zero"""
     mods = list(ring.moduli)
+    if isinstance(params, GroupedRaised):                 # row g: P at the limbs of group g of the key's own top level, zero elsewhere
+        top = ring.L - params.n_special
+        P = math.prod(mods[top:])
+        return [[(P % q if j in G else 0) for j, q in enumerate(mods)] for G in params.digit_groups(top)]
     P = mods[-1] if isinstance(params, ModulusRaised) else 1
     if params.relin_window != 0:                          # base-2^w gadget: 2^(i w) mod Q, Q the key ring's modulus
         w, Q = params.relin_window, ring.modulus()
@@ -1277,7 +1340,15 @@ def _make_eval_key_composed(rng, old: RingElement, new: PrivKey) -> KeySwitchKey
     if isinstance(params, ModulusRaised):
         old = old * ring.moduli[-1]                       # P * old over the key ring Q P; the gadget below is the parent's
     key = []
-    if params.relin_window != 0:                          # base-2^w gadget, rlwe_she.jl:281-283
+    if isinstance(params, GroupedRaised):
+        top = ring.L - params.n_special
+        res = (old * math.prod(ring.moduli[top:])).to_numpy("primal")
+        gadget = []
+        for G in params.digit_groups(top):
+            g = np.zeros_like(res)
+            g[list(G)] = res[list(G)]
+            gadget.append(RingElement.from_host(ring, g))
+    elif params.relin_window != 0:                          # base-2^w gadget, rlwe_she.jl:281-283
         w = params.relin_window
         nwin = -(-ring.modulus().bit_length() // w)       # ndigits(Q, base = 2^w)
         gadget = [old * pow(2, i * w, ring.modulus()) for i in range(nwin)]
@@ -1369,6 +1440,7 @@ def keyswitch(ek, c: CipherText, _galois=None, _gk=None) -> CipherText:
             ring.ctx.wait_for(keyring.ctx)
         return CipherText(c.params, res, c.scale)
     special = isinstance(params, ModulusRaised)
+    grouped = isinstance(params, GroupedRaised)
     ring = c.ring()
     n, batch = c._shape()
     level = ring.L
@@ -1384,7 +1456,12 @@ def keyswitch(ek, c: CipherText, _galois=None, _gk=None) -> CipherText:
             keyring.ctx.wait_for(ring.ctx)                 # ... so the hand-over to the key ring's stream comes after them
         ct = c._packed_for(prim, keyring.ctx, consume=True) or _pack(prim, ring, n, ctx=keyring.ctx)
     out = DeviceBuffer(n * 2 * sz)
-    if _galois is None:
+    if grouped:
+        if _galois is None:
+            keyring.ctx.keyswitch_grouped(keyring.L, level, params.n_special, params.group, ek.packed().ptr, len(ek.key), ct.ptr, len(c), out.ptr, n)
+        else:
+            keyring.ctx.rotate_grouped(keyring.L, level, params.n_special, params.group, ek.packed().ptr, len(ek.key), _galois, ct.ptr, out.ptr, n)
+    elif _galois is None:
         keyring.ctx.keyswitch(keyring.L, level, special, ek.packed().ptr, len(ek.key), ct.ptr, len(c), out.ptr, n)
     elif _gk is not None and ring.N >= (1 << 15) and n >= 8:
         # N >= 2^15, 8 ciphertexts or more: the rotation is finished in the key switch's tail on the key as
@@ -1413,6 +1490,7 @@ def mul_relin(ek, c1: CipherText, c2: CipherText, rescale: bool = False) -> Ciph
         ek = ek.key
     if c1.params is not c2.params:
         raise UsageError("Attempting to multiply ciphertexts with differing parameters")
+    _refuse_grouped(ek.params, "mul_relin")
     inner = c1.params.params if isinstance(c1.params, ModulusRaised) else c1.params
     if isinstance(inner, BFVParams):
         raise UsageError("mul_relin serves the schemes without mul_expand / mul_contract (CKKS, BGV); "
@@ -1478,6 +1556,7 @@ def rotate_many(gks, c: CipherText):
     """[rotate(gk, c) for gk in gks] from one digit decomposition of c (tfhe_rotate_many: the forward transforms of the RNS
     digits are shared by all rotations); each result is bit-identical to `rotate(gk, c)`.  RNS-digit keys (relin_window = 0)."""
     gks = list(gks)
+    _refuse_grouped_keys(gks, "rotate_many")
     if len(c) != 2:
         raise AssertionError("rotate takes a 2-element ciphertext")
     if not gks:
@@ -1517,6 +1596,7 @@ def matmul_diag(gks, diags, c: CipherText) -> CipherText:
     ckks_encode returns for a [len(gks) + 1][N/2] array of slot vectors).  Bit-identical to
     `CipherText.dot_plain([c] + rotate_many(gks, c), diags)`; the result is in the NTT domain, at the squared scale."""
     gks = list(gks)
+    _refuse_grouped_keys(gks, "matmul_diag")
     if len(c) != 2:
         raise AssertionError("rotate takes a 2-element ciphertext")
     c._need_scale()
@@ -1600,6 +1680,7 @@ def matmul_bsgs(baby_gks, giant_gks, diags, c: CipherText) -> CipherText:
     (bsgs_diagonals).  Word for word rotate_many -> dot_plain per giant step -> rotate -> +; the result is in the coefficient
     domain, at the squared scale."""
     baby_gks, giant_gks = list(baby_gks), list(giant_gks)
+    _refuse_grouped_keys(baby_gks + giant_gks, "matmul_bsgs")
     if len(c) != 2:
         raise AssertionError("rotate takes a 2-element ciphertext")
     c._need_scale()
@@ -1679,6 +1760,7 @@ def rotate_sum(gk_groups, c: CipherText) -> CipherText:
     group, the result holds in every slot the sum of the slots s apart ("sum of slots"; the fold that closes a product by extended
     diagonals, rect_diagonals).  Word for word rotate_many over a group's keys -> + per group; scale and domain are c's."""
     groups = _fold_groups(gk_groups)
+    _refuse_grouped_keys([g for grp in groups for g in grp], "rotate_sum")
     if len(c) != 2:
         raise AssertionError("rotate takes a 2-element ciphertext")
     gks = [g for grp in groups for g in grp]
@@ -1763,6 +1845,7 @@ def rect_diagonals(W, n1: int, block: int = 1, fold_radix: int = 4):
 def _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, fold_groups):
     """matmul_bsgs_blocks (fold_groups None) and matmul_bsgs_fold (a list of lists of Galois keys, possibly empty)"""
     baby_gks, giant_gks, cs, diags = list(baby_gks), list(giant_gks), list(cs), list(diags)
+    _refuse_grouped_keys(baby_gks + giant_gks + [g for grp in fold_groups or [] for g in grp], "matmul_bsgs_blocks / matmul_bsgs_fold")
     if len(diags) != len(cs) or not cs:
         raise UsageError("matmul_bsgs_blocks: one set of diagonals per input ciphertext, at least one input")
     if len(cs) > DOT_MAX:
