@@ -98,9 +98,9 @@ def encrypted_matmul(gk, W, x, B, cache=None, fused=False):
             enc = tf.ckks_encode(vs, x.ring(), x.scale)                       # the 64 diagonals as one stacked plaintext element
             enc.coeffs_dual()
             cache[key] = enc
-        return tf.matmul_diag(gk, cache[key], x)
+        return (tf.matmul_diag_grouped if _grouped(gk) else tf.matmul_diag)(gk, cache[key], x)
     if isinstance(gk, (list, tuple)):
-        rots = [x] + list(tf.rotate_many(gk, x))
+        rots = [x] + list((tf.rotate_many_grouped if _grouped(gk) else tf.rotate_many)(gk, x))
     else:
         rots = [x]
         for k in range(1, n):
@@ -111,6 +111,11 @@ def encrypted_matmul(gk, W, x, B, cache=None, fused=False):
     for k in range(1, n):
         result = result + rots[k].mul_plain(diag(k))
     return result
+
+
+def _grouped(gks):
+    """whether a list of Galois keys has grouped digits (GroupedRaised): the hoisted rotations and the product have entry points of their own"""
+    return isinstance(gks[0].key.params, tf.GroupedRaised)
 
 
 def bsgs_encoded(gk, W, x, B, cache=None):
@@ -199,8 +204,12 @@ def load_model(path=GOLDEN_MODEL):
 
 
 def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None,
-        mul_relin=False, bsgs=0, blocks=False, rect=False):
-    """`rect` (with `bsgs`): the last layer -- 10 x 64, .+ b -- as ONE tfhe_matmul_bsgs_fold call over 16 extended diagonals and the fold
+        mul_relin=False, bsgs=0, blocks=False, rect=False, grouped=None):
+    """`grouped` = (K, G) (with `hoisted`): the key ring ends in K 60-bit special primes instead of one and every key
+    has grouped digits of G limbs (tf.GroupedRaised): the 63 Galois keys shrink from 6 to ceil(6 / G) components.  The square
+    layers go through tf.matmul_diag_grouped (with `fused`) or tf.rotate_many_grouped and the plaintext sum; the squares through
+    keyswitch.  The baby-step/giant-step products and mul_relin have no grouped form.
+    `rect` (with `bsgs`): the last layer -- 10 x 64, .+ b -- as ONE tfhe_matmul_bsgs_fold call over 16 extended diagonals and the fold
     of the four partial sums instead of the full product of the matrix padded to 64 x 64 (the key sets: the square product's baby and
     giant keys where the steps coincide, new keys for the rest).
     `blocks` (with `bsgs`): the first dense layer -- a 64 x 256 matrix over the four squares, .+ b -- as ONE tfhe_matmul_bsgs_blocks
@@ -213,6 +222,9 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
     of K, so each device call covers K ciphertexts (the batch the engine shards across GPUs)."""
     if (blocks or rect) and not bsgs:
         raise ValueError("blocks and rect need bsgs = n1 > 0")
+    if grouped is not None and (not hoisted or bsgs or mul_relin):
+        raise ValueError("grouped keys are covered for the hoisted circuit only (hoisted, with or without fused): the chained rotation by one "
+                         "prepared key, the baby-step/giant-step products (bsgs, blocks, rect) and mul_relin have no grouped form")
     N = 1 << logn
     B = N // 128                                                   # images per ciphertext
     K = int(batches)
@@ -232,8 +244,22 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
     qs = [tf.nextprime(2**40 + 1, 1, 2 * N)]
     for _ in range(4):
         qs.append(tf.nextprime(qs[-1] + 2 * N, 1, 2 * N))
-    ring = tf.NegacyclicRing(N, [q0] + qs + [ps])
-    params = tf.ModulusRaised(tf.CKKSParams(ring, 0, 3.2))
+    if grouped is None:
+        ring = tf.NegacyclicRing(N, [q0] + qs + [ps])
+        params = tf.ModulusRaised(tf.CKKSParams(ring, 0, 3.2))
+    else:              # the same ciphertext ring under K 60-bit special primes (the reference's own first), G limbs per digit
+        n_special, group = (int(v) for v in grouped)
+        sp = [ps]
+        for _ in range(n_special - 1):
+            sp.append(tf.nextprime(sp[-1] + 2 * N, 1, 2 * N))
+        ring = tf.NegacyclicRing(N, [q0] + qs + sp[:n_special])
+        params = tf.GroupedRaised(tf.CKKSParams(ring, 0, 3.2), n_special, group)
+        # the key-switch noise is the key's noise times Q_g / P: the special primes' product has to reach the largest digit modulus
+        P, top = int(np.prod([int(p) for p in sp[:n_special]], dtype=object)), [q0] + qs
+        Qg = max(int(np.prod([int(q) for q in top[i:i + group]], dtype=object)) for i in range(0, len(top), group))
+        if P < Qg:
+            raise ValueError(f"grouped = ({n_special}, {group}): {n_special} 60-bit special primes ({P.bit_length()} bits) are below the largest digit "
+                             f"modulus ({Qg.bit_length()} bits); the rotations would drown the 2^40 scale in key-switch noise: more special primes or smaller digits")
     rng = tf.DeviceRng(seed + 1)                                   # all sampling on the GPU
     t0 = time.perf_counter()
     kp = tf.keygen(rng, params)
@@ -337,10 +363,16 @@ if __name__ == "__main__":
                     help="each matrix product as one tfhe_matmul_bsgs call: N1 - 1 baby and ceil(64 / N1) - 1 giant Galois keys instead of 63")
     ap.add_argument("--blocks", action="store_true",
                     help="with --bsgs N1: the first dense layer (64 x 256 over the four squares, + bias) as one tfhe_matmul_bsgs_blocks call")
+    ap.add_argument("--grouped", default=None, metavar="K,G",
+                    help="with --hoisted: K 60-bit special primes and G limbs per digit (GroupedRaised keys); the products through "
+                         "tfhe_matmul_diag_grouped (--fused) or tfhe_rotate_many_grouped")
     ap.add_argument("--rect", action="store_true",
                     help="with --bsgs N1: the last layer (10 x 64, + bias) as one tfhe_matmul_bsgs_fold call: 16 extended diagonals and a fold")
     a = ap.parse_args()
     if (a.blocks or a.rect) and not a.bsgs:
         ap.error("--blocks and --rect need --bsgs N1")
+    grouped = tuple(int(v) for v in a.grouped.split(",")) if a.grouped else None
+    if grouped is not None and (len(grouped) != 2 or not a.hoisted or a.bsgs or a.mul_relin):
+        ap.error("--grouped K,G needs --hoisted and goes with neither --bsgs nor --mul-relin")
     run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin, bsgs=a.bsgs,
-        blocks=a.blocks, rect=a.rect)
+        blocks=a.blocks, rect=a.rect, grouped=grouped)

@@ -346,6 +346,37 @@ int tfhe_keyswitch_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_specia
                            const uint64_t *ct, int polys, uint64_t *out, int64_t batch);
 int tfhe_rotate_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *evk, int n_digits,
                         uint64_t galois_element, const uint64_t *ct, uint64_t *out, int64_t batch);
+/* Hoisted rotations and the diagonal product on grouped-digit keys.  The grouped digit is the centred representative modulo the odd
+ * Q_g (no tie, centred(-x) = -centred(x)), so it commutes with the automorphism in every working limb and the identity of
+ * tfhe_rotate_many carries over: the digits of c are decomposed and transformed ONCE -- d (level + k) forward transforms instead of
+ * that per rotation -- and each rotation costs one key sum against its PREPARED key, one inverse transform and one tail, in which
+ * the automorphism is applied to INTT(S') BEFORE the k-step contraction (the floor does not commute with sign changes).
+ *   evks: HOST array of n_rot device pointers to prepared grouped Galois keys: tfhe_galois_key_prepare(key_limbs, the key's own
+ *         component count, g_r) of the key tfhe_rotate_grouped takes.  There is no unprepared mode.  A key may appear more than once.
+ *   galois_elements: HOST array [n_rot].
+ * tfhe_rotate_many_grouped:  ct [batch][2][level][N], out [n_rot][batch][2][level][N], both in the coefficient domain; out[r] equals,
+ *   word for word, tfhe_rotate_grouped(the unprepared key r, galois_elements[r], ct).  n_rot is not limited: the keys are taken in
+ *   tiles of 64.
+ * tfhe_matmul_diag_grouped:  out = diags[0] .* NTT(c) + sum_{r < n_rot} diags[r+1] .* NTT(rotate_grouped(gk_r, c));
+ *   diags: device [n_rot + 1][level][N], NTT domain, shared by the batch; ct: [batch][2][level][N] coefficient domain; out:
+ *   [batch][2][level][N] NTT domain; n_rot <= 64 -- the contract of tfhe_matmul_diag.  Word for word tfhe_rotate_many_grouped ->
+ *   tfhe_nntt -> tfhe_dot.  Every limb of every key sum is inverse-transformed: the evaluation-domain form of tfhe_matmul_diag is
+ *   not built for several special primes.
+ * Checked on the host before any device use, in this order: a null ctx, evks, galois_elements, ct, out (diags for the product) or
+ * n_rot < 0 (TFHE_E_BADARG); n_rot > 64, the product only (TFHE_E_UNSUPPORTED); for r = 0, 1, .. in turn the checks of
+ * tfhe_rotate_grouped on (evks[r], galois_elements[r]) in that entry point's order, a null evks[r] being its null argument; `out`
+ * overlapping `ct` (or `diags`) anywhere (TFHE_E_BADARG: the tail scatters into out while it reads ct).  tfhe_rotate_many_grouped with
+ * n_rot == 0 returns TFHE_OK right after the null checks, as tfhe_rotate_many; tfhe_matmul_diag_grouped with n_rot == 0 runs the shape
+ * checks of tfhe_keyswitch_grouped once and computes diags[0] .* NTT(c).  batch == 0 does nothing after the checks.  The result does
+ * not depend on the chunk (tfhe_ctx_set_chunk) or the tile.
+ * Workspace: tfhe_rotate_many_grouped takes its block -- digits and key sums of a chunk, up to 8 GiB, and as much again for the transforms
+ * above N = 2^14 -- from the context's long-lived workspace, where it STAYS after the call (as tfhe_rotate_many's does) until a larger
+ * request or tfhe_ctx_destroy; tfhe_ctx_set_chunk bounds it.  tfhe_matmul_diag_grouped borrows its block for the call, as tfhe_matmul_diag.
+ * Still refused on grouped keys: tfhe_matmul_bsgs*, tfhe_rotate_sum, tfhe_mul_relin and the fused N <= 2^14 key switch. */
+int tfhe_rotate_many_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *const *evks, int n_digits,
+                             const uint64_t *galois_elements, int n_rot, const uint64_t *ct, uint64_t *out, int64_t batch);
+int tfhe_matmul_diag_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *const *evks, int n_digits,
+                             const uint64_t *galois_elements, int n_rot, const uint64_t *diags, const uint64_t *ct, uint64_t *out, int64_t batch);
 
 /* ---- CKKS encode / decode (float; ckksencoding.jl:56-97, FixedRational ckks.jl:35-59) -- SURVEY §8(f) ----
  * The ring is limbs 0..level-1 of ctx.  scale = scale_mant * 2^scale_exp2 (2^40 = (1, 40); any positive scale to

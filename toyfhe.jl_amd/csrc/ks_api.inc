@@ -756,6 +756,20 @@ static int ksg_plan(tfhe_ctx* c, int Lk, int level, int k, int group, int polys,
     P->ntt_tmp = c->logN > 14 ? (size_t)P->chunk * std::max(2, d) * nw * P->N * 8 : 0;
     return ksg_table(c, Lk, level, k, group, &P->tabs);
 }
+// the digits of `batch` ciphertexts, transformed: dig [batch][d][nw][N], NTT domain; v2: two coefficients per thread
+static int ksg_digits_fwd(tfhe_ctx* c, const ksg_plan_t& P, const u64* ct, u64* dig, int64_t batch, bool v2) {
+    const ks_group_arg_t& G = P.G;
+    const u32 n = (u32)c->N;
+    const u32 gx = v2 ? (n / 2 + 255) / 256 : (n + 255) / 256;
+    const dim3 dgrid((unsigned)(batch * G.d * gx));
+    const int rc = dispatch_int<0, 4>(G.group <= 4 ? G.group : 0, [&](auto gc) {
+        constexpr int GG = decltype(gc)::value;
+        return v2 ? launch(c, k_ks_group_digits<GG, 2>, dgrid, dim3(256), 0, ct, dig, P.tabs, G, n, gx)
+                  : launch(c, k_ks_group_digits<GG, 1>, dgrid, dim3(256), 0, ct, dig, P.tabs, G, n, gx);
+    });
+    if (rc) return rc;
+    return run_ntt(c, false, dig, dig, batch * G.d * G.nw, P.A.w);
+}
 // one chunk of `batch` ciphertexts: `ct` the chunk's input (the rotated copy for a rotation)
 static int ksg_chunk(tfhe_ctx* c, const ksg_plan_t& P, const u64* evk, const u64* ct, u64* out, int64_t batch, u64* S, u64* dig) {
     const ks_group_arg_t& G = P.G;
@@ -763,14 +777,8 @@ static int ksg_chunk(tfhe_ctx* c, const ksg_plan_t& P, const u64* evk, const u64
     // two coefficients per thread (16-byte loads and stores) where the rows allow it
     const bool v2 = n % 2 == 0 && (((uintptr_t)ct | (uintptr_t)out) & 15u) == 0;
     const u32 gx = v2 ? (n / 2 + 255) / 256 : (n + 255) / 256;
-    const dim3 dgrid((unsigned)(batch * G.d * gx)), tgrid((unsigned)(batch * 2 * gx));
-    int rc = dispatch_int<0, 4>(G.group <= 4 ? G.group : 0, [&](auto gc) {
-        constexpr int GG = decltype(gc)::value;
-        return v2 ? launch(c, k_ks_group_digits<GG, 2>, dgrid, dim3(256), 0, ct, dig, P.tabs, G, n, gx)
-                  : launch(c, k_ks_group_digits<GG, 1>, dgrid, dim3(256), 0, ct, dig, P.tabs, G, n, gx);
-    });
-    if (rc) return rc;
-    rc = run_ntt(c, false, dig, dig, batch * G.d * G.nw, P.A.w);
+    const dim3 tgrid((unsigned)(batch * 2 * gx));
+    int rc = ksg_digits_fwd(c, P, ct, dig, batch, v2);
     if (rc) return rc;
     rc = ks_inner_launch(c, P.A, P.Lk, evk, dig, S, batch);
     if (rc) return rc;
@@ -827,4 +835,86 @@ int tfhe_rotate_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, in
     const int rc = ksg_check(c, key_limbs, level, n_special, group, evk, n_digits, ct, 2, out, batch, true, galois_element);
     if (rc) return rc;
     return ksg_impl(c, key_limbs, level, n_special, group, evk, ct, 2, out, batch, galois_element, true);
+}
+
+// ---- hoisted rotations on grouped-digit keys -------------------------------------------------------------------------------------
+// out[r] = tfhe_rotate_grouped(key_r, g_r, ct) for every r from ONE digit decomposition: the grouped digit is the centred
+// representative modulo the odd Q_g -- no tie, a symmetric range, centred(-x) = -centred(x) -- so it commutes with the signed
+// permutation sigma_g in every working limb, and the identity of tfhe_rotate_many carries over: the key sums of the UNROTATED digits
+// against the key permuted by g^-1 (tfhe_galois_key_prepare, which does not care what a digit is) are sigma_g^-1 of the sums, and
+// sigma_g is applied to INTT(S') BEFORE the K-step contraction, whose floor does not commute with sign changes (k_ks_group_rot_tail).
+//   k_ks_group_digits on ct itself -> run_ntt over d nw rows, once -> per tile of up to 64 keys (ks_keys_t, ks_group_rot_t):
+//   ks_inner_launch against all the tile's keys -> run_ntt inverse over n_tile 2 nw rows -> k_ks_group_rot_tail, every rotation at once
+// d nw forward transforms per ciphertext instead of per rotation, no rotated copies.  Shared with tfhe_matmul_diag_grouped (md_api.inc).
+struct ksg_hoist_t {
+    ksg_plan_t P;        // G, A, the digit tables (its workspace figures are the single key switch's: unused here)
+    int R_tile;          // keys per launch
+    size_t dig_rows, S_rows;   // rows (N words) per ciphertext: digits d nw, key sums R_tile 2 nw
+};
+static int ksg_hoist_plan(tfhe_ctx* c, int Lk, int level, int k, int group, int n_rot, ksg_hoist_t* H) {
+    group = std::min(group, level);   // (one digit: every larger group is the whole ciphertext ring)
+    const int rc = ksg_plan(c, Lk, level, k, group, 2, 1, false, &H->P);
+    if (rc) return rc;
+    H->R_tile = std::min(n_rot, TFHE_DOT_MAX);
+    H->dig_rows = (size_t)H->P.G.d * H->P.G.nw;
+    H->S_rows = (size_t)H->R_tile * 2 * H->P.G.nw;
+    return TFHE_OK;
+}
+// rotations r0 .. r0 + n_tile - 1 of one chunk from its transformed digits: dst[r][b][s][level][N], r local to the tile, rotations
+// dst_stride words apart
+static int ksg_hoist_tile(tfhe_ctx* c, const ksg_hoist_t& H, const uint64_t* const* evks, const uint64_t* galois, int n_tile, const u64* cin,
+                          int64_t nb, const u64* dig, u64* S, u64* dst, size_t dst_stride) {
+    const ksg_plan_t& P = H.P;
+    int rc = ks_inner_launch(c, P.A, P.Lk, nullptr, dig, S, nb, evks, n_tile);
+    if (rc) return rc;
+    rc = run_ntt(c, true, S, S, (int64_t)n_tile * nb * 2 * P.G.nw, P.A.w);
+    if (rc) return rc;
+    ks_group_rot_t R{};
+    for (int r = 0; r < n_tile; r++) R.g[r] = galois[r];
+    R.out_stride = dst_stride;
+    return dispatch_int<0, TFHE_KSG_MAX_SPECIAL>(P.G.k, [&](auto kc) {
+        return launch(c, k_ks_group_rot_tail<decltype(kc)::value>, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, (const u64*)S, cin, dst, c->limbs_dev,
+                      P.G, R, (u32)c->N, (u32)nb, (u32)((int64_t)n_tile * nb * 2));
+    });
+}
+static int ksg_many_check(tfhe_ctx* c, bool product, int Lk, int level, int k, int group, const uint64_t* const* evks, int n_digits,
+                          const uint64_t* galois, int n_rot, const void* diags, const void* ct, const void* out, int64_t batch, bool* nothing_to_do) {
+    char msg[160];
+    const int rc = ks_group_many_check(product, !c || !evks || !galois || !ct || !out || (product && !diags), c ? c->L : 0, c ? c->N : 0, Lk, level, k,
+                                       group, n_digits, batch, evks, galois, n_rot, (uintptr_t)ct, (uintptr_t)out, (uintptr_t)diags, nothing_to_do, msg,
+                                       sizeof msg, TFHE_DOT_MAX);
+    return rc ? fail(rc, "%s", msg) : TFHE_OK;
+}
+// workspace: [ transform scratch above N = 2^14 | digits: [chunk][d][nw][N] | S: [chunk][R_tile][2][nw][N] ]
+int tfhe_rotate_many_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* evks, int n_digits,
+                             const uint64_t* galois_elements, int n_rot, const uint64_t* ct, uint64_t* out, int64_t batch) {
+    bool nothing = false;
+    int rc = ksg_many_check(c, false, key_limbs, level, n_special, group, evks, n_digits, galois_elements, n_rot, nullptr, ct, out, batch, &nothing);
+    if (rc || nothing) return rc;
+    ksg_hoist_t H;
+    rc = ksg_hoist_plan(c, key_limbs, level, n_special, group, n_rot, &H);
+    if (rc) return rc;
+    const size_t N = (size_t)c->N, ct_words = (size_t)2 * level * N;
+    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, (H.dig_rows + H.S_rows) * N * 8);
+    // transforms above N = 2^14 use the start of the context workspace: ours is kept apart from it (as ks_plan)
+    const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * std::max(H.dig_rows, H.S_rows) * N * 8 : 0;
+    void* ws = nullptr;
+    rc = ensure_ws(c, ntt_tmp + (size_t)chunk * (H.dig_rows + H.S_rows) * N * 8, &ws);
+    if (rc) return rc;
+    u64* const dig = (u64*)((char*)ws + ntt_tmp);
+    u64* const S = dig + (size_t)chunk * H.dig_rows * N;
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const u64* cin = ct + (size_t)b0 * ct_words;
+        rc = ksg_digits_fwd(c, H.P, cin, dig, nb, N % 2 == 0 && ((uintptr_t)cin & 15u) == 0);
+        if (rc) return rc;
+        for (int r0 = 0; r0 < n_rot; r0 += H.R_tile) {
+            const int n_tile = std::min(H.R_tile, n_rot - r0);
+            // straight into the caller's array: rotations a whole batch apart, the chunk at its place in each
+            rc = ksg_hoist_tile(c, H, evks + r0, galois_elements + r0, n_tile, cin, nb, dig, S, out + ((size_t)r0 * batch + b0) * ct_words,
+                                (size_t)batch * ct_words);
+            if (rc) return rc;
+        }
+    }
+    return TFHE_OK;
 }

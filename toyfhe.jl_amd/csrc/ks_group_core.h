@@ -36,6 +36,37 @@ inline int ks_group_check(bool any_null, int L, int64_t N, int Lk, int level, in
     return TFHE_OK;
 }
 
+// The host checks of tfhe_rotate_many_grouped (product = false) / tfhe_matmul_diag_grouped in the order include/toyfhe_hip.h states, on
+// plain numbers: any_null -- a null context, evks, galois_elements, ct, out (or diags); evks / galois -- the caller's HOST arrays, of
+// which only evks[r] == nullptr and galois[r] are looked at; ct / out / diags -- the operands' addresses, compared and never followed.
+// *nothing_to_do comes back true where the call returns TFHE_OK without work (no rotations to hoist, an empty batch).
+inline int ks_group_many_check(bool product, bool any_null, int L, int64_t N, int Lk, int level, int k, int group, int n_digits, int64_t batch,
+                               const uint64_t* const* evks, const uint64_t* galois, int n_rot, uintptr_t ct, uintptr_t out, uintptr_t diags,
+                               bool* nothing_to_do, char* msg, size_t cap, int max_rot = 64) {
+    msg[0] = 0;
+    *nothing_to_do = false;
+    if (any_null || n_rot < 0) return snprintf(msg, cap, "null argument"), TFHE_E_BADARG;
+    if (product && n_rot > max_rot)
+        return snprintf(msg, cap, "tfhe_matmul_diag_grouped takes at most %d rotations per call", max_rot), TFHE_E_UNSUPPORTED;
+    if (!product && n_rot == 0) return *nothing_to_do = true, TFHE_OK;
+    for (int r = 0; r < n_rot; r++) {
+        const int rc = ks_group_check(evks[r] == nullptr, L, N, Lk, level, k, group, n_digits, 2, batch, true, galois[r], msg, cap);
+        if (rc) return rc;
+    }
+    if (n_rot == 0) {
+        const int rc = ks_group_check(false, L, N, Lk, level, k, group, n_digits, 2, batch, false, 0, msg, cap);
+        if (rc) return rc;
+    }
+    // the tail scatters into `out` while other workgroups still read `ct`; the accumulation reads `diags` while it writes
+    const uint64_t ct_bytes = (uint64_t)batch * 2 * level * (uint64_t)N * 8;
+    const uint64_t out_bytes = product ? ct_bytes : ct_bytes * (uint64_t)n_rot;
+    const auto overlap = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a < b + nb && b < a + na; };
+    if (overlap(out, out_bytes, ct, ct_bytes) || (product && overlap(out, out_bytes, diags, (uint64_t)(n_rot + 1) * level * (uint64_t)N * 8)))
+        return snprintf(msg, cap, "out overlaps an operand"), TFHE_E_BADARG;
+    *nothing_to_do = batch == 0;
+    return TFHE_OK;
+}
+
 // ---- digits: conv_prepare (centred) over the group's residues, conv_eval into each working limb ------------------------------
 // G: the residues a thread holds, at least the group's size T.k (a group cut short by the level has fewer); G = 0: any size
 template <int G>
@@ -67,6 +98,36 @@ TFHE_HD u64 ks_group_tail_limb(u64 x, const u64 (&last)[K], const barrett_t& bj,
 #pragma unroll
     for (int t = K - 1; t >= 0; t--) x = shoup_full(submod(x, barrett_reduce128(last[t], 0, bj), bj.q), inv[t][j], bj.q);
     return x;
+}
+
+// ---- tail of a hoisted rotation: the signed permutation sigma_g BEFORE the K steps (the floor does not commute with sign changes) ----
+// One coefficient i of one row group (rotation, ciphertext, component): t -> coefficient i of limb 0 of T = INTT(S') (nw rows of n
+// words), c -> coefficient i of limb 0 of the addend c_0 (component 0) or nullptr, o -> limb 0 of the output rows; the coefficient
+// goes to position m = g i mod n, negated (neg) where floor(g i / n) is odd.  lb: the nw working limbs' Barrett words, the special
+// primes last.  The K special words first, the ciphertext limbs stream through: K + 2 words live per coefficient.
+template <int K>
+TFHE_HD void ks_group_rot_tail_coeff(const u64* t, const u64* c, u64* o, size_t n, u32 m, bool neg, int level, const barrett_t* lb,
+                                     const tw_t (*inv)[TFHE_MAX_LIMBS]) {
+    u64 y[K ? K : 1];
+    if constexpr (K > 0) {
+#pragma unroll
+        for (int u = 0; u < K; u++) {
+            const u64 v = t[(size_t)(level + u) * n];
+            y[u] = neg ? negmod(v, lb[level + u].q) : v;
+        }
+        ks_group_tail_special<K>(y, lb + level, inv, level);
+    }
+    for (int j = 0; j < level; j++) {
+        const barrett_t bj = lb[j];
+        u64 x = t[(size_t)j * n];
+        if (neg) x = negmod(x, bj.q);
+        if constexpr (K > 0) x = ks_group_tail_limb<K>(x, y, bj, inv, j);
+        if (c) {
+            const u64 a = c[(size_t)j * n];
+            x = addmod(x, neg ? negmod(a, bj.q) : a, bj.q);
+        }
+        o[(size_t)j * n + m] = x;
+    }
 }
 
 #if defined(__HIPCC__)
@@ -173,6 +234,46 @@ __global__ __launch_bounds__(256) void k_ks_group_tail(const u64* __restrict__ T
             u64 r = ks_group_tail_limb<K>(t[(size_t)j * n], y[0], bj, A.inv, j);
             if (c) r = addmod(r, c[(size_t)j * n], bj.q);
             o[(size_t)j * n] = r;
+        }
+    }
+}
+
+// Hoisted rotations on grouped-digit keys, the tail of ALL rotations of a tile in one launch (tfhe_rotate_many_grouped,
+// tfhe_matmul_diag_grouped): T = INTT(S') [n_tile][batch][2][nw][N], the inverse-transformed key sums of the UNROTATED digits against
+// the prepared keys;  out[r][b][s] = sigma_g(c_s) [s = 0] + the K-step contraction of sigma_g(T[r][b][s])  (ks_group_rot_tail_coeff).
+// The grouped counterpart of k_ks_rot_tail, with its two measured decisions: scatter form -- the nw source rows and the addend are
+// read in order and coefficient i is stored at g i mod N -- and the XCD-cooperative walk -- the workgroups of one XCD (blockIdx.x & 7)
+// share ONE row group (r, b, s) at a time, so that its level windows of N words stay in that XCD's L2 until their lines are complete.
+// Per row group nw rows (+ level addend rows for s = 0) in and level rows out.  The per-limb constants sit in LDS.
+// out_stride: words of `out` between two rotations (the caller's whole batch, not the chunk).  grid: 8 * TFHE_ROT_TAIL_SLOTS.
+struct ks_group_rot_t {
+    u64 g[TFHE_DOT_MAX];
+    size_t out_stride;
+};
+template <int K>
+__global__ __launch_bounds__(256) void k_ks_group_rot_tail(const u64* __restrict__ T, const u64* __restrict__ ct, u64* __restrict__ out,
+                                                            const ntt_limb_t* __restrict__ LT, ks_group_arg_t A, ks_group_rot_t G, u32 n, u32 batch,
+                                                            u32 ngroups) {
+    __shared__ barrett_t lb[TFHE_MAX_LIMBS];
+    __shared__ tw_t linv[K ? K : 1][TFHE_MAX_LIMBS];
+    const u32 level = (u32)A.level, nw = (u32)A.nw;
+    for (u32 j = threadIdx.x; j < nw; j += blockDim.x) {
+        lb[j] = LT[A.w.idx[j]].br;
+#pragma unroll
+        for (int t = 0; t < K; t++) linv[t][j] = A.inv[t][j];
+    }
+    __syncthreads();
+    const u32 xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
+    const u64 mask2n = 2ull * n - 1;
+    for (u32 grp = xcd; grp < ngroups; grp += 8u) {   // grp = (r * batch + b) * 2 + s
+        const u32 s = grp & 1u, b = (grp >> 1) % batch, r = (grp >> 1) / batch;
+        const u64 g = G.g[r];
+        const u64* tg = T + (size_t)grp * nw * n;
+        const u64* cg = s == 0 ? ct + ((size_t)b * 2 * level) * n : nullptr;   // 2-element input: only c_1 has an addend (rlwe_she.jl:324)
+        u64* og = out + (size_t)r * G.out_stride + ((size_t)b * 2 + s) * level * n;
+        for (u32 i = slot * blockDim.x + threadIdx.x; i < n; i += nslot * blockDim.x) {
+            const u64 t = ((u64)i * g) & mask2n;
+            ks_group_rot_tail_coeff<K>(tg + i, cg ? cg + i : nullptr, og, n, (u32)t & (n - 1), t >= n, (int)level, lb, linv);
         }
     }
 }

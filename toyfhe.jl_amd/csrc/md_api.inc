@@ -630,3 +630,49 @@ int tfhe_matmul_bsgs_fold(tfhe_ctx* c, int Lk, int level, int special, const uin
     const md_fold_t F = md_fold_plan(c, Lk, level, special, fold_evks, fold_galois, fold_group_sizes, n_fold_groups);
     return matmul_bsgs_run(c, Lk, level, special, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags, cts, n_in, bias, out, batch, &F);
 }
+
+// ---- the diagonal product on grouped-digit keys -----------------------------------------------------------------------------------
+// out = diags[0] (.) NTT(c) + sum_r diags[r+1] (.) NTT(rotate_grouped(gk_r, c)): the hoisted rotations of tfhe_rotate_many_grouped
+// (ksg_hoist_tile, all n_rot <= 64 keys in one tile) into the workspace, then the coefficient-domain finish of tfhe_matmul_diag --
+// forward transforms of the rotated ciphertexts and of c, k_md_acc_dense.  The words of tfhe_rotate_many_grouped -> tfhe_nntt ->
+// tfhe_dot.  The evaluation-domain form of the per-limb product (k_md_special_perm, k_md_lift, k_md_acc) is not built for k special
+// primes: every limb of every key sum is inverse-transformed here.
+// workspace: [ region 0 | digits: [chunk][d][nw][N] | S: [chunk][R][2][nw][N] | ROT: [chunk][R][2][level][N] | X: [chunk][2][level][N] ]
+int tfhe_matmul_diag_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* evks, int n_digits,
+                             const uint64_t* galois_elements, int n_rot, const uint64_t* diags, const uint64_t* ct, uint64_t* out, int64_t batch) {
+    bool nothing = false;
+    int rc = ksg_many_check(c, true, key_limbs, level, n_special, group, evks, n_digits, galois_elements, n_rot, diags, ct, out, batch, &nothing);
+    if (rc || nothing) return rc;
+    ksg_hoist_t H;
+    rc = ksg_hoist_plan(c, key_limbs, level, n_special, group, n_rot, &H);
+    if (rc) return rc;
+    const size_t N = (size_t)c->N, R = (size_t)n_rot, ct_rows = (size_t)2 * level;
+    const size_t dig_rows = R ? H.dig_rows : 0, rows = dig_rows + H.S_rows + R * ct_rows + ct_rows;
+    const size_t ntt_rows = std::max({dig_rows, H.S_rows, R * ct_rows, ct_rows});
+    const md_ws_t W(c, batch, rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : (size_t)0; });
+    if (W.rc) return W.rc;
+    const int64_t chunk = W.chunk;
+    u64* const dig = W.base();
+    u64* const S = dig + (size_t)chunk * dig_rows * N;
+    u64* const ROT = S + (size_t)chunk * H.S_rows * N;
+    u64* const X = ROT + (size_t)chunk * R * ct_rows * N;
+    const limb_sel_t sl = first_limbs(level);
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const u64* cin = ct + (size_t)b0 * ct_rows * N;
+        if (n_rot) {
+            rc = ksg_digits_fwd(c, H.P, cin, dig, nb, N % 2 == 0 && ((uintptr_t)cin & 15u) == 0);
+            if (rc) return rc;
+            rc = ksg_hoist_tile(c, H, evks, galois_elements, n_rot, cin, nb, dig, S, ROT, (size_t)nb * ct_rows * N);
+            if (rc) return rc;
+            rc = run_ntt(c, false, ROT, ROT, (int64_t)n_rot * nb * 2 * level, sl);
+            if (rc) return rc;
+        }
+        rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
+        if (rc) return rc;
+        rc = launch(c, k_md_acc_dense<1>, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, X, ROT, diags, out + (size_t)b0 * ct_rows * N,
+                    c->limbs_dev, sl, (u32)N, (u32)n_rot, (u32)(nb * 2 * level), 1u);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}

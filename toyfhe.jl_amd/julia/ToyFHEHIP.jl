@@ -538,6 +538,48 @@ function rotate_grouped(gk::ToyFHE.GaloisKey, c::CipherText{Enc,P,<:RingElement{
                 ctx.handle, Lk, level, n_special, group, key.ptr, length(ek.key), gk.galois_element, ct.ptr, out.ptr, cnt))
     CipherText{Enc}(c.params, unpack(ctx, out, ℛ, 2))
 end
+# hoisted rotations on such keys: [rotate_grouped(gk, c, ..) for gk in gks] from one digit decomposition of c
+# (tfhe_rotate_many_grouped); the keys go through `prepared`, which permutes rows whatever a digit is.  (Not executed anywhere yet:
+# the tests check the ccall against the header.)
+function rotate_many_grouped(gks::Vector{<:ToyFHE.GaloisKey}, c::CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}, n_special::Integer, group::Integer) where {Enc,P,ℛ,T}
+    @assert length(c.cs) == 2
+    ek1 = gks[1].key; keyring = NTT.ring(ek1.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T); cnt = batchsize(c)
+    ctx = hipring(keyring); ct = pack(ctx, c); n = degree(ℛ); nrot = length(gks)
+    packed = HipVector[prepared(gk) for gk in gks]; out = HipVector{T}(2 * level, n, cnt * nrot); on(ctx, (out,), (ct, packed...))
+    keys = Ptr{UInt64}[k.ptr for k in packed]; gs = UInt64[gk.galois_element for gk in gks]
+    # prepared keys only: where rotate_many passes `keys, length(ek1.key), 1, gs` (prepared = 1), this entry point has no such flag
+    GC.@preserve packed ct out check(ccall((:tfhe_rotate_many_grouped, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Ptr{UInt64}}, Cint, Ptr{UInt64}, Cint, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, n_special, group, keys, length(ek1.key), gs, nrot, ct.ptr, out.ptr, cnt))
+    map(1:nrot) do r                                             # out: [nrot][cnt][2][level][N]
+        part = HipVector{T}(2 * level, n, cnt); on(ctx, (part,), (out,))
+        GC.@preserve part out check(ccall((:tfhe_memcpy_d2d, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t),
+                    ctx.handle, part.ptr, out.ptr + 8 * (r - 1) * cnt * 2 * level * n, 8 * cnt * 2 * level * n))
+        CipherText{Enc}(c.params, unpack(ctx, part, ℛ, 2))
+    end
+end
+# diags[1] .* c + sum_k diags[k+1] .* rotate_grouped(gks[k], c, ..) in one device call (tfhe_matmul_diag_grouped), NTT domain
+function matmul_diag_grouped(gks::Vector{<:ToyFHE.GaloisKey}, diags::Vector{<:RingElement{ℛ,T,<:HipVector}},
+                             c::CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}, n_special::Integer, group::Integer) where {Enc,P,ℛ,T}
+    @assert length(c.cs) == 2 && !isempty(gks) && length(diags) == length(gks) + 1
+    length(gks) <= 64 || throw(ToyFHE.UsageError("matmul_diag_grouped: at most 64 rotations per call (TFHE_DOT_MAX); split the product and add the parts"))
+    ek1 = gks[1].key; keyring = NTT.ring(ek1.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T); cnt = batchsize(c)
+    ctx = hipring(keyring); ct = pack(ctx, c); n = degree(ℛ); nrot = length(gks)
+    packed = HipVector[prepared(gk) for gk in gks]
+    dparts = HipVector[coeffs_dual(d).parent for d in diags]
+    all(d -> d.count == 1, dparts) || throw(ToyFHE.UsageError("matmul_diag_grouped: one polynomial per diagonal"))
+    dg = HipVector{T}(level, n, nrot + 1); on(ctx, (dg,), (dparts...,))
+    GC.@preserve dparts dg for (k, d) in enumerate(dparts)                    # dg: [nrot + 1][level][N]
+        check(ccall((:tfhe_memcpy_d2d, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t),
+              ctx.handle, dg.ptr + 8 * (k - 1) * level * n, d.ptr, 8 * level * n))
+    end
+    out = HipVector{T}(2 * level, n, cnt); on(ctx, (out,), (ct, dg, packed...))
+    keys = Ptr{UInt64}[k.ptr for k in packed]; gs = UInt64[gk.galois_element for gk in gks]
+    GC.@preserve packed ct dg out check(ccall((:tfhe_matmul_diag_grouped, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Ptr{UInt64}}, Cint, Ptr{UInt64}, Cint, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, n_special, group, keys, length(ek1.key), gs, nrot, dg.ptr, ct.ptr, out.ptr, cnt))
+    CipherText{squared_encoding(Enc)}(c.params, unpack(ctx, out, ℛ, 2; dual=true))
+end
 
 # hoisted rotations: [rotate(gk, c) for gk in gks] from one digit decomposition of c (tfhe_rotate_many)
 function rotate_many(gks::Vector{<:ToyFHE.GaloisKey}, c::CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}) where {Enc,P,ℛ,T}

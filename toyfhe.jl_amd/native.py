@@ -126,6 +126,8 @@ def lib():
         "tfhe_keyswitch_window": [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i64],
         "tfhe_keyswitch_grouped": [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i64],
         "tfhe_rotate_grouped": [vp, i32, i32, i32, i32, vp, i32, u64, vp, vp, i64],
+        "tfhe_rotate_many_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), i32, u64p, i32, vp, vp, i64],
+        "tfhe_matmul_diag_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), i32, u64p, i32, vp, vp, vp, i64],
         "tfhe_rotate_many": [vp, i32, i32, i32, C.POINTER(vp), i32, i32, u64p, i32, vp, vp, i64],
         "tfhe_galois_key_prepare": [vp, i32, i32, u64, vp, vp],
         "tfhe_matmul_diag": [vp, i32, i32, i32, C.POINTER(vp), i32, u64p, i32, vp, vp, vp, i64],
@@ -180,7 +182,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_ctx_set_stream", "tfhe_ctx_sync", "tfhe_ctx_wait_for", "tfhe_ctx_set_ntt_variant", "tfhe_ctx_set_chunk", "tfhe_ctx_workspace", "tfhe_malloc", "tfhe_free", "tfhe_memcpy_h2d",
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
-    "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_keyswitch_grouped", "tfhe_rotate_grouped", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
+    "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_keyswitch_grouped", "tfhe_rotate_grouped", "tfhe_rotate_many_grouped", "tfhe_matmul_diag_grouped", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
     "tfhe_bfv_plan_set_variant", "tfhe_bfv_plan_workspace", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
@@ -498,6 +500,22 @@ class Context:
 
     def rotate_grouped(self, key_limbs, level, n_special, group, evk, n_digits, g, ct, out, batch):
         check(lib().tfhe_rotate_grouped(self.h, key_limbs, level, n_special, group, evk, n_digits, int(g), ct, out, batch))
+
+    @staticmethod
+    def _key_arrays(evks, gs):
+        ptrs = (C.c_void_p * max(1, len(evks)))(*[None if p is None else int(p) for p in evks])
+        return ptrs, (C.c_uint64 * max(1, len(gs)))(*[int(g) for g in gs])
+
+    def rotate_many_grouped(self, key_limbs, level, n_special, group, evks, n_digits, gs, ct, out, batch):
+        """hoisted rotations on grouped-digit keys (tfhe_rotate_many_grouped): `evks` device pointers of PREPARED keys (galois_key_prepare
+        with the key's own component count), `gs` their Galois elements; out [len(evks)][batch][2][level][N]"""
+        ptrs, garr = self._key_arrays(evks, gs)
+        check(lib().tfhe_rotate_many_grouped(self.h, key_limbs, level, n_special, group, ptrs, n_digits, garr, len(evks), ct, out, batch))
+
+    def matmul_diag_grouped(self, key_limbs, level, n_special, group, evks, n_digits, gs, diags, ct, out, batch):
+        """the diagonal product on grouped-digit keys (tfhe_matmul_diag_grouped); operands as matmul_diag, keys as rotate_many_grouped"""
+        ptrs, garr = self._key_arrays(evks, gs)
+        check(lib().tfhe_matmul_diag_grouped(self.h, key_limbs, level, n_special, group, ptrs, n_digits, garr, len(evks), diags, ct, out, batch))
 
     def sample_uniform(self, level, seed, stream, first_poly, out, count):
         check(lib().tfhe_sample_uniform(self.h, level, int(seed), int(stream), int(first_poly), out, count))

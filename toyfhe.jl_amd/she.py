@@ -468,10 +468,9 @@ class GaloisKey:
         self.galois_element, self.key = galois_element, key
         self._prepared = None
 
-    def prepared(self) -> DeviceBuffer:
-        """the packed key with its NTT-domain rows permuted by g^-1 (tfhe_galois_key_prepare), once per key: what the hoisted
-        rotations consume"""
-        _refuse_grouped(self.key.params, "GaloisKey.prepared (hoisted rotations)")
+    def _prepare(self) -> DeviceBuffer:
+        """the packed key with its NTT-domain rows permuted by g^-1 (tfhe_galois_key_prepare, which does not care what a digit is), once
+        per key"""
         if self._prepared is None:
             ring = self.key.key[0].mask.ring
             src = self.key.packed()
@@ -479,6 +478,18 @@ class GaloisKey:
             ring.ctx.galois_key_prepare(ring.L, len(self.key.key), self.galois_element, src.ptr, dst.ptr)
             self._prepared = dst
         return self._prepared
+
+    def prepared(self) -> DeviceBuffer:
+        """the prepared key of the per-limb hoisted rotations (rotate_many, matmul_*, the prepared-key rotation): they have no grouped
+        form, so a key with grouped digits is refused here"""
+        _refuse_grouped(self.key.params, "GaloisKey.prepared (hoisted rotations)")
+        return self._prepare()
+
+    def prepared_grouped(self) -> DeviceBuffer:
+        """the prepared key of rotate_many_grouped and matmul_diag_grouped: a key with grouped digits (GroupedRaised) only"""
+        if not isinstance(self.key.params, GroupedRaised):
+            raise UsageError("GaloisKey.prepared_grouped takes a key with grouped digits (GroupedRaised); the others go through prepared()")
+        return self._prepare()
 
 
 # the forward transforms of many small ring elements in one launch (CipherText.dot_plain).  Above _BATCH_NTT_MAX_WORDS a single element's
@@ -1643,6 +1654,97 @@ def matmul_diag(gks, diags, c: CipherText) -> CipherText:
     out = DeviceBuffer(n * 2 * sz)
     keyring.ctx.matmul_diag(keyring.L, level, special, [g.prepared().ptr for g in gks], len(gks[0].key.key) if gks else level,
                             [g.galois_element for g in gks], dg.ptr, ct.ptr, out.ptr, n)
+    res = _unpack(out, ring, n, 2, batch, primal=False, ctx=keyring.ctx)
+    if ring.ctx is not keyring.ctx:
+        ring.ctx.wait_for(keyring.ctx)
+    return CipherText(c.params, res, Fraction(c.scale) ** 2)
+
+
+def _grouped_key_set(gks, c, what):
+    """the argument rules of rotate_many / matmul_diag for keys with grouped digits: (params, keyring)"""
+    if len(c) != 2:
+        raise AssertionError("rotate takes a 2-element ciphertext")
+    params = gks[0].key.params
+    if not isinstance(params, GroupedRaised) or any(g.key.params is not params for g in gks):
+        raise UsageError(f"{what} needs Galois keys of one parameter set with grouped digits (GroupedRaised)")
+    keyring = gks[0].key.key[0].mask.ring
+    ring = c[0].ring
+    if keyring.idx != list(range(keyring.L)) or ring.idx != list(range(ring.L)):
+        raise UsageError("ciphertext ring is not a prefix of the key ring")
+    if ring.ctx is not keyring.ctx and (ring.N != keyring.N or ring.moduli != keyring.moduli[:ring.L] or ring.psi != keyring.psi[:ring.L]):
+        raise UsageError("ciphertext and key belong to different rings")
+    return params, keyring
+
+
+def rotate_many_grouped(gks, c: CipherText):
+    """[rotate(gk, c) for gk in gks] on keys with grouped digits, from one digit decomposition of c (tfhe_rotate_many_grouped): the
+    digits are decomposed and transformed once, each rotation costs one key sum, one inverse transform and one tail.  Each result is
+    bit-identical to `rotate(gk, c)`."""
+    gks = list(gks)
+    if not gks:
+        if len(c) != 2:
+            raise AssertionError("rotate takes a 2-element ciphertext")
+        return []
+    params, keyring = _grouped_key_set(gks, c, "rotate_many_grouped")
+    ring, n, batch = c[0].ring, c[0].count, c[0].batch
+    level = ring.L
+    prim = [x.coeffs_primal() for x in c.cs]               # before the hand-over (see keyswitch)
+    if ring.ctx is not keyring.ctx:
+        keyring.ctx.wait_for(ring.ctx)
+    sz = level * ring.N
+    ct = _pack(prim, ring, n, ctx=keyring.ctx)
+    out = DeviceBuffer(len(gks) * n * 2 * sz)
+    keyring.ctx.rotate_many_grouped(keyring.L, level, params.n_special, params.group, [g.prepared_grouped().ptr for g in gks],
+                                    len(gks[0].key.key), [g.galois_element for g in gks], ct.ptr, out.ptr, n)
+    res = []
+    for r in range(len(gks)):
+        view = _View(out, r * n * 2 * sz)
+        res.append(CipherText(c.params, _unpack(view, ring, n, 2, batch, primal=True, ctx=keyring.ctx), c.scale))
+    if ring.ctx is not keyring.ctx:
+        ring.ctx.wait_for(keyring.ctx)
+    return res
+
+
+def matmul_diag_grouped(gks, diags, c: CipherText) -> CipherText:
+    """matmul_diag on keys with grouped digits (tfhe_matmul_diag_grouped): diags[0] .* c + sum_k diags[k] .* rotate(gks[k-1], c) in one
+    device call, the rotations hoisted as in rotate_many_grouped.  `diags` as for matmul_diag; at least one key (the parameter set is
+    read from it).  Bit-identical to `CipherText.dot_plain([c] + rotate_many_grouped(gks, c), diags)`; NTT domain, squared scale."""
+    gks = list(gks)
+    if not gks:
+        raise UsageError("matmul_diag_grouped needs at least one Galois key (GroupedRaised); without rotations it is a plain product")
+    params, keyring = _grouped_key_set(gks, c, "matmul_diag_grouped")
+    c._need_scale()
+    ring, n, batch = c[0].ring, c[0].count, c[0].batch
+    level = ring.L
+    if len(gks) > DOT_MAX:          # as matmul_diag: partial products of DOT_MAX rotations, the later ones weigh c itself by 0
+        dl = diags.split([1] * diags.count) if isinstance(diags, RingElement) else list(diags)
+        if len(dl) != len(gks) + 1:
+            raise AssertionError("matmul_diag_grouped: one diagonal for the ciphertext itself and one per rotation")
+        out = matmul_diag_grouped(gks[:DOT_MAX], dl[:DOT_MAX + 1], c)
+        for k in range(DOT_MAX, len(gks), DOT_MAX):
+            out = out + matmul_diag_grouped(gks[k:k + DOT_MAX], [ring.zero()] + dl[k + 1:k + DOT_MAX + 1], c)
+        return out
+    stacked = isinstance(diags, RingElement)
+    if stacked:
+        if diags.ring != ring or diags.count != len(gks) + 1:
+            raise UsageError("matmul_diag_grouped: a stacked plaintext element must hold one diagonal per rotation plus one")
+    else:
+        diags = list(diags)
+        if len(diags) != len(gks) + 1:
+            raise AssertionError("matmul_diag_grouped: one diagonal for the ciphertext itself and one per rotation")
+        for d in diags:
+            if not isinstance(d, RingElement) or d.ring != ring or d.count != 1:
+                raise UsageError("matmul_diag_grouped: the diagonals are single plaintext elements of the ciphertext's ring")
+    prim = [x.coeffs_primal() for x in c.cs]               # both before the hand-over (see keyswitch)
+    duals = [diags.coeffs_dual()] if stacked else [d.coeffs_dual() for d in diags]
+    if ring.ctx is not keyring.ctx:
+        keyring.ctx.wait_for(ring.ctx)
+    sz = level * ring.N
+    dg = duals[0] if stacked else _pack(duals, ring, 1, ctx=keyring.ctx)   # [R+1][level][N]
+    ct = _pack(prim, ring, n, ctx=keyring.ctx)
+    out = DeviceBuffer(n * 2 * sz)
+    keyring.ctx.matmul_diag_grouped(keyring.L, level, params.n_special, params.group, [g.prepared_grouped().ptr for g in gks],
+                                    len(gks[0].key.key), [g.galois_element for g in gks], dg.ptr, ct.ptr, out.ptr, n)
     res = _unpack(out, ring, n, 2, batch, primal=False, ctx=keyring.ctx)
     if ring.ctx is not keyring.ctx:
         ring.ctx.wait_for(keyring.ctx)
