@@ -204,11 +204,13 @@ def load_model(path=GOLDEN_MODEL):
 
 
 def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None,
-        mul_relin=False, bsgs=0, blocks=False, rect=False, grouped=None):
+        mul_relin=False, bsgs=0, blocks=False, rect=False, grouped=None, mul_relin_grouped=False):
     """`grouped` = (K, G) (with `hoisted`): the key ring ends in K 60-bit special primes instead of one and every key
     has grouped digits of G limbs (tf.GroupedRaised): the 63 Galois keys shrink from 6 to ceil(6 / G) components.  The square
     layers go through tf.matmul_diag_grouped (with `fused`) or tf.rotate_many_grouped and the plaintext sum; the squares through
-    keyswitch.  The baby-step/giant-step products and mul_relin have no grouped form.
+    keyswitch (or `mul_relin_grouped`, below).  The baby-step/giant-step products have no grouped form and mul_relin takes per-limb keys.
+    `mul_relin_grouped` (with `hoisted` and `grouped`): the two square layers as one device call each (tf.mul_relin_grouped =
+    tfhe_mul_relin_grouped, rescale=True) instead of modswitch(keyswitch(ek, c * c)); same logits, bit for bit.
     `rect` (with `bsgs`): the last layer -- 10 x 64, .+ b -- as ONE tfhe_matmul_bsgs_fold call over 16 extended diagonals and the fold
     of the four partial sums instead of the full product of the matrix padded to 64 x 64 (the key sets: the square product's baby and
     giant keys where the steps coincide, new keys for the rest).
@@ -225,6 +227,14 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
     if grouped is not None and (not hoisted or bsgs or mul_relin):
         raise ValueError("grouped keys are covered for the hoisted circuit only (hoisted, with or without fused): the chained rotation by one "
                          "prepared key, the baby-step/giant-step products (bsgs, blocks, rect) and mul_relin have no grouped form")
+    if mul_relin_grouped and (grouped is None or not hoisted):
+        raise ValueError("mul_relin_grouped is the square layer on grouped keys: it needs hoisted and grouped = (K, G)")
+    if mul_relin_grouped:
+        square = lambda c: tf.mul_relin_grouped(ek, c, c, rescale=True)
+    elif mul_relin:
+        square = lambda c: tf.she.mul_relin(ek, c, c, rescale=True)
+    else:
+        square = lambda c: tf.modswitch(tf.keyswitch(ek, c * c))
     N = 1 << logn
     B = N // 128                                                   # images per ciphertext
     K = int(batches)
@@ -309,11 +319,9 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
           conved.append(tf.modswitch(add_bias(acc, float(model["conv_b"][ch]), cache, ("conv", ch))))
       if fused:    # the four channels' squares, relinearisations and rescales as ONE batch of 4 K ciphertexts
           big = tf.CipherText.concat(conved)
-          sq1 = (tf.she.mul_relin(ek, big, big, rescale=True) if mul_relin else tf.modswitch(tf.keyswitch(ek, big * big))).split([K] * 4)
-      elif mul_relin:
-          sq1 = [tf.she.mul_relin(ek, c, c, rescale=True) for c in conved]
+          sq1 = square(big).split([K] * 4)
       else:
-          sq1 = [tf.modswitch(tf.keyswitch(ek, c * c)) for c in conved]
+          sq1 = [square(c) for c in conved]
       if blocks:
           fq1 = tf.modswitch(encrypted_matmul_blocks(gk, fq1_blocks, list(sq1), B, np.repeat(model["fq1_b"], B), cache, "fq1"))
       else:
@@ -322,7 +330,7 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
               part = encrypted_matmul(gk, fq1_blocks[i], sq1[i], B, cache, fused)
               fq1 = part if fq1 is None else fq1 + part
           fq1 = tf.modswitch(add_bias(fq1, np.repeat(model["fq1_b"], B), cache, "fq1"))
-      sq2 = tf.she.mul_relin(ek, fq1, fq1, rescale=True) if mul_relin else tf.modswitch(tf.keyswitch(ek, fq1 * fq1))
+      sq2 = square(fq1)
       if rect:
           res = encrypted_matmul_rect(gk_rect, model["fq2_w"], sq2, B, model["fq2_b"], cache, "fq2")
       else:
@@ -366,6 +374,9 @@ if __name__ == "__main__":
     ap.add_argument("--grouped", default=None, metavar="K,G",
                     help="with --hoisted: K 60-bit special primes and G limbs per digit (GroupedRaised keys); the products through "
                          "tfhe_matmul_diag_grouped (--fused) or tfhe_rotate_many_grouped")
+    ap.add_argument("--mul-relin-grouped", action="store_true",
+                    help="with --hoisted --grouped K,G: the two square layers through tf.mul_relin_grouped (one tfhe_mul_relin_grouped call "
+                         "each, the rescale on the key switch's tail) instead of modswitch(keyswitch(ek, c * c))")
     ap.add_argument("--rect", action="store_true",
                     help="with --bsgs N1: the last layer (10 x 64, + bias) as one tfhe_matmul_bsgs_fold call: 16 extended diagonals and a fold")
     a = ap.parse_args()
@@ -374,5 +385,7 @@ if __name__ == "__main__":
     grouped = tuple(int(v) for v in a.grouped.split(",")) if a.grouped else None
     if grouped is not None and (len(grouped) != 2 or not a.hoisted or a.bsgs or a.mul_relin):
         ap.error("--grouped K,G needs --hoisted and goes with neither --bsgs nor --mul-relin")
+    if a.mul_relin_grouped and (grouped is None or not a.hoisted):
+        ap.error("--mul-relin-grouped needs --hoisted --grouped K,G")
     run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin, bsgs=a.bsgs,
-        blocks=a.blocks, rect=a.rect, grouped=grouped)
+        blocks=a.blocks, rect=a.rect, grouped=grouped, mul_relin_grouped=a.mul_relin_grouped)

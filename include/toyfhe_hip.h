@@ -372,11 +372,33 @@ int tfhe_rotate_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, 
  * Workspace: tfhe_rotate_many_grouped takes its block -- digits and key sums of a chunk, up to 8 GiB, and as much again for the transforms
  * above N = 2^14 -- from the context's long-lived workspace, where it STAYS after the call (as tfhe_rotate_many's does) until a larger
  * request or tfhe_ctx_destroy; tfhe_ctx_set_chunk bounds it.  tfhe_matmul_diag_grouped borrows its block for the call, as tfhe_matmul_diag.
- * Still refused on grouped keys: tfhe_matmul_bsgs*, tfhe_rotate_sum, tfhe_mul_relin and the fused N <= 2^14 key switch. */
+ * Still refused on grouped keys: tfhe_matmul_bsgs*, tfhe_rotate_sum and the fused N <= 2^14 key switch; tfhe_mul_relin takes per-limb
+ * keys only -- the product on grouped keys is tfhe_mul_relin_grouped, below. */
 int tfhe_rotate_many_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *const *evks, int n_digits,
                              const uint64_t *galois_elements, int n_rot, const uint64_t *ct, uint64_t *out, int64_t batch);
 int tfhe_matmul_diag_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *const *evks, int n_digits,
                              const uint64_t *galois_elements, int n_rot, const uint64_t *diags, const uint64_t *ct, uint64_t *out, int64_t batch);
+/* The ciphertext product, relinearised on a grouped-digit key and optionally rescaled, in one call: tfhe_mul_relin on the keys of
+ * tfhe_keyswitch_grouped (a grouped-digit key is first of all a relinearisation key: ceil(level / group) components instead of level).
+ *   c1, c2: [batch][2][level][N]; ntt_in = 0: coefficient domain, 1: NTT domain (natural order).  c1 == c2 (squaring) allowed.
+ *   evk, key_limbs, level, n_special, group, n_digits: as tfhe_keyswitch_grouped; the key comes from tfhe_evalkey_gen unchanged.
+ *   rescale = 0: out [batch][2][level][N];  rescale = 1 (level >= 2): out [batch][2][level-1][N].  Coefficient domain.
+ * The words are those of tfhe_nntt x2 (skipped with ntt_in) -> tfhe_tensor -> tfhe_inntt -> tfhe_keyswitch_grouped(polys = 3)
+ * [-> tfhe_rescale] on the same packed buffers, bit for bit, every word canonical; they do not depend on the chunk
+ * (tfhe_ctx_set_chunk).  (n_special, group) = (1, 1) gives the words of tfhe_mul_relin(special = 1), (0, 1) those of
+ * tfhe_mul_relin(special = 0); group above level is clamped to level (one digit).
+ * The product stage is tfhe_mul_relin's (fused cores at N = 2^12 .. 2^14, batched kernels elsewhere); the intermediates live in the
+ * context workspace, sized once before the first launch.  With n_special >= 1 and rescale = 1 the modswitch rides on the key
+ * switch's tail: it is one more step of the tail's own form, so the key switch's result is never written out and read back and the
+ * rescaled words go straight into `out`.  With n_special == 0 there is no tail to ride on: the inverse transform with the addends
+ * and tfhe_rescale's kernel are composed through the workspace.  rescale = 0 runs the tail of tfhe_keyswitch_grouped.
+ * Checked on the host before any device use, in this order: a null argument (TFHE_E_BADARG); a negative batch (TFHE_E_BADARG);
+ * ntt_in or rescale not 0 or 1 (TFHE_E_BADARG); rescale with level < 2 (TFHE_E_LEVEL_MISMATCH); out == c1 or out == c2
+ * (TFHE_E_BADARG); the checks of tfhe_keyswitch_grouped with polys = 3, in that entry point's order; `out` overlapping c1 or c2 as
+ * byte ranges (TFHE_E_BADARG); batch == 0 returns TFHE_OK and does nothing; (batch * 4 * level) << max(0, log2 N - 14) above 2^31 - 1
+ * (TFHE_E_BADARG, the row-count bound of tfhe_mul_relin). */
+int tfhe_mul_relin_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *evk, int n_digits,
+                           const uint64_t *c1, const uint64_t *c2, int ntt_in, int rescale, uint64_t *out, int64_t batch);
 
 /* ---- CKKS encode / decode (float; ckksencoding.jl:56-97, FixedRational ckks.jl:35-59) -- SURVEY §8(f) ----
  * The ring is limbs 0..level-1 of ctx.  scale = scale_mant * 2^scale_exp2 (2^40 = (1, 40); any positive scale to

@@ -770,8 +770,11 @@ static int ksg_digits_fwd(tfhe_ctx* c, const ksg_plan_t& P, const u64* ct, u64* 
     if (rc) return rc;
     return run_ntt(c, false, dig, dig, batch * G.d * G.nw, P.A.w);
 }
-// one chunk of `batch` ciphertexts: `ct` the chunk's input (the rotated copy for a rotation)
-static int ksg_chunk(tfhe_ctx* c, const ksg_plan_t& P, const u64* evk, const u64* ct, u64* out, int64_t batch, u64* S, u64* dig) {
+// one chunk of `batch` ciphertexts: `ct` the chunk's input (the rotated copy for a rotation).  The caller hands over the plan and its
+// carved regions S and dig, so whoever has sized ONE block for several users (tfhe_mul_relin_grouped) runs the chunk without a second
+// ensure_ws.  rs (n_special >= 1, a 3-element input): the modswitch of both components rides on the tail -- out: [batch][2][level - 1][N]
+static int ksg_chunk(tfhe_ctx* c, const ksg_plan_t& P, const u64* evk, const u64* ct, u64* out, int64_t batch, u64* S, u64* dig,
+                     const ks_group_rescale_t* rs = nullptr) {
     const ks_group_arg_t& G = P.G;
     const u32 n = (u32)c->N;
     // two coefficients per thread (16-byte loads and stores) where the rows allow it
@@ -782,9 +785,18 @@ static int ksg_chunk(tfhe_ctx* c, const ksg_plan_t& P, const u64* evk, const u64
     if (rc) return rc;
     rc = ks_inner_launch(c, P.A, P.Lk, evk, dig, S, batch);
     if (rc) return rc;
-    if (G.k == 0) return ks_plain_tail(c, P.At, rescale_arg_t{}, S, ct, out, batch);
+    if (G.k == 0) return rs ? fail(TFHE_E_UNSUPPORTED, "internal: no special prime, no tail for the rescale to ride on")
+                            : ks_plain_tail(c, P.At, rescale_arg_t{}, S, ct, out, batch);
     rc = run_ntt(c, true, S, S, batch * 2 * G.nw, P.A.w);
     if (rc) return rc;
+    if (rs) {
+        if (G.polys != 3 || G.level < 2) return fail(TFHE_E_UNSUPPORTED, "internal: the rescaling tail takes a 3-element input of two limbs or more");
+        return dispatch_int<1, TFHE_KSG_MAX_SPECIAL>(G.k, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            return v2 ? launch(c, k_ks_group_tail_rescale<K, 2>, tgrid, dim3(256), 0, (const u64*)S, ct, out, c->limbs_dev, G, *rs, n, gx)
+                      : launch(c, k_ks_group_tail_rescale<K, 1>, tgrid, dim3(256), 0, (const u64*)S, ct, out, c->limbs_dev, G, *rs, n, gx);
+        });
+    }
     const u32 add_s = G.polys == 3 ? 2u : 1u;   // c2 starts from zero for a 2-element input (rlwe_she.jl:324)
     return dispatch_int<1, TFHE_KSG_MAX_SPECIAL>(G.k, [&](auto kc) {
         constexpr int K = decltype(kc)::value;

@@ -1,5 +1,5 @@
-// ks_group_core.h -- the two kernels of the key switch with grouped RNS digits and several special primes
-// (tfhe_keyswitch_grouped, ks_api.inc), and their per-coefficient bodies.
+// ks_group_core.h -- the kernels of the key switch with grouped RNS digits and several special primes (tfhe_keyswitch_grouped and the
+// hoisted rotations, ks_api.inc; the tail that carries the rescale of tfhe_mul_relin_grouped, mul_api.inc), and their per-coefficient bodies.
 //
 // Digit g of c[end] is the centred representative of c[end] modulo Q_g = prod_{i in G_g} q_i (the exact CRT value with the tie
 // rule of signedmod.jl:12-19, n > Q_g ÷ 2 => n - Q_g; switch(ℛ_W, .) of bfv.jl:202-226 on the sub-ring of the group; with one limb
@@ -67,6 +67,29 @@ inline int ks_group_many_check(bool product, bool any_null, int L, int64_t N, in
     return TFHE_OK;
 }
 
+// The host checks of tfhe_mul_relin_grouped in the order include/toyfhe_hip.h states, on plain numbers: any_null -- a null context,
+// evk, c1, c2 or out; logN -- log2 of the ring degree; c1 / c2 / out -- the operands' addresses, compared and never followed.
+// *nothing_to_do comes back true where the call returns TFHE_OK without work (an empty batch).
+inline int ks_group_mul_check(bool any_null, int L, int64_t N, int logN, int Lk, int level, int k, int group, int n_digits, int64_t batch, int ntt_in,
+                              int rescale, uintptr_t c1, uintptr_t c2, uintptr_t out, bool* nothing_to_do, char* msg, size_t cap) {
+    msg[0] = 0;
+    *nothing_to_do = false;
+    if (any_null) return snprintf(msg, cap, "null argument"), TFHE_E_BADARG;
+    if (batch < 0) return snprintf(msg, cap, "negative batch"), TFHE_E_BADARG;
+    if ((ntt_in != 0 && ntt_in != 1) || (rescale != 0 && rescale != 1)) return snprintf(msg, cap, "ntt_in and rescale are 0 or 1"), TFHE_E_BADARG;
+    if (rescale && level < 2) return snprintf(msg, cap, "modswitch after the product needs level >= 2, got %d", level), TFHE_E_LEVEL_MISMATCH;
+    if (out == c1 || out == c2) return snprintf(msg, cap, "out overlaps an operand"), TFHE_E_BADARG;
+    const int rc = ks_group_check(false, L, N, Lk, level, k, group, n_digits, 3, batch, false, 0, msg, cap);
+    if (rc) return rc;
+    const uint64_t in_bytes = (uint64_t)batch * 2 * level * (uint64_t)N * 8, out_bytes = (uint64_t)batch * 2 * (level - rescale) * (uint64_t)N * 8;
+    const auto overlap = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a < b + nb && b < a + na; };
+    if (overlap(out, out_bytes, c1, in_bytes) || overlap(out, out_bytes, c2, in_bytes)) return snprintf(msg, cap, "out overlaps an operand"), TFHE_E_BADARG;
+    if (batch == 0) return *nothing_to_do = true, TFHE_OK;
+    // the transforms count rows in 31 bits (tfhe_mul_relin's bound)
+    if ((batch * 4 * level) << (logN > 14 ? logN - 14 : 0) > 0x7fffffffll) return snprintf(msg, cap, "bad batch"), TFHE_E_BADARG;
+    return TFHE_OK;
+}
+
 // ---- digits: conv_prepare (centred) over the group's residues, conv_eval into each working limb ------------------------------
 // G: the residues a thread holds, at least the group's size T.k (a group cut short by the level has fewer); G = 0: any size
 template <int G>
@@ -98,6 +121,24 @@ TFHE_HD u64 ks_group_tail_limb(u64 x, const u64 (&last)[K], const barrett_t& bj,
 #pragma unroll
     for (int t = K - 1; t >= 0; t--) x = shoup_full(submod(x, barrett_reduce128(last[t], 0, bj), bj.q), inv[t][j], bj.q);
     return x;
+}
+
+// ---- tail with a rescale riding on it (tfhe_mul_relin_grouped): the modswitch that follows the key switch is one more step of the
+// same form, (x - [last]_{q_j}) q_last^-1 mod q_j with the unsigned last (k_rescale), last = word level - 1 of the key switch's result
+struct ks_group_rescale_t {
+    tw_t qlinv[TFHE_MAX_LIMBS];   // q_{level-1}^-1 mod q_j, j < level - 1
+};
+// the rescale's `last`: ciphertext limb level - 1 through the K steps, plus its addend
+template <int K>
+TFHE_HD u64 ks_group_tail_last(u64 x, u64 addend, const u64 (&y)[K], const barrett_t& bl, const tw_t (*inv)[TFHE_MAX_LIMBS], int level) {
+    return addmod(ks_group_tail_limb<K>(x, y, bl, inv, level - 1), addend, bl.q);
+}
+// ciphertext limb j < level - 1: the K steps, the addend, then the (K+1)-th step against `last`
+template <int K>
+TFHE_HD u64 ks_group_tail_rescale_limb(u64 x, u64 addend, const u64 (&y)[K], u64 last, const barrett_t& bj, const tw_t (*inv)[TFHE_MAX_LIMBS],
+                                       const tw_t& qlinv, int j) {
+    x = addmod(ks_group_tail_limb<K>(x, y, bj, inv, j), addend, bj.q);
+    return shoup_full(submod(x, barrett_reduce128(last, 0, bj), bj.q), qlinv, bj.q);
 }
 
 // ---- tail of a hoisted rotation: the signed permutation sigma_g BEFORE the K steps (the floor does not commute with sign changes) ----
@@ -234,6 +275,84 @@ __global__ __launch_bounds__(256) void k_ks_group_tail(const u64* __restrict__ T
             u64 r = ks_group_tail_limb<K>(t[(size_t)j * n], y[0], bj, A.inv, j);
             if (c) r = addmod(r, c[(size_t)j * n], bj.q);
             o[(size_t)j * n] = r;
+        }
+    }
+}
+
+// k_ks_group_tail with the modswitch of BOTH components riding on it (tfhe_mul_relin_grouped, rescale = 1; a 3-element input: both
+// components carry addends): out [batch][2][level - 1][N] = tfhe_rescale of what k_ks_group_tail would have written, straight into
+// the caller's array.  A thread takes V coefficients of one (ciphertext, component): the K special words, the triangular steps in
+// registers; then limb level - 1 through the K steps plus its addend -- the rescale's unsigned `last`; then the limbs j < level - 1
+// stream through: K steps, the addend, the (K+1)-th step with R.qlinv[j], the store.  No thread holds nw words.  The limbs go in
+// blocks of JB: the 2 JB rows of a block (T and the addend) are requested before the first is used, as in k_rescale_cm -- one limb
+// at a time the loop runs at the latency of its loads.  2 nw + 2 level rows in and 2 (level - 1) rows out per ciphertext: against
+// k_ks_group_tail -> k_rescale_cm, 2 level rows written and 2 level rows read are gone.  grid: batch * 2 * gx workgroups.
+template <int K, int V>
+__global__ __launch_bounds__(256) void k_ks_group_tail_rescale(const u64* __restrict__ T, const u64* __restrict__ ct, u64* __restrict__ out,
+                                                                const ntt_limb_t* __restrict__ LT, ks_group_arg_t A, ks_group_rescale_t R, u32 n,
+                                                                u32 gx) {
+    const u32 i = ((blockIdx.x % gx) * 256 + threadIdx.x) * (u32)V;
+    const u32 s = (blockIdx.x / gx) & 1u;
+    const size_t b = blockIdx.x / (gx * 2u);
+    if (i >= n) return;
+    const int jl = A.level - 1;   // the limb the rescale drops
+    const u64* t = T + ((b * 2 + s) * A.nw) * n + i;
+    const u64* c = ct + ((b * A.polys + s) * A.level) * n + i;
+    u64* o = out + ((b * 2 + s) * jl) * n + i;
+    struct word_t { u64 v[V]; };
+    const auto ld = [](const u64* p) {
+        word_t w;
+        if constexpr (V == 2) {
+            const u64x2_t x = *(const u64x2_t*)p;
+            w.v[0] = x.x; w.v[1] = x.y;
+        } else {
+            w.v[0] = *p;
+        }
+        return w;
+    };
+    barrett_t pb[K];
+    u64 y[V][K];
+#pragma unroll
+    for (int u = 0; u < K; u++) {
+        pb[u] = LT[A.w.idx[A.level + u]].br;
+        const word_t x = ld(t + (size_t)(A.level + u) * n);
+#pragma unroll
+        for (int v = 0; v < V; v++) y[v][u] = x.v[v];
+    }
+    const word_t tl = ld(t + (size_t)jl * n), cl = ld(c + (size_t)jl * n);
+#pragma unroll
+    for (int v = 0; v < V; v++) ks_group_tail_special<K>(y[v], pb, A.inv, A.level);
+    u64 last[V];
+    {
+        const barrett_t bl = LT[A.w.idx[jl]].br;
+#pragma unroll
+        for (int v = 0; v < V; v++) last[v] = ks_group_tail_last<K>(tl.v[v], cl.v[v], y[v], bl, A.inv, A.level);
+    }
+    constexpr int JB = 4;
+    for (int j0 = 0; j0 < jl; j0 += JB) {
+        word_t xt[JB], xc[JB];
+#pragma unroll
+        for (int r = 0; r < JB; r++) {
+            const int j = j0 + r < jl ? j0 + r : jl - 1;   // past the end: the block's spare registers repeat the last row, unused
+            xt[r] = ld(t + (size_t)j * n);
+            xc[r] = ld(c + (size_t)j * n);
+        }
+#pragma unroll
+        for (int r = 0; r < JB; r++) {
+            const int j = j0 + r;
+            if (j < jl) {
+                const barrett_t bj = LT[A.w.idx[j]].br;
+                u64 res[V];
+#pragma unroll
+                for (int v = 0; v < V; v++) res[v] = ks_group_tail_rescale_limb<K>(xt[r].v[v], xc[r].v[v], y[v], last[v], bj, A.inv, R.qlinv[j], j);
+                if constexpr (V == 2) {
+                    u64x2_t w;
+                    w.x = res[0]; w.y = res[1];
+                    *(u64x2_t*)(o + (size_t)j * n) = w;
+                } else {
+                    o[(size_t)j * n] = res[0];
+                }
+            }
         }
     }
 }

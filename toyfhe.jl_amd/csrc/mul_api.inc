@@ -1,5 +1,6 @@
-// mul_api.inc -- tfhe_mul_relin: ciphertext product + relinearisation (+ modswitch) of the schemes whose mul_expand /
-// mul_contract are the identity (CKKS, BGV: rlwe_she.jl:39-40, :247-262); included by toyfhe_hip.hip.
+// mul_api.inc -- tfhe_mul_relin and, on grouped-digit keys, tfhe_mul_relin_grouped (at the end): ciphertext product + relinearisation
+// (+ modswitch) of the schemes whose mul_expand / mul_contract are the identity (CKKS, BGV: rlwe_she.jl:39-40, :247-262); included by
+// toyfhe_hip.hip.
 //
 // The call is the chain  nntt x2 -> tensor -> inntt -> keyswitch(polys = 3) -> rescale  run directly on the packed
 // ciphertexts ([batch][2][level][N] is 2 batch polynomials), with the intermediates in the context workspace:
@@ -102,6 +103,37 @@ int mr_product_composed(tfhe_ctx* c, const u64* a, const u64* b, u64* F, u64* T,
     return run_ntt(c, true, T, T, nct * 3 * level, sel);
 }
 
+// The product stage of one call, decided once: what tfhe_mul_relin and tfhe_mul_relin_grouped share -- it does not depend on the key.
+struct mr_product_t {
+    bool square, ntt_in, fused;
+    u32 fp_mask, int_mask;   // fused: the limbs of each core
+    size_t f_rows;           // rows per limb of F (the NTT images of the operands: the batched path only)
+    size_t park;             // words of parking rows per fused core
+    size_t park_bytes() const { return fused ? 2 * park * 8 : 0; }
+};
+mr_product_t mr_product_plan(const tfhe_ctx* c, int level, bool square, bool ntt_in) {
+    mr_product_t M{};
+    M.square = square; M.ntt_in = ntt_in;
+    const policy_split_t ps = policy_split(c, first_limbs(level));
+    // fused product cores: N = 2^12 .. 2^14, variant 0.  The general form of the fp64 core with a limb subset is not built at 2^14
+    // (it does not fit the registers there, DESIGN.md): a ring that mixes the policies takes the batched kernels for that form.
+    M.fused = fused_rows_ok(c, level) && !(c->logN == 14 && ps.mixed_fp() && !square && !ntt_in);
+    M.fp_mask = M.fused ? ps.fpmask : 0u;
+    M.int_mask = M.fused ? (ps.all & ~ps.fpmask) : 0u;
+    M.f_rows = (M.fused || ntt_in) ? 0 : (square ? 2 : 4);
+    M.park = mr_park_rows(c) * (size_t)c->N;
+    return M;
+}
+// T [nct][3][level][N], coefficient domain, from the packed operands a, b of one chunk; SCR: the parking rows of the two cores
+int mr_product(tfhe_ctx* c, const mr_product_t& M, const u64* a, const u64* b, u64* F, u64* T, u64* SCR, int64_t nct, int level) {
+    if (!M.fused) return mr_product_composed(c, a, b, F, T, nct, level, M.square, M.ntt_in);
+    // both cores side by side (both_policies), over disjoint rows of T; the lanes join before the key switch reads T
+    return both_policies(c, M.int_mask, M.fp_mask, [&](auto pol, u32 mask) {
+        if constexpr (std::is_same<decltype(pol), ArithInt>::value) return mr_core_int(c, a, b, T, SCR, nct, level, mask, M.square, M.ntt_in);
+        else return mr_core_fp(c, a, b, T, SCR + M.park, nct, level, mask, M.int_mask == 0, M.square, M.ntt_in);
+    });
+}
+
 }  // namespace
 
 extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* evk, int n_digits, const uint64_t* c1,
@@ -121,44 +153,28 @@ extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const
     if (batch == 0) return TFHE_OK;
     if ((batch * 4 * level) << std::max(0, c->logN - 14) > 0x7fffffffll) return fail(TFHE_E_BADARG, "bad batch");
 
-    const bool square = c1 == c2;
     const limb_sel_t sel = first_limbs(level);
-    const policy_split_t ps = policy_split(c, sel);
-    // fused product cores: N = 2^12 .. 2^14, variant 0.  The general form of the fp64 core with a limb subset is not built at 2^14
-    // (it does not fit the registers there, DESIGN.md): a ring that mixes the policies takes the batched kernels for that form.
-    const bool fused = fused_rows_ok(c, level) && !(c->logN == 14 && ps.mixed_fp() && !square && !ntt_in);
-    const u32 fp_mask = fused ? ps.fpmask : 0u, int_mask = fused ? (ps.all & ~ps.fpmask) : 0u;
+    const mr_product_t M = mr_product_plan(c, level, c1 == c2, ntt_in != 0);
 
     // chunk: F (NTT images of the operands: the batched path only), T (3 rows per limb), R (2: the key switch's result when a
     // modswitch follows)
-    const size_t f_rows = (fused || ntt_in) ? 0 : (square ? 2 : 4), r_rows = rescale ? 2 : 0;
-    const size_t per_ct = (f_rows + 3 + r_rows) * level * N * 8;
+    const size_t r_rows = rescale ? 2 : 0;
+    const size_t per_ct = (M.f_rows + 3 + r_rows) * level * N * 8;
     const int64_t chunk = chunk_of(c, batch, 256, (size_t)4096 << 20, per_ct);
-    const size_t park = mr_park_rows(c) * N;   // words, per core
     size_t region0 = mr_ks_bytes(c, Lk, level, special, chunk);
     if (c->logN > 14) region0 = std::max(region0, (size_t)chunk * 3 * level * N * 8);   // run_ntt's scratch for N > 2^14
     region0 = (region0 + 255) & ~(size_t)255;
     void* ws = nullptr;
-    rc = ensure_ws(c, region0 + (size_t)chunk * per_ct + (fused ? 2 * park * 8 : 0), &ws);   // once, for both users, before any fork
+    rc = ensure_ws(c, region0 + (size_t)chunk * per_ct + M.park_bytes(), &ws);   // once, for both users, before any fork
     if (rc) return rc;
     u64* F = (u64*)((char*)ws + region0);
-    u64* T = F + (size_t)chunk * f_rows * level * N;
+    u64* T = F + (size_t)chunk * M.f_rows * level * N;
     u64* R = T + (size_t)chunk * 3 * level * N;
     u64* SCR = R + (size_t)chunk * r_rows * level * N;
     const int lo = level - (rescale ? 1 : 0);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nct = std::min(chunk, batch - b0);
-        const u64* a = c1 + (size_t)b0 * 2 * level * N;
-        const u64* b = c2 + (size_t)b0 * 2 * level * N;
-        if (fused) {
-            // both cores side by side (both_policies), over disjoint rows of T; the lanes join before the key switch reads T
-            rc = both_policies(c, int_mask, fp_mask, [&](auto pol, u32 mask) {
-                if constexpr (std::is_same<decltype(pol), ArithInt>::value) return mr_core_int(c, a, b, T, SCR, nct, level, mask, square, ntt_in != 0);
-                else return mr_core_fp(c, a, b, T, SCR + park, nct, level, mask, int_mask == 0, square, ntt_in != 0);
-            });
-        } else {
-            rc = mr_product_composed(c, a, b, F, T, nct, level, square, ntt_in != 0);
-        }
+        rc = mr_product(c, M, c1 + (size_t)b0 * 2 * level * N, c2 + (size_t)b0 * 2 * level * N, F, T, SCR, nct, level);
         if (rc) return rc;
         u64* ks_out = rescale ? R : out + (size_t)b0 * 2 * level * N;
         rc = keyswitch_impl(c, Lk, level, special, evk, T, 3, ks_out, nct, 0, false);   // rlwe_she.jl:315-347
@@ -166,6 +182,67 @@ extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const
         if (c->ws != ws) return fail(TFHE_E_HIP, "internal: the key switch moved the workspace");
         if (rescale) {
             rc = do_rescale(c, R, out + (size_t)b0 * 2 * lo * N, nct * 2, sel);       // crt.jl:215-228 on both components
+            if (rc) return rc;
+        }
+    }
+    return TFHE_OK;
+}
+
+// ---- the same on grouped-digit keys (tfhe_keyswitch_grouped's gadget): tfhe_mul_relin_grouped ---------------------------------------
+// The product stage is tfhe_mul_relin's; the key switch is ksg_chunk on a plan and regions carved HERE, from one block sized before the
+// first launch:
+//     ws = [ ksg region: transform scratch above 2^14 | S | digits (ksg_plan_t::bytes()) | F | T | R (n_special == 0 only) | parking rows x 2 ]
+// With a special prime the modswitch rides on the key switch's tail (k_ks_group_tail_rescale: no R region, the result goes straight
+// into `out`); without one there is no tail to ride on and ks_plain_tail -> do_rescale are composed through R.  The chunk follows
+// chunk_of over the larger of the two per-ciphertext footprints (the product's rows, the key switch's rows).
+extern "C" int tfhe_mul_relin_grouped(tfhe_ctx* c, int Lk, int level, int k, int group, const uint64_t* evk, int n_digits, const uint64_t* c1,
+                                      const uint64_t* c2, int ntt_in, int rescale, uint64_t* out, int64_t batch) {
+    // every check runs on the host before any device use (ks_group_mul_check, ks_group_core.h)
+    char msg[160];
+    bool nothing = false;
+    int rc = ks_group_mul_check(!c || !evk || !c1 || !c2 || !out, c ? c->L : 0, c ? c->N : 0, c ? c->logN : 0, Lk, level, k, group, n_digits, batch, ntt_in,
+                                rescale, (uintptr_t)c1, (uintptr_t)c2, (uintptr_t)out, &nothing, msg, sizeof msg);
+    if (rc) return fail(rc, "%s", msg);
+    if (nothing) return TFHE_OK;
+    group = std::min(group, level);   // (one digit: every larger group is the whole ciphertext ring)
+
+    const size_t N = (size_t)c->N;
+    const limb_sel_t sel = first_limbs(level);
+    const mr_product_t M = mr_product_plan(c, level, c1 == c2, ntt_in != 0);
+    const bool ride = rescale && k > 0;                       // the rescale rides on the tail
+    const size_t r_rows = rescale && !ride ? 2 : 0;
+    const int d = (level + group - 1) / group, nw = level + k;
+    const size_t per_ct = (M.f_rows + 3 + r_rows) * level * N * 8, per_ct_ks = ((size_t)2 * nw + (size_t)d * nw) * N * 8;
+    const int64_t chunk = chunk_of(c, batch, 256, (size_t)4096 << 20, std::max(per_ct, per_ct_ks));
+    ksg_plan_t P;
+    rc = ksg_plan(c, Lk, level, k, group, 3, chunk, false, &P);
+    if (rc) return rc;
+    if (P.chunk != chunk) return fail(TFHE_E_HIP, "internal: the key switch plans another chunk");
+    ks_group_rescale_t rs{};
+    if (ride)
+        for (int j = 0; j < level - 1; j++) rs.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(c->q[level - 1] % c->q[j], c->q[j]), c->q[j]);
+    size_t region0 = P.bytes();
+    if (c->logN > 14) region0 = std::max(region0, (size_t)chunk * 3 * level * N * 8);   // run_ntt's scratch for the product at N > 2^14
+    region0 = (region0 + 255) & ~(size_t)255;
+    void* ws = nullptr;
+    rc = ensure_ws(c, region0 + (size_t)chunk * per_ct + M.park_bytes(), &ws);   // once, for both users, before any fork
+    if (rc) return rc;
+    u64 *S = P.region(ws, 0), *dig = P.region(ws, P.S_rows);
+    u64* F = (u64*)((char*)ws + region0);
+    u64* T = F + (size_t)chunk * M.f_rows * level * N;
+    u64* R = T + (size_t)chunk * 3 * level * N;
+    u64* SCR = R + (size_t)chunk * r_rows * level * N;
+    const int lo = level - (rescale ? 1 : 0);
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nct = std::min(chunk, batch - b0);
+        rc = mr_product(c, M, c1 + (size_t)b0 * 2 * level * N, c2 + (size_t)b0 * 2 * level * N, F, T, SCR, nct, level);
+        if (rc) return rc;
+        u64* dst = out + (size_t)b0 * 2 * lo * N;
+        rc = ksg_chunk(c, P, evk, T, r_rows ? R : dst, nct, S, dig, ride ? &rs : nullptr);
+        if (rc) return rc;
+        if (c->ws != ws) return fail(TFHE_E_HIP, "internal: the key switch moved the workspace");
+        if (r_rows) {
+            rc = do_rescale(c, R, dst, nct * 2, sel);         // crt.jl:215-228 on both components
             if (rc) return rc;
         }
     }

@@ -892,6 +892,26 @@ function mul_relin(ek::KeySwitchKey, c1::CipherText{E1,P,<:RingElement{ℛ,T,<:H
     rescale || return CipherText{Eo}(c1.params, unpack(ctx, out, ℛo, 2))
     rescaled_like(CipherText{Eo}(c1.params, c1.cs), unpack(ctx, out, ℛo, 2))
 end
+# The same on a key with grouped RNS digits and several special primes (tfhe_mul_relin_grouped; the key of keyswitch_grouped):
+# bit-identical to modswitch(keyswitch_grouped(ek, c1 * c2, ..)) (rescale = true) / keyswitch_grouped(ek, c1 * c2, ..); with a special
+# prime the rescale rides on the key switch's tail.  (Not executed anywhere yet: the tests check the ccall against the header.)
+function mul_relin_grouped(ek::KeySwitchKey, c1::CipherText{E1,P,<:RingElement{ℛ,T,<:HipVector}}, c2::CipherText{E2,P}, n_special::Integer, group::Integer;
+                           rescale::Bool=false) where {E1,E2,P,ℛ,T}
+    c1.params !== c2.params && throw(ToyFHE.UsageError("Attempting to multiply ciphertexts with differing parameters"))
+    @assert length(c1.cs) == 2 && length(c2.cs) == 2 && ToyFHE.relin_window(ek.params) == 0
+    keyring = NTT.ring(ek.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T)
+    rescale && level < 2 && throw(ToyFHE.UsageError("modswitch needs at least two CRT moduli"))
+    ctx = hipring(keyring); key = pack(ek)
+    a = pack(ctx, c1); b = c1 === c2 ? a : pack(ctx, c2); cnt = samecount(a, b)
+    ℛo = rescale ? ToyFHE.drop_last(ℛ) : ℛ; To = eltype(ℛo)
+    out = HipVector{To}(2 * nlimbs(To), degree(ℛ), cnt); on(ctx, (out,), (a, b, key))
+    GC.@preserve key a b out check(ccall((:tfhe_mul_relin_grouped, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{UInt64}, Cint, Ptr{UInt64}, Ptr{UInt64}, Cint, Cint, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, n_special, group, key.ptr, length(ek.key), a.ptr, b.ptr, 0, rescale ? 1 : 0, out.ptr, cnt))
+    Eo = product_encoding(E1, E2)
+    rescale || return CipherText{Eo}(c1.params, unpack(ctx, out, ℛo, 2))
+    rescaled_like(CipherText{Eo}(c1.params, c1.cs), unpack(ctx, out, ℛo, 2))
+end
 
 # ---- tensor for schemes whose mul_expand / mul_contract are the identity (BGV, CKKS; rlwe_she.jl:39-40,255-258) -----------
 function ToyFHE.enc_mul(c1::CipherText{E,P,<:RingElement{ℛ,T,<:HipVector}}, c2::CipherText{E,P}) where {E,P,ℛ,T}

@@ -152,6 +152,7 @@ def lib():
         "tfhe_bfv_contract": [vp, vp, vp, i64],
         "tfhe_bfv_mul_relin": [vp, vp, i32, vp, vp, vp, i64],
         "tfhe_mul_relin": [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, i64],
+        "tfhe_mul_relin_grouped": [vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, i64],
         "tfhe_encrypt": [vp, i32, i32, vp, C.c_double, C.c_double, u64, u64, C.c_uint32, u64, vp, vp, vp, i64],
         "tfhe_decrypt_phase": [vp, i32, i32, vp, vp, i32, i32, vp, i64],
         "tfhe_dot_plain": [vp, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint8), C.POINTER(vp), C.POINTER(sz), i32, vp, sz, i64, i32, i32p],
@@ -183,7 +184,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
     "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_keyswitch_grouped", "tfhe_rotate_grouped", "tfhe_rotate_many_grouped", "tfhe_matmul_diag_grouped", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
-    "tfhe_bfv_plan_set_variant", "tfhe_bfv_plan_workspace", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
+    "tfhe_bfv_plan_set_variant", "tfhe_bfv_plan_workspace", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_mul_relin_grouped", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
 ]
@@ -453,6 +454,12 @@ class Context:
         [batch][2][level][N], out [batch][2][level - rescale][N] coefficient domain; c1 == c2 squares"""
         check(lib().tfhe_mul_relin(self.h, key_limbs, level, int(bool(special)), evk, n_digits, c1, c2, int(bool(ntt_in)),
                                    int(bool(rescale)), out, batch))
+
+    def mul_relin_grouped(self, key_limbs, level, n_special, group, evk, n_digits, c1, c2, out, batch, ntt_in=False, rescale=False):
+        """mul_relin on a key with digits of `group` limbs and the key's last n_special limbs as special primes
+        (tfhe_mul_relin_grouped); operands as mul_relin, key as keyswitch_grouped"""
+        check(lib().tfhe_mul_relin_grouped(self.h, key_limbs, level, n_special, group, evk, n_digits, c1, c2, int(bool(ntt_in)),
+                                           int(bool(rescale)), out, batch))
 
     def encrypt(self, key_limbs, level, pk, out, batch, msg=None, rand=None, sigma_u=0.0, sigma_e=0.0, mult_e=1, seed=0, stream=1, first_poly=0):
         """public-key encryption of a batch in one call (tfhe_encrypt): pk [2][key_limbs][N] (mask, masked; NTT domain),

@@ -1502,7 +1502,25 @@ def mul_relin(ek, c1: CipherText, c2: CipherText, rescale: bool = False) -> Ciph
     if c1.params is not c2.params:
         raise UsageError("Attempting to multiply ciphertexts with differing parameters")
     _refuse_grouped(ek.params, "mul_relin")
-    inner = c1.params.params if isinstance(c1.params, ModulusRaised) else c1.params
+    return _mul_relin_packed(ek, c1, c2, rescale)
+
+
+def mul_relin_grouped(ek, c1: CipherText, c2: CipherText, rescale: bool = False) -> CipherText:
+    """mul_relin on a key with grouped digits (GroupedRaised; tfhe_mul_relin_grouped): modswitch(keyswitch(ek, c1 * c2)) (rescale=True)
+    or keyswitch(ek, c1 * c2), word for word, in ONE device call on the packed operands -- with a special prime the rescale rides on
+    the key switch's tail.  Usage checks, operand handling, scales and the packed result are mul_relin's."""
+    if isinstance(ek, (EvalMultKey, GaloisKey)):
+        ek = ek.key
+    if c1.params is not c2.params:
+        raise UsageError("Attempting to multiply ciphertexts with differing parameters")
+    if not isinstance(ek.params, GroupedRaised):
+        raise UsageError("mul_relin_grouped takes a key with grouped digits (GroupedRaised); the others go through mul_relin")
+    return _mul_relin_packed(ek, c1, c2, rescale)
+
+
+def _mul_relin_packed(ek, c1: CipherText, c2: CipherText, rescale: bool) -> CipherText:
+    """what mul_relin and mul_relin_grouped share, after the checks of the key's kind: `ek` a KeySwitchKey"""
+    inner = c1.params.params if isinstance(c1.params, (ModulusRaised, GroupedRaised)) else c1.params
     if isinstance(inner, BFVParams):
         raise UsageError("mul_relin serves the schemes without mul_expand / mul_contract (CKKS, BGV); "
                          "BFV multiplies and relinearises through its plan: BFVParams.plan().mul_relin")
@@ -1540,7 +1558,11 @@ def mul_relin(ek, c1: CipherText, c2: CipherText, rescale: bool = False) -> Ciph
     a, b = images[0], images[-1]
     ring_out = ring.drop_last() if rescale else ring
     out = DeviceBuffer(n * 2 * ring_out.L * ring.N)
-    keyring.ctx.mul_relin(keyring.L, level, special, ek.packed().ptr, len(ek.key), a.ptr, b.ptr, out.ptr, n, ntt_in=ntt_in, rescale=rescale)
+    if isinstance(params, GroupedRaised):
+        keyring.ctx.mul_relin_grouped(keyring.L, level, params.n_special, params.group, ek.packed().ptr, len(ek.key), a.ptr, b.ptr, out.ptr, n,
+                                      ntt_in=ntt_in, rescale=rescale)
+    else:
+        keyring.ctx.mul_relin(keyring.L, level, special, ek.packed().ptr, len(ek.key), a.ptr, b.ptr, out.ptr, n, ntt_in=ntt_in, rescale=rescale)
     scale = None if c1.scale is None else c1.scale * c2.scale   # ckksencoding.jl:133-135
     if rescale and scale is not None:
         scale = scale / ring.moduli[-1]                     # ckksencoding.jl:127-130
