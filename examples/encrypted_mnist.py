@@ -89,7 +89,8 @@ def encrypted_matmul(gk, W, x, B, cache=None, fused=False):
     if isinstance(gk, BsgsKeys):
         # the whole product in one device call by baby and giant steps (tfhe_matmul_bsgs): n1 + 64 / n1 - 2 keys instead of 63; the
         # diagonals are pre-rotated on the host (bsgs_diagonals) and encoded once per (matrix, level, scale)
-        return tf.matmul_bsgs(gk.baby, gk.giant, bsgs_encoded(gk, W, x, B, cache), x)
+        # (on keys with grouped digits: tfhe_matmul_bsgs_grouped)
+        return (tf.matmul_bsgs_grouped if _grouped(gk.baby + gk.giant) else tf.matmul_bsgs)(gk.baby, gk.giant, bsgs_encoded(gk, W, x, B, cache), x)
     if isinstance(gk, (list, tuple)) and cache is not None and fused:
         # the whole product in one device call (tfhe_matmul_diag): the diagonals are single plaintexts shared by the batch
         key = (id(W), "fused", x.ring().L, x.scale)
@@ -147,7 +148,8 @@ def encrypted_matmul_blocks(gk, Ws, xs, B, b, cache=None, name=None):
         bias = tf.ckks_encode(np.asarray(b, dtype=np.complex128), x.ring(), scale2)
         if cache is not None:
             cache[key] = bias
-    return tf.matmul_bsgs_blocks(gk.baby, gk.giant, [bsgs_encoded(gk, W, x, B, cache) for W in Ws], xs, bias)
+    product = tf.matmul_bsgs_blocks_grouped if _grouped(gk.baby + gk.giant) else tf.matmul_bsgs_blocks
+    return product(gk.baby, gk.giant, [bsgs_encoded(gk, W, x, B, cache) for W in Ws], xs, bias)
 
 
 class RectKeys:
@@ -205,10 +207,11 @@ def load_model(path=GOLDEN_MODEL):
 
 def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None,
         mul_relin=False, bsgs=0, blocks=False, rect=False, grouped=None, mul_relin_grouped=False):
-    """`grouped` = (K, G) (with `hoisted`): the key ring ends in K 60-bit special primes instead of one and every key
-    has grouped digits of G limbs (tf.GroupedRaised): the 63 Galois keys shrink from 6 to ceil(6 / G) components.  The square
-    layers go through tf.matmul_diag_grouped (with `fused`) or tf.rotate_many_grouped and the plaintext sum; the squares through
-    keyswitch (or `mul_relin_grouped`, below).  The baby-step/giant-step products have no grouped form and mul_relin takes per-limb keys.
+    """`grouped` = (K, G) (with `hoisted`, or with `bsgs` alone): the key ring ends in K 60-bit special primes instead of one and every key
+    has grouped digits of G limbs (tf.GroupedRaised): the Galois keys shrink from 6 to ceil(6 / G) components.  With `hoisted` the square
+    layers go through tf.matmul_diag_grouped (with `fused`) or tf.rotate_many_grouped and the plaintext sum; with `bsgs` (with or without
+    `blocks`) through tf.matmul_bsgs_grouped / tf.matmul_bsgs_blocks_grouped (tfhe_matmul_bsgs_grouped).  The squares go through
+    keyswitch (or `mul_relin_grouped`, below).  The fold (`rect`) has no grouped form and mul_relin takes per-limb keys.
     `mul_relin_grouped` (with `hoisted` and `grouped`): the two square layers as one device call each (tf.mul_relin_grouped =
     tfhe_mul_relin_grouped, rescale=True) instead of modswitch(keyswitch(ek, c * c)); same logits, bit for bit.
     `rect` (with `bsgs`): the last layer -- 10 x 64, .+ b -- as ONE tfhe_matmul_bsgs_fold call over 16 extended diagonals and the fold
@@ -224,9 +227,12 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
     of K, so each device call covers K ciphertexts (the batch the engine shards across GPUs)."""
     if (blocks or rect) and not bsgs:
         raise ValueError("blocks and rect need bsgs = n1 > 0")
-    if grouped is not None and (not hoisted or bsgs or mul_relin):
-        raise ValueError("grouped keys are covered for the hoisted circuit only (hoisted, with or without fused): the chained rotation by one "
-                         "prepared key, the baby-step/giant-step products (bsgs, blocks, rect) and mul_relin have no grouped form")
+    if grouped is not None and rect:
+        raise ValueError("rect goes through tfhe_matmul_bsgs_fold, which refuses keys with grouped digits: grouped goes with bsgs and blocks only")
+    if grouped is not None and (bool(hoisted) == bool(bsgs) or mul_relin):
+        raise ValueError("grouped keys are covered for the hoisted circuit only (hoisted, with or without fused) or, instead of it, for the "
+                         "baby-step/giant-step products (bsgs, with or without blocks): the chained rotation by one prepared key, the fold "
+                         "(rect) and mul_relin have no grouped form")
     if mul_relin_grouped and (grouped is None or not hoisted):
         raise ValueError("mul_relin_grouped is the square layer on grouped keys: it needs hoisted and grouped = (K, G)")
     if mul_relin_grouped:
@@ -372,8 +378,8 @@ if __name__ == "__main__":
     ap.add_argument("--blocks", action="store_true",
                     help="with --bsgs N1: the first dense layer (64 x 256 over the four squares, + bias) as one tfhe_matmul_bsgs_blocks call")
     ap.add_argument("--grouped", default=None, metavar="K,G",
-                    help="with --hoisted: K 60-bit special primes and G limbs per digit (GroupedRaised keys); the products through "
-                         "tfhe_matmul_diag_grouped (--fused) or tfhe_rotate_many_grouped")
+                    help="with --hoisted or with --bsgs N1 [--blocks]: K 60-bit special primes and G limbs per digit (GroupedRaised keys); the "
+                         "products through tfhe_matmul_diag_grouped (--fused), tfhe_rotate_many_grouped or tfhe_matmul_bsgs_grouped (--bsgs)")
     ap.add_argument("--mul-relin-grouped", action="store_true",
                     help="with --hoisted --grouped K,G: the two square layers through tf.mul_relin_grouped (one tfhe_mul_relin_grouped call "
                          "each, the rescale on the key switch's tail) instead of modswitch(keyswitch(ek, c * c))")
@@ -383,8 +389,10 @@ if __name__ == "__main__":
     if (a.blocks or a.rect) and not a.bsgs:
         ap.error("--blocks and --rect need --bsgs N1")
     grouped = tuple(int(v) for v in a.grouped.split(",")) if a.grouped else None
-    if grouped is not None and (len(grouped) != 2 or not a.hoisted or a.bsgs or a.mul_relin):
-        ap.error("--grouped K,G needs --hoisted and goes with neither --bsgs nor --mul-relin")
+    if grouped is not None and a.rect:
+        ap.error("--rect goes through tfhe_matmul_bsgs_fold, which refuses grouped keys: --grouped K,G goes with --bsgs N1 [--blocks] only")
+    if grouped is not None and (len(grouped) != 2 or bool(a.hoisted) == bool(a.bsgs) or a.mul_relin):
+        ap.error("--grouped K,G needs either --hoisted or --bsgs N1 [--blocks], and does not go with --mul-relin")
     if a.mul_relin_grouped and (grouped is None or not a.hoisted):
         ap.error("--mul-relin-grouped needs --hoisted --grouped K,G")
     run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin, bsgs=a.bsgs,

@@ -360,8 +360,10 @@ int tfhe_rotate_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, 
  * tfhe_matmul_diag_grouped:  out = diags[0] .* NTT(c) + sum_{r < n_rot} diags[r+1] .* NTT(rotate_grouped(gk_r, c));
  *   diags: device [n_rot + 1][level][N], NTT domain, shared by the batch; ct: [batch][2][level][N] coefficient domain; out:
  *   [batch][2][level][N] NTT domain; n_rot <= 64 -- the contract of tfhe_matmul_diag.  Word for word tfhe_rotate_many_grouped ->
- *   tfhe_nntt -> tfhe_dot.  Every limb of every key sum is inverse-transformed: the evaluation-domain form of tfhe_matmul_diag is
- *   not built for several special primes.
+ *   tfhe_nntt -> tfhe_dot.  With n_special >= 1 and n_rot >= 1 the rotations are finished in the evaluation domain: the k-step
+ *   contraction of a limb is affine in its word, so only the n_special special limbs of every key sum are inverse-transformed (after
+ *   the permutation pi_g) and their lift costs `level` forward transforms; TFHE_MD_COEFF=1 (read once per process) keeps the
+ *   coefficient-domain tail, which also serves n_special == 0.  Both routes give the same words.
  * Checked on the host before any device use, in this order: a null ctx, evks, galois_elements, ct, out (diags for the product) or
  * n_rot < 0 (TFHE_E_BADARG); n_rot > 64, the product only (TFHE_E_UNSUPPORTED); for r = 0, 1, .. in turn the checks of
  * tfhe_rotate_grouped on (evks[r], galois_elements[r]) in that entry point's order, a null evks[r] being its null argument; `out`
@@ -371,13 +373,43 @@ int tfhe_rotate_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, 
  * not depend on the chunk (tfhe_ctx_set_chunk) or the tile.
  * Workspace: tfhe_rotate_many_grouped takes its block -- digits and key sums of a chunk, up to 8 GiB, and as much again for the transforms
  * above N = 2^14 -- from the context's long-lived workspace, where it STAYS after the call (as tfhe_rotate_many's does) until a larger
- * request or tfhe_ctx_destroy; tfhe_ctx_set_chunk bounds it.  tfhe_matmul_diag_grouped borrows its block for the call, as tfhe_matmul_diag.
- * Still refused on grouped keys: tfhe_matmul_bsgs*, tfhe_rotate_sum and the fused N <= 2^14 key switch; tfhe_mul_relin takes per-limb
- * keys only -- the product on grouped keys is tfhe_mul_relin_grouped, below. */
+ * request or tfhe_ctx_destroy; tfhe_ctx_set_chunk bounds it.  tfhe_matmul_diag_grouped borrows its block for the call, as tfhe_matmul_diag:
+ * per ciphertext of a chunk d nw + R 2 nw + R 2 level + 2 level + R 2 n_special rows of N words (digits, key sums, lifts or rotated
+ * ciphertexts, the ciphertext's transform, the permuted special limbs), and above N = 2^14 the largest transform's rows once more.
+ * Still refused on grouped keys: the per-limb entry points tfhe_matmul_bsgs* (the product by baby and giant steps on grouped keys is
+ * tfhe_matmul_bsgs_grouped, below; the fold, tfhe_matmul_bsgs_fold, has no grouped form), tfhe_rotate_sum and the
+ * fused N <= 2^14 key switch; tfhe_mul_relin takes per-limb keys only -- the product on grouped keys is tfhe_mul_relin_grouped, below. */
 int tfhe_rotate_many_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *const *evks, int n_digits,
                              const uint64_t *galois_elements, int n_rot, const uint64_t *ct, uint64_t *out, int64_t batch);
 int tfhe_matmul_diag_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *const *evks, int n_digits,
                              const uint64_t *galois_elements, int n_rot, const uint64_t *diags, const uint64_t *ct, uint64_t *out, int64_t batch);
+/* The block-row product by baby and giant steps on grouped-digit keys, in one call: the contract of tfhe_matmul_bsgs_blocks (n_in = 1,
+ * bias = NULL: of tfhe_matmul_bsgs) with every rotation a tfhe_rotate_grouped.
+ *     inner_j = sum_{m < n_in} sum_{i = 0 .. n_baby} diags[m][j][i] .* NTT(r_i(cts[m]))      j = 0 .. n_giant,  r_0 = identity
+ *     out     = INTT(inner_0) + sum_{j = 1 .. n_giant} rotate_grouped(giant key j - 1, INTT(inner_j))   (+ bias on component 0)
+ *   key_limbs, level, n_special, group, n_digits: as tfhe_rotate_many_grouped;  baby_evks / giant_evks: HOST arrays of device pointers
+ *   to PREPARED grouped Galois keys (tfhe_galois_key_prepare), as for tfhe_rotate_many_grouped -- there is no unprepared mode, a key may
+ *   appear more than once;  baby_galois / giant_galois: HOST arrays;  n_baby, n_giant in [0, 64];  diags, cts, n_in in [1, 64], bias,
+ *   out: the layouts of tfhe_matmul_bsgs_blocks.
+ * The result equals, word for word, per input tfhe_rotate_many_grouped over the baby keys -> tfhe_nntt; per giant step ONE tfhe_dot over
+ * all n_in (n_baby + 1) terms; -> tfhe_inntt -> tfhe_rotate_grouped per giant step j >= 1 -> tfhe_add -> tfhe_add of the bias onto
+ * component 0, on either route of the baby phase (evaluation-domain or TFHE_MD_COEFF=1, see tfhe_matmul_diag_grouped) and for every
+ * tfhe_ctx_set_chunk.  (n_special, group) = (1, 1) and (0, 1) give the words of tfhe_matmul_bsgs_blocks with special = 1 and 0;
+ * n_giant = 0 gives tfhe_inntt of tfhe_matmul_diag_grouped.  The giant steps are hoisted rotations with a tile of one key, finished in
+ * the coefficient domain.
+ * Checked on the host before any device use, in this order: a null ctx, baby_evks, baby_galois, giant_evks, giant_galois, diags, cts
+ * or out; a null key among the first n_baby / n_giant, a null diags[m] or cts[m] among the first n_in; n_baby / n_giant outside
+ * [0, 64], n_in outside [1, 64] (all TFHE_E_BADARG); for the baby keys, then the giant keys, in turn the shape checks of
+ * tfhe_rotate_grouped on galois[r] in that entry point's order (without any key: those of tfhe_keyswitch_grouped, once); `out`
+ * starting where, or overlapping anywhere, bias, any cts[m] or any diags[m] (TFHE_E_BADARG).  `out` is untouched on every refusal.
+ * batch == 0 does nothing after the checks.  The call borrows its workspace block, as tfhe_matmul_bsgs_blocks: the rows of
+ * tfhe_matmul_diag_grouped with R = n_baby (at least one key sum when there are giant steps) plus (2 n_giant + 1) 2 level rows per
+ * ciphertext; the giant rotations run in the baby phase's digit and key-sum regions. */
+int tfhe_matmul_bsgs_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group,
+                             const uint64_t *const *baby_evks, const uint64_t *baby_galois, int n_baby,
+                             const uint64_t *const *giant_evks, const uint64_t *giant_galois, int n_giant, int n_digits,
+                             const uint64_t *const *diags, const uint64_t *const *cts, int n_in,
+                             const uint64_t *bias, uint64_t *out, int64_t batch);
 /* The ciphertext product, relinearised on a grouped-digit key and optionally rescaled, in one call: tfhe_mul_relin on the keys of
  * tfhe_keyswitch_grouped (a grouped-digit key is first of all a relinearisation key: ceil(level / group) components instead of level).
  *   c1, c2: [batch][2][level][N]; ntt_in = 0: coefficient domain, 1: NTT domain (natural order).  c1 == c2 (squaring) allowed.

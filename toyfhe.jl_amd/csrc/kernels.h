@@ -1380,6 +1380,8 @@ struct ks_keys_t {
     size_t s_stride;  // words of S per key
     const u64* epi_x; // EPI kernels (tfhe_matmul_diag, evaluation-domain form): X [batch][2][level][N]; limb j < level of the sums
                       // leaves as V = S P^-1 (+ X[b][0][j] for s = 0) instead of S (k_md_v folded into the store)
+    int epi_level;    // EPI kernels: the ciphertext's limb count -- A.level on per-limb keys, where a digit is a limb; on grouped-digit
+                      // keys A.level counts the digits (make_ks_arg_grouped) and the ciphertext has its own
     const u64* key[TFHE_DOT_MAX];
 };
 // Layout of the key sums in the EPI kernels (tfhe_matmul_diag, evaluation-domain form), per ciphertext a block of 2 nw n words:
@@ -1482,8 +1484,8 @@ __global__ __launch_bounds__(256) void k_ks_inner(const u64* __restrict__ evk, c
                     r2[h] = addmod(r2[h], reduce(s2), L.q);
                 }
                 if constexpr (EPI) {
-                    if (i0 + DCH >= A.level && j < (u32)A.level) {
-                        r1[h] = addmod(shoup_full(r1[h], A.pinv[j], L.q), K.epi_x[(((size_t)bb[h] * 2) * A.level + j) * n + k], L.q);
+                    if (i0 + DCH >= A.level && j < (u32)K.epi_level) {
+                        r1[h] = addmod(shoup_full(r1[h], A.pinv[j], L.q), K.epi_x[(((size_t)bb[h] * 2) * K.epi_level + j) * n + k], L.q);
                         r2[h] = shoup_full(r2[h], A.pinv[j], L.q);
                     }
                 }
@@ -1580,8 +1582,8 @@ __global__ __launch_bounds__(256) void k_ks_inner_n2(const u64* __restrict__ evk
                 r2[v] = barrett_reduce128(lo, hi, br);
             }
             if constexpr (EPI) {
-                if (i0 + DCH >= A.level && j < (u32)A.level) {
-                    const u64x2_t x = *(const u64x2_t*)(K.epi_x + (((size_t)b * 2) * A.level + j) * n + k);
+                if (i0 + DCH >= A.level && j < (u32)K.epi_level) {
+                    const u64x2_t x = *(const u64x2_t*)(K.epi_x + (((size_t)b * 2) * K.epi_level + j) * n + k);
 #pragma unroll
                     for (int v = 0; v < 2; v++) {
                         r1[v] = addmod(shoup_full(r1[v], A.pinv[j], br.q), x[v], br.q);

@@ -91,7 +91,7 @@ static int ks_digits_fwd(tfhe_ctx* c, const ks_arg_t& A, const u64* ct, u64* dig
 // S_s = sum_i evk_{i,s} (.) digit_i over the working limbs (NTT domain), S: [batch][2][nw][N]
 // keys != nullptr: `nkeys` keys against the same digits in one launch, key r writing S + r * batch*2*nw*N (tfhe_matmul_diag)
 static int ks_inner_launch(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* evk, const u64* dig, u64* S, int64_t batch,
-                           const uint64_t* const* keys = nullptr, int nkeys = 0, const u64* epi_x = nullptr) {
+                           const uint64_t* const* keys = nullptr, int nkeys = 0, const u64* epi_x = nullptr, int epi_level = 0) {
     const int nw = A.nw;
     ks_keys_t K{};
     if (keys) {
@@ -100,6 +100,7 @@ static int ks_inner_launch(tfhe_ctx* c, const ks_arg_t& A, int Lk, const u64* ev
         for (int r = 0; r < nkeys; r++) K.key[r] = keys[r];
         evk = keys[0];
         K.epi_x = epi_x;
+        K.epi_level = epi_level ? epi_level : A.level;   // (grouped-digit keys: A.level counts digits, the caller names the ciphertext's limbs)
     }
     const unsigned gy = keys ? (unsigned)nkeys : 1u;
     const u32 n = (u32)c->N;

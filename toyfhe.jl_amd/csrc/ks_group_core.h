@@ -1,11 +1,12 @@
 // ks_group_core.h -- the kernels of the key switch with grouped RNS digits and several special primes (tfhe_keyswitch_grouped and the
-// hoisted rotations, ks_api.inc; the tail that carries the rescale of tfhe_mul_relin_grouped, mul_api.inc), and their per-coefficient bodies.
+// hoisted rotations, ks_api.inc; the tail that carries the rescale of tfhe_mul_relin_grouped, mul_api.inc; the permutation and the lift of
+// the evaluation-domain rotation phase of tfhe_matmul_diag_grouped / tfhe_matmul_bsgs_grouped, md_api.inc), and their per-coefficient bodies.
 //
 // Digit g of c[end] is the centred representative of c[end] modulo Q_g = prod_{i in G_g} q_i (the exact CRT value with the tie
 // rule of signedmod.jl:12-19, n > Q_g ÷ 2 => n - Q_g; switch(ℛ_W, .) of bfv.jl:202-226 on the sub-ring of the group; with one limb
 // per group the digit of rlwe_she.jl:326-329), reduced into every working limb W = [0 .. level-1] ∪ [the k special primes].  The
 // key sums over W are contracted by modswitch (crt.jl:215-228, unsigned c_last) once per special prime, the last one first.
-// The bodies are TFHE_HD: tests/ks_group_emul runs them on the host.
+// The bodies are TFHE_HD: tests/ks_group_emul, tests/ks_group_rot_emul and tests/mdg_lift_emul run them on the host.
 #pragma once
 #include <cstdio>
 
@@ -63,6 +64,49 @@ inline int ks_group_many_check(bool product, bool any_null, int L, int64_t N, in
     const auto overlap = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a < b + nb && b < a + na; };
     if (overlap(out, out_bytes, ct, ct_bytes) || (product && overlap(out, out_bytes, diags, (uint64_t)(n_rot + 1) * level * (uint64_t)N * 8)))
         return snprintf(msg, cap, "out overlaps an operand"), TFHE_E_BADARG;
+    *nothing_to_do = batch == 0;
+    return TFHE_OK;
+}
+
+// The host checks of tfhe_matmul_bsgs_grouped in the order include/toyfhe_hip.h states, on plain numbers: any_null -- a null context, key
+// or Galois array, diags, cts or out; the HOST arrays are read no further than a valid count reaches; bias / out -- addresses, compared
+// and never followed (bias may be 0).  *nothing_to_do comes back true where the call returns TFHE_OK without work (an empty batch).
+inline int ks_group_bsgs_check(bool any_null, int L, int64_t N, int Lk, int level, int k, int group, int n_digits, int64_t batch,
+                               const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby, const uint64_t* const* giant_evks,
+                               const uint64_t* giant_galois, int n_giant, const uint64_t* const* diags, const uint64_t* const* cts, int n_in,
+                               uintptr_t bias, uintptr_t out, bool* nothing_to_do, char* msg, size_t cap, int max_n = 64) {
+    msg[0] = 0;
+    *nothing_to_do = false;
+    if (any_null) return snprintf(msg, cap, "null argument"), TFHE_E_BADARG;
+    const auto within = [max_n](int n) { return n < 0 ? 0 : (n > max_n ? max_n : n); };
+    for (int r = 0; r < within(n_baby); r++)
+        if (!baby_evks[r]) return snprintf(msg, cap, "null baby key %d", r), TFHE_E_BADARG;
+    for (int r = 0; r < within(n_giant); r++)
+        if (!giant_evks[r]) return snprintf(msg, cap, "null giant key %d", r), TFHE_E_BADARG;
+    for (int m = 0; m < within(n_in); m++) {
+        if (!diags[m]) return snprintf(msg, cap, "null diagonals of input %d", m), TFHE_E_BADARG;
+        if (!cts[m]) return snprintf(msg, cap, "null ciphertext of input %d", m), TFHE_E_BADARG;
+    }
+    if (n_baby < 0 || n_baby > max_n) return snprintf(msg, cap, "n_baby=%d outside [0,%d]", n_baby, max_n), TFHE_E_BADARG;
+    if (n_giant < 0 || n_giant > max_n) return snprintf(msg, cap, "n_giant=%d outside [0,%d]", n_giant, max_n), TFHE_E_BADARG;
+    if (n_in < 1 || n_in > max_n) return snprintf(msg, cap, "n_in=%d outside [1,%d]", n_in, max_n), TFHE_E_BADARG;
+    for (int r = 0; r < n_baby + n_giant; r++) {
+        const uint64_t g = r < n_baby ? baby_galois[r] : giant_galois[r - n_baby];
+        const int rc = ks_group_check(false, L, N, Lk, level, k, group, n_digits, 2, batch, true, g, msg, cap);
+        if (rc) return rc;
+    }
+    if (n_baby + n_giant == 0) {
+        const int rc = ks_group_check(false, L, N, Lk, level, k, group, n_digits, 2, batch, false, 0, msg, cap);
+        if (rc) return rc;
+    }
+    // the closing sum writes `out` while other workgroups still read the operands of the next chunk
+    const uint64_t ct_bytes = (uint64_t)batch * 2 * level * (uint64_t)N * 8;
+    const uint64_t diag_bytes = (uint64_t)(n_giant + 1) * (n_baby + 1) * level * (uint64_t)N * 8;
+    const auto overlap = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a == b || (a < b + nb && b < a + na); };
+    bool hit = bias && overlap(out, ct_bytes, bias, (uint64_t)level * (uint64_t)N * 8);
+    for (int m = 0; m < n_in && !hit; m++)
+        hit = overlap(out, ct_bytes, (uintptr_t)cts[m], ct_bytes) || overlap(out, ct_bytes, (uintptr_t)diags[m], diag_bytes);
+    if (hit) return snprintf(msg, cap, "out overlaps an operand"), TFHE_E_BADARG;
     *nothing_to_do = batch == 0;
     return TFHE_OK;
 }
@@ -169,6 +213,26 @@ TFHE_HD void ks_group_rot_tail_coeff(const u64* t, const u64* c, u64* o, size_t 
         }
         o[(size_t)j * n + m] = x;
     }
+}
+
+// ---- the lift of the evaluation-domain rotation phase (mdg_rotations, md_api.inc) ----------------------------------------------------
+// ks_group_tail_limb is affine in x: tail_j(x) = x Pinv_j + tail_j(0), Pinv_j = prod_t inv[t][j].  In the evaluation domain the key
+// sums of a hoisted rotation keep the first term (V = S' Pinv_j, the key-sum kernels' epilogue) and only the second needs the
+// coefficient domain -- it depends on the K special words alone:  U_j = -tail_j(0) = negmod(ks_group_tail_limb<K>(0, y)), with y the
+// "lasts" ks_group_tail_special<K> leaves from the special words of sigma_g(INTT(S')).  The rotated ciphertext is V o pi_g - NTT_j(U_j).
+template <int K>
+TFHE_HD u64 mdg_lift_limb(const u64 (&y)[K], const barrett_t& bj, const tw_t (*inv)[TFHE_MAX_LIMBS], int j) {
+    return negmod(ks_group_tail_limb<K>(0, y, bj, inv, j), bj.q);
+}
+// One coefficient of one row group: p -> the coefficient in special row 0 (K rows of n words), u -> the same coefficient in row 0 of
+// the group's `level` output rows.  lb: the nw working limbs' Barrett words, the special primes last.
+template <int K>
+TFHE_HD void mdg_lift_coeff(const u64* p, u64* u, size_t n, int level, const barrett_t* lb, const tw_t (*inv)[TFHE_MAX_LIMBS]) {
+    u64 y[K];
+#pragma unroll
+    for (int t = 0; t < K; t++) y[t] = p[(size_t)t * n];
+    ks_group_tail_special<K>(y, lb + level, inv, level);
+    for (int j = 0; j < level; j++) u[(size_t)j * n] = mdg_lift_limb<K>(y, lb[j], inv, j);
 }
 
 #if defined(__HIPCC__)
@@ -394,6 +458,68 @@ __global__ __launch_bounds__(256) void k_ks_group_rot_tail(const u64* __restrict
             const u64 t = ((u64)i * g) & mask2n;
             ks_group_rot_tail_coeff<K>(tg + i, cg ? cg + i : nullptr, og, n, (u32)t & (n - 1), t >= n, (int)level, lb, linv);
         }
+    }
+}
+// ---- the evaluation-domain rotation phase on grouped-digit keys (mdg_rotations, md_api.inc) -------------------------------------------
+// k_md_special_perm for K special limbs: PB[grp][t] = S'[grp][level + t] o pi_g, grp = (r * batch + b) * 2 + s, out of the key sums in
+// the EPI layout (epi_pair): both components of a position come from one 16-byte gather.  The XCD-cooperative walk of
+// k_md_special_perm over the rows (ciphertext, special limb): one window of 2 N words per XCD at a time, teams for small rows.
+__global__ __launch_bounds__(256) void k_mdg_special_perm(const u64* __restrict__ S, u64* __restrict__ PB, rot_tail_arg_t G, u32 n, u32 nw,
+                                                           u32 level, u32 nsp, u32 batch, u32 ngroups) {
+    const u32 xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
+    const u32 spt = n / blockDim.x >= nslot ? nslot : (n / blockDim.x ? n / blockDim.x : 1u), teams = nslot / spt, team = slot / spt, ts = slot % spt;
+    if (team >= teams) return;
+    for (u32 row = team * 8u + xcd; row < (ngroups / 2u) * nsp; row += 8u * teams) {   // row = ci * nsp + t, ciphertext ci = r * batch + b
+        const u32 ci = row / nsp, t = row % nsp;
+        const u64 g = G.g[ci / batch];
+        const u64x2_t* s = (const u64x2_t*)(S + epi_pair(ci, level + t, 0u, nw, n));
+        u64 *d0 = PB + ((size_t)(2u * ci) * nsp + t) * n, *d1 = d0 + (size_t)nsp * n;
+        for (u32 m = ts * blockDim.x + threadIdx.x; m < n; m += spt * blockDim.x) {
+            const u64x2_t w = s[galois_ntt_pos(m, g, n)];
+            d0[m] = w.x;
+            d1[m] = w.y;
+        }
+    }
+}
+// U [groups][level][N] from PB [groups][K][N], the inverse-transformed special limbs (coefficient domain, canonical): per coefficient
+// the triangular steps on the K special words, then -tail_j(0) for every ciphertext limb (mdg_lift_coeff).  A stream: K rows in,
+// `level` rows out per group, V coefficients per thread (V = 2: 16-byte loads and stores, as k_ks_group_tail); the constants sit in
+// LDS, as in k_ks_group_rot_tail.  K + 1 words live per coefficient.  grid: groups * gx workgroups, gx = ceil(N / (256 V)).
+template <int K, int V>
+__global__ __launch_bounds__(256) void k_mdg_lift(const u64* __restrict__ PB, u64* __restrict__ U, const ntt_limb_t* __restrict__ LT,
+                                                   ks_group_arg_t A, u32 n, u32 gx) {
+    __shared__ barrett_t lb[TFHE_MAX_LIMBS];
+    __shared__ tw_t linv[K][TFHE_MAX_LIMBS];
+    const u32 level = (u32)A.level, nw = (u32)A.nw;
+    for (u32 j = threadIdx.x; j < nw; j += blockDim.x) {
+        lb[j] = LT[A.w.idx[j]].br;
+#pragma unroll
+        for (int t = 0; t < K; t++) linv[t][j] = A.inv[t][j];
+    }
+    __syncthreads();
+    const u32 i = ((blockIdx.x % gx) * 256 + threadIdx.x) * (u32)V;
+    const size_t grp = blockIdx.x / gx;
+    if (i >= n) return;
+    const u64* p = PB + grp * K * n + i;
+    u64* u = U + grp * level * n + i;
+    if constexpr (V == 2) {
+        u64 y[2][K];
+#pragma unroll
+        for (int t = 0; t < K; t++) {
+            const u64x2_t x = *(const u64x2_t*)(p + (size_t)t * n);
+            y[0][t] = x.x; y[1][t] = x.y;
+        }
+#pragma unroll
+        for (int v = 0; v < 2; v++) ks_group_tail_special<K>(y[v], lb + level, linv, (int)level);
+        for (u32 j = 0; j < level; j++) {
+            const barrett_t bj = lb[j];
+            u64x2_t r;
+            r.x = mdg_lift_limb<K>(y[0], bj, linv, (int)j);
+            r.y = mdg_lift_limb<K>(y[1], bj, linv, (int)j);
+            *(u64x2_t*)(u + (size_t)j * n) = r;
+        }
+    } else {
+        mdg_lift_coeff<K>(p, u, n, (int)level, lb, linv);
     }
 }
 #endif  // __HIPCC__

@@ -2,6 +2,8 @@
 // tfhe_rotate_sum and the rectangular product tfhe_matmul_bsgs_fold: the shared rotation phase (md_plan, md_bufs, md_rotations), its
 // workspace, the fold (md_fold_plan, md_fold_run) and the five entry points; included by toyfhe_hip.hip after ks_api.inc, whose key-sum, digit and
 // rotation helpers (ks_digits_fwd, ks_inner_launch, keyswitch_impl, ks_plan, rotate_many_ws) it calls.  Kernels: kernels.h k_md_*.
+// At the end: the same rotation phase on grouped-digit keys (mdg_plan, mdg_bufs, mdg_rotations; kernels ks_group_core.h k_mdg_*) with its
+// two entry points, tfhe_matmul_diag_grouped and tfhe_matmul_bsgs_grouped, on the hoisting helpers of ks_api.inc (ksg_*).
 
 // tfhe_matmul_diag, evaluation-domain form: U[grp][j] = NTT_j( [P[grp]] mod q_j ) (x P^-1 unless *scaled comes back false) for
 // the `groups` special-limb rows P (coefficient domain, canonical) and the limbs j of `sl`.  At N = 2^16 the lift rides on the
@@ -631,48 +633,210 @@ int tfhe_matmul_bsgs_fold(tfhe_ctx* c, int Lk, int level, int special, const uin
     return matmul_bsgs_run(c, Lk, level, special, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags, cts, n_in, bias, out, batch, &F);
 }
 
+// ---- the rotation phase on grouped-digit keys -------------------------------------------------------------------------------------
+// md_plan / md_bufs / md_rotations for keys with grouped RNS digits and K = n_special special primes (ks_group_core.h).  The K-step
+// contraction of one ciphertext limb is affine in its word, tail_j(x) = x Pinv_j + tail_j(0) with Pinv_j = prod_t p_t^-1 mod q_j, NTT_j
+// is linear and sigma_g is the permutation pi_g in the evaluation domain, so exactly as for one special prime (kernels.h, above
+// k_md_special_perm)
+//     NTT_j(rotate_grouped(gk, c))_s [k] = V_s,j[pi_g k] - U_s,j[k]
+//     V_s,j = S'_s,j Pinv_j + NTT_j(c_0) [s = 0]                       the key-sum kernels' epilogue (EPI), unpermuted
+//     y     = ks_group_tail_special<K>( INTT_{p_u}( S'_s,p_u o pi_g ), u < K )      k_mdg_special_perm, K inverse transforms
+//     U_s,j = NTT_j( negmod( ks_group_tail_limb<K>(0, y) ) )             k_mdg_lift, `level` forward transforms in place
+// The special limbs are permuted BEFORE their inverse transform: the unsigned representatives the floors take are the rotated
+// polynomial's (the point k_ks_group_rot_tail makes about signs).  K inverse and `level` forward transforms per key-sum component
+// instead of level + K inverse, the tail and `level` forward.  Exact arithmetic on canonical residues: the words of
+// tfhe_rotate_many_grouped -> tfhe_nntt.  U carries its scale: k_md_acc<false, ..> reads V, U, X as the per-limb phase leaves them.
+// The coefficient route (K = 0, no rotations, or TFHE_MD_COEFF=1): ksg_hoist_tile -> forward transforms, for k_md_acc_dense.
+struct mdg_plan_t {
+    ksg_hoist_t H;
+    ks_arg_t A;          // H.P.A with pinv[j] = Pinv_j: the key sums' epilogue
+    limb_sel_t sl, sp;   // the ciphertext's limbs; the K special primes
+    rot_tail_arg_t G;
+    rescale_arg_t ra;    // (k_md_acc's USCALE factors: unused, U carries its scale)
+    int Lk, level, K, nw, R;
+    bool eval_form;
+    // workspace rows (N words) per ciphertext: digits d nw + key sums max(R, giant) 2 nw + U / rotated ciphertexts R 2 level + the
+    // ciphertext's own transform 2 level + the permuted special limbs R 2 K
+    size_t dig_rows, S_rows, rows;
+    size_t ntt_rows;     // rows of the largest stand-alone transform, per ciphertext
+};
+// giant: the digits and ONE key sum are also wanted when there is no baby step (the giant rotations of tfhe_matmul_bsgs_grouped reuse
+// the two regions once the baby phase of the chunk is over)
+static int mdg_plan(tfhe_ctx* c, int Lk, int level, int k, int group, const uint64_t* galois, int R, bool giant, mdg_plan_t* P) {
+    *P = mdg_plan_t{};
+    const int rc = ksg_hoist_plan(c, Lk, level, k, group, std::max(R, giant ? 1 : 0), &P->H);
+    if (rc) return rc;
+    const ks_group_arg_t& G = P->H.P.G;
+    P->Lk = Lk; P->level = level; P->K = k; P->nw = G.nw; P->R = R;
+    P->sl = first_limbs(level);
+    P->sp.n = k;
+    for (int t = 0; t < k; t++) P->sp.idx[t] = G.w.idx[level + t];
+    P->A = P->H.P.A;
+    for (int j = 0; j < level && k > 0; j++) {
+        const u64 qj = c->q[j];
+        u64 pinv = 1 % qj;
+        for (int t = 0; t < k; t++) pinv = hostmath::mulmod_slow(pinv, G.inv[t][j].w, qj);
+        P->A.pinv[j] = hostmath::make_tw(pinv, qj);
+    }
+    for (int r = 0; r < R; r++) P->G.g[r] = galois[r];
+    static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
+    P->eval_form = k >= 1 && R >= 1 && !md_coeff;
+    const size_t ct_rows = (size_t)2 * level;
+    P->dig_rows = (R || giant) ? P->H.dig_rows : 0;
+    P->S_rows = (size_t)std::max(R, giant ? 1 : 0) * 2 * G.nw;
+    P->rows = P->dig_rows + P->S_rows + (size_t)R * ct_rows + ct_rows + (size_t)R * 2 * k;
+    P->ntt_rows = std::max({P->dig_rows, P->S_rows, (size_t)R * ct_rows, ct_rows});
+    return TFHE_OK;
+}
+// S: the key sums -- V in the EPI layout (evaluation-domain form) or [R][nb][2][nw][N];  ROT: U, or the transformed rotated
+// ciphertexts, [R][nb][2][level][N];  PB: [R][nb][2][K][N]
+struct mdg_bufs_t { u64 *dig, *S, *ROT, *X, *PB, *end; };
+static mdg_bufs_t mdg_bufs(const mdg_plan_t& P, u64* base, int64_t chunk, size_t N) {
+    mdg_bufs_t B{};
+    B.dig = base;
+    B.S = B.dig + (size_t)chunk * P.dig_rows * N;
+    B.ROT = B.S + (size_t)chunk * P.S_rows * N;
+    B.X = B.ROT + (size_t)chunk * P.R * 2 * P.level * N;
+    B.PB = B.X + (size_t)chunk * 2 * P.level * N;
+    B.end = base + (size_t)chunk * P.rows * N;
+    return B;
+}
+// X = NTT(cin) and, per rotation r: evaluation-domain form -- V in S and U in ROT; otherwise NTT(rotate_grouped(gk_r, cin)) in ROT
+static int mdg_rotations(tfhe_ctx* c, const mdg_plan_t& P, const uint64_t* const* evks, const u64* cin, int64_t nb, const mdg_bufs_t& B) {
+    const int level = P.level, R = P.R;
+    const size_t N = (size_t)c->N;
+    const u32 n = (u32)N;
+    const bool v2 = N % 2 == 0 && ((uintptr_t)cin & 15u) == 0;
+    int rc = run_ntt(c, false, cin, B.X, nb * 2 * level, P.sl);
+    if (rc || R == 0) return rc;
+    rc = ksg_digits_fwd(c, P.H.P, cin, B.dig, nb, v2);
+    if (rc) return rc;
+    if (!P.eval_form) {
+        rc = ksg_hoist_tile(c, P.H, evks, P.G.g, R, cin, nb, B.dig, B.S, B.ROT, (size_t)nb * 2 * level * N);
+        if (rc) return rc;
+        return run_ntt(c, false, B.ROT, B.ROT, (int64_t)R * nb * 2 * level, P.sl);
+    }
+    const int64_t groups = (int64_t)R * nb * 2;
+    rc = ks_inner_launch(c, P.A, P.Lk, nullptr, B.dig, B.S, nb, evks, R, B.X, level);   // limbs j < level leave as V = S' Pinv + X0 [s = 0]
+    if (rc) return rc;
+    rc = launch(c, k_mdg_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, (const u64*)B.S, B.PB, P.G, n, (u32)P.nw, (u32)level, (u32)P.K,
+                (u32)nb, (u32)groups);
+    if (rc) return rc;
+    rc = run_ntt(c, true, B.PB, B.PB, groups * P.K, P.sp);
+    if (rc) return rc;
+    const bool lv2 = N % 2 == 0 && (((uintptr_t)B.PB | (uintptr_t)B.ROT) & 15u) == 0;
+    const u32 gx = lv2 ? (n / 2 + 255) / 256 : (n + 255) / 256;
+    rc = dispatch_int<1, TFHE_KSG_MAX_SPECIAL>(P.K, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        auto lift = lv2 ? k_mdg_lift<K, 2> : k_mdg_lift<K, 1>;
+        return launch(c, lift, dim3((unsigned)(groups * gx)), dim3(256), 0, (const u64*)B.PB, B.ROT, c->limbs_dev, P.H.P.G, n, gx);
+    });
+    if (rc) return rc;
+    return run_ntt(c, false, B.ROT, B.ROT, groups * level, P.sl);
+}
+// the accumulation after mdg_rotations over one chunk: ngiant1 sums into `inner`, tiled (bsgs_log_tile); seeded: continue from `inner`
+static int mdg_accumulate(tfhe_ctx* c, const mdg_plan_t& P, const mdg_bufs_t& B, const u64* diags, u64* inner, int64_t nb, int ngiant1, bool seeded) {
+    const size_t N = (size_t)c->N;
+    const int level = P.level;
+    return dispatch_int<0, 2>(bsgs_log_tile(ngiant1), [&](auto lg) {
+        constexpr int NG = 1 << decltype(lg)::value;
+        if (P.eval_form) {
+            auto acc = seeded ? k_md_acc<false, NG, true> : k_md_acc<false, NG>;
+            return launch(c, acc, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, (const u64*)B.X, (const u64*)B.S, (const u64*)B.ROT, diags, inner, c->limbs_dev,
+                          P.sl, P.G, P.ra, (u32)N, (u32)P.nw, (u32)P.R, (u32)nb, (u32)ngiant1);
+        }
+        auto acc = seeded ? k_md_acc_dense<NG, true> : k_md_acc_dense<NG>;
+        return launch(c, acc, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)B.X, (const u64*)B.ROT, diags, inner, c->limbs_dev,
+                      P.sl, (u32)N, (u32)P.R, (u32)(nb * 2 * level), (u32)ngiant1);
+    });
+}
+
 // ---- the diagonal product on grouped-digit keys -----------------------------------------------------------------------------------
-// out = diags[0] (.) NTT(c) + sum_r diags[r+1] (.) NTT(rotate_grouped(gk_r, c)): the hoisted rotations of tfhe_rotate_many_grouped
-// (ksg_hoist_tile, all n_rot <= 64 keys in one tile) into the workspace, then the coefficient-domain finish of tfhe_matmul_diag --
-// forward transforms of the rotated ciphertexts and of c, k_md_acc_dense.  The words of tfhe_rotate_many_grouped -> tfhe_nntt ->
-// tfhe_dot.  The evaluation-domain form of the per-limb product (k_md_special_perm, k_md_lift, k_md_acc) is not built for k special
-// primes: every limb of every key sum is inverse-transformed here.
-// workspace: [ region 0 | digits: [chunk][d][nw][N] | S: [chunk][R][2][nw][N] | ROT: [chunk][R][2][level][N] | X: [chunk][2][level][N] ]
+// out = diags[0] (.) NTT(c) + sum_r diags[r+1] (.) NTT(rotate_grouped(gk_r, c)): mdg_rotations over all n_rot <= 64 keys, then one
+// accumulation (ngiant1 = 1) written where it belongs.  The words of tfhe_rotate_many_grouped -> tfhe_nntt -> tfhe_dot on either route.
+// workspace: [ region 0 | digits: [chunk][d][nw][N] | S / V: [chunk][R][2][nw][N] | ROT / U: [chunk][R][2][level][N] | X: [chunk][2][level][N]
+//              | PB: [chunk][R][2][K][N] ]
 int tfhe_matmul_diag_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* evks, int n_digits,
                              const uint64_t* galois_elements, int n_rot, const uint64_t* diags, const uint64_t* ct, uint64_t* out, int64_t batch) {
     bool nothing = false;
     int rc = ksg_many_check(c, true, key_limbs, level, n_special, group, evks, n_digits, galois_elements, n_rot, diags, ct, out, batch, &nothing);
     if (rc || nothing) return rc;
-    ksg_hoist_t H;
-    rc = ksg_hoist_plan(c, key_limbs, level, n_special, group, n_rot, &H);
+    mdg_plan_t P;
+    rc = mdg_plan(c, key_limbs, level, n_special, group, galois_elements, n_rot, false, &P);
     if (rc) return rc;
-    const size_t N = (size_t)c->N, R = (size_t)n_rot, ct_rows = (size_t)2 * level;
-    const size_t dig_rows = R ? H.dig_rows : 0, rows = dig_rows + H.S_rows + R * ct_rows + ct_rows;
-    const size_t ntt_rows = std::max({dig_rows, H.S_rows, R * ct_rows, ct_rows});
-    const md_ws_t W(c, batch, rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : (size_t)0; });
+    const size_t N = (size_t)c->N, ct_words = (size_t)2 * level * N;
+    const md_ws_t W(c, batch, P.rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * P.ntt_rows * N * 8 : (size_t)0; });
     if (W.rc) return W.rc;
     const int64_t chunk = W.chunk;
-    u64* const dig = W.base();
-    u64* const S = dig + (size_t)chunk * dig_rows * N;
-    u64* const ROT = S + (size_t)chunk * H.S_rows * N;
-    u64* const X = ROT + (size_t)chunk * R * ct_rows * N;
-    const limb_sel_t sl = first_limbs(level);
+    const mdg_bufs_t B = mdg_bufs(P, W.base(), chunk, N);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
-        const u64* cin = ct + (size_t)b0 * ct_rows * N;
-        if (n_rot) {
-            rc = ksg_digits_fwd(c, H.P, cin, dig, nb, N % 2 == 0 && ((uintptr_t)cin & 15u) == 0);
-            if (rc) return rc;
-            rc = ksg_hoist_tile(c, H, evks, galois_elements, n_rot, cin, nb, dig, S, ROT, (size_t)nb * ct_rows * N);
-            if (rc) return rc;
-            rc = run_ntt(c, false, ROT, ROT, (int64_t)n_rot * nb * 2 * level, sl);
-            if (rc) return rc;
-        }
-        rc = run_ntt(c, false, cin, X, nb * 2 * level, sl);
+        rc = mdg_rotations(c, P, evks, ct + (size_t)b0 * ct_words, nb, B);
         if (rc) return rc;
-        rc = launch(c, k_md_acc_dense<1>, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, X, ROT, diags, out + (size_t)b0 * ct_rows * N,
-                    c->limbs_dev, sl, (u32)N, (u32)n_rot, (u32)(nb * 2 * level), 1u);
+        rc = mdg_accumulate(c, P, B, diags, out + (size_t)b0 * ct_words, nb, 1, false);
         if (rc) return rc;
     }
     return TFHE_OK;
 }
+
+// ---- the product by baby and giant steps on grouped-digit keys -------------------------------------------------------------------
+// tfhe_matmul_bsgs_blocks on prepared grouped Galois keys, with matmul_bsgs_run's structure and its one borrowed block:
+//     inner_j = sum_m sum_{i = 0 .. n_baby} diags[m][j][i] (.) NTT(r_i(cts[m]))            mdg_rotations + mdg_accumulate per input (seeded after the first)
+//     out     = INTT(inner_0) + sum_{j >= 1} rotate_grouped(giant key j - 1, INTT(inner_j)) (+ bias on component 0)
+// One batched inverse transform covers all inner sums.  Giant step j is a hoisted rotation with a tile of one key: ksg_digits_fwd on
+// INNER_j, ksg_hoist_tile into GOUT_j -- in the digit and key-sum regions of the baby phase, which is over by then (one stream, in
+// order), so no nested ensure_ws.  k_bsgs_sum adds up.  The words of tfhe_rotate_many_grouped -> tfhe_nntt -> tfhe_dot -> tfhe_inntt ->
+// tfhe_rotate_grouped -> tfhe_add.
+// workspace: [ region 0 | the baby phase (mdg_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ]
+int tfhe_matmul_bsgs_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* baby_evks,
+                             const uint64_t* baby_galois, int n_baby, const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant,
+                             int n_digits, const uint64_t* const* diags, const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out,
+                             int64_t batch) {
+    bool nothing = false;
+    {
+        char msg[160];
+        const int rc = ks_group_bsgs_check(!c || !baby_evks || !baby_galois || !giant_evks || !giant_galois || !diags || !cts || !out, c ? c->L : 0,
+                                           c ? c->N : 0, key_limbs, level, n_special, group, n_digits, batch, baby_evks, baby_galois, n_baby, giant_evks,
+                                           giant_galois, n_giant, diags, cts, n_in, (uintptr_t)bias, (uintptr_t)out, &nothing, msg, sizeof msg,
+                                           TFHE_DOT_MAX);
+        if (rc) return fail(rc, "%s", msg);
+    }
+    if (nothing) return TFHE_OK;
+    const int Lk = key_limbs, ng1 = n_giant + 1;
+    mdg_plan_t P;
+    int rc = mdg_plan(c, Lk, level, n_special, group, baby_galois, n_baby, n_giant > 0, &P);
+    if (rc) return rc;
+    const size_t N = (size_t)c->N;
+    const size_t rows = P.rows + (size_t)(ng1 + n_giant) * 2 * level;
+    const size_t ntt_rows = std::max(P.ntt_rows, (size_t)ng1 * 2 * level);
+    const md_ws_t W(c, batch, rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : (size_t)0; });
+    if (W.rc) return W.rc;
+    const int64_t chunk = W.chunk;
+    const mdg_bufs_t B = mdg_bufs(P, W.base(), chunk, N);
+    u64* const INNER = B.end;
+    u64* const GOUT = INNER + (size_t)chunk * ng1 * 2 * level * N;
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        const size_t ct_words = (size_t)nb * 2 * level * N;   // one inner sum / one giant result of this chunk
+        for (int m = 0; m < n_in; m++) {
+            rc = mdg_rotations(c, P, baby_evks, cts[m] + (size_t)b0 * 2 * level * N, nb, B);
+            if (rc) return rc;
+            rc = mdg_accumulate(c, P, B, diags[m], INNER, nb, ng1, m > 0);
+            if (rc) return rc;
+        }
+        rc = run_ntt(c, true, INNER, INNER, (int64_t)ng1 * nb * 2 * level, P.sl);
+        if (rc) return rc;
+        for (int j = 1; j <= n_giant; j++) {
+            const u64* const src = INNER + (size_t)j * ct_words;
+            rc = ksg_digits_fwd(c, P.H.P, src, B.dig, nb, N % 2 == 0 && ((uintptr_t)src & 15u) == 0);
+            if (rc) return rc;
+            rc = ksg_hoist_tile(c, P.H, giant_evks + (j - 1), giant_galois + (j - 1), 1, src, nb, B.dig, B.S, GOUT + (size_t)(j - 1) * ct_words, ct_words);
+            if (rc) return rc;
+        }
+        rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)INNER, (const u64*)GOUT,
+                    out + (size_t)b0 * 2 * level * N, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words, bias);
+        if (rc) return rc;
+    }
+    return TFHE_OK;
+}
+

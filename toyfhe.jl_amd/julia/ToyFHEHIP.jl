@@ -580,6 +580,46 @@ function matmul_diag_grouped(gks::Vector{<:ToyFHE.GaloisKey}, diags::Vector{<:Ri
                 ctx.handle, Lk, level, n_special, group, keys, length(ek1.key), gs, nrot, dg.ptr, ct.ptr, out.ptr, cnt))
     CipherText{squared_encoding(Enc)}(c.params, unpack(ctx, out, ℛ, 2; dual=true))
 end
+# The block-row product by baby and giant steps on grouped-digit keys in one device call (tfhe_matmul_bsgs_grouped): the operands of
+# matmul_bsgs_blocks, every rotation a rotate_grouped.  (Not executed anywhere yet: the tests check the ccall against the header.)
+function matmul_bsgs_blocks_grouped(baby::Vector{<:ToyFHE.GaloisKey}, giant::Vector{<:ToyFHE.GaloisKey},
+                                    diags::Vector{<:Vector{<:Vector{<:RingElement{ℛ,T,<:HipVector}}}},
+                                    cs::Vector{<:CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}}, n_special::Integer, group::Integer,
+                                    bias=nothing) where {Enc,P,ℛ,T}
+    nin = length(cs); nb = length(baby); ng = length(giant)
+    @assert 1 <= nin <= 64 && length(diags) == nin && all(c -> length(c.cs) == 2, cs)
+    @assert all(m -> length(m) == ng + 1 && all(r -> length(r) == nb + 1, m), diags)
+    max(nb, ng) <= 64 || throw(ToyFHE.UsageError("matmul_bsgs_blocks_grouped: at most 64 baby and 64 giant steps per call (TFHE_DOT_MAX)"))
+    isempty(baby) && isempty(giant) && throw(ToyFHE.UsageError("matmul_bsgs_blocks_grouped: no Galois key at all -- plain products, use .* and +"))
+    ek1 = (isempty(baby) ? giant[1] : baby[1]).key; keyring = NTT.ring(ek1.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T)
+    cnt = batchsize(cs[1]); ctx = hipring(keyring); n = degree(ℛ)
+    cts = HipVector[pack(ctx, c) for c in cs]
+    pb = HipVector[prepared(gk) for gk in baby]; pg = HipVector[prepared(gk) for gk in giant]     # PREPARED keys only
+    dgs = HipVector[]
+    for m in diags                                                              # one [ng + 1][nb + 1][level][N] per input
+        dparts = HipVector[coeffs_dual(d).parent for row in m for d in row]
+        all(d -> d.count == 1, dparts) || throw(ToyFHE.UsageError("matmul_bsgs_blocks_grouped: one polynomial per diagonal"))
+        dg = HipVector{T}(level, n, (ng + 1) * (nb + 1)); on(ctx, (dg,), (dparts...,))
+        GC.@preserve dparts dg for (k, d) in enumerate(dparts)
+            check(ccall((:tfhe_memcpy_d2d, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t),
+                  ctx.handle, dg.ptr + 8 * (k - 1) * level * n, d.ptr, 8 * level * n))
+        end
+        push!(dgs, dg)
+    end
+    bv = bias === nothing ? nothing : coeffs_primal(bias).parent
+    out = HipVector{T}(2 * level, n, cnt)
+    on(ctx, (out,), bv === nothing ? (cts..., dgs..., pb..., pg...) : (cts..., dgs..., pb..., pg..., bv))
+    bkeys = Ptr{UInt64}[k.ptr for k in pb]; bgs = UInt64[gk.galois_element for gk in baby]
+    gkeys = Ptr{UInt64}[k.ptr for k in pg]; ggs = UInt64[gk.galois_element for gk in giant]
+    dptrs = Ptr{UInt64}[d.ptr for d in dgs]; cptrs = Ptr{UInt64}[c.ptr for c in cts]
+    bptr = bv === nothing ? Ptr{UInt64}(0) : bv.ptr
+    GC.@preserve pb pg cts dgs bv out check(ccall((:tfhe_matmul_bsgs_grouped, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Cint, Cint,
+                 Ptr{Ptr{UInt64}}, Ptr{Ptr{UInt64}}, Cint, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, n_special, group, bkeys, bgs, nb, gkeys, ggs, ng, length(ek1.key),
+                dptrs, cptrs, nin, bptr, out.ptr, cnt))
+    CipherText{squared_encoding(Enc)}(cs[1].params, unpack(ctx, out, ℛ, 2))
+end
 
 # hoisted rotations: [rotate(gk, c) for gk in gks] from one digit decomposition of c (tfhe_rotate_many)
 function rotate_many(gks::Vector{<:ToyFHE.GaloisKey}, c::CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}) where {Enc,P,ℛ,T}

@@ -128,6 +128,8 @@ def lib():
         "tfhe_rotate_grouped": [vp, i32, i32, i32, i32, vp, i32, u64, vp, vp, i64],
         "tfhe_rotate_many_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), i32, u64p, i32, vp, vp, i64],
         "tfhe_matmul_diag_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), i32, u64p, i32, vp, vp, vp, i64],
+        "tfhe_matmul_bsgs_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), u64p, i32, C.POINTER(vp), u64p, i32, i32, C.POINTER(vp), C.POINTER(vp),
+                                     i32, vp, vp, i64],
         "tfhe_rotate_many": [vp, i32, i32, i32, C.POINTER(vp), i32, i32, u64p, i32, vp, vp, i64],
         "tfhe_galois_key_prepare": [vp, i32, i32, u64, vp, vp],
         "tfhe_matmul_diag": [vp, i32, i32, i32, C.POINTER(vp), i32, u64p, i32, vp, vp, vp, i64],
@@ -183,7 +185,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_ctx_set_stream", "tfhe_ctx_sync", "tfhe_ctx_wait_for", "tfhe_ctx_set_ntt_variant", "tfhe_ctx_set_chunk", "tfhe_ctx_workspace", "tfhe_malloc", "tfhe_free", "tfhe_memcpy_h2d",
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
-    "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_keyswitch_grouped", "tfhe_rotate_grouped", "tfhe_rotate_many_grouped", "tfhe_matmul_diag_grouped", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
+    "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_keyswitch_grouped", "tfhe_rotate_grouped", "tfhe_rotate_many_grouped", "tfhe_matmul_diag_grouped", "tfhe_matmul_bsgs_grouped", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
     "tfhe_bfv_plan_set_variant", "tfhe_bfv_plan_workspace", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_mul_relin_grouped", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
@@ -523,6 +525,19 @@ class Context:
         """the diagonal product on grouped-digit keys (tfhe_matmul_diag_grouped); operands as matmul_diag, keys as rotate_many_grouped"""
         ptrs, garr = self._key_arrays(evks, gs)
         check(lib().tfhe_matmul_diag_grouped(self.h, key_limbs, level, n_special, group, ptrs, n_digits, garr, len(evks), diags, ct, out, batch))
+
+    def matmul_bsgs_grouped(self, key_limbs, level, n_special, group, baby_evks, baby_gs, giant_evks, giant_gs, n_digits, diags, cts, bias, out,
+                            batch):
+        """the product by baby and giant steps on grouped-digit keys (tfhe_matmul_bsgs_grouped); operands as matmul_bsgs_blocks, keys as
+        rotate_many_grouped (PREPARED grouped Galois keys)"""
+        if len(diags) != len(cts):
+            raise AssertionError("tfhe_matmul_bsgs_grouped: one set of diagonals per input")
+        bp, bg = self._key_arrays(baby_evks, baby_gs)
+        gp, gg = self._key_arrays(giant_evks, giant_gs)
+        dp, _ = self._key_arrays(diags, [])
+        cp, _ = self._key_arrays(cts, [])
+        check(lib().tfhe_matmul_bsgs_grouped(self.h, key_limbs, level, n_special, group, bp, bg, len(baby_evks), gp, gg, len(giant_evks), n_digits,
+                                             dp, cp, len(cts), bias, out, batch))
 
     def sample_uniform(self, level, seed, stream, first_poly, out, count):
         check(lib().tfhe_sample_uniform(self.h, level, int(seed), int(stream), int(first_poly), out, count))

@@ -1966,10 +1966,31 @@ def rect_diagonals(W, n1: int, block: int = 1, fold_radix: int = 4):
     return bsgs_diagonals(dv, n1, block) + (folds,)
 
 
-def _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, fold_groups):
-    """matmul_bsgs_blocks (fold_groups None) and matmul_bsgs_fold (a list of lists of Galois keys, possibly empty)"""
+def matmul_bsgs_grouped(baby_gks, giant_gks, diags, c: CipherText) -> CipherText:
+    """matmul_bsgs on keys with grouped digits (tfhe_matmul_bsgs_grouped, one input): operands, diagonal handling (bsgs_diagonals), scale
+    and result as for matmul_bsgs; at least one key (the parameter set is read from it).  Word for word rotate_many_grouped -> dot_plain
+    per giant step -> rotate -> +."""
+    return _matmul_bsgs_blocks(baby_gks, giant_gks, [diags], [c], None, None, grouped="matmul_bsgs_grouped")
+
+
+def matmul_bsgs_blocks_grouped(baby_gks, giant_gks, diags, cs, bias=None) -> CipherText:
+    """matmul_bsgs_blocks on keys with grouped digits (tfhe_matmul_bsgs_grouped): operands, usage errors, scale and result as for
+    matmul_bsgs_blocks; the keys are Galois keys of ONE GroupedRaised parameter set, at least one of them."""
+    return _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, None, grouped="matmul_bsgs_blocks_grouped")
+
+
+def _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, fold_groups, grouped=None):
+    """matmul_bsgs_blocks (fold_groups None) and matmul_bsgs_fold (a list of lists of Galois keys, possibly empty); grouped: the name of
+    the caller that takes keys with grouped digits (matmul_bsgs_grouped / matmul_bsgs_blocks_grouped), which have no fold"""
     baby_gks, giant_gks, cs, diags = list(baby_gks), list(giant_gks), list(cs), list(diags)
-    _refuse_grouped_keys(baby_gks + giant_gks + [g for grp in fold_groups or [] for g in grp], "matmul_bsgs_blocks / matmul_bsgs_fold")
+    if grouped:
+        if not baby_gks + giant_gks:
+            raise UsageError(f"{grouped}: no Galois key at all (GroupedRaised) -- plain products, use .* and +")
+        if not cs:
+            raise UsageError("matmul_bsgs_blocks: one set of diagonals per input ciphertext, at least one input")
+        gparams, gkeyring = _grouped_key_set(baby_gks + giant_gks, cs[0], grouped)
+    else:
+        _refuse_grouped_keys(baby_gks + giant_gks + [g for grp in fold_groups or [] for g in grp], "matmul_bsgs_blocks / matmul_bsgs_fold")
     if len(diags) != len(cs) or not cs:
         raise UsageError("matmul_bsgs_blocks: one set of diagonals per input ciphertext, at least one input")
     if len(cs) > DOT_MAX:
@@ -2005,7 +2026,9 @@ def _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, fold_groups):
     if bias is not None and (not isinstance(bias, RingElement) or bias.ring != ring or bias.count != 1):
         raise UsageError("matmul_bsgs_blocks: the bias is a single plaintext element of the ciphertexts' ring")
     gks = baby_gks + giant_gks + [g for grp in fold_groups or [] for g in grp]
-    if gks:
+    if grouped:
+        keyring, special = gkeyring, False
+    elif gks:
         params = gks[0].key.params
         if any(g.key.params is not params for g in gks) or params.relin_window != 0:
             raise UsageError("hoisted rotations need Galois keys of one parameter set with RNS digits")
@@ -2027,6 +2050,15 @@ def _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, fold_groups):
     packed = {}                                            # (a ciphertext given twice is packed once: the call takes repeated pointers)
     cts = [packed[id(x)] if id(x) in packed else packed.setdefault(id(x), _pack(p, ring, n, ctx=keyring.ctx)) for x, p in zip(cs, prims)]
     out = DeviceBuffer(n * 2 * sz)
+    if grouped:
+        keyring.ctx.matmul_bsgs_grouped(keyring.L, level, gparams.n_special, gparams.group, [g.prepared_grouped().ptr for g in baby_gks],
+                                        [g.galois_element for g in baby_gks], [g.prepared_grouped().ptr for g in giant_gks],
+                                        [g.galois_element for g in giant_gks], len(gks[0].key.key), [d.ptr for d in dgs], [t.ptr for t in cts],
+                                        None if bprim is None else bprim.ptr, out.ptr, n)
+        res = _unpack(out, ring, n, 2, batch, primal=True, ctx=keyring.ctx)
+        if ring.ctx is not keyring.ctx:
+            ring.ctx.wait_for(keyring.ctx)
+        return CipherText(c.params, res, Fraction(c.scale) ** 2)
     keys = (keyring.L, level, special, [g.prepared().ptr for g in baby_gks], [g.galois_element for g in baby_gks],
             [g.prepared().ptr for g in giant_gks], [g.galois_element for g in giant_gks], len(gks[0].key.key) if gks else level,
             [d.ptr for d in dgs], [t.ptr for t in cts])
