@@ -31,7 +31,9 @@
  *     object's own stream first and must only not race with a call that is still USING that object.
  *     tfhe_ctx_destroy DRAINS the context's streams (main and side lane) BEFORE the allocator forgets them: a tfhe_free that arrives
  *     from another thread while the destroy runs still parks its block behind the context's queued work.  tfhe_bfv_plan_destroy
- *     drains the main stream and the side lane of both of its contexts.
+ *     drains the main stream and the side lane of both of its contexts, and tfhe_plain_plan_destroy its context's stream: a plan is
+ *     destroyed BEFORE the contexts it was made on.  (The Python binding sees to it when finalizers run in another order: a Context
+ *     closed while plans on it are open is destroyed by the last plan's close -- tests/test_native_lifetime_cpu.py.)
  *     Held by: contexts / plans on different threads, first use at once, the thread-local error text --
  *     tests/test_gpu_threads.py test_four_rings_on_four_threads_first_use_at_once_and_error_text_per_thread; tfhe_free from any
  *     thread -- test_frees_from_a_finaliser_thread_while_the_producer_keeps_enqueuing; a freed block is not handed out while

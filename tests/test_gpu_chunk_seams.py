@@ -250,7 +250,7 @@ def spec_window(qs, level, special, w, evk_coeff, ct_b):
 @pytest.mark.parametrize("N,bits,Lk,level,special,w", [(64, 50, 3, 3, False, 16), (64, 50, 4, 3, True, 16), (2048, 50, 4, 3, True, 20),
                                                        (1 << 15, 50, 2, 2, False, 20)])
 def test_keyswitch_window_across_chunks(N, bits, Lk, level, special, w):
-    """ksw_table built once outside the loop; N = 2^15 takes the over-allocated transform scratch (ntt_tmp).  The oracle is the
+    """ksw_table built once outside the loop; N = 2^15 takes the transform scratch in region 0 of its layout.  The oracle is the
     composition window_oracle, itself checked here against spec.keyswitch at N = 64, with and without the special prime."""
     qs = H.chain(bits, Lk, N)
     ctx, ref = tf.Context(N, qs), ref_cpu.RefCtx(N, qs)
@@ -280,7 +280,7 @@ def test_keyswitch_window_across_chunks(N, bits, Lk, level, special, w):
 
 # ---------------------------------------------------------------------------------------------------
 # tfhe_mul_relin, composed path (below and above the fused sizes): its own chunk loop around keyswitch_impl's, one workspace
-# sized for both (mr_ks_bytes)
+# sized for both (region 0 of its layout is the key switch's span)
 # ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N,qspec,special", [(1 << 11, "40x3", False), (1 << 15, "40x4", True)])
 def test_mul_relin_composed_across_chunks(N, qspec, special):

@@ -3,7 +3,7 @@
 //
 // Key switching (rlwe_she.jl:315-347).  By linearity of the NTT the expanded inputs never need transforming:
 // out_s = c_s + INTT(S_s)  (plain)   or   c_s + modswitch-part of INTT(S_s)  (ModulusRaised),
-// with S_s = Σ_i evk_{i,s} ⊙ NTT(digit_i)  (see k_ks_inner, k_ks_rescale_add); the buffers are laid out at ks_plan_t.
+// with S_s = Σ_i evk_{i,s} ⊙ NTT(digit_i)  (see k_ks_inner, k_ks_rescale_add); the buffers are laid out at ks_plan_t, through ws_layout.h.
 
 // whether the fused key switches (k_ks_fused at N = 2^13 / 2^14, k_ks_fused_sub at 2^15 / 2^16) take this ring and level
 static bool ks_fused14(const tfhe_ctx* c, int Lk, int level, int special) {
@@ -63,7 +63,7 @@ static int ks_digits_fwd(tfhe_ctx* c, const ks_arg_t& A, const u64* ct, u64* dig
         const int64_t rows = batch * level * nw;
         const int x = c->logN - 14;
         void* tmp = nullptr;
-        rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);   // (before the fork: growing the workspace synchronises)
+        rc = ws_scratch(c, (size_t)rows * c->N * 8, &tmp);   // (before the fork: growing the workspace synchronises)
         if (rc) return rc;
         lanes_t lanes(c);   // the fp64-size working limbs on the side lane, beside the u64 ones
         lanes.use(1);
@@ -170,8 +170,8 @@ static int ks_plain_tail(tfhe_ctx* c, const ks_arg_t& A, const rescale_arg_t& ra
 
 // ---- the plan of one key switch ----------------------------------------------------------------------------------------
 // Everything a call decides -- its route, how a rotation is carried, what is done to the key, the chunk and the workspace -- is
-// decided once, by ks_plan; keyswitch_impl and ks_chunk read the plan, and so does whoever sizes a workspace for them
-// (mr_ks_bytes, mul_api.inc).  Every environment switch of the key switch is read here or in ks_fused14, once per process.
+// decided once, by ks_plan; keyswitch_impl and ks_chunk read the plan, and so does whoever sizes a span for them (tfhe_mul_relin,
+// matmul_bsgs_run).  Every environment switch of the key switch is read here or in ks_fused14, once per process.
 //   KS_ROW: k_ks_fused, N = 2^13 / 2^14    KS_SUB: k_ks_fused_sub, N = 2^15 / 2^16, then the inverse top stages with the tail
 //   KS_THREE: digit transforms (ks_digits_fwd), key sums (ks_inner_launch), inverse transforms + tail
 enum ks_path_t { KS_ROW, KS_SUB, KS_THREE };
@@ -190,14 +190,15 @@ struct ks_plan_t {
     ks_rot_t rot;
     u64 g_tail;          // KS_ROT_TAIL: the Galois element, otherwise 0
     bool key_perm;       // the key is permuted by g^-1: in k_evk_to_f64 on the fused paths, by k_ntt_perm on KS_THREE (else read in place)
-    // workspace: [ transform scratch | S: [chunk][2][nw][N] | NTT'd digits: [chunk][level][nw][N], or T: [chunk][2][nw][N] on the fused
-    // paths | rotated copy: [chunk][polys][level][N] ], then the key as doubles (k_evk_to_f64, fused paths) or permuted (k_ntt_perm)
+    // workspace: [ region 0: transform scratch | S: [chunk][2][nw][N] | NTT'd digits: [chunk][level][nw][N], or T: [chunk][2][nw][N] on the
+    // fused paths | rotated copy: [chunk][polys][level][N] ], then the key as doubles (k_evk_to_f64, fused paths) or permuted (k_ntt_perm)
     int64_t chunk;
-    size_t N, S_rows, dig_rows, rot_rows, ntt_tmp, key_bytes;
-    size_t bytes() const { return ntt_tmp + (size_t)chunk * (S_rows + dig_rows + rot_rows) * N * 8 + key_bytes; }
-    u64* region(void* ws, size_t before) const { return (u64*)((char*)ws + ntt_tmp) + (size_t)chunk * before * N; }   // after `before` rows
+    size_t N;
+    ws_layout_t L;
+    ws_region_t rS, rdig, rrot, rkey;   // the regions above, in that order
 };
-// `batch` is the CALL's batch; `ct` / `out` are the caller's operands (read for rotations and for the alignment of the lift's loads).
+// `batch` is the CALL's batch; `ct` / `out` are the caller's operands (read for rotations and for the alignment of the lift's loads;
+// none given: taken as disjoint and aligned -- whoever sizes a span for a call on operands of its own, ks_rot_prepared_bytes).
 // key_prepared (rotations only, tfhe_rotate_prepared): the key is the output of tfhe_galois_key_prepare for `galois` -- the paths
 // that finish the rotation in their tail consume it as it is (no per-call k_ntt_perm / permuting conversion); the others take the
 // hoisted form of tfhe_rotate_many, which is defined on prepared keys (same bits)
@@ -237,7 +238,7 @@ static ks_plan_t ks_plan(const tfhe_ctx* c, int Lk, int level, int special, int 
     // ADVICE r04: pointer inequality let a partially overlapping out / ct race).  TFHE_ROT_TAIL=0 keeps the separate pass.
     if (rotate) {
         static const bool rot_tail_on = env_flag("TFHE_ROT_TAIL", true);
-        const bool io_disjoint = (const char*)(out + (size_t)batch * 2 * level * N) <= (const char*)ct ||
+        const bool io_disjoint = !ct || (const char*)(out + (size_t)batch * 2 * level * N) <= (const char*)ct ||
                                  (const char*)(ct + (size_t)batch * polys * level * N) <= (const char*)out;
         const bool can = P.path == KS_ROW ? (c->logN == 14 && P.two_launch) : (batch >= 8 && (P.path == KS_SUB || P.tail16));
         P.rot = (can && rot_tail_on && io_disjoint) ? KS_ROT_TAIL : (key_prepared ? KS_ROT_HOISTED : KS_ROT_COPY);
@@ -252,14 +253,15 @@ static ks_plan_t ks_plan(const tfhe_ctx* c, int Lk, int level, int special, int 
     // chunk the batch so that the digit tensor stays at a few GiB.  The fused key switches never write the digit rows: at
     // N = 2^15 the "digit" buffer only carries the sub-block sums T (2 nw rows per ciphertext), so a whole batch is one launch
     // (cfg#3, 512 ciphertexts: 248 + 248 + 16 before -- the 16 ran as two nearly empty item rounds of k_ks_fused_sub)
-    P.S_rows = (size_t)2 * nw;
-    P.dig_rows = f14 ? (size_t)2 * nw : (size_t)level * nw;
-    P.rot_rows = rotate ? (size_t)polys * level : 0;
-    P.chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, (P.S_rows + P.dig_rows + P.rot_rows) * N * 8);
-    // NTT of N > 2^14 and the mixed lift use the start of the context workspace as well: keep ours separate by over-allocating, so
-    // that nothing grows the workspace once the lanes have forked (the fused paths run no stand-alone transform)
-    P.ntt_tmp = (c->logN > 14 && !f14) ? (size_t)P.chunk * std::max(2, level) * nw * N * 8 : 0;
-    P.key_bytes = f14 ? (size_t)level * 2 * nw * N * 8 : (P.key_perm ? (size_t)level * 2 * Lk * N * 8 : 0);
+    P.L = ws_layout_t(N);
+    // the digit transforms (level nw rows), the mixed lift and the key sums' inverse (2 nw) take region 0; the fused paths run no
+    // stand-alone transform
+    P.L.scratch(f14 ? 0 : (size_t)std::max(2, level) * nw);
+    P.rS = P.L.rows((size_t)2 * nw);
+    P.rdig = P.L.rows(f14 ? (size_t)2 * nw : (size_t)level * nw);
+    P.rrot = P.L.rows(rotate ? (size_t)polys * level : 0);
+    P.chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, P.L.per_ct_bytes());
+    P.rkey = P.L.tail(f14 ? (size_t)level * 2 * nw * N * 8 : (P.key_perm ? (size_t)level * 2 * Lk * N * 8 : 0));
     return P;
 }
 
@@ -394,9 +396,9 @@ static u64 inv_mod_2n(u64 g, u64 twoN) {  // g odd, twoN a power of two: Newton 
 // A key switch in two steps.  ks_prepare: the plan, the workspace and what is done to the KEY (k_evk_to_f64 on the fused paths,
 // k_ntt_perm for a rotation finished in the tail) -- everything that depends on the key and the shape only.  ks_run: the ciphertexts.
 // One preparation serves any number of runs of at most the prepared `batch` each with the same key (tfhe_bfv_mul_relin: one per
-// chunk of its own pipeline), PROVIDED nobody else takes the context's workspace in between: ensure_ws hands the start of the one
-// block to every caller and frees it when a larger one is asked for, so the regions below -- the key among them -- are only ours
-// from the preparation to the last run if no other entry point of this context runs between them.
+// chunk of its own pipeline).  `span`: a nested call's block -- its caller's region 0 -- instead of the context's own; without one the
+// regions below, the key among them, are ours from the preparation to the last run only if no other entry point of this context runs
+// between them (tfhe_bfv_mul_relin sees to that).
 struct ks_prepared_t {
     ks_plan_t P;
     const u64* key;      // the caller's key, or the workspace copy
@@ -405,7 +407,7 @@ struct ks_prepared_t {
     int polys;
 };
 static int ks_prepare(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, const u64* out, int64_t batch,
-                      u64 galois, bool rotate, bool prelifted, bool key_prepared, ks_prepared_t* K) {
+                      u64 galois, bool rotate, bool prelifted, bool key_prepared, ks_prepared_t* K, const ws_span_t* span = nullptr) {
     if (prelifted && (rotate || special || !ks_prelift_ok(c, level))) return fail(TFHE_E_UNSUPPORTED, "internal: pre-lifted rows need the fused key switch");
     K->P = ks_plan(c, Lk, level, special, polys, batch, ct, out, galois, rotate, prelifted, key_prepared);
     ks_plan_t& P = K->P;
@@ -414,10 +416,10 @@ static int ks_prepare(tfhe_ctx* c, int Lk, int level, int special, const u64* ev
     if (special) special_inv_table(c, Lk, level, P.ra.qlinv);
     const size_t N = P.N;
     void* ws = nullptr;
-    int rc = ensure_ws(c, P.bytes(), &ws);
+    int rc = ws_begin(c, P.L, P.chunk, span, &ws, nullptr);   // (in force while the ciphertexts run: ks_run)
     if (rc) return rc;
-    K->S = P.region(ws, 0); K->dig = P.region(ws, P.S_rows); K->rot = P.region(ws, P.S_rows + P.dig_rows);
-    u64* const kw = P.region(ws, P.S_rows + P.dig_rows + P.rot_rows);
+    K->S = P.L.at(ws, P.chunk, P.rS); K->dig = P.L.at(ws, P.chunk, P.rdig); K->rot = P.L.at(ws, P.chunk, P.rrot);
+    u64* const kw = P.L.at(ws, P.chunk, P.rkey);
     const u64 ginv = P.key_perm ? inv_mod_2n(galois, 2 * (u64)c->N) : (u64)0;
     if (P.path != KS_THREE) {
         rc = launch(c, k_evk_to_f64, row_grid((unsigned)(level * 2 * P.A.nw), N), dim3(256), 0, evk, kw, c->limbs_dev, P.A, Lk, (u32)N, c->logN <= 14 ? 1 : 0,
@@ -434,6 +436,7 @@ static int ks_run(tfhe_ctx* c, const ks_prepared_t& K, const u64* ct, u64* out, 
     const ks_plan_t& P = K.P;
     const int level = P.A.level, polys = K.polys;
     const size_t N = P.N;
+    const ws_scope_t scope(c->ws_scratch, P.L.region0(P.chunk));
     for (int64_t b0 = 0; b0 < batch; b0 += P.chunk) {
         const int64_t nb = std::min(P.chunk, batch - b0);
         const u64* cin = ct + (size_t)b0 * polys * level * N;
@@ -447,14 +450,16 @@ static int ks_run(tfhe_ctx* c, const ks_prepared_t& K, const u64* ct, u64* out, 
     }
     return TFHE_OK;
 }
+static int rotate_many_run(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, int prepared, const uint64_t* galois,
+                           int n_rot, const uint64_t* ct, uint64_t* out, int64_t batch, const ws_span_t* span);
 static int keyswitch_impl(tfhe_ctx* c, int Lk, int level, int special, const u64* evk, const u64* ct, int polys, u64* out, int64_t batch,
-                          u64 galois, bool rotate, bool prelifted = false, bool key_prepared = false) {
+                          u64 galois, bool rotate, bool prelifted = false, bool key_prepared = false, const ws_span_t* span = nullptr) {
     ks_prepared_t K;
-    const int rc = ks_prepare(c, Lk, level, special, evk, ct, polys, out, batch, galois, rotate, prelifted, key_prepared, &K);
+    const int rc = ks_prepare(c, Lk, level, special, evk, ct, polys, out, batch, galois, rotate, prelifted, key_prepared, &K, span);
     if (rc) return rc;
     if (K.P.rot == KS_ROT_HOISTED) {
         const uint64_t* one[1] = {evk};
-        return tfhe_rotate_many(c, Lk, level, special, one, level, 1, &galois, 1, ct, out, batch);
+        return rotate_many_run(c, Lk, level, special, one, level, 1, &galois, 1, ct, out, batch, span);
     }
     return ks_run(c, K, ct, out, batch);
 }
@@ -479,20 +484,29 @@ int tfhe_galois_key_prepare(tfhe_ctx* c, int Lk, int n_digits, uint64_t g, const
     return launch(c, k_ntt_perm, row_grid((unsigned)(n_digits * 2 * Lk), (size_t)c->N), dim3(256), 0, evk, evk_out, ginv, (u32)c->N);
 }
 
-// the workspace of the hoisted rotations for a call of `batch` ciphertexts (also read by whoever nests such a call in a workspace of
-// its own, tfhe_matmul_bsgs): per ciphertext S (2 nw rows) + digits (level nw) + T (2 nw) + rotated input (2 level); then one
-// prepared key where the caller's are plain
+// the workspace of the hoisted rotations for a call of `batch` ciphertexts (also read by whoever nests such a call in a span of its
+// own, ks_rot_prepared_bytes): [ region 0: transform scratch (digits level nw rows, key sums 2 nw) | S: [chunk][2][nw][N] | digits:
+// [chunk][level][nw][N] | T: [chunk][2][nw][N] | rotated input: [chunk][2][level][N] ], then one prepared key where the caller's are plain
 struct rotate_many_ws_t {
-    size_t per_ct, ntt_tmp;
+    ws_layout_t L;
+    ws_region_t S, dig, T, rot, keytmp;
     int64_t chunk;
-    size_t bytes() const { return ntt_tmp + (size_t)chunk * per_ct; }
 };
-static rotate_many_ws_t rotate_many_ws(const tfhe_ctx* c, int level, int nw, int64_t batch) {
+static rotate_many_ws_t rotate_many_ws(const tfhe_ctx* c, int level, int nw, int64_t batch, size_t key_bytes) {
     rotate_many_ws_t W{};
-    W.per_ct = ((size_t)4 * nw + (size_t)level * nw + (size_t)2 * level) * (size_t)c->N * 8;
-    W.chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, W.per_ct);
-    W.ntt_tmp = c->logN > 14 ? (size_t)W.chunk * std::max(2, level) * nw * (size_t)c->N * 8 : 0;
+    W.L = ws_layout_t((size_t)c->N);
+    W.L.scratch((size_t)std::max(2, level) * nw);
+    W.S = W.L.rows((size_t)2 * nw); W.dig = W.L.rows((size_t)level * nw); W.T = W.L.rows((size_t)2 * nw); W.rot = W.L.rows((size_t)2 * level);
+    W.keytmp = W.L.tail(key_bytes);
+    W.chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, W.L.per_ct_bytes());
     return W;
+}
+// the span a prepared-key rotation of `batch` ciphertexts may ask of its caller (matmul_bsgs_run, whose operands are its own: disjoint
+// and aligned): the larger of the two routes ks_plan picks between by the batch -- finished in the tail, or handed to the hoisted form
+static size_t ks_rot_prepared_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t batch) {
+    const ks_plan_t P = ks_plan(c, Lk, level, special, 2, batch, nullptr, nullptr, 1, true, false, true);   // (KS_ROT_HOISTED: an empty layout)
+    const rotate_many_ws_t W = rotate_many_ws(c, level, special ? level + 1 : level, batch, 0);
+    return std::max(P.L.bytes(P.chunk), W.L.bytes(W.chunk));
 }
 int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, int prepared,
                      const uint64_t* galois, int n_rot, const uint64_t* ct, uint64_t* out, int64_t batch) {
@@ -503,30 +517,31 @@ int tfhe_rotate_many(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
         if (!rc) rc = galois_check(c, galois[r]);
         if (rc) return rc;
     }
+    return rotate_many_run(c, Lk, level, special, evks, n_digits, prepared, galois, n_rot, ct, out, batch, nullptr);
+}
+// the rotations after the host checks; `span`: a nested call's block instead of the context's own (keyswitch_impl)
+static int rotate_many_run(tfhe_ctx* c, int Lk, int level, int special, const uint64_t* const* evks, int n_digits, int prepared, const uint64_t* galois,
+                           int n_rot, const uint64_t* ct, uint64_t* out, int64_t batch, const ws_span_t* span) {
     const int nw = special ? level + 1 : level, polys = 2;
     const size_t N = (size_t)c->N;
     if (!prepared && c->logN <= 14 && ks_fused14(c, Lk, level, special)) {
         // N = 2^14 on fp64-size moduli: the fused key switch (digits never leave the registers) beats the hoisted three-kernel
         // path (measured 126 k against 110 k rotations/s at 6 limbs + special prime) -- same bits either way
         for (int r = 0; r < n_rot; r++) {
-            int rc = keyswitch_impl(c, Lk, level, special, evks[r], ct, 2, out + (size_t)r * batch * 2 * level * N, batch, galois[r], true);
+            int rc = keyswitch_impl(c, Lk, level, special, evks[r], ct, 2, out + (size_t)r * batch * 2 * level * N, batch, galois[r], true, false, false, span);
             if (rc) return rc;
         }
         return TFHE_OK;
     }
     const ks_arg_t A = make_ks_arg(Lk, level, special, polys);
-    const rotate_many_ws_t W = rotate_many_ws(c, level, nw, batch);
-    const size_t per_ct = W.per_ct, ntt_tmp = W.ntt_tmp;
+    const rotate_many_ws_t W = rotate_many_ws(c, level, nw, batch, prepared ? 0 : (size_t)n_digits * 2 * Lk * N * 8);
     const int64_t chunk = W.chunk;
-    const size_t key_bytes = prepared ? 0 : (size_t)n_digits * 2 * Lk * N * 8;
     void* ws = nullptr;
-    int rc = ensure_ws(c, ntt_tmp + chunk * per_ct + key_bytes, &ws);
+    ws_scope_t scope;
+    int rc = ws_begin(c, W.L, chunk, span, &ws, &scope);
     if (rc) return rc;
-    u64* S = (u64*)((char*)ws + ntt_tmp);
-    u64* dig = S + (size_t)chunk * 2 * nw * N;
-    u64* T = dig + (size_t)chunk * level * nw * N;
-    u64* rot = T + (size_t)chunk * 2 * nw * N;
-    u64* keytmp = rot + (size_t)chunk * polys * level * N;
+    u64 *S = W.L.at(ws, chunk, W.S), *dig = W.L.at(ws, chunk, W.dig), *T = W.L.at(ws, chunk, W.T), *rot = W.L.at(ws, chunk, W.rot);
+    u64* keytmp = W.L.at(ws, chunk, W.keytmp);
     const limb_sel_t sl = first_limbs(level);
     rescale_arg_t ra{};
     if (special) special_inv_table(c, Lk, level, ra.qlinv);
@@ -640,14 +655,16 @@ int tfhe_keyswitch_window(tfhe_ctx* c, int key_limbs, int level, int special, in
     const size_t N = (size_t)c->N;
     const u32 n = (u32)c->N;
     const int nw = special ? level + 1 : level;  // working limbs: [0 .. level-1] (+ the special prime, downswitch_keyelement modulusraising.jl:43-49)
-    const size_t per_ct = ((size_t)2 * nw + (size_t)need * nw) * N * 8;
-    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, per_ct);
-    const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * need * nw * N * 8 : 0;
+    // workspace: [ region 0: transform scratch (the digits' transforms; need >= 2) | S: [chunk][2][nw][N] | digits: [chunk][need][nw][N] ]
+    ws_layout_t L(N);
+    L.scratch((size_t)need * nw);
+    const ws_region_t rS = L.rows((size_t)2 * nw), rdig = L.rows((size_t)need * nw);
+    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, L.per_ct_bytes());
     void* ws = nullptr;
-    rc = ensure_ws(c, ntt_tmp + chunk * per_ct, &ws);
+    ws_scope_t scope;
+    rc = ws_begin(c, L, chunk, nullptr, &ws, &scope);
     if (rc) return rc;
-    u64* S = (u64*)((char*)ws + ntt_tmp);
-    u64* dig = S + (size_t)chunk * 2 * nw * N;
+    u64 *S = L.at(ws, chunk, rS), *dig = L.at(ws, chunk, rdig);
     const ks_arg_t Al = make_ks_arg(Lk, level, special ? 1 : 0, polys);  // row bookkeeping of the tail kernels: `level` = ciphertext limbs
     ks_arg_t A = Al;   // inner product: `level` field = number of digits, nw = working limbs
     A.level = need;
@@ -679,17 +696,17 @@ int tfhe_keyswitch_window(tfhe_ctx* c, int key_limbs, int level, int special, in
 // W = [0 .. level-1] ∪ [key_limbs - n_special .. key_limbs - 1];  S_s = P c_s ⊕ zeros + sum_g key_{g,s} digit_g over W;  out_s =
 // modswitch (crt.jl:215-228) applied n_special times, the last special prime first = c_s + the contraction of INTT(sum_g ...).
 //   k_ks_group_digits -> run_ntt over W -> ks_inner_launch (A.level = digits, A.w = W) -> run_ntt -> k_ks_group_tail
-// workspace: [ transform scratch | S: [chunk][2][nw][N] | digits: [chunk][d][nw][N] | rotated copy: [chunk][2][level][N] ]
+// workspace: [ region 0: transform scratch | S: [chunk][2][nw][N] | digits: [chunk][d][nw][N] | rotated copy: [chunk][2][level][N] ]
 struct ksg_plan_t {
     ks_group_arg_t G;
     ks_arg_t A;          // the key sums: A.level = digits
     ks_arg_t At;         // n_special == 0: the row bookkeeping of ks_plain_tail (level = ciphertext limbs)
     int Lk;
     const conv_tab_t* tabs;
-    int64_t chunk;
-    size_t N, S_rows, dig_rows, rot_rows, ntt_tmp;
-    size_t bytes() const { return ntt_tmp + (size_t)chunk * (S_rows + dig_rows + rot_rows) * N * 8; }
-    u64* region(void* ws, size_t before) const { return (u64*)((char*)ws + ntt_tmp) + (size_t)chunk * before * N; }
+    int64_t chunk;       // of ksg_impl; who carves the regions from a block of its own brings its own (tfhe_mul_relin_grouped)
+    size_t N;
+    ws_layout_t L;
+    ws_region_t S, dig, rot;
 };
 // one conv_tab_t per digit (source: the group cut at this level, targets: W), built on first use and kept with the context
 static int ksg_table(tfhe_ctx* c, int Lk, int level, int k, int group, const conv_tab_t** out) {
@@ -749,12 +766,10 @@ static int ksg_plan(tfhe_ctx* c, int Lk, int level, int k, int group, int polys,
     }
     P->A = make_ks_arg_grouped(Lk, level, k, d, polys);
     P->At = make_ks_arg(Lk, level, 0, polys);
-    P->S_rows = (size_t)2 * nw;
-    P->dig_rows = (size_t)d * nw;
-    P->rot_rows = rotate ? (size_t)2 * level : 0;
-    P->chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, (P->S_rows + P->dig_rows + P->rot_rows) * P->N * 8);
-    // transforms above N = 2^14 use the start of the context workspace: ours is kept apart from it (as ks_plan)
-    P->ntt_tmp = c->logN > 14 ? (size_t)P->chunk * std::max(2, d) * nw * P->N * 8 : 0;
+    P->L = ws_layout_t(P->N);
+    P->L.scratch((size_t)std::max(2, d) * nw);   // the digits' transforms (d nw rows), the key sums' inverse (2 nw)
+    P->S = P->L.rows((size_t)2 * nw); P->dig = P->L.rows((size_t)d * nw); P->rot = P->L.rows(rotate ? (size_t)2 * level : 0);
+    P->chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, P->L.per_ct_bytes());
     return ksg_table(c, Lk, level, k, group, &P->tabs);
 }
 // the digits of `batch` ciphertexts, transformed: dig [batch][d][nw][N], NTT domain; v2: two coefficients per thread
@@ -772,8 +787,8 @@ static int ksg_digits_fwd(tfhe_ctx* c, const ksg_plan_t& P, const u64* ct, u64* 
     return run_ntt(c, false, dig, dig, batch * G.d * G.nw, P.A.w);
 }
 // one chunk of `batch` ciphertexts: `ct` the chunk's input (the rotated copy for a rotation).  The caller hands over the plan and its
-// carved regions S and dig, so whoever has sized ONE block for several users (tfhe_mul_relin_grouped) runs the chunk without a second
-// ensure_ws.  rs (n_special >= 1, a 3-element input): the modswitch of both components rides on the tail -- out: [batch][2][level - 1][N]
+// carved regions S and dig, with the plan's region 0 in force, so whoever has sized ONE block for several users (tfhe_mul_relin_grouped)
+// runs the chunk without a second allocation.  rs (n_special >= 1, a 3-element input): the modswitch of both components rides on the tail -- out: [batch][2][level - 1][N]
 static int ksg_chunk(tfhe_ctx* c, const ksg_plan_t& P, const u64* evk, const u64* ct, u64* out, int64_t batch, u64* S, u64* dig,
                      const ks_group_rescale_t* rs = nullptr) {
     const ks_group_arg_t& G = P.G;
@@ -820,9 +835,10 @@ static int ksg_impl(tfhe_ctx* c, int Lk, int level, int k, int group, const u64*
     int rc = ksg_plan(c, Lk, level, k, group, polys, batch, rotate, &P);
     if (rc) return rc;
     void* ws = nullptr;
-    rc = ensure_ws(c, P.bytes(), &ws);
+    ws_scope_t scope;
+    rc = ws_begin(c, P.L, P.chunk, nullptr, &ws, &scope);
     if (rc) return rc;
-    u64 *S = P.region(ws, 0), *dig = P.region(ws, P.S_rows), *rot = P.region(ws, P.S_rows + P.dig_rows);
+    u64 *S = P.L.at(ws, P.chunk, P.S), *dig = P.L.at(ws, P.chunk, P.dig), *rot = P.L.at(ws, P.chunk, P.rot);
     const size_t N = P.N;
     for (int64_t b0 = 0; b0 < batch; b0 += P.chunk) {
         const int64_t nb = std::min(P.chunk, batch - b0);
@@ -860,7 +876,7 @@ int tfhe_rotate_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, in
 //   ks_inner_launch against all the tile's keys -> run_ntt inverse over n_tile 2 nw rows -> k_ks_group_rot_tail, every rotation at once
 // d nw forward transforms per ciphertext instead of per rotation, no rotated copies.  Shared with tfhe_matmul_diag_grouped (md_api.inc).
 struct ksg_hoist_t {
-    ksg_plan_t P;        // G, A, the digit tables (its workspace figures are the single key switch's: unused here)
+    ksg_plan_t P;        // G, A, the digit tables (its layout is the single key switch's: unused here)
     int R_tile;          // keys per launch
     size_t dig_rows, S_rows;   // rows (N words) per ciphertext: digits d nw, key sums R_tile 2 nw
 };
@@ -898,7 +914,7 @@ static int ksg_many_check(tfhe_ctx* c, bool product, int Lk, int level, int k, i
                                        sizeof msg, TFHE_DOT_MAX);
     return rc ? fail(rc, "%s", msg) : TFHE_OK;
 }
-// workspace: [ transform scratch above N = 2^14 | digits: [chunk][d][nw][N] | S: [chunk][R_tile][2][nw][N] ]
+// workspace: [ region 0: transform scratch (the larger of the two regions' rows) | digits: [chunk][d][nw][N] | S: [chunk][R_tile][2][nw][N] ]
 int tfhe_rotate_many_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* evks, int n_digits,
                              const uint64_t* galois_elements, int n_rot, const uint64_t* ct, uint64_t* out, int64_t batch) {
     bool nothing = false;
@@ -908,14 +924,15 @@ int tfhe_rotate_many_grouped(tfhe_ctx* c, int key_limbs, int level, int n_specia
     rc = ksg_hoist_plan(c, key_limbs, level, n_special, group, n_rot, &H);
     if (rc) return rc;
     const size_t N = (size_t)c->N, ct_words = (size_t)2 * level * N;
-    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, (H.dig_rows + H.S_rows) * N * 8);
-    // transforms above N = 2^14 use the start of the context workspace: ours is kept apart from it (as ks_plan)
-    const size_t ntt_tmp = c->logN > 14 ? (size_t)chunk * std::max(H.dig_rows, H.S_rows) * N * 8 : 0;
+    ws_layout_t L(N);
+    L.scratch(std::max(H.dig_rows, H.S_rows));
+    const ws_region_t rdig = L.rows(H.dig_rows), rS = L.rows(H.S_rows);
+    const int64_t chunk = chunk_of(c, batch, 512, (size_t)8192 << 20, L.per_ct_bytes());
     void* ws = nullptr;
-    rc = ensure_ws(c, ntt_tmp + (size_t)chunk * (H.dig_rows + H.S_rows) * N * 8, &ws);
+    ws_scope_t scope;
+    rc = ws_begin(c, L, chunk, nullptr, &ws, &scope);
     if (rc) return rc;
-    u64* const dig = (u64*)((char*)ws + ntt_tmp);
-    u64* const S = dig + (size_t)chunk * H.dig_rows * N;
+    u64 *const dig = L.at(ws, chunk, rdig), *const S = L.at(ws, chunk, rS);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
         const u64* cin = ct + (size_t)b0 * ct_words;

@@ -1,7 +1,7 @@
 // md_api.inc -- the diagonal matrix products tfhe_matmul_diag, tfhe_matmul_bsgs and tfhe_matmul_bsgs_blocks, the rotate-and-sum fold
 // tfhe_rotate_sum and the rectangular product tfhe_matmul_bsgs_fold: the shared rotation phase (md_plan, md_bufs, md_rotations), its
 // workspace, the fold (md_fold_plan, md_fold_run) and the five entry points; included by toyfhe_hip.hip after ks_api.inc, whose key-sum, digit and
-// rotation helpers (ks_digits_fwd, ks_inner_launch, keyswitch_impl, ks_plan, rotate_many_ws) it calls.  Kernels: kernels.h k_md_*.
+// rotation helpers (ks_digits_fwd, ks_inner_launch, keyswitch_impl, ks_rot_prepared_bytes) it calls.  Kernels: kernels.h k_md_*.
 // At the end: the same rotation phase on grouped-digit keys (mdg_plan, mdg_bufs, mdg_rotations; kernels ks_group_core.h k_mdg_*) with its
 // two entry points, tfhe_matmul_diag_grouped and tfhe_matmul_bsgs_grouped, on the hoisting helpers of ks_api.inc (ksg_*).
 
@@ -39,7 +39,7 @@ static int md_lift_fwd(tfhe_ctx* c, const ks_arg_t& A, const limb_sel_t& sl, con
         int rc;
         void* tmp = nullptr;
         if (tmask != tall) {   // (before the fork: growing the workspace synchronises)
-            rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
+            rc = ws_scratch(c, (size_t)rows * c->N * 8, &tmp);
             if (rc) return rc;
         }
         lanes_t lanes(c, tmask != 0 && tmask != tall);   // both kinds of limbs: side by side
@@ -110,27 +110,28 @@ static size_t md_ws_cap(const tfhe_ctx* c) {
     return ws_cap;
 }
 
-// The workspace of one call, [ region 0 | chunk x per_ct bytes ]: the largest chunk of the batch that md_ws_cap admits, halved
-// while the allocation fails.  region0_of(chunk) gives the bytes at the start of the context workspace that the stand-alone
-// transforms of N > 2^14 and nested calls take for themselves (ensure_ws hands out the start of whatever is allocated).
+// The workspace of one call by its layout: the largest chunk of the batch that md_ws_cap admits, halved while the allocation
+// fails; the layout is in force from the allocation until this object goes.
 struct md_ws_t {
     ws_borrow_t borrow;   // a workspace above ws_keep_bytes() is this call's: back to the allocator on every return path
+    const ws_layout_t& L;
     int rc = TFHE_OK;
     int64_t chunk;
-    size_t region0 = 0;
     void* ws = nullptr;
-    md_ws_t(tfhe_ctx* c, int64_t batch, size_t per_ct, const std::function<size_t(int64_t)>& region0_of)
-        : borrow(c), chunk(chunk_of(c, batch, 512, md_ws_cap(c), per_ct)) {
+    ws_scope_t scope;
+    md_ws_t(tfhe_ctx* c, int64_t batch, const ws_layout_t& layout)
+        : borrow(c), L(layout), chunk(chunk_of(c, batch, 512, md_ws_cap(c), layout.per_ct_bytes())) {
         for (bool first_try = true;; first_try = false) {
-            region0 = region0_of(chunk);
-            const size_t need = region0 + chunk * per_ct;
+            const size_t need = L.bytes(chunk);
             if (first_try && need > ws_keep_bytes() && need > c->ws_bytes) borrow.begin();
             rc = ensure_ws(c, need, &ws, borrow.active);
             if (rc != TFHE_E_NOMEM || chunk == 1) break;
             chunk = (chunk + 1) / 2;
         }
+        if (!rc) scope.set(c->ws_scratch, L.region0(chunk));
     }
-    u64* base() const { return (u64*)((char*)ws + region0); }   // the first word after region 0
+    u64* at(ws_region_t h) const { return L.at(ws, chunk, h); }
+    ws_span_t region0() const { return ws_span_t{ws, L.region0(chunk)}; }   // what a nested user is handed
 };
 
 // The rotation phase of a diagonal product -- everything up to the accumulation -- is shared by tfhe_matmul_diag and
@@ -143,10 +144,11 @@ struct md_plan_t {
     // inverse-transformed); TFHE_MD_COEFF=1 keeps the coefficient-domain tail (k_ks_rot_tail) for comparisons.
     bool eval_form;
     bool need_lf;        // the untransformed lifts: only where the lift is not fused into the transforms' loads
-    // workspace rows (N words) per ciphertext: digits (level nw) + S / T (R 2 nw) + rotated ciphertexts (R 2 level) + the ciphertext's
-    // own transform (2 level) (+ evaluation-domain form: the lifted special limbs before their transforms (R 2 level) and the
-    // special limbs themselves (R 2))
-    size_t rows;
+    // The phase's rows of a chunk, from wherever the caller puts them (no region 0 of its own): digits (level nw rows per ciphertext),
+    // S / T (R 2 nw), ROT: rotated ciphertexts (R 2 level), X: the ciphertext's own transform (2 level); evaluation-domain form: LF, the
+    // lifted special limbs before their transforms (R 2 level, where the lift is not fused), and PB, the special limbs themselves (R 2)
+    ws_layout_t L;
+    ws_region_t dig, S, ROT, X, LF, PB;
     size_t ntt_rows;     // rows of the largest stand-alone transform, per ciphertext
 };
 static md_plan_t md_plan(const tfhe_ctx* c, int Lk, int level, int special, const uint64_t* galois, int R) {
@@ -163,24 +165,19 @@ static md_plan_t md_plan(const tfhe_ctx* c, int Lk, int level, int special, cons
     static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
     P.eval_form = special && R > 0 && !md_coeff;
     P.need_lf = P.eval_form && !(md_lift_is_fused(c, P.A, P.sl) && (size_t)R * 2 * level * 4 * 512 <= 0x7fffffffull);
-    P.rows = (size_t)level * nw + (size_t)R * 2 * nw + (size_t)R * 2 * level + (size_t)2 * level +
-             (P.eval_form ? (P.need_lf ? (size_t)R * 2 * level : 0) + (size_t)R * 2 : 0);
+    P.L = ws_layout_t((size_t)c->N);
+    P.dig = P.L.rows((size_t)level * nw); P.S = P.L.rows((size_t)R * 2 * nw); P.ROT = P.L.rows((size_t)R * 2 * level);
+    P.X = P.L.rows((size_t)2 * level); P.LF = P.L.rows(P.need_lf ? (size_t)R * 2 * level : 0); P.PB = P.L.rows(P.eval_form ? (size_t)R * 2 : 0);
     P.ntt_rows = std::max<size_t>({(size_t)level * nw, (size_t)R * 2 * nw, (size_t)2 * level});
     return P;
 }
 // ROT: the transformed rotated ciphertexts [R][nb][2][level][N], in the evaluation-domain form the lifts U of the same shape
-struct md_bufs_t { u64 *dig, *S, *ROT, *X, *LF, *PB, *end; };
-static md_bufs_t md_bufs(const md_plan_t& P, u64* base, int64_t chunk, size_t N) {
-    md_bufs_t B{};
-    const size_t R = (size_t)P.R, level = (size_t)P.level, nw = (size_t)P.nw;
-    B.dig = base;
-    B.S = B.dig + (size_t)chunk * level * nw * N;
-    B.ROT = B.S + (size_t)chunk * R * 2 * nw * N;
-    B.X = B.ROT + (size_t)chunk * R * 2 * level * N;
-    B.LF = P.need_lf ? B.X + (size_t)chunk * 2 * level * N : nullptr;   // lifted special limbs, untransformed (same shape as U)
-    B.PB = B.X + (size_t)chunk * 2 * level * N + (P.need_lf ? (size_t)chunk * R * 2 * level * N : 0);   // [R][nb][2][N]
-    B.end = base + (size_t)chunk * P.rows * N;
-    return B;
+struct md_bufs_t { u64 *dig, *S, *ROT, *X, *LF, *PB; };
+static md_bufs_t md_bufs(const md_plan_t& P, u64* base, int64_t chunk) {
+    const auto at = [&](ws_region_t h) { return P.L.at(base, chunk, h); };
+    return md_bufs_t{at(P.dig), at(P.S), at(P.ROT), at(P.X),
+                     P.need_lf ? at(P.LF) : nullptr,   // lifted special limbs, untransformed (same shape as U)
+                     at(P.PB)};                        // [R][nb][2][N]
 }
 // The coefficient tail of the rotation phase (no special prime, or TFHE_MD_COEFF=1; R >= 1): ROT = rotate(gk_r, cin) for every r, in the
 // COEFFICIENT domain, [R][nb][2][level][N] -- where the products transform them next (md_rotations) and the fold adds them as they are
@@ -249,11 +246,14 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
     if (batch == 0) return TFHE_OK;
     const size_t N = (size_t)c->N;
     const md_plan_t P = md_plan(c, Lk, level, special, galois, n_rot);
-    // region 0: the scratch of the stand-alone transforms of N > 2^14
-    const md_ws_t W(c, batch, P.rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * P.ntt_rows * N * 8 : (size_t)0; });
+    // workspace: [ region 0: transform scratch | the rotation phase (md_bufs) ]
+    ws_layout_t L(N);
+    L.scratch(P.ntt_rows);
+    const ws_region_t phase = L.rows(P.L.rows_per_ct());
+    const md_ws_t W(c, batch, L);
     if (W.rc) return W.rc;
     const int64_t chunk = W.chunk;
-    const md_bufs_t B = md_bufs(P, W.base(), chunk, N);
+    const md_bufs_t B = md_bufs(P, W.at(phase), chunk);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
         bool scaled = true;
@@ -282,16 +282,6 @@ int tfhe_matmul_diag(tfhe_ctx* c, int Lk, int level, int special, const uint64_t
 // k_md_acc / k_md_acc_dense, tiled; one batched inverse transform covers all inner sums; the giant rotations go through the
 // prepared-key key switch (keyswitch_impl), one per giant step over the chunk; k_bsgs_sum adds up.  Exact arithmetic on canonical
 // residues throughout: the words of tfhe_rotate_many -> tfhe_nntt -> tfhe_dot -> tfhe_inntt -> tfhe_rotate_prepared -> tfhe_add.
-//
-// The workspace the giant rotations' key switch asks for at the start of the context workspace, for `batch` ciphertexts: either
-// route a prepared-key rotation can take (ks_plan decides by the operands' addresses, which are ours and always disjoint)
-static size_t bsgs_nested_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t batch) {
-    const int nw = special ? level + 1 : level;
-    const u64* const in = (const u64*)(uintptr_t)4096;   // two disjoint, aligned ranges: never dereferenced by the plan
-    const ks_plan_t P = ks_plan(c, Lk, level, special, 2, batch, in, in + (size_t)batch * 2 * level * (size_t)c->N, 1, true, false, true);
-    const size_t tail = P.rot == KS_ROT_HOISTED ? 0 : P.bytes();
-    return std::max(tail, rotate_many_ws(c, level, nw, batch).bytes());
-}
 // ---- the rotate-and-sum fold ---------------------------------------------------------------------------------------------------
 // F_0 = the input;  F_{t+1} = F_t + sum_{u < sizes[t]} rotate(key_{t,u}, F_t): log2(n / m) steps of it add up the n / m partial sums a
 // product by m extended diagonals leaves (tfhe_matmul_bsgs_fold), and by itself it is the sum of slots (tfhe_rotate_sum).  One step over
@@ -316,7 +306,7 @@ static md_fold_t md_fold_plan(const tfhe_ctx* c, int Lk, int level, int special,
     F.plans.reserve((size_t)n_groups);
     for (int t = 0, off = 0; t < n_groups; off += sizes[t], t++) {
         F.plans.push_back(md_plan(c, Lk, level, special, galois + off, sizes[t]));
-        F.rows = std::max(F.rows, F.plans.back().rows);
+        F.rows = std::max(F.rows, F.plans.back().L.rows_per_ct());
         F.ntt_rows = std::max(F.ntt_rows, F.plans.back().ntt_rows);
     }
     return F;
@@ -329,7 +319,7 @@ static int md_fold_run(tfhe_ctx* c, const md_fold_t& F, u64* base, int64_t chunk
     const u64* src = in;
     for (int t = 0, off = 0; t < F.n_groups; off += F.sizes[t], t++) {
         const md_plan_t& P = F.plans[(size_t)t];
-        const md_bufs_t B = md_bufs(P, base, chunk, N);
+        const md_bufs_t B = md_bufs(P, base, chunk);
         const bool last = t + 1 == F.n_groups;
         const size_t ct_words = (size_t)nb * 2 * P.level * N;
         const dim3 rows = row_grid((unsigned)(nb * 2 * P.level), N);
@@ -377,27 +367,26 @@ static int matmul_bsgs_run(tfhe_ctx* c, int Lk, int level, int special, const ui
     const md_plan_t P = md_plan(c, Lk, level, special, baby_galois, n_baby);
     // One allocation: [ region 0 | the baby phase (md_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N]
     // (| F [2][chunk][2][level][N] with fold steps) ].
-    // Region 0 is the start of the context workspace, which the stand-alone transforms of N > 2^14 and the nested key switch
-    // take for themselves (ensure_ws hands out the start of whatever is allocated): sized for the larger of the two, so that a
-    // nested ensure_ws neither grows -- moves -- the workspace nor reaches our buffers.  Nothing scales with n_in.
+    // Region 0 holds the scratch of the largest stand-alone transform (the baby phase's, the inner sums' inverse, the fold's) and is the
+    // span the giant rotations' key switch lays out its own block in.  Nothing scales with n_in.
     // With fold steps (tfhe_matmul_bsgs_fold) the baby-phase region is as large as the largest fold group needs -- the fold runs when the
     // baby phase of the chunk is over -- and two ping-pong ciphertext buffers F follow the giant results: the closing sum writes F_0 into
     // FB[1] instead of `out`, and the last fold step writes `out`, with the bias.
-    const size_t phase_rows = std::max(P.rows, fold ? fold->rows : (size_t)0);
-    const size_t rows = phase_rows + (size_t)(ng1 + n_giant + (fold ? 2 : 0)) * 2 * level, per_ct = rows * N * 8;
-    const size_t ntt_rows = std::max({P.ntt_rows, (size_t)ng1 * 2 * level, fold ? fold->ntt_rows : (size_t)0});
-    const md_ws_t W(c, batch, per_ct, [&](int64_t chunk) {
-        size_t r0 = c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : 0;
-        if (n_giant) r0 = std::max(r0, bsgs_nested_bytes(c, Lk, level, special, chunk));
-        return (r0 + 255) & ~(size_t)255;
-    });
+    const size_t ct_rows = (size_t)2 * level;
+    std::function<size_t(int64_t)> nested;
+    if (n_giant) nested = [=](int64_t chunk) { return ks_rot_prepared_bytes(c, Lk, level, special, chunk); };
+    ws_layout_t L(N);
+    L.scratch(std::max({P.ntt_rows, (size_t)ng1 * ct_rows, fold ? fold->ntt_rows : (size_t)0}), nested);
+    const ws_region_t phase = L.rows(std::max(P.L.rows_per_ct(), fold ? fold->rows : (size_t)0));
+    const ws_region_t inner = L.rows((size_t)ng1 * ct_rows), gout = L.rows((size_t)n_giant * ct_rows);
+    const ws_region_t f0 = L.rows(fold ? ct_rows : 0), f1 = L.rows(fold ? ct_rows : 0);
+    const md_ws_t W(c, batch, L);
     if (W.rc) return W.rc;
     const int64_t chunk = W.chunk;
-    const size_t region0 = W.region0;
-    const md_bufs_t B = md_bufs(P, W.base(), chunk, N);
-    u64* const INNER = W.base() + (size_t)chunk * phase_rows * N;   // (= B.end without fold steps)
-    u64* const GOUT = INNER + (size_t)chunk * ng1 * 2 * level * N;
-    u64* const FB[2] = {GOUT + (size_t)chunk * n_giant * 2 * level * N, GOUT + (size_t)chunk * (n_giant + 1) * 2 * level * N};
+    const ws_span_t span = W.region0();
+    const md_bufs_t B = md_bufs(P, W.at(phase), chunk);
+    u64 *const INNER = W.at(inner), *const GOUT = W.at(gout);
+    u64* const FB[2] = {W.at(f0), W.at(f1)};
     int rc;
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
@@ -423,18 +412,9 @@ static int matmul_bsgs_run(tfhe_ctx* c, int Lk, int level, int special, const ui
         }
         rc = run_ntt(c, true, INNER, INNER, (int64_t)ng1 * nb * 2 * level, P.sl);
         if (rc) return rc;
-        // What the nested key switch will ask for, from its own plan on the real operands: it must stay inside region 0.  The plan of
-        // the first giant step stands for all of them: it depends on the operands only through their disjointness and 16-byte
-        // alignment, and step j reads INNER + j ct_words and writes GOUT + (j - 1) ct_words -- disjoint ranges of one allocation, every
-        // offset a multiple of 8 N bytes from a 256-byte aligned base -- and on the Galois element only for what it writes into the plan.
-        if (n_giant) {
-            const ks_plan_t Q = ks_plan(c, Lk, level, special, 2, nb, INNER + ct_words, GOUT, giant_galois[0], true, false, true);
-            const size_t nested = Q.rot == KS_ROT_HOISTED ? rotate_many_ws(c, level, P.nw, nb).bytes() : Q.bytes();
-            if (nested > region0) return fail(TFHE_E_UNSUPPORTED, "internal: the nested key switch needs %zu bytes, region 0 holds %zu", nested, region0);
-        }
-        for (int j = 1; j <= n_giant; j++) {   // (the nested call finds the workspace large enough: same block, region 0)
+        for (int j = 1; j <= n_giant; j++) {   // (the nested call lays out its block in region 0)
             rc = keyswitch_impl(c, Lk, level, special, giant_evks[j - 1], INNER + (size_t)j * ct_words, 2, GOUT + (size_t)(j - 1) * ct_words, nb,
-                                giant_galois[j - 1], true, false, true);
+                                giant_galois[j - 1], true, false, true, &span);
             if (rc) return rc;
         }
         u64* const o = out + (size_t)b0 * 2 * level * N;
@@ -442,7 +422,7 @@ static int matmul_bsgs_run(tfhe_ctx* c, int Lk, int level, int special, const ui
                     fold ? FB[1] : o, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words, fold ? (const u64*)nullptr : (const u64*)bias);
         if (rc) return rc;
         if (fold) {
-            rc = md_fold_run(c, *fold, W.base(), chunk, FB, FB[1], nb, bias, o);
+            rc = md_fold_run(c, *fold, W.at(phase), chunk, FB, FB[1], nb, bias, o);
             if (rc) return rc;
         }
     }
@@ -568,16 +548,17 @@ int tfhe_rotate_sum(tfhe_ctx* c, int Lk, int level, int special, const uint64_t*
         return TFHE_OK;
     }
     const md_fold_t F = md_fold_plan(c, Lk, level, special, evks, galois, group_sizes, n_groups);
-    // One allocation: [ region 0 | the rotation phase of the largest group (md_bufs) | two ping-pong ciphertext buffers F ].
-    const size_t rows = F.rows + (size_t)2 * 2 * level;
-    const md_ws_t W(c, batch, rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * F.ntt_rows * N * 8 : (size_t)0; });
+    // One allocation: [ region 0: transform scratch | the rotation phase of the largest group (md_bufs) | two ping-pong ciphertext buffers F ].
+    ws_layout_t L(N);
+    L.scratch(F.ntt_rows);
+    const ws_region_t phase = L.rows(F.rows), f0 = L.rows((size_t)2 * level), f1 = L.rows((size_t)2 * level);
+    const md_ws_t W(c, batch, L);
     if (W.rc) return W.rc;
     const int64_t chunk = W.chunk;
-    u64* const F0 = W.base() + (size_t)chunk * F.rows * N;
-    u64* const FB[2] = {F0, F0 + (size_t)chunk * 2 * level * N};
+    u64* const FB[2] = {W.at(f0), W.at(f1)};
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
-        rc = md_fold_run(c, F, W.base(), chunk, FB, ct + (size_t)b0 * 2 * level * N, nb, nullptr, out + (size_t)b0 * 2 * level * N);
+        rc = md_fold_run(c, F, W.at(phase), chunk, FB, ct + (size_t)b0 * 2 * level * N, nb, nullptr, out + (size_t)b0 * 2 * level * N);
         if (rc) return rc;
     }
     return TFHE_OK;
@@ -655,9 +636,11 @@ struct mdg_plan_t {
     rescale_arg_t ra;    // (k_md_acc's USCALE factors: unused, U carries its scale)
     int Lk, level, K, nw, R;
     bool eval_form;
-    // workspace rows (N words) per ciphertext: digits d nw + key sums max(R, giant) 2 nw + U / rotated ciphertexts R 2 level + the
-    // ciphertext's own transform 2 level + the permuted special limbs R 2 K
-    size_t dig_rows, S_rows, rows;
+    // The phase's rows of a chunk, from wherever the caller puts them (no region 0 of its own): digits (d nw rows per ciphertext), key
+    // sums (max(R, giant) 2 nw), ROT: U / rotated ciphertexts (R 2 level), X: the ciphertext's own transform (2 level), PB: the permuted
+    // special limbs (R 2 K)
+    ws_layout_t L;
+    ws_region_t dig, S, ROT, X, PB;
     size_t ntt_rows;     // rows of the largest stand-alone transform, per ciphertext
 };
 // giant: the digits and ONE key sum are also wanted when there is no baby step (the giant rotations of tfhe_matmul_bsgs_grouped reuse
@@ -682,24 +665,19 @@ static int mdg_plan(tfhe_ctx* c, int Lk, int level, int k, int group, const uint
     static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
     P->eval_form = k >= 1 && R >= 1 && !md_coeff;
     const size_t ct_rows = (size_t)2 * level;
-    P->dig_rows = (R || giant) ? P->H.dig_rows : 0;
-    P->S_rows = (size_t)std::max(R, giant ? 1 : 0) * 2 * G.nw;
-    P->rows = P->dig_rows + P->S_rows + (size_t)R * ct_rows + ct_rows + (size_t)R * 2 * k;
-    P->ntt_rows = std::max({P->dig_rows, P->S_rows, (size_t)R * ct_rows, ct_rows});
+    const size_t dig_rows = (R || giant) ? P->H.dig_rows : 0, S_rows = (size_t)std::max(R, giant ? 1 : 0) * 2 * G.nw;
+    P->L = ws_layout_t((size_t)c->N);
+    P->dig = P->L.rows(dig_rows); P->S = P->L.rows(S_rows); P->ROT = P->L.rows((size_t)R * ct_rows);
+    P->X = P->L.rows(ct_rows); P->PB = P->L.rows((size_t)R * 2 * k);
+    P->ntt_rows = std::max({dig_rows, S_rows, (size_t)R * ct_rows, ct_rows});
     return TFHE_OK;
 }
 // S: the key sums -- V in the EPI layout (evaluation-domain form) or [R][nb][2][nw][N];  ROT: U, or the transformed rotated
 // ciphertexts, [R][nb][2][level][N];  PB: [R][nb][2][K][N]
-struct mdg_bufs_t { u64 *dig, *S, *ROT, *X, *PB, *end; };
-static mdg_bufs_t mdg_bufs(const mdg_plan_t& P, u64* base, int64_t chunk, size_t N) {
-    mdg_bufs_t B{};
-    B.dig = base;
-    B.S = B.dig + (size_t)chunk * P.dig_rows * N;
-    B.ROT = B.S + (size_t)chunk * P.S_rows * N;
-    B.X = B.ROT + (size_t)chunk * P.R * 2 * P.level * N;
-    B.PB = B.X + (size_t)chunk * 2 * P.level * N;
-    B.end = base + (size_t)chunk * P.rows * N;
-    return B;
+struct mdg_bufs_t { u64 *dig, *S, *ROT, *X, *PB; };
+static mdg_bufs_t mdg_bufs(const mdg_plan_t& P, u64* base, int64_t chunk) {
+    const auto at = [&](ws_region_t h) { return P.L.at(base, chunk, h); };
+    return mdg_bufs_t{at(P.dig), at(P.S), at(P.ROT), at(P.X), at(P.PB)};
 }
 // X = NTT(cin) and, per rotation r: evaluation-domain form -- V in S and U in ROT; otherwise NTT(rotate_grouped(gk_r, cin)) in ROT
 static int mdg_rotations(tfhe_ctx* c, const mdg_plan_t& P, const uint64_t* const* evks, const u64* cin, int64_t nb, const mdg_bufs_t& B) {
@@ -754,7 +732,7 @@ static int mdg_accumulate(tfhe_ctx* c, const mdg_plan_t& P, const mdg_bufs_t& B,
 // ---- the diagonal product on grouped-digit keys -----------------------------------------------------------------------------------
 // out = diags[0] (.) NTT(c) + sum_r diags[r+1] (.) NTT(rotate_grouped(gk_r, c)): mdg_rotations over all n_rot <= 64 keys, then one
 // accumulation (ngiant1 = 1) written where it belongs.  The words of tfhe_rotate_many_grouped -> tfhe_nntt -> tfhe_dot on either route.
-// workspace: [ region 0 | digits: [chunk][d][nw][N] | S / V: [chunk][R][2][nw][N] | ROT / U: [chunk][R][2][level][N] | X: [chunk][2][level][N]
+// workspace: [ region 0: transform scratch | digits: [chunk][d][nw][N] | S / V: [chunk][R][2][nw][N] | ROT / U: [chunk][R][2][level][N] | X: [chunk][2][level][N]
 //              | PB: [chunk][R][2][K][N] ]
 int tfhe_matmul_diag_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* evks, int n_digits,
                              const uint64_t* galois_elements, int n_rot, const uint64_t* diags, const uint64_t* ct, uint64_t* out, int64_t batch) {
@@ -765,10 +743,13 @@ int tfhe_matmul_diag_grouped(tfhe_ctx* c, int key_limbs, int level, int n_specia
     rc = mdg_plan(c, key_limbs, level, n_special, group, galois_elements, n_rot, false, &P);
     if (rc) return rc;
     const size_t N = (size_t)c->N, ct_words = (size_t)2 * level * N;
-    const md_ws_t W(c, batch, P.rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * P.ntt_rows * N * 8 : (size_t)0; });
+    ws_layout_t L(N);
+    L.scratch(P.ntt_rows);
+    const ws_region_t phase = L.rows(P.L.rows_per_ct());
+    const md_ws_t W(c, batch, L);
     if (W.rc) return W.rc;
     const int64_t chunk = W.chunk;
-    const mdg_bufs_t B = mdg_bufs(P, W.base(), chunk, N);
+    const mdg_bufs_t B = mdg_bufs(P, W.at(phase), chunk);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
         rc = mdg_rotations(c, P, evks, ct + (size_t)b0 * ct_words, nb, B);
@@ -785,9 +766,9 @@ int tfhe_matmul_diag_grouped(tfhe_ctx* c, int key_limbs, int level, int n_specia
 //     out     = INTT(inner_0) + sum_{j >= 1} rotate_grouped(giant key j - 1, INTT(inner_j)) (+ bias on component 0)
 // One batched inverse transform covers all inner sums.  Giant step j is a hoisted rotation with a tile of one key: ksg_digits_fwd on
 // INNER_j, ksg_hoist_tile into GOUT_j -- in the digit and key-sum regions of the baby phase, which is over by then (one stream, in
-// order), so no nested ensure_ws.  k_bsgs_sum adds up.  The words of tfhe_rotate_many_grouped -> tfhe_nntt -> tfhe_dot -> tfhe_inntt ->
+// order), so no nested workspace.  k_bsgs_sum adds up.  The words of tfhe_rotate_many_grouped -> tfhe_nntt -> tfhe_dot -> tfhe_inntt ->
 // tfhe_rotate_grouped -> tfhe_add.
-// workspace: [ region 0 | the baby phase (mdg_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ]
+// workspace: [ region 0: transform scratch | the baby phase (mdg_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ]
 int tfhe_matmul_bsgs_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* baby_evks,
                              const uint64_t* baby_galois, int n_baby, const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant,
                              int n_digits, const uint64_t* const* diags, const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out,
@@ -807,14 +788,14 @@ int tfhe_matmul_bsgs_grouped(tfhe_ctx* c, int key_limbs, int level, int n_specia
     int rc = mdg_plan(c, Lk, level, n_special, group, baby_galois, n_baby, n_giant > 0, &P);
     if (rc) return rc;
     const size_t N = (size_t)c->N;
-    const size_t rows = P.rows + (size_t)(ng1 + n_giant) * 2 * level;
-    const size_t ntt_rows = std::max(P.ntt_rows, (size_t)ng1 * 2 * level);
-    const md_ws_t W(c, batch, rows * N * 8, [&](int64_t chunk) { return c->logN > 14 ? (size_t)chunk * ntt_rows * N * 8 : (size_t)0; });
+    ws_layout_t L(N);
+    L.scratch(std::max(P.ntt_rows, (size_t)ng1 * 2 * level));
+    const ws_region_t phase = L.rows(P.L.rows_per_ct()), inner = L.rows((size_t)ng1 * 2 * level), gout = L.rows((size_t)n_giant * 2 * level);
+    const md_ws_t W(c, batch, L);
     if (W.rc) return W.rc;
     const int64_t chunk = W.chunk;
-    const mdg_bufs_t B = mdg_bufs(P, W.base(), chunk, N);
-    u64* const INNER = B.end;
-    u64* const GOUT = INNER + (size_t)chunk * ng1 * 2 * level * N;
+    const mdg_bufs_t B = mdg_bufs(P, W.at(phase), chunk);
+    u64 *const INNER = W.at(inner), *const GOUT = W.at(gout);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
         const size_t ct_words = (size_t)nb * 2 * level * N;   // one inner sum / one giant result of this chunk

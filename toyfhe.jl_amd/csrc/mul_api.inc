@@ -4,9 +4,9 @@
 //
 // The call is the chain  nntt x2 -> tensor -> inntt -> keyswitch(polys = 3) -> rescale  run directly on the packed
 // ciphertexts ([batch][2][level][N] is 2 batch polynomials), with the intermediates in the context workspace:
-//     ws = [ key-switch region / transform scratch | F: 4 rows per limb (NTT images) | T: 3 rows | R: 2 rows | parking rows x 2 ]
-// keyswitch_impl sizes and carves ITS region from the start of the context workspace and would move the block if it had to
-// grow it, so the block is sized once, before the first launch, for both users (mr_ks_bytes asks ks_plan, as keyswitch_impl does).
+//     ws = [ region 0: the key switch's block / transform scratch | F: 4 rows per limb (NTT images) | T: 3 rows | R: 2 rows | parking rows x 2 ]
+// The block is sized once, before the first launch, for both users (ws_layout.h): keyswitch_impl is handed region 0 as its span and
+// lays out its own block there, by the plan that sized it.
 //
 // Routing of the product (forward transforms + tensor + inverse transforms) per limb:
 //   N = 2^12 .. 2^14, variant 0, fp64-size limb : k_bfv_core_fused (MODE: packed operands / squaring / NTT-domain input)
@@ -16,11 +16,6 @@
 // Every path leaves canonical residues, so the words are those of the chain through the public entry points.
 
 namespace {
-
-// bytes keyswitch_impl (rotate = false) asks of the context workspace for `batch` ciphertexts: its own plan's
-size_t mr_ks_bytes(const tfhe_ctx* c, int Lk, int level, int special, int64_t batch) {
-    return ks_plan(c, Lk, level, special, 3, batch).bytes();   // no rotation: sizes only, no table is computed
-}
 
 // parking rows (N words each) the two fused cores may ask for: one per workgroup (k_bfv_core_fused; k_mul_core_int below 2^14), two per
 // workgroup at 2^14 (k_mul_core_int) -- the grids are at most two workgroups per CU below 2^14 and one at 2^14
@@ -110,6 +105,14 @@ struct mr_product_t {
     size_t f_rows;           // rows per limb of F (the NTT images of the operands: the batched path only)
     size_t park;             // words of parking rows per fused core
     size_t park_bytes() const { return fused ? 2 * park * 8 : 0; }
+    // F, T and R (r_rows per limb: the key switch's result where a pass of its own follows it), then the parking rows
+    ws_region_t F, T, R, SCR;
+    void declare(ws_layout_t& L, int level, size_t r_rows) {
+        F = L.rows(f_rows * level);
+        T = L.rows((size_t)3 * level);
+        R = L.rows(r_rows * level);
+        SCR = L.tail(park_bytes());
+    }
 };
 mr_product_t mr_product_plan(const tfhe_ctx* c, int level, bool square, bool ntt_in) {
     mr_product_t M{};
@@ -154,32 +157,32 @@ extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const
     if ((batch * 4 * level) << std::max(0, c->logN - 14) > 0x7fffffffll) return fail(TFHE_E_BADARG, "bad batch");
 
     const limb_sel_t sel = first_limbs(level);
-    const mr_product_t M = mr_product_plan(c, level, c1 == c2, ntt_in != 0);
+    mr_product_t M = mr_product_plan(c, level, c1 == c2, ntt_in != 0);
 
-    // chunk: F (NTT images of the operands: the batched path only), T (3 rows per limb), R (2: the key switch's result when a
-    // modswitch follows)
-    const size_t r_rows = rescale ? 2 : 0;
-    const size_t per_ct = (M.f_rows + 3 + r_rows) * level * N * 8;
-    const int64_t chunk = chunk_of(c, batch, 256, (size_t)4096 << 20, per_ct);
-    size_t region0 = mr_ks_bytes(c, Lk, level, special, chunk);
-    if (c->logN > 14) region0 = std::max(region0, (size_t)chunk * 3 * level * N * 8);   // run_ntt's scratch for N > 2^14
-    region0 = (region0 + 255) & ~(size_t)255;
+    // region 0: the key switch's block, by its own plan (no rotation: sizes only, no table is computed), and the scratch of the product's
+    // transforms (3 level rows: T's inverse).  chunk: F (NTT images of the operands: the batched path only), T (3 rows per limb), R (2:
+    // the key switch's result when a modswitch follows)
+    ws_layout_t L(N);
+    L.scratch((size_t)3 * level, [=](int64_t chunk) {
+        const ks_plan_t P = ks_plan(c, Lk, level, special, 3, chunk);
+        return P.L.bytes(P.chunk);
+    });
+    M.declare(L, level, rescale ? 2 : 0);
+    const int64_t chunk = chunk_of(c, batch, 256, (size_t)4096 << 20, L.per_ct_bytes());
     void* ws = nullptr;
-    rc = ensure_ws(c, region0 + (size_t)chunk * per_ct + M.park_bytes(), &ws);   // once, for both users, before any fork
+    ws_scope_t scope;
+    rc = ws_begin(c, L, chunk, nullptr, &ws, &scope);   // once, for both users, before any fork
     if (rc) return rc;
-    u64* F = (u64*)((char*)ws + region0);
-    u64* T = F + (size_t)chunk * M.f_rows * level * N;
-    u64* R = T + (size_t)chunk * 3 * level * N;
-    u64* SCR = R + (size_t)chunk * r_rows * level * N;
+    const ws_span_t span{ws, L.region0(chunk)};
+    u64 *F = L.at(ws, chunk, M.F), *T = L.at(ws, chunk, M.T), *R = L.at(ws, chunk, M.R), *SCR = L.at(ws, chunk, M.SCR);
     const int lo = level - (rescale ? 1 : 0);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nct = std::min(chunk, batch - b0);
         rc = mr_product(c, M, c1 + (size_t)b0 * 2 * level * N, c2 + (size_t)b0 * 2 * level * N, F, T, SCR, nct, level);
         if (rc) return rc;
         u64* ks_out = rescale ? R : out + (size_t)b0 * 2 * level * N;
-        rc = keyswitch_impl(c, Lk, level, special, evk, T, 3, ks_out, nct, 0, false);   // rlwe_she.jl:315-347
+        rc = keyswitch_impl(c, Lk, level, special, evk, T, 3, ks_out, nct, 0, false, false, false, &span);   // rlwe_she.jl:315-347
         if (rc) return rc;
-        if (c->ws != ws) return fail(TFHE_E_HIP, "internal: the key switch moved the workspace");
         if (rescale) {
             rc = do_rescale(c, R, out + (size_t)b0 * 2 * lo * N, nct * 2, sel);       // crt.jl:215-228 on both components
             if (rc) return rc;
@@ -191,7 +194,7 @@ extern "C" int tfhe_mul_relin(tfhe_ctx* c, int Lk, int level, int special, const
 // ---- the same on grouped-digit keys (tfhe_keyswitch_grouped's gadget): tfhe_mul_relin_grouped ---------------------------------------
 // The product stage is tfhe_mul_relin's; the key switch is ksg_chunk on a plan and regions carved HERE, from one block sized before the
 // first launch:
-//     ws = [ ksg region: transform scratch above 2^14 | S | digits (ksg_plan_t::bytes()) | F | T | R (n_special == 0 only) | parking rows x 2 ]
+//     ws = [ region 0: the plan's block (its transform scratch | S | digits) | F | T | R (n_special == 0 only) | parking rows x 2 ]
 // With a special prime the modswitch rides on the key switch's tail (k_ks_group_tail_rescale: no R region, the result goes straight
 // into `out`); without one there is no tail to ride on and ks_plain_tail -> do_rescale are composed through R.  The chunk follows
 // chunk_of over the larger of the two per-ciphertext footprints (the product's rows, the key switch's rows).
@@ -208,39 +211,37 @@ extern "C" int tfhe_mul_relin_grouped(tfhe_ctx* c, int Lk, int level, int k, int
 
     const size_t N = (size_t)c->N;
     const limb_sel_t sel = first_limbs(level);
-    const mr_product_t M = mr_product_plan(c, level, c1 == c2, ntt_in != 0);
+    mr_product_t M = mr_product_plan(c, level, c1 == c2, ntt_in != 0);
     const bool ride = rescale && k > 0;                       // the rescale rides on the tail
     const size_t r_rows = rescale && !ride ? 2 : 0;
-    const int d = (level + group - 1) / group, nw = level + k;
-    const size_t per_ct = (M.f_rows + 3 + r_rows) * level * N * 8, per_ct_ks = ((size_t)2 * nw + (size_t)d * nw) * N * 8;
-    const int64_t chunk = chunk_of(c, batch, 256, (size_t)4096 << 20, std::max(per_ct, per_ct_ks));
-    ksg_plan_t P;
-    rc = ksg_plan(c, Lk, level, k, group, 3, chunk, false, &P);
+    ksg_plan_t P;                                             // (the regions are carved here, for the chunk decided here: not P.chunk)
+    rc = ksg_plan(c, Lk, level, k, group, 3, batch, false, &P);
     if (rc) return rc;
-    if (P.chunk != chunk) return fail(TFHE_E_HIP, "internal: the key switch plans another chunk");
+    // region 0: the plan's block, and the scratch of the product's transforms (3 level rows: T's inverse)
+    ws_layout_t L(N);
+    L.scratch((size_t)3 * level, [&P](int64_t chunk) { return P.L.bytes(chunk); });
+    M.declare(L, level, r_rows);
+    const int64_t chunk = chunk_of(c, batch, 256, (size_t)4096 << 20, std::max(L.per_ct_bytes(), P.L.per_ct_bytes()));
     ks_group_rescale_t rs{};
     if (ride)
         for (int j = 0; j < level - 1; j++) rs.qlinv[j] = hostmath::make_tw(hostmath::invmod_prime(c->q[level - 1] % c->q[j], c->q[j]), c->q[j]);
-    size_t region0 = P.bytes();
-    if (c->logN > 14) region0 = std::max(region0, (size_t)chunk * 3 * level * N * 8);   // run_ntt's scratch for the product at N > 2^14
-    region0 = (region0 + 255) & ~(size_t)255;
     void* ws = nullptr;
-    rc = ensure_ws(c, region0 + (size_t)chunk * per_ct + M.park_bytes(), &ws);   // once, for both users, before any fork
+    ws_scope_t scope;
+    rc = ws_begin(c, L, chunk, nullptr, &ws, &scope);   // once, for both users, before any fork
     if (rc) return rc;
-    u64 *S = P.region(ws, 0), *dig = P.region(ws, P.S_rows);
-    u64* F = (u64*)((char*)ws + region0);
-    u64* T = F + (size_t)chunk * M.f_rows * level * N;
-    u64* R = T + (size_t)chunk * 3 * level * N;
-    u64* SCR = R + (size_t)chunk * r_rows * level * N;
+    u64 *S = P.L.at(ws, chunk, P.S), *dig = P.L.at(ws, chunk, P.dig);
+    u64 *F = L.at(ws, chunk, M.F), *T = L.at(ws, chunk, M.T), *R = L.at(ws, chunk, M.R), *SCR = L.at(ws, chunk, M.SCR);
     const int lo = level - (rescale ? 1 : 0);
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nct = std::min(chunk, batch - b0);
         rc = mr_product(c, M, c1 + (size_t)b0 * 2 * level * N, c2 + (size_t)b0 * 2 * level * N, F, T, SCR, nct, level);
         if (rc) return rc;
         u64* dst = out + (size_t)b0 * 2 * lo * N;
-        rc = ksg_chunk(c, P, evk, T, r_rows ? R : dst, nct, S, dig, ride ? &rs : nullptr);
+        {
+            const ws_scope_t ks(c->ws_scratch, P.L.region0(chunk));   // the key switch's transforms stay in ITS region 0, before S
+            rc = ksg_chunk(c, P, evk, T, r_rows ? R : dst, nct, S, dig, ride ? &rs : nullptr);
+        }
         if (rc) return rc;
-        if (c->ws != ws) return fail(TFHE_E_HIP, "internal: the key switch moved the workspace");
         if (r_rows) {
             rc = do_rescale(c, R, dst, nct * 2, sel);         // crt.jl:215-228 on both components
             if (rc) return rc;

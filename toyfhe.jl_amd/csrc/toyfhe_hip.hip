@@ -30,6 +30,7 @@
 #include "dot_core.h"
 #include "ntt_tables.h"
 #include "dev_alloc.h"
+#include "ws_layout.h"
 
 namespace {
 
@@ -96,6 +97,7 @@ struct tfhe_ctx {
     void* ws = nullptr;
     size_t ws_bytes = 0;
     bool ws_pooled = false;   // the block came from the recycling allocator (large per-call workspaces, ws_borrow_t)
+    ws_scratch_state_t ws_scratch;   // the layout in force, if any: what of the block's start the transforms may take (ws_layout.h)
     // profiling
     bool prof = false;
     std::vector<prof_pair> prof_pairs;
@@ -144,6 +146,27 @@ int ensure_ws(tfhe_ctx* c, size_t bytes, void** out, bool pooled = false) {
     }
     *out = c->ws;
     return TFHE_OK;
+}
+// The one allocation of a call that lays out the block (ws_layout.h): the context's own, grown to the layout, or -- for a nested user --
+// the span its caller carved for it, which must hold the layout.  `scope`: the layout is in force until it goes (nullptr: the caller
+// sets its own scope later).
+int ws_begin(tfhe_ctx* c, const ws_layout_t& L, int64_t chunk, const ws_span_t* span, void** ws, ws_scope_t* scope) {
+    const size_t bytes = L.bytes(chunk);
+    if (span) {
+        if (bytes > span->bytes) return fail(TFHE_E_HIP, "internal: a nested workspace of %zu bytes, its span holds %zu", bytes, span->bytes);
+        *ws = span->ptr;
+    } else if (int rc = ensure_ws(c, bytes, ws)) return rc;
+    if (scope) scope->set(c->ws_scratch, L.region0(chunk));
+    return TFHE_OK;
+}
+// The intermediate of a transform (run_ntt_large, run_ntt's two lanes, the mixed lifts of ks_digits_fwd and md_lift_fwd): the start of
+// the context's block -- grown to the request when no layout is in force, region 0 of the layout otherwise, never more
+int ws_scratch(tfhe_ctx* c, size_t bytes, void** out) {
+    switch (ws_scratch_decide(c->ws_scratch, bytes)) {
+    case WS_SCRATCH_GROW: return ensure_ws(c, bytes, out);
+    case WS_SCRATCH_FITS: *out = c->ws; return TFHE_OK;
+    default: return fail(TFHE_E_HIP, "internal: transform scratch of %zu bytes, region 0 holds %zu", bytes, c->ws_scratch.region0);
+    }
 }
 // The ciphertexts (polynomials, for the samplers and codecs) one iteration of a chunked entry point takes: the whole batch, at
 // most `dflt` of it, at most what `bytes_cap` holds at `per_ct` bytes each (per_ct = 0: no such bound), at most the context's
@@ -488,7 +511,7 @@ int run_ntt_large(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t r
         return launch_prof(c, rows, k_ntt_inv_quad2<ArithFp, 14, LOGT>, dim3(cu_grid(c, items)), block, lds, src, dst, c->limbs_dev, sel, items, io.limb_mask);
     }
     void* tmp = nullptr;
-    int rc = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
+    int rc = ws_scratch(c, (size_t)rows * c->N * 8, &tmp);
     if (rc) return rc;
     u64* t = (u64*)tmp;
     const dim3 tg((unsigned)((((c->N >> x) + 255) / 256) * rows));
@@ -560,7 +583,7 @@ int run_ntt(tfhe_ctx* c, bool inverse, const u64* src, u64* dst, int64_t rows, c
     if (!iop && c->variant == 0 && enough) {
         // the transform scratch of both policies (disjoint rows of it) is sized before the fork: growing it synchronises
         void* tmp = nullptr;
-        int rc1 = ensure_ws(c, (size_t)rows * c->N * 8, &tmp);
+        int rc1 = ws_scratch(c, (size_t)rows * c->N * 8, &tmp);
         if (rc1) return rc1;
         lanes_t lanes(c);
         // (which policy is enqueued first makes no difference: TFHE_LANE_FP_FIRST A/B, profiles/r06b_lane_order_ab.txt)

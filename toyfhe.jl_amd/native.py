@@ -278,7 +278,23 @@ class Context:
     def L(self):
         return len(self.qs)
 
+    # A plan's destroy call drains the streams of its contexts, so a context outlives the plans made on it: the plans count
+    # themselves in and out, and a close that arrives while one is still open -- finalizers of a garbage cycle run in any
+    # order, a context's before its plan's -- is carried out by the last plan's close.
+    _users, _close_pending = 0, False
+
+    def _retain(self):
+        self._users += 1
+
+    def _release(self):
+        self._users -= 1
+        if not self._users and self._close_pending:
+            self.close()
+
     def close(self):
+        if self._users:
+            self._close_pending = True
+            return
         if getattr(self, "h", None):
             lib().tfhe_ctx_destroy(self.h)
             self.h = None
@@ -584,11 +600,15 @@ class BfvPlan:
         h = C.c_void_p()
         check(lib().tfhe_bfv_plan_create(small.h, _idx(idx_s), self.ns, big.h, _idx(idx_b), self.nb, self.t, C.byref(h)))
         self.h = h.value
+        for c in {id(small): small, id(big): big}.values():
+            c._retain()
 
     def close(self):
         if getattr(self, "h", None):
-            lib().tfhe_bfv_plan_destroy(self.h)
+            lib().tfhe_bfv_plan_destroy(self.h)             # (drains both contexts' streams: they are still there, Context.close)
             self.h = None
+            for c in {id(self.small): self.small, id(self.big): self.big}.values():
+                c._release()
 
     def __del__(self):
         try:
@@ -635,6 +655,7 @@ class PlainPlan:
         h = C.c_void_p()
         check(lib().tfhe_plain_plan_create(ctx.h, _idx(self.idx), self.limbs, self.t, C.byref(h)))
         self.h = h.value
+        ctx._retain()
         Q = 1
         for i in self.idx:
             Q *= ctx.qs[i]
@@ -642,8 +663,9 @@ class PlainPlan:
 
     def close(self):
         if getattr(self, "h", None):
-            lib().tfhe_plain_plan_destroy(self.h)
+            lib().tfhe_plain_plan_destroy(self.h)          # (synchronises its context's stream: still there, Context.close)
             self.h = None
+            self.ctx._release()
 
     def __del__(self):
         try:
