@@ -177,7 +177,9 @@ def encrypted_matmul_rect(gk, W, x, B, b, cache=None, name=None):
         bias = tf.ckks_encode(np.repeat(np.tile(bp, W.shape[1] // m), B).astype(np.complex128), x.ring(), scale2)
         if cache is not None:
             cache[key] = (enc, bias)
-    return tf.matmul_bsgs_fold(gk.baby, gk.giant, [enc], [x], gk.folds, bias)
+    # (on keys with grouped digits: tfhe_matmul_bsgs_fold_grouped)
+    fold = tf.matmul_bsgs_fold_grouped if _grouped(gk.baby + gk.giant + [g for st in gk.folds for g in st]) else tf.matmul_bsgs_fold
+    return fold(gk.baby, gk.giant, [enc], [x], gk.folds, bias)
 
 
 def add_bias(ct, x, cache=None, name=None):
@@ -206,12 +208,15 @@ def load_model(path=GOLDEN_MODEL):
 
 
 def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=False, repeat=1, fused=False, return_logits=False, stats=None,
-        mul_relin=False, bsgs=0, blocks=False, rect=False, grouped=None, mul_relin_grouped=False):
+        mul_relin=False, bsgs=0, blocks=False, rect=False, grouped=None, mul_relin_grouped=False, fold_grouped=False):
     """`grouped` = (K, G) (with `hoisted`, or with `bsgs` alone): the key ring ends in K 60-bit special primes instead of one and every key
     has grouped digits of G limbs (tf.GroupedRaised): the Galois keys shrink from 6 to ceil(6 / G) components.  With `hoisted` the square
     layers go through tf.matmul_diag_grouped (with `fused`) or tf.rotate_many_grouped and the plaintext sum; with `bsgs` (with or without
     `blocks`) through tf.matmul_bsgs_grouped / tf.matmul_bsgs_blocks_grouped (tfhe_matmul_bsgs_grouped).  The squares go through
-    keyswitch (or `mul_relin_grouped`, below).  The fold (`rect`) has no grouped form and mul_relin takes per-limb keys.
+    keyswitch (or `mul_relin_grouped`, below).  The fold (`rect`) on grouped keys is asked for by `fold_grouped`; mul_relin takes per-limb
+    keys.
+    `fold_grouped` (with `bsgs`, `rect` and `grouped`): the rectangular last layer as ONE tf.matmul_bsgs_fold_grouped call
+    (tfhe_matmul_bsgs_fold_grouped) on the grouped keys.  Without it `rect` with `grouped` is refused, as before.
     `mul_relin_grouped` (with `hoisted` and `grouped`): the two square layers as one device call each (tf.mul_relin_grouped =
     tfhe_mul_relin_grouped, rescale=True) instead of modswitch(keyswitch(ek, c * c)); same logits, bit for bit.
     `rect` (with `bsgs`): the last layer -- 10 x 64, .+ b -- as ONE tfhe_matmul_bsgs_fold call over 16 extended diagonals and the fold
@@ -227,7 +232,9 @@ def run(logn=13, seed=0, verbose=True, model="reference", batches=1, hoisted=Fal
     of K, so each device call covers K ciphertexts (the batch the engine shards across GPUs)."""
     if (blocks or rect) and not bsgs:
         raise ValueError("blocks and rect need bsgs = n1 > 0")
-    if grouped is not None and rect:
+    if fold_grouped and not (bsgs and rect and grouped is not None):
+        raise ValueError("fold_grouped is the rectangular last layer on grouped keys: it needs bsgs = n1 > 0, rect and grouped = (K, G)")
+    if grouped is not None and rect and not fold_grouped:
         raise ValueError("rect goes through tfhe_matmul_bsgs_fold, which refuses keys with grouped digits: grouped goes with bsgs and blocks only")
     if grouped is not None and (bool(hoisted) == bool(bsgs) or mul_relin):
         raise ValueError("grouped keys are covered for the hoisted circuit only (hoisted, with or without fused) or, instead of it, for the "
@@ -385,15 +392,19 @@ if __name__ == "__main__":
                          "each, the rescale on the key switch's tail) instead of modswitch(keyswitch(ek, c * c))")
     ap.add_argument("--rect", action="store_true",
                     help="with --bsgs N1: the last layer (10 x 64, + bias) as one tfhe_matmul_bsgs_fold call: 16 extended diagonals and a fold")
+    ap.add_argument("--fold-grouped", action="store_true",
+                    help="with --bsgs N1 --rect --grouped K,G: the rectangular last layer as one tfhe_matmul_bsgs_fold_grouped call on the grouped keys")
     a = ap.parse_args()
     if (a.blocks or a.rect) and not a.bsgs:
         ap.error("--blocks and --rect need --bsgs N1")
     grouped = tuple(int(v) for v in a.grouped.split(",")) if a.grouped else None
-    if grouped is not None and a.rect:
+    if a.fold_grouped and not (a.bsgs and a.rect and grouped is not None):
+        ap.error("--fold-grouped needs --bsgs N1 --rect --grouped K,G")
+    if grouped is not None and a.rect and not a.fold_grouped:
         ap.error("--rect goes through tfhe_matmul_bsgs_fold, which refuses grouped keys: --grouped K,G goes with --bsgs N1 [--blocks] only")
     if grouped is not None and (len(grouped) != 2 or bool(a.hoisted) == bool(a.bsgs) or a.mul_relin):
         ap.error("--grouped K,G needs either --hoisted or --bsgs N1 [--blocks], and does not go with --mul-relin")
     if a.mul_relin_grouped and (grouped is None or not a.hoisted):
         ap.error("--mul-relin-grouped needs --hoisted --grouped K,G")
     run(a.logn, a.seed, model=a.model, batches=a.batches, hoisted=a.hoisted, repeat=a.repeat, fused=a.fused, mul_relin=a.mul_relin, bsgs=a.bsgs,
-        blocks=a.blocks, rect=a.rect, grouped=grouped, mul_relin_grouped=a.mul_relin_grouped)
+        blocks=a.blocks, rect=a.rect, grouped=grouped, mul_relin_grouped=a.mul_relin_grouped, fold_grouped=a.fold_grouped)

@@ -378,8 +378,9 @@ int tfhe_rotate_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, 
  * request or tfhe_ctx_destroy; tfhe_ctx_set_chunk bounds it.  tfhe_matmul_diag_grouped borrows its block for the call, as tfhe_matmul_diag:
  * per ciphertext of a chunk d nw + R 2 nw + R 2 level + 2 level + R 2 n_special rows of N words (digits, key sums, lifts or rotated
  * ciphertexts, the ciphertext's transform, the permuted special limbs), and above N = 2^14 the largest transform's rows once more.
- * Still refused on grouped keys: the per-limb entry points tfhe_matmul_bsgs* (the product by baby and giant steps on grouped keys is
- * tfhe_matmul_bsgs_grouped, below; the fold, tfhe_matmul_bsgs_fold, has no grouped form), tfhe_rotate_sum and the
+ * Still refused on grouped keys: the per-limb entry points tfhe_matmul_bsgs*, tfhe_matmul_bsgs_fold and tfhe_rotate_sum (on grouped keys
+ * the product by baby and giant steps is tfhe_matmul_bsgs_grouped, the fold tfhe_rotate_sum_grouped and the rectangular product
+ * tfhe_matmul_bsgs_fold_grouped, all below) and the
  * fused N <= 2^14 key switch; tfhe_mul_relin takes per-limb keys only -- the product on grouped keys is tfhe_mul_relin_grouped, below. */
 int tfhe_rotate_many_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group, const uint64_t *const *evks, int n_digits,
                              const uint64_t *galois_elements, int n_rot, const uint64_t *ct, uint64_t *out, int64_t batch);
@@ -412,6 +413,51 @@ int tfhe_matmul_bsgs_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_spec
                              const uint64_t *const *giant_evks, const uint64_t *giant_galois, int n_giant, int n_digits,
                              const uint64_t *const *diags, const uint64_t *const *cts, int n_in,
                              const uint64_t *bias, uint64_t *out, int64_t batch);
+/* Rotate and sum, and the product of a rectangular matrix, on grouped-digit keys: the contracts of tfhe_rotate_sum and
+ * tfhe_matmul_bsgs_fold with every rotation a tfhe_rotate_grouped.  (`group` is the number of limbs per digit, as everywhere on these
+ * keys; the key lists of the fold are called fold steps here.)
+ *     F_0 = ct;   F_{t+1} = F_t + sum_{u < group_sizes[t]} rotate_grouped(key_{t,u}, F_t);   out = F_{n_groups}
+ *   key_limbs, level, n_special, group, n_digits: as tfhe_rotate_many_grouped;  evks / galois_elements (fold_evks / fold_galois): HOST
+ *   arrays over all fold steps back to back: device pointers to PREPARED grouped Galois keys (tfhe_galois_key_prepare) and their Galois
+ *   elements -- there is no unprepared mode, a key may appear more than once;  group_sizes (fold_group_sizes): HOST array [n_groups], the
+ *   number of keys of every fold step, each >= 1, their sum <= 64;  n_groups in [0, 64];  the other operands of
+ *   tfhe_matmul_bsgs_fold_grouped: as for tfhe_matmul_bsgs_grouped;  ct, out: [batch][2][level][N], coefficient domain.
+ * tfhe_rotate_sum_grouped equals, word for word, per fold step tfhe_rotate_many_grouped over the step's keys on F_t -> tfhe_add of every
+ * result onto F_t;  tfhe_matmul_bsgs_fold_grouped equals, word for word, tfhe_matmul_bsgs_grouped (bias = NULL) ->
+ * tfhe_rotate_sum_grouped -> tfhe_add of the bias onto component 0.  (n_special, group) = (1, 1) and (0, 1) give the words of
+ * tfhe_rotate_sum / tfhe_matmul_bsgs_fold with special = 1 and 0.  n_groups = 0 gives out = ct for the fold and the words of
+ * tfhe_matmul_bsgs_grouped for the product.  The result depends neither on tfhe_ctx_set_chunk nor on the route of a fold step:
+ *   evaluation route (n_special >= 1): X = NTT(F_t) and the key sums V_r as in tfhe_matmul_diag_grouped, E = X + sum_r V_r o pi_r, ONE
+ *     inverse transform of E, and the lifts of the n_special special limbs of every key sum taken off in the coefficient domain --
+ *     they never enter the evaluation domain: per ciphertext and step d nw + 2 level forward and R 2 n_special + 2 level inverse rows;
+ *   coefficient route (n_special == 0, or TFHE_MD_COEFF=1): the hoisted rotations of tfhe_rotate_many_grouped into the workspace and
+ *     one sum: d nw forward and R 2 nw inverse rows.
+ *   The coefficient route is the default: measured, the evaluation route is ahead in steps of three keys and behind in steps of one
+ *   (README, profiles/LOG.md), so it did not win everywhere.  TFHE_MDG_FOLD_EVAL=1 (read once per process) asks for the evaluation
+ *   route; TFHE_MD_COEFF=1 wins over it.
+ * Checked on the host before any device use, in this order: a null ctx or array (evks, galois_elements, group_sizes, ct, out; for the
+ * product baby_evks, baby_galois, giant_evks, giant_galois, diags, cts, fold_evks, fold_galois, fold_group_sizes, out); the fold's host
+ * rules, as tfhe_rotate_sum: n_groups outside [0, 64], a fold step size below 1, more than 64 fold keys in all, a null fold key; for the
+ * product the null-key and count rules of tfhe_matmul_bsgs_grouped: a null key among the first n_baby / n_giant, a null diags[m] or
+ * cts[m] among the first n_in, n_baby / n_giant outside [0, 64], n_in outside [1, 64] (all TFHE_E_BADARG); for the baby keys, then the
+ * giant keys, then the fold keys, in turn the shape checks of tfhe_rotate_grouped on galois[r] in that entry point's order (without any
+ * key: those of tfhe_keyswitch_grouped, once); `out` starting where, or overlapping anywhere, ct / bias, any cts[m] or any diags[m]
+ * (TFHE_E_BADARG).  `out` is untouched on every refusal.  batch == 0 does nothing after the checks.
+ * Workspace: one borrowed block, as tfhe_matmul_bsgs_grouped.  Per ciphertext of a chunk, with step(R) = d nw + R 2 nw + R 2 level +
+ * 2 level + R 2 n_special rows of N words (the rows of tfhe_matmul_diag_grouped; E lives in the R 2 level rows):
+ *   tfhe_rotate_sum_grouped        step(largest fold step) + 2 * 2 level (two ciphertext buffers F)
+ *   tfhe_matmul_bsgs_fold_grouped  max(step(n_baby, at least one key sum with giant steps), step(largest fold step)) + (2 n_giant + 1) 2 level
+ *                                  (+ 2 * 2 level with fold steps)
+ * and above N = 2^14 the largest stand-alone transform's rows once more (region 0).  No nested request. */
+int tfhe_rotate_sum_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group,
+                            const uint64_t *const *evks, const uint64_t *galois_elements, const int *group_sizes, int n_groups,
+                            int n_digits, const uint64_t *ct, uint64_t *out, int64_t batch);
+int tfhe_matmul_bsgs_fold_grouped(tfhe_ctx *ctx, int key_limbs, int level, int n_special, int group,
+                                  const uint64_t *const *baby_evks, const uint64_t *baby_galois, int n_baby,
+                                  const uint64_t *const *giant_evks, const uint64_t *giant_galois, int n_giant, int n_digits,
+                                  const uint64_t *const *diags, const uint64_t *const *cts, int n_in,
+                                  const uint64_t *const *fold_evks, const uint64_t *fold_galois, const int *fold_group_sizes, int n_fold_groups,
+                                  const uint64_t *bias, uint64_t *out, int64_t batch);
 /* The ciphertext product, relinearised on a grouped-digit key and optionally rescaled, in one call: tfhe_mul_relin on the keys of
  * tfhe_keyswitch_grouped (a grouped-digit key is first of all a relinearisation key: ceil(level / group) components instead of level).
  *   c1, c2: [batch][2][level][N]; ntt_in = 0: coefficient domain, 1: NTT domain (natural order).  c1 == c2 (squaring) allowed.

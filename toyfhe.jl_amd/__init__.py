@@ -11,5 +11,5 @@ from .ring import NegacyclicRing, PlainElement, PlainRing, RingElement, nextprim
 from . import wire  # noqa: F401,E402
 from .she import (DeviceRng, BFVParams, BGVParams, CKKSParams, CipherText, GroupedRaised, ModulusRaised, apply_galois_element, bsgs_diagonals,  # noqa: F401,E402
                   ckks_decode, ckks_encode, decrypt, decrypt_array, enc_mul, encrypt, invariant_noise_budget, keygen, keygen_evalmult, keygen_galois, keygen_galois_many,
-                  keyswitch, make_eval_key, matmul_bsgs, matmul_bsgs_blocks, matmul_bsgs_blocks_grouped, matmul_bsgs_fold, matmul_bsgs_grouped, matmul_diag, matmul_diag_grouped, modswitch, mul_relin, mul_relin_grouped,
-                  rect_diagonals, rotate, rotate_many, rotate_many_grouped, rotate_sum)
+                  keyswitch, make_eval_key, matmul_bsgs, matmul_bsgs_blocks, matmul_bsgs_blocks_grouped, matmul_bsgs_fold, matmul_bsgs_fold_grouped, matmul_bsgs_grouped, matmul_diag, matmul_diag_grouped, modswitch, mul_relin, mul_relin_grouped,
+                  rect_diagonals, rotate, rotate_many, rotate_many_grouped, rotate_sum, rotate_sum_grouped)

@@ -1,12 +1,13 @@
 // ks_group_core.h -- the kernels of the key switch with grouped RNS digits and several special primes (tfhe_keyswitch_grouped and the
 // hoisted rotations, ks_api.inc; the tail that carries the rescale of tfhe_mul_relin_grouped, mul_api.inc; the permutation and the lift of
-// the evaluation-domain rotation phase of tfhe_matmul_diag_grouped / tfhe_matmul_bsgs_grouped, md_api.inc), and their per-coefficient bodies.
+// the evaluation-domain rotation phase of tfhe_matmul_diag_grouped / tfhe_matmul_bsgs_grouped and the gather and the finish of a fold step
+// of tfhe_rotate_sum_grouped / tfhe_matmul_bsgs_fold_grouped, md_api.inc), and their per-coefficient bodies.
 //
 // Digit g of c[end] is the centred representative of c[end] modulo Q_g = prod_{i in G_g} q_i (the exact CRT value with the tie
 // rule of signedmod.jl:12-19, n > Q_g ÷ 2 => n - Q_g; switch(ℛ_W, .) of bfv.jl:202-226 on the sub-ring of the group; with one limb
 // per group the digit of rlwe_she.jl:326-329), reduced into every working limb W = [0 .. level-1] ∪ [the k special primes].  The
 // key sums over W are contracted by modswitch (crt.jl:215-228, unsigned c_last) once per special prime, the last one first.
-// The bodies are TFHE_HD: tests/ks_group_emul, tests/ks_group_rot_emul and tests/mdg_lift_emul run them on the host.
+// The bodies are TFHE_HD: tests/ks_group_emul, tests/ks_group_rot_emul, tests/mdg_lift_emul and tests/mdg_fold_emul run them on the host.
 #pragma once
 #include <cstdio>
 
@@ -106,6 +107,65 @@ inline int ks_group_bsgs_check(bool any_null, int L, int64_t N, int Lk, int leve
     bool hit = bias && overlap(out, ct_bytes, bias, (uint64_t)level * (uint64_t)N * 8);
     for (int m = 0; m < n_in && !hit; m++)
         hit = overlap(out, ct_bytes, (uintptr_t)cts[m], ct_bytes) || overlap(out, ct_bytes, (uintptr_t)diags[m], diag_bytes);
+    if (hit) return snprintf(msg, cap, "out overlaps an operand"), TFHE_E_BADARG;
+    *nothing_to_do = batch == 0;
+    return TFHE_OK;
+}
+
+// The host checks of tfhe_rotate_sum_grouped (product = false: no baby or giant key, diags unused, cts = the one input, n_in = 1) and
+// tfhe_matmul_bsgs_fold_grouped in the order include/toyfhe_hip.h states, on plain numbers: any_null -- a null context or array; the
+// HOST arrays are read no further than a valid count reaches; fold_evks / fold_galois: all fold steps back to back, fold_sizes
+// [n_fold_steps]; bias / out -- addresses, compared and never followed (bias may be 0).  The fold's rules and messages are fold_check_host's
+// (md_api.inc).  *nothing_to_do comes back true where the call returns TFHE_OK without work (an empty batch).
+inline int ks_group_fold_check(bool product, bool any_null, int L, int64_t N, int Lk, int level, int k, int group, int n_digits, int64_t batch,
+                               const uint64_t* const* baby_evks, const uint64_t* baby_galois, int n_baby, const uint64_t* const* giant_evks,
+                               const uint64_t* giant_galois, int n_giant, const uint64_t* const* diags, const uint64_t* const* cts, int n_in,
+                               const uint64_t* const* fold_evks, const uint64_t* fold_galois, const int* fold_sizes, int n_fold_steps, uintptr_t bias,
+                               uintptr_t out, bool* nothing_to_do, char* msg, size_t cap, int max_n = 64) {
+    msg[0] = 0;
+    *nothing_to_do = false;
+    if (any_null) return snprintf(msg, cap, "null argument"), TFHE_E_BADARG;
+    if (n_fold_steps < 0 || n_fold_steps > max_n) return snprintf(msg, cap, "n_fold_groups=%d outside [0,%d]", n_fold_steps, max_n), TFHE_E_BADARG;
+    int n_fold = 0;
+    for (int t = 0; t < n_fold_steps; t++) {
+        if (fold_sizes[t] < 1) return snprintf(msg, cap, "fold group %d has size %d, below 1", t, fold_sizes[t]), TFHE_E_BADARG;
+        if (fold_sizes[t] > max_n || (n_fold += fold_sizes[t]) > max_n) return snprintf(msg, cap, "more than %d fold keys", max_n), TFHE_E_BADARG;
+    }
+    for (int r = 0; r < n_fold; r++)
+        if (!fold_evks[r]) return snprintf(msg, cap, "null fold key %d", r), TFHE_E_BADARG;
+    if (product) {
+        const auto within = [max_n](int n) { return n < 0 ? 0 : (n > max_n ? max_n : n); };
+        for (int r = 0; r < within(n_baby); r++)
+            if (!baby_evks[r]) return snprintf(msg, cap, "null baby key %d", r), TFHE_E_BADARG;
+        for (int r = 0; r < within(n_giant); r++)
+            if (!giant_evks[r]) return snprintf(msg, cap, "null giant key %d", r), TFHE_E_BADARG;
+        for (int m = 0; m < within(n_in); m++) {
+            if (!diags[m]) return snprintf(msg, cap, "null diagonals of input %d", m), TFHE_E_BADARG;
+            if (!cts[m]) return snprintf(msg, cap, "null ciphertext of input %d", m), TFHE_E_BADARG;
+        }
+        if (n_baby < 0 || n_baby > max_n) return snprintf(msg, cap, "n_baby=%d outside [0,%d]", n_baby, max_n), TFHE_E_BADARG;
+        if (n_giant < 0 || n_giant > max_n) return snprintf(msg, cap, "n_giant=%d outside [0,%d]", n_giant, max_n), TFHE_E_BADARG;
+        if (n_in < 1 || n_in > max_n) return snprintf(msg, cap, "n_in=%d outside [1,%d]", n_in, max_n), TFHE_E_BADARG;
+    } else {
+        n_baby = n_giant = 0;
+        n_in = 1;
+    }
+    for (int r = 0; r < n_baby + n_giant + n_fold; r++) {
+        const uint64_t g = r < n_baby ? baby_galois[r] : (r < n_baby + n_giant ? giant_galois[r - n_baby] : fold_galois[r - n_baby - n_giant]);
+        const int rc = ks_group_check(false, L, N, Lk, level, k, group, n_digits, 2, batch, true, g, msg, cap);
+        if (rc) return rc;
+    }
+    if (n_baby + n_giant + n_fold == 0) {
+        const int rc = ks_group_check(false, L, N, Lk, level, k, group, n_digits, 2, batch, false, 0, msg, cap);
+        if (rc) return rc;
+    }
+    // the last step writes `out` while other workgroups still read the operands (of the next chunk)
+    const uint64_t ct_bytes = (uint64_t)batch * 2 * level * (uint64_t)N * 8;
+    const uint64_t diag_bytes = (uint64_t)(n_giant + 1) * (n_baby + 1) * level * (uint64_t)N * 8;
+    const auto overlap = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a == b || (a < b + nb && b < a + na); };
+    bool hit = bias && overlap(out, ct_bytes, bias, (uint64_t)level * (uint64_t)N * 8);
+    for (int m = 0; m < n_in && !hit; m++)
+        hit = overlap(out, ct_bytes, (uintptr_t)cts[m], ct_bytes) || (product && overlap(out, ct_bytes, (uintptr_t)diags[m], diag_bytes));
     if (hit) return snprintf(msg, cap, "out overlaps an operand"), TFHE_E_BADARG;
     *nothing_to_do = batch == 0;
     return TFHE_OK;
@@ -234,6 +294,24 @@ TFHE_HD void mdg_lift_coeff(const u64* p, u64* u, size_t n, int level, const bar
     ks_group_tail_special<K>(y, lb + level, inv, level);
     for (int j = 0; j < level; j++) u[(size_t)j * n] = mdg_lift_limb<K>(y, lb[j], inv, j);
 }
+
+// ---- one fold step in the evaluation domain (mdg_fold_run, md_api.inc) ---------------------------------------------------------------
+// In a fold step every rotation has the coefficient 1 and the step ends in an inverse transform, so the lifts never enter the
+// evaluation domain:   F + sum_r rotate_grouped(gk_r, F) = INTT( X + sum_r V_r o pi_r ) - sum_r mdg_lift_limb(y_r),   X = NTT(F).
+// The gather adds one permuted key-sum word to the running sum of a position (k_mdg_fold_gather); the finish takes, per coefficient
+// and rotation, the K special words through the triangular steps and the lift of every limb of a block off the block's words.
+// One rotation's share of one coefficient: y -- its K special words (the "lasts" on return), acc -- the words of limbs j0 .. j0 + nj - 1
+// (nj <= JB), which lose the limb's lift.  lb: the nw working limbs' Barrett words, the special primes last.
+template <int K, int JB>
+TFHE_HD void mdg_fold_finish_coeff(u64 (&acc)[JB], u64 (&y)[K], int j0, int nj, int level, const barrett_t* lb, const tw_t (*inv)[TFHE_MAX_LIMBS]) {
+    ks_group_tail_special<K>(y, lb + level, inv, level);
+#pragma unroll
+    for (int r = 0; r < JB; r++)
+        if (r < nj) acc[r] = submod(acc[r], mdg_lift_limb<K>(y, lb[j0 + r], inv, j0 + r), lb[j0 + r].q);
+}
+#ifndef TFHE_MDG_FOLD_JB
+#define TFHE_MDG_FOLD_JB 6   // limbs of a block: level 6 is one block; 2 JB accumulator and 2 K special words live at V = 2 (8: scratch at K = 4)
+#endif
 
 #if defined(__HIPCC__)
 struct ks_group_arg_t {
@@ -520,6 +598,146 @@ __global__ __launch_bounds__(256) void k_mdg_lift(const u64* __restrict__ PB, u6
         }
     } else {
         mdg_lift_coeff<K>(p, u, n, (int)level, lb, linv);
+    }
+}
+// ---- one fold step of tfhe_rotate_sum_grouped / tfhe_matmul_bsgs_fold_grouped in the evaluation domain (mdg_fold_run, md_api.inc) -------
+// E[b][s][j][k] = X[b][s][j][k] + sum_{r < nrot} V[(r batch + b)][j][pi_r k].{s}: k_md_fold without the U stream and its factor -- the
+// lifts are taken off after the inverse transform of E (k_mdg_fold_finish).  k_md_fold's walk, for its reasons: one XCD takes the row
+// pair (b, 0, j), (b, 1, j) at a time, so that the two V windows of one rotation stay in one L2; teams for small rows; TFHE_MD_KB
+// coefficients per thread; both components of a position from one 16-byte gather (epi_pair); rotation t + 1 requested before rotation
+// t is added.  X, E: [batch][2][level][N], NTT domain; E may not be X.  grid: 8 * TFHE_MD_SLOTS.
+__global__ __launch_bounds__(256) void k_mdg_fold_gather(const u64* __restrict__ X, const u64* __restrict__ V, u64* __restrict__ E,
+                                                          const ntt_limb_t* __restrict__ LT, limb_sel_t sel, rot_tail_arg_t G, u32 n, u32 nw,
+                                                          u32 nrot, u32 batch) {
+    constexpr int KB = TFHE_MD_KB;
+    const u32 level = (u32)sel.n;
+    const u32 xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
+    const u32 per = blockDim.x * KB, spt = n / per >= nslot ? nslot : (n / per ? n / per : 1u), teams = nslot / spt, team = slot / spt, ts = slot % spt;
+    if (team >= teams) return;
+    const u32 stride = spt * blockDim.x;
+    struct term_t { u64 v0[KB], v1[KB]; };
+    for (u32 pr = team * 8u + xcd; pr < batch * level; pr += 8u * teams) {
+        const u32 j = pr % level, b = pr / level;
+        const u64 q = LT[sel.idx[j]].q;
+        const size_t row0 = ((size_t)b * 2 * level + j) * n, row1 = row0 + (size_t)level * n;
+        for (u32 kb = ts * blockDim.x + threadIdx.x; kb < n; kb += stride * KB) {
+            u32 k[KB];
+#pragma unroll
+            for (int i = 0; i < KB; i++) k[i] = kb + (u32)i * stride < n ? kb + (u32)i * stride : kb;   // (a clamped lane repeats kb; not stored)
+            auto fetch = [&](u32 t, term_t& T) {
+                const u64 g = G.g[t];
+                const u64x2_t* pv = (const u64x2_t*)(V + epi_pair(t * batch + b, j, 0u, nw, n));   // both components of a position: one gather
+#pragma unroll
+                for (int i = 0; i < KB; i++) {
+                    const u64x2_t vv = pv[galois_ntt_pos(k[i], g, n)];
+                    T.v0[i] = vv.x; T.v1[i] = vv.y;
+                }
+            };
+            u64 a0[KB], a1[KB];
+#pragma unroll
+            for (int i = 0; i < KB; i++) { a0[i] = X[row0 + k[i]]; a1[i] = X[row1 + k[i]]; }
+            term_t cur;
+            fetch(0, cur);
+            for (u32 t = 0; t < nrot; t++) {
+                term_t nxt;
+                fetch(t + 1 < nrot ? t + 1 : t, nxt);
+#pragma unroll
+                for (int i = 0; i < KB; i++) {
+                    a0[i] = addmod(a0[i], cur.v0[i], q);
+                    a1[i] = addmod(a1[i], cur.v1[i], q);
+                }
+                cur = nxt;
+            }
+#pragma unroll
+            for (int i = 0; i < KB; i++) {
+                if (kb + (u32)i * stride < n) {
+                    E[row0 + k[i]] = a0[i];
+                    E[row1 + k[i]] = a1[i];
+                }
+            }
+        }
+    }
+}
+// dst[b][s][j] = E[b][s][j] - sum_{r < nrot} mdg_lift_limb(y_r)[j] (+ bias[j] for s = 0): E the inverse-transformed sum of
+// k_mdg_fold_gather, y_r the "lasts" of the K inverse-transformed special rows PB[(r batch + b) 2 + s][t] (coefficient domain, canonical).
+// A stream per (ciphertext, component): K nrot + level rows in (the special rows once per block of TFHE_MDG_FOLD_JB limbs), level rows
+// out; V coefficients per thread (V = 2: 16-byte loads and stores, k_mdg_lift's alignment rule); the block's words stay in registers
+// while the rotations go by, the block's E rows requested before the first special word is used; the constants sit in LDS, as in
+// k_mdg_lift.  bias: null, or [level][N].  grid: batch * 2 * gx workgroups, gx = ceil(N / (256 V)).
+template <int K, int V>
+__global__ __launch_bounds__(256) void k_mdg_fold_finish(const u64* __restrict__ PB, const u64* __restrict__ E, const u64* __restrict__ bias,
+                                                          u64* __restrict__ dst, const ntt_limb_t* __restrict__ LT, ks_group_arg_t A, u32 n, u32 gx,
+                                                          u32 nrot, u32 batch) {
+    constexpr int JB = TFHE_MDG_FOLD_JB;
+    __shared__ barrett_t lb[TFHE_MAX_LIMBS];
+    __shared__ tw_t linv[K][TFHE_MAX_LIMBS];
+    const u32 level = (u32)A.level, nw = (u32)A.nw;
+    for (u32 j = threadIdx.x; j < nw; j += blockDim.x) {
+        lb[j] = LT[A.w.idx[j]].br;
+#pragma unroll
+        for (int t = 0; t < K; t++) linv[t][j] = A.inv[t][j];
+    }
+    __syncthreads();
+    const u32 i = ((blockIdx.x % gx) * 256 + threadIdx.x) * (u32)V;
+    const size_t grp = blockIdx.x / gx;   // b * 2 + s
+    if (i >= n) return;
+    const u64* p = PB + grp * K * n + i;
+    const size_t rstride = (size_t)batch * 2 * K * n;   // one rotation's special rows
+    const u64* e = E + grp * level * n + i;
+    u64* o = dst + grp * level * n + i;
+    const u64* bs = bias != nullptr && (grp & 1u) == 0 ? bias + i : nullptr;
+    const auto ld = [](const u64* q, u64 (&w)[V]) {
+        if constexpr (V == 2) {
+            const u64x2_t x = *(const u64x2_t*)q;
+            w[0] = x.x; w[1] = x.y;
+        } else {
+            w[0] = *q;
+        }
+    };
+    for (u32 j0 = 0; j0 < level; j0 += JB) {
+        const int nj = (int)(level - j0 < (u32)JB ? level - j0 : (u32)JB);
+        u64 acc[V][JB];
+#pragma unroll
+        for (int r = 0; r < JB; r++) {
+            u64 w[V];
+            ld(e + (size_t)(j0 + (u32)(r < nj ? r : nj - 1)) * n, w);   // past the end: the spare registers repeat the last row, unused
+#pragma unroll
+            for (int v = 0; v < V; v++) acc[v][r] = w[v];
+        }
+        for (u32 r = 0; r < nrot; r++) {
+            u64 y[V][K];
+#pragma unroll
+            for (int t = 0; t < K; t++) {
+                u64 w[V];
+                ld(p + (size_t)r * rstride + (size_t)t * n, w);
+#pragma unroll
+                for (int v = 0; v < V; v++) y[v][t] = w[v];
+            }
+#pragma unroll
+            for (int v = 0; v < V; v++) mdg_fold_finish_coeff<K, JB>(acc[v], y[v], (int)j0, nj, (int)level, lb, linv);
+        }
+#pragma unroll
+        for (int r = 0; r < JB; r++) {
+            if (r < nj) {
+                const u32 j = j0 + (u32)r;
+                u64 res[V];
+#pragma unroll
+                for (int v = 0; v < V; v++) res[v] = acc[v][r];
+                if (bs) {
+                    u64 w[V];
+                    ld(bs + (size_t)j * n, w);
+#pragma unroll
+                    for (int v = 0; v < V; v++) res[v] = addmod(res[v], w[v], lb[j].q);
+                }
+                if constexpr (V == 2) {
+                    u64x2_t w;
+                    w.x = res[0]; w.y = res[1];
+                    *(u64x2_t*)(o + (size_t)j * n) = w;
+                } else {
+                    o[(size_t)j * n] = res[0];
+                }
+            }
+        }
     }
 }
 #endif  // __HIPCC__

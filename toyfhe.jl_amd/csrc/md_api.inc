@@ -3,7 +3,8 @@
 // workspace, the fold (md_fold_plan, md_fold_run) and the five entry points; included by toyfhe_hip.hip after ks_api.inc, whose key-sum, digit and
 // rotation helpers (ks_digits_fwd, ks_inner_launch, keyswitch_impl, ks_rot_prepared_bytes) it calls.  Kernels: kernels.h k_md_*.
 // At the end: the same rotation phase on grouped-digit keys (mdg_plan, mdg_bufs, mdg_rotations; kernels ks_group_core.h k_mdg_*) with its
-// two entry points, tfhe_matmul_diag_grouped and tfhe_matmul_bsgs_grouped, on the hoisting helpers of ks_api.inc (ksg_*).
+// entry points tfhe_matmul_diag_grouped and tfhe_matmul_bsgs_grouped, and the fold on such keys (mdg_fold_plan, mdg_fold_run; kernels
+// k_mdg_fold_gather, k_mdg_fold_finish) with tfhe_rotate_sum_grouped and tfhe_matmul_bsgs_fold_grouped, on the hoisting helpers of ks_api.inc (ksg_*).
 
 // tfhe_matmul_diag, evaluation-domain form: U[grp][j] = NTT_j( [P[grp]] mod q_j ) (x P^-1 unless *scaled comes back false) for
 // the `groups` special-limb rows P (coefficient domain, canonical) and the limbs j of `sl`.  At N = 2^16 the lift rides on the
@@ -760,6 +761,106 @@ int tfhe_matmul_diag_grouped(tfhe_ctx* c, int key_limbs, int level, int n_specia
     return TFHE_OK;
 }
 
+// ---- the rotate-and-sum fold on grouped-digit keys ----------------------------------------------------------------------------------
+// md_fold_t / md_fold_plan / md_fold_run for grouped keys: one mdg_plan_t per fold step with R = the step's size.  One step over a chunk,
+//   evaluation route (K >= 1, TFHE_MDG_FOLD_EVAL=1):  X = NTT(F), the digits, V = the key sums with the Pinv epilogue, the permuted special limbs and their K
+//                          inverse transforms as in mdg_rotations; then k_mdg_fold_gather writes E = X + sum_r V_r o pi_r into the
+//                          step's ROT region (which this route does not otherwise use: R 2 level >= 2 level rows), ONE inverse
+//                          transform of E, and k_mdg_fold_finish takes the lifts off in the coefficient domain, adds the bias in
+//                          the last step and writes the step's result: no k_mdg_lift, no forward transform of a lift, no bias pass.
+//                          Per ciphertext and step d nw + 2 level forward and R 2 K + 2 level inverse rows.
+//   coefficient route (the default -- see mdg_fold_eval; K = 0 and TFHE_MD_COEFF=1 know no other):  the digits, ksg_hoist_tile into ROT in the
+//                          coefficient domain, k_bsgs_sum (+ bias in the last step).  d nw forward and R 2 nw inverse rows.
+// Exact arithmetic on canonical residues, NTT_j linear: the words of tfhe_rotate_many_grouped over the step's keys -> tfhe_add, step by step.
+// Which route a fold step takes where both exist.  Measured (profiles/matmul_rect_grouped_bench.txt, profiles/LOG.md): the evaluation
+// route is ahead in steps of three keys (fold radix 4) and behind in steps of one key (radix 2: at R = 1 it transforms MORE rows,
+// d nw + 2 level + 2 K + 2 level against d nw + 2 nw), so it did not win at every measured shape and the coefficient route is the
+// default.  TFHE_MDG_FOLD_EVAL=1 asks for the evaluation route (read once per process); TFHE_MD_COEFF=1 wins over it.
+static bool mdg_fold_eval(int k) {
+    static const bool md_coeff = env_flag("TFHE_MD_COEFF", false);
+    static const bool fold_eval = env_flag("TFHE_MDG_FOLD_EVAL", false);
+    return k >= 1 && !md_coeff && fold_eval;
+}
+struct mdg_fold_t {
+    const uint64_t* const* evks;   // all steps back to back
+    const uint64_t* galois;
+    const int* sizes;
+    int n_steps;
+    std::vector<mdg_plan_t> plans; // one per step
+    size_t rows = 0, ntt_rows = 0; // the largest step's (mdg_plan_t)
+};
+static int mdg_fold_plan(tfhe_ctx* c, int Lk, int level, int k, int group, const uint64_t* const* evks, const uint64_t* galois, const int* sizes,
+                         int n_steps, mdg_fold_t* F) {
+    *F = mdg_fold_t{evks, galois, sizes, n_steps, {}, 0, 0};
+    F->plans.resize((size_t)n_steps);
+    for (int t = 0, off = 0; t < n_steps; off += sizes[t], t++) {
+        mdg_plan_t& P = F->plans[(size_t)t];
+        const int rc = mdg_plan(c, Lk, level, k, group, galois + off, sizes[t], false, &P);
+        if (rc) return rc;
+        P.eval_form = mdg_fold_eval(k);
+        F->rows = std::max(F->rows, P.L.rows_per_ct());
+        F->ntt_rows = std::max(F->ntt_rows, P.ntt_rows);
+    }
+    return TFHE_OK;
+}
+// All steps over one chunk.  `in`: F_0, [nb][2][level][N]; it may be FB[1] (step t reads FB[(t - 1) & 1] and writes FB[t & 1]), the
+// last step writes `out` (+ bias on component 0).  `base`: F.rows rows per ciphertext of the chunk, laid out per step (mdg_bufs).
+static int mdg_fold_run(tfhe_ctx* c, const mdg_fold_t& F, u64* base, int64_t chunk, u64* const FB[2], const u64* in, int64_t nb, const u64* bias,
+                        u64* out) {
+    const size_t N = (size_t)c->N;
+    const u32 n = (u32)N;
+    const u64* src = in;
+    for (int t = 0, off = 0; t < F.n_steps; off += F.sizes[t], t++) {
+        const mdg_plan_t& P = F.plans[(size_t)t];
+        const mdg_bufs_t B = mdg_bufs(P, base, chunk);
+        const bool last = t + 1 == F.n_steps;
+        const int level = P.level, R = P.R;
+        const size_t ct_words = (size_t)nb * 2 * level * N;
+        u64* const dst = last ? out : FB[t & 1];
+        const u64* const bs = last ? bias : (const u64*)nullptr;
+        int rc;
+        if (P.eval_form) {
+            rc = run_ntt(c, false, src, B.X, nb * 2 * level, P.sl);
+            if (rc) return rc;
+        }
+        rc = ksg_digits_fwd(c, P.H.P, src, B.dig, nb, N % 2 == 0 && ((uintptr_t)src & 15u) == 0);
+        if (rc) return rc;
+        if (P.eval_form) {
+            const int64_t groups = (int64_t)R * nb * 2;
+            rc = ks_inner_launch(c, P.A, P.Lk, nullptr, B.dig, B.S, nb, F.evks + off, R, B.X, level);   // limbs j < level leave as V = S' Pinv + X0 [s = 0]
+            if (rc) return rc;
+            rc = launch(c, k_mdg_special_perm, dim3(8 * TFHE_ROT_TAIL_SLOTS), dim3(256), 0, (const u64*)B.S, B.PB, P.G, n, (u32)P.nw, (u32)level,
+                        (u32)P.K, (u32)nb, (u32)groups);
+            if (rc) return rc;
+            rc = run_ntt(c, true, B.PB, B.PB, groups * P.K, P.sp);
+            if (rc) return rc;
+            u64* const E = B.ROT;
+            rc = launch(c, k_mdg_fold_gather, dim3(8 * TFHE_MD_SLOTS), dim3(256), 0, (const u64*)B.X, (const u64*)B.S, E, c->limbs_dev, P.sl, P.G, n,
+                        (u32)P.nw, (u32)R, (u32)nb);
+            if (rc) return rc;
+            rc = run_ntt(c, true, E, E, nb * 2 * level, P.sl);
+            if (rc) return rc;
+            const bool v2 = N % 2 == 0 && (((uintptr_t)B.PB | (uintptr_t)E | (uintptr_t)dst | (uintptr_t)bs) & 15u) == 0;
+            const u32 gx = v2 ? (n / 2 + 255) / 256 : (n + 255) / 256;
+            rc = dispatch_int<1, TFHE_KSG_MAX_SPECIAL>(P.K, [&](auto kc) {
+                constexpr int K = decltype(kc)::value;
+                auto finish = v2 ? k_mdg_fold_finish<K, 2> : k_mdg_fold_finish<K, 1>;
+                return launch(c, finish, dim3((unsigned)(nb * 2 * gx)), dim3(256), 0, (const u64*)B.PB, (const u64*)E, bs, dst, c->limbs_dev, P.H.P.G, n,
+                              gx, (u32)R, (u32)nb);
+            });
+            if (rc) return rc;
+        } else {
+            rc = ksg_hoist_tile(c, P.H, F.evks + off, P.G.g, R, src, nb, B.dig, B.S, B.ROT, ct_words);
+            if (rc) return rc;
+            rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, src, (const u64*)B.ROT, dst, c->limbs_dev, P.sl, n, (u32)R,
+                        ct_words, bs);
+            if (rc) return rc;
+        }
+        src = dst;
+    }
+    return TFHE_OK;
+}
+
 // ---- the product by baby and giant steps on grouped-digit keys -------------------------------------------------------------------
 // tfhe_matmul_bsgs_blocks on prepared grouped Galois keys, with matmul_bsgs_run's structure and its one borrowed block:
 //     inner_j = sum_m sum_{i = 0 .. n_baby} diags[m][j][i] (.) NTT(r_i(cts[m]))            mdg_rotations + mdg_accumulate per input (seeded after the first)
@@ -768,34 +869,30 @@ int tfhe_matmul_diag_grouped(tfhe_ctx* c, int key_limbs, int level, int n_specia
 // INNER_j, ksg_hoist_tile into GOUT_j -- in the digit and key-sum regions of the baby phase, which is over by then (one stream, in
 // order), so no nested workspace.  k_bsgs_sum adds up.  The words of tfhe_rotate_many_grouped -> tfhe_nntt -> tfhe_dot -> tfhe_inntt ->
 // tfhe_rotate_grouped -> tfhe_add.
-// workspace: [ region 0: transform scratch | the baby phase (mdg_bufs) | inner sums [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] ]
-int tfhe_matmul_bsgs_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* baby_evks,
-                             const uint64_t* baby_galois, int n_baby, const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant,
-                             int n_digits, const uint64_t* const* diags, const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out,
-                             int64_t batch) {
-    bool nothing = false;
-    {
-        char msg[160];
-        const int rc = ks_group_bsgs_check(!c || !baby_evks || !baby_galois || !giant_evks || !giant_galois || !diags || !cts || !out, c ? c->L : 0,
-                                           c ? c->N : 0, key_limbs, level, n_special, group, n_digits, batch, baby_evks, baby_galois, n_baby, giant_evks,
-                                           giant_galois, n_giant, diags, cts, n_in, (uintptr_t)bias, (uintptr_t)out, &nothing, msg, sizeof msg,
-                                           TFHE_DOT_MAX);
-        if (rc) return fail(rc, "%s", msg);
-    }
-    if (nothing) return TFHE_OK;
-    const int Lk = key_limbs, ng1 = n_giant + 1;
+// With fold steps (tfhe_matmul_bsgs_fold_grouped) the closing sum writes F_0 into FB[1] without the bias, the steps ping-pong FB[0] / FB[1]
+// (mdg_fold_run, in the phase region: the baby phase of the chunk is over) and the last step writes `out`, with the bias.
+// workspace: [ region 0: transform scratch | the baby phase (mdg_bufs) or the largest fold step's, whichever is larger | inner sums
+//              [ng1][chunk][2][level][N] | giant results [n_giant][chunk][2][level][N] (| F [2][chunk][2][level][N] with fold steps) ]
+static int matmul_bsgs_grouped_run(tfhe_ctx* c, int Lk, int level, int n_special, int group, const uint64_t* const* baby_evks,
+                                   const uint64_t* baby_galois, int n_baby, const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant,
+                                   const uint64_t* const* diags, const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out,
+                                   int64_t batch, const mdg_fold_t* fold = nullptr) {
+    const int ng1 = n_giant + 1;
     mdg_plan_t P;
     int rc = mdg_plan(c, Lk, level, n_special, group, baby_galois, n_baby, n_giant > 0, &P);
     if (rc) return rc;
-    const size_t N = (size_t)c->N;
+    const size_t N = (size_t)c->N, ct_rows = (size_t)2 * level;
     ws_layout_t L(N);
-    L.scratch(std::max(P.ntt_rows, (size_t)ng1 * 2 * level));
-    const ws_region_t phase = L.rows(P.L.rows_per_ct()), inner = L.rows((size_t)ng1 * 2 * level), gout = L.rows((size_t)n_giant * 2 * level);
+    L.scratch(std::max({P.ntt_rows, (size_t)ng1 * ct_rows, fold ? fold->ntt_rows : (size_t)0}));
+    const ws_region_t phase = L.rows(std::max(P.L.rows_per_ct(), fold ? fold->rows : (size_t)0));
+    const ws_region_t inner = L.rows((size_t)ng1 * ct_rows), gout = L.rows((size_t)n_giant * ct_rows);
+    const ws_region_t f0 = L.rows(fold ? ct_rows : 0), f1 = L.rows(fold ? ct_rows : 0);
     const md_ws_t W(c, batch, L);
     if (W.rc) return W.rc;
     const int64_t chunk = W.chunk;
     const mdg_bufs_t B = mdg_bufs(P, W.at(phase), chunk);
     u64 *const INNER = W.at(inner), *const GOUT = W.at(gout);
+    u64* const FB[2] = {W.at(f0), W.at(f1)};
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t nb = std::min(chunk, batch - b0);
         const size_t ct_words = (size_t)nb * 2 * level * N;   // one inner sum / one giant result of this chunk
@@ -814,10 +911,102 @@ int tfhe_matmul_bsgs_grouped(tfhe_ctx* c, int key_limbs, int level, int n_specia
             rc = ksg_hoist_tile(c, P.H, giant_evks + (j - 1), giant_galois + (j - 1), 1, src, nb, B.dig, B.S, GOUT + (size_t)(j - 1) * ct_words, ct_words);
             if (rc) return rc;
         }
-        rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)INNER, (const u64*)GOUT,
-                    out + (size_t)b0 * 2 * level * N, c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words, bias);
+        u64* const o = out + (size_t)b0 * 2 * level * N;
+        rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, (const u64*)INNER, (const u64*)GOUT, fold ? FB[1] : o,
+                    c->limbs_dev, P.sl, (u32)N, (u32)n_giant, ct_words, fold ? (const u64*)nullptr : bias);
+        if (rc) return rc;
+        if (fold) {
+            rc = mdg_fold_run(c, *fold, W.at(phase), chunk, FB, FB[1], nb, bias, o);
+            if (rc) return rc;
+        }
+    }
+    return TFHE_OK;
+}
+int tfhe_matmul_bsgs_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* baby_evks,
+                             const uint64_t* baby_galois, int n_baby, const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant,
+                             int n_digits, const uint64_t* const* diags, const uint64_t* const* cts, int n_in, const uint64_t* bias, uint64_t* out,
+                             int64_t batch) {
+    bool nothing = false;
+    {
+        char msg[160];
+        const int rc = ks_group_bsgs_check(!c || !baby_evks || !baby_galois || !giant_evks || !giant_galois || !diags || !cts || !out, c ? c->L : 0,
+                                           c ? c->N : 0, key_limbs, level, n_special, group, n_digits, batch, baby_evks, baby_galois, n_baby, giant_evks,
+                                           giant_galois, n_giant, diags, cts, n_in, (uintptr_t)bias, (uintptr_t)out, &nothing, msg, sizeof msg,
+                                           TFHE_DOT_MAX);
+        if (rc) return fail(rc, "%s", msg);
+    }
+    if (nothing) return TFHE_OK;
+    return matmul_bsgs_grouped_run(c, key_limbs, level, n_special, group, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags, cts,
+                                   n_in, bias, out, batch);
+}
+
+// ---- rotate-and-sum and the rectangular product on grouped-digit keys ------------------------------------------------------------
+// tfhe_rotate_sum / tfhe_matmul_bsgs_fold with every rotation a tfhe_rotate_grouped (mdg_fold_plan, mdg_fold_run).
+// workspace of tfhe_rotate_sum_grouped: [ region 0: transform scratch | the largest fold step (mdg_bufs) | two ping-pong ciphertext buffers F ]
+int tfhe_rotate_sum_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* evks,
+                            const uint64_t* galois_elements, const int* group_sizes, int n_groups, int n_digits, const uint64_t* ct, uint64_t* out,
+                            int64_t batch) {
+    bool nothing = false;
+    {
+        char msg[160];
+        const int rc = ks_group_fold_check(false, !c || !evks || !galois_elements || !group_sizes || !ct || !out, c ? c->L : 0, c ? c->N : 0, key_limbs,
+                                           level, n_special, group, n_digits, batch, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, &ct, 1, evks,
+                                           galois_elements, group_sizes, n_groups, 0, (uintptr_t)out, &nothing, msg, sizeof msg, TFHE_DOT_MAX);
+        if (rc) return fail(rc, "%s", msg);
+    }
+    if (nothing) return TFHE_OK;
+    const size_t N = (size_t)c->N, ct_words = (size_t)2 * level * N;
+    int rc;
+    if (n_groups == 0) {   // out = ct
+        const limb_sel_t sl = first_limbs(level);
+        for (int64_t b0 = 0; b0 < batch; b0 += 0x10000) {   // (the row count of one launch stays far below 2^31)
+            const int64_t nb = std::min<int64_t>(0x10000, batch - b0);
+            const u64* s = ct + (size_t)b0 * ct_words;
+            rc = launch(c, k_bsgs_sum, row_grid((unsigned)(nb * 2 * level), N), dim3(256), 0, s, s, out + (size_t)b0 * ct_words, c->limbs_dev, sl, (u32)N,
+                        0u, (size_t)0, (const u64*)nullptr);
+            if (rc) return rc;
+        }
+        return TFHE_OK;
+    }
+    mdg_fold_t F;
+    rc = mdg_fold_plan(c, key_limbs, level, n_special, group, evks, galois_elements, group_sizes, n_groups, &F);
+    if (rc) return rc;
+    ws_layout_t L(N);
+    L.scratch(F.ntt_rows);
+    const ws_region_t phase = L.rows(F.rows), f0 = L.rows((size_t)2 * level), f1 = L.rows((size_t)2 * level);
+    const md_ws_t W(c, batch, L);
+    if (W.rc) return W.rc;
+    const int64_t chunk = W.chunk;
+    u64* const FB[2] = {W.at(f0), W.at(f1)};
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t nb = std::min(chunk, batch - b0);
+        rc = mdg_fold_run(c, F, W.at(phase), chunk, FB, ct + (size_t)b0 * ct_words, nb, nullptr, out + (size_t)b0 * ct_words);
         if (rc) return rc;
     }
     return TFHE_OK;
 }
-
+int tfhe_matmul_bsgs_fold_grouped(tfhe_ctx* c, int key_limbs, int level, int n_special, int group, const uint64_t* const* baby_evks,
+                                  const uint64_t* baby_galois, int n_baby, const uint64_t* const* giant_evks, const uint64_t* giant_galois, int n_giant,
+                                  int n_digits, const uint64_t* const* diags, const uint64_t* const* cts, int n_in, const uint64_t* const* fold_evks,
+                                  const uint64_t* fold_galois, const int* fold_group_sizes, int n_fold_groups, const uint64_t* bias, uint64_t* out,
+                                  int64_t batch) {
+    bool nothing = false;
+    {
+        char msg[160];
+        const int rc = ks_group_fold_check(true, !c || !baby_evks || !baby_galois || !giant_evks || !giant_galois || !diags || !cts || !fold_evks ||
+                                                     !fold_galois || !fold_group_sizes || !out,
+                                           c ? c->L : 0, c ? c->N : 0, key_limbs, level, n_special, group, n_digits, batch, baby_evks, baby_galois, n_baby,
+                                           giant_evks, giant_galois, n_giant, diags, cts, n_in, fold_evks, fold_galois, fold_group_sizes, n_fold_groups,
+                                           (uintptr_t)bias, (uintptr_t)out, &nothing, msg, sizeof msg, TFHE_DOT_MAX);
+        if (rc) return fail(rc, "%s", msg);
+    }
+    if (nothing) return TFHE_OK;
+    if (n_fold_groups == 0)
+        return matmul_bsgs_grouped_run(c, key_limbs, level, n_special, group, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags,
+                                       cts, n_in, bias, out, batch);
+    mdg_fold_t F;
+    const int rc = mdg_fold_plan(c, key_limbs, level, n_special, group, fold_evks, fold_galois, fold_group_sizes, n_fold_groups, &F);
+    if (rc) return rc;
+    return matmul_bsgs_grouped_run(c, key_limbs, level, n_special, group, baby_evks, baby_galois, n_baby, giant_evks, giant_galois, n_giant, diags, cts,
+                                   n_in, bias, out, batch, &F);
+}

@@ -798,6 +798,66 @@ function matmul_bsgs_fold(baby::Vector{<:ToyFHE.GaloisKey}, giant::Vector{<:ToyF
                 dptrs, cptrs, nin, fkeys, fgs, sizes, length(folds), bptr, out.ptr, cnt))
     CipherText{squared_encoding(Enc)}(cs[1].params, unpack(ctx, out, ℛ, 2))
 end
+# Rotate and sum on grouped-digit keys in one device call (tfhe_rotate_sum_grouped): rotate_sum with every rotation a rotate_grouped.
+# (Not executed anywhere yet: the tests check the ccall against the header.)
+function rotate_sum_grouped(steps::Vector{<:Vector{<:ToyFHE.GaloisKey}}, c::CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}},
+                            n_special::Integer, group::Integer) where {Enc,P,ℛ,T}
+    @assert length(c.cs) == 2 && !isempty(steps) && all(g -> !isempty(g), steps)
+    gks = ToyFHE.GaloisKey[gk for g in steps for gk in g]
+    length(gks) <= 64 || throw(ToyFHE.UsageError("rotate_sum_grouped: at most 64 fold keys per call (TFHE_DOT_MAX)"))
+    ek1 = gks[1].key; keyring = NTT.ring(ek1.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T); cnt = batchsize(c)
+    ctx = hipring(keyring); ct = pack(ctx, c); n = degree(ℛ)
+    packed = HipVector[prepared(gk) for gk in gks]; out = HipVector{T}(2 * level, n, cnt); on(ctx, (out,), (ct, packed...))   # PREPARED keys only
+    keys = Ptr{UInt64}[k.ptr for k in packed]; gs = UInt64[gk.galois_element for gk in gks]; sizes = Cint[length(g) for g in steps]
+    GC.@preserve packed ct out check(ccall((:tfhe_rotate_sum_grouped, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Ptr{Cint}, Cint, Cint, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, n_special, group, keys, gs, sizes, length(steps), length(ek1.key),
+                ct.ptr, out.ptr, cnt))
+    CipherText{Enc}(c.params, unpack(ctx, out, ℛ, 2))
+end
+# The product of a rectangular matrix on grouped-digit keys in one device call (tfhe_matmul_bsgs_fold_grouped): the operands of
+# matmul_bsgs_fold, every rotation a rotate_grouped.  (Not executed anywhere yet: the tests check the ccall against the header.)
+function matmul_bsgs_fold_grouped(baby::Vector{<:ToyFHE.GaloisKey}, giant::Vector{<:ToyFHE.GaloisKey},
+                                  diags::Vector{<:Vector{<:Vector{<:RingElement{ℛ,T,<:HipVector}}}},
+                                  cs::Vector{<:CipherText{Enc,P,<:RingElement{ℛ,T,<:HipVector}}},
+                                  folds::Vector{<:Vector{<:ToyFHE.GaloisKey}}, n_special::Integer, group::Integer, bias=nothing) where {Enc,P,ℛ,T}
+    nin = length(cs); nb = length(baby); ng = length(giant)
+    @assert 1 <= nin <= 64 && length(diags) == nin && all(c -> length(c.cs) == 2, cs) && all(g -> !isempty(g), folds)
+    @assert all(m -> length(m) == ng + 1 && all(r -> length(r) == nb + 1, m), diags)
+    fold = ToyFHE.GaloisKey[gk for g in folds for gk in g]
+    max(nb, ng, length(fold)) <= 64 || throw(ToyFHE.UsageError("matmul_bsgs_fold_grouped: at most 64 baby, 64 giant and 64 fold keys per call (TFHE_DOT_MAX)"))
+    isempty(baby) && isempty(giant) && isempty(fold) && throw(ToyFHE.UsageError("matmul_bsgs_fold_grouped: no Galois key at all -- plain products, use .* and +"))
+    ek1 = (isempty(baby) ? (isempty(giant) ? fold[1] : giant[1]) : baby[1]).key
+    keyring = NTT.ring(ek1.key[1].mask); Lk = nlimbs(eltype(keyring)); level = nlimbs(T)
+    cnt = batchsize(cs[1]); ctx = hipring(keyring); n = degree(ℛ)
+    cts = HipVector[pack(ctx, c) for c in cs]
+    pb = HipVector[prepared(gk) for gk in baby]; pg = HipVector[prepared(gk) for gk in giant]; pf = HipVector[prepared(gk) for gk in fold]
+    dgs = HipVector[]
+    for m in diags                                                              # one [ng + 1][nb + 1][level][N] per input
+        dparts = HipVector[coeffs_dual(d).parent for row in m for d in row]
+        all(d -> d.count == 1, dparts) || throw(ToyFHE.UsageError("matmul_bsgs_fold_grouped: one polynomial per diagonal"))
+        dg = HipVector{T}(level, n, (ng + 1) * (nb + 1)); on(ctx, (dg,), (dparts...,))
+        GC.@preserve dparts dg for (k, d) in enumerate(dparts)
+            check(ccall((:tfhe_memcpy_d2d, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t),
+                  ctx.handle, dg.ptr + 8 * (k - 1) * level * n, d.ptr, 8 * level * n))
+        end
+        push!(dgs, dg)
+    end
+    bv = bias === nothing ? nothing : coeffs_primal(bias).parent
+    out = HipVector{T}(2 * level, n, cnt)
+    on(ctx, (out,), bv === nothing ? (cts..., dgs..., pb..., pg..., pf...) : (cts..., dgs..., pb..., pg..., pf..., bv))
+    bkeys = Ptr{UInt64}[k.ptr for k in pb]; bgs = UInt64[gk.galois_element for gk in baby]
+    gkeys = Ptr{UInt64}[k.ptr for k in pg]; ggs = UInt64[gk.galois_element for gk in giant]
+    fkeys = Ptr{UInt64}[k.ptr for k in pf]; fgs = UInt64[gk.galois_element for gk in fold]; sizes = Cint[length(g) for g in folds]
+    dptrs = Ptr{UInt64}[d.ptr for d in dgs]; cptrs = Ptr{UInt64}[c.ptr for c in cts]
+    bptr = bv === nothing ? Ptr{UInt64}(0) : bv.ptr
+    GC.@preserve pb pg pf cts dgs bv out check(ccall((:tfhe_matmul_bsgs_fold_grouped, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Cint, Cint,
+                 Ptr{Ptr{UInt64}}, Ptr{Ptr{UInt64}}, Cint, Ptr{Ptr{UInt64}}, Ptr{UInt64}, Ptr{Cint}, Cint, Ptr{UInt64}, Ptr{UInt64}, Int64),
+                ctx.handle, Lk, level, n_special, group, bkeys, bgs, nb, gkeys, ggs, ng, length(ek1.key),
+                dptrs, cptrs, nin, fkeys, fgs, sizes, length(folds), bptr, out.ptr, cnt))
+    CipherText{squared_encoding(Enc)}(cs[1].params, unpack(ctx, out, ℛ, 2))
+end
 squared_encoding(::Type{CKKSEncoding{Tscale}}) where {Tscale} = CKKSEncoding{Tscale^2}
 squared_encoding(::Type{E}) where {E} = E
 

@@ -130,6 +130,9 @@ def lib():
         "tfhe_matmul_diag_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), i32, u64p, i32, vp, vp, vp, i64],
         "tfhe_matmul_bsgs_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), u64p, i32, C.POINTER(vp), u64p, i32, i32, C.POINTER(vp), C.POINTER(vp),
                                      i32, vp, vp, i64],
+        "tfhe_rotate_sum_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), u64p, C.POINTER(i32), i32, i32, vp, vp, i64],
+        "tfhe_matmul_bsgs_fold_grouped": [vp, i32, i32, i32, i32, C.POINTER(vp), u64p, i32, C.POINTER(vp), u64p, i32, i32, C.POINTER(vp),
+                                          C.POINTER(vp), i32, C.POINTER(vp), u64p, C.POINTER(i32), i32, vp, vp, i64],
         "tfhe_rotate_many": [vp, i32, i32, i32, C.POINTER(vp), i32, i32, u64p, i32, vp, vp, i64],
         "tfhe_galois_key_prepare": [vp, i32, i32, u64, vp, vp],
         "tfhe_matmul_diag": [vp, i32, i32, i32, C.POINTER(vp), i32, u64p, i32, vp, vp, vp, i64],
@@ -185,7 +188,7 @@ EXPORTED_SYMBOLS = [
     "tfhe_ctx_set_stream", "tfhe_ctx_sync", "tfhe_ctx_wait_for", "tfhe_ctx_set_ntt_variant", "tfhe_ctx_set_chunk", "tfhe_ctx_workspace", "tfhe_malloc", "tfhe_free", "tfhe_memcpy_h2d",
     "tfhe_memcpy_d2h", "tfhe_memcpy_d2d", "tfhe_memset", "tfhe_pack_poly", "tfhe_unpack_poly", "tfhe_broadcast_poly", "tfhe_alloc_stats", "tfhe_alloc_trim", "tfhe_comm_id", "tfhe_comm_create", "tfhe_comm_destroy", "tfhe_gather", "tfhe_nntt", "tfhe_inntt", "tfhe_add", "tfhe_sub", "tfhe_neg",
     "tfhe_mul", "tfhe_mad", "tfhe_dot", "tfhe_scalar_mul", "tfhe_tensor", "tfhe_rescale", "tfhe_select_limbs", "tfhe_galois",
-    "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_keyswitch_grouped", "tfhe_rotate_grouped", "tfhe_rotate_many_grouped", "tfhe_matmul_diag_grouped", "tfhe_matmul_bsgs_grouped", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
+    "tfhe_keyswitch", "tfhe_rotate", "tfhe_rotate_prepared", "tfhe_rotate_many", "tfhe_galois_key_prepare", "tfhe_matmul_diag", "tfhe_matmul_bsgs", "tfhe_matmul_bsgs_blocks", "tfhe_rotate_sum", "tfhe_matmul_bsgs_fold", "tfhe_lincomb", "tfhe_lincomb_many", "tfhe_keyswitch_window", "tfhe_keyswitch_grouped", "tfhe_rotate_grouped", "tfhe_rotate_many_grouped", "tfhe_matmul_diag_grouped", "tfhe_matmul_bsgs_grouped", "tfhe_rotate_sum_grouped", "tfhe_matmul_bsgs_fold_grouped", "tfhe_ckks_encode", "tfhe_ckks_decode", "tfhe_sample_uniform", "tfhe_sample_gaussian", "tfhe_bfv_plan_create", "tfhe_bfv_plan_destroy", "tfhe_bfv_plan_set_chunk",
     "tfhe_bfv_plan_set_variant", "tfhe_bfv_plan_workspace", "tfhe_bfv_mul", "tfhe_bfv_expand", "tfhe_bfv_contract", "tfhe_bfv_mul_relin", "tfhe_mul_relin", "tfhe_mul_relin_grouped", "tfhe_encrypt", "tfhe_decrypt_phase", "tfhe_dot_plain", "tfhe_evalkey_gen", "tfhe_plain_plan_create", "tfhe_plain_plan_destroy", "tfhe_plain_encode",
     "tfhe_plain_decode", "tfhe_bfv_noise_max", "tfhe_prof_enable", "tfhe_prof_read",
     "tfhe_event_create", "tfhe_event_destroy", "tfhe_event_record", "tfhe_event_elapsed_ms",
@@ -554,6 +557,32 @@ class Context:
         cp, _ = self._key_arrays(cts, [])
         check(lib().tfhe_matmul_bsgs_grouped(self.h, key_limbs, level, n_special, group, bp, bg, len(baby_evks), gp, gg, len(giant_evks), n_digits,
                                              dp, cp, len(cts), bias, out, batch))
+
+    def rotate_sum_grouped(self, key_limbs, level, n_special, group, evk_steps, g_steps, n_digits, ct, out, batch):
+        """rotate and sum on grouped-digit keys (tfhe_rotate_sum_grouped): `evk_steps` / `g_steps` lists of lists -- per fold step the device
+        pointers of its PREPARED grouped Galois keys and their Galois elements; ct, out [batch][2][level][N] (coefficient domain)"""
+        if [len(x) for x in evk_steps] != [len(x) for x in g_steps]:
+            raise AssertionError("tfhe_rotate_sum_grouped: one Galois element per key")
+        fp, fg = self._key_arrays([p for st in evk_steps for p in st], [g for st in g_steps for g in st])
+        fs = (C.c_int * max(1, len(evk_steps)))(*[len(st) for st in evk_steps])
+        check(lib().tfhe_rotate_sum_grouped(self.h, key_limbs, level, n_special, group, fp, fg, fs, len(evk_steps), n_digits, ct, out, batch))
+
+    def matmul_bsgs_fold_grouped(self, key_limbs, level, n_special, group, baby_evks, baby_gs, giant_evks, giant_gs, n_digits, diags, cts,
+                                 fold_evk_steps, fold_g_steps, bias, out, batch):
+        """the rectangular product on grouped-digit keys (tfhe_matmul_bsgs_fold_grouped): matmul_bsgs_grouped's operands, then the fold steps
+        as for rotate_sum_grouped; the bias is added after the fold"""
+        if len(diags) != len(cts):
+            raise AssertionError("tfhe_matmul_bsgs_fold_grouped: one set of diagonals per input")
+        if [len(x) for x in fold_evk_steps] != [len(x) for x in fold_g_steps]:
+            raise AssertionError("tfhe_matmul_bsgs_fold_grouped: one Galois element per key")
+        bp, bg = self._key_arrays(baby_evks, baby_gs)
+        gp, gg = self._key_arrays(giant_evks, giant_gs)
+        dp, _ = self._key_arrays(diags, [])
+        cp, _ = self._key_arrays(cts, [])
+        fp, fg = self._key_arrays([p for st in fold_evk_steps for p in st], [g for st in fold_g_steps for g in st])
+        fs = (C.c_int * max(1, len(fold_evk_steps)))(*[len(st) for st in fold_evk_steps])
+        check(lib().tfhe_matmul_bsgs_fold_grouped(self.h, key_limbs, level, n_special, group, bp, bg, len(baby_evks), gp, gg, len(giant_evks),
+                                                  n_digits, dp, cp, len(cts), fp, fg, fs, len(fold_evk_steps), bias, out, batch))
 
     def sample_uniform(self, level, seed, stream, first_poly, out, count):
         check(lib().tfhe_sample_uniform(self.h, level, int(seed), int(stream), int(first_poly), out, count))

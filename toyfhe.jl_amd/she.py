@@ -1979,16 +1979,50 @@ def matmul_bsgs_blocks_grouped(baby_gks, giant_gks, diags, cs, bias=None) -> Cip
     return _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, None, grouped="matmul_bsgs_blocks_grouped")
 
 
+def rotate_sum_grouped(gk_groups, c: CipherText) -> CipherText:
+    """rotate_sum on keys with grouped digits (tfhe_rotate_sum_grouped): `gk_groups` a list of lists of Galois keys of ONE GroupedRaised
+    parameter set, one list per fold step.  Word for word rotate_many_grouped over a step's keys -> + per step; scale and domain are c's."""
+    groups = _fold_groups(gk_groups)
+    if len(c) != 2:
+        raise AssertionError("rotate takes a 2-element ciphertext")
+    gks = [g for grp in groups for g in grp]
+    if not gks:
+        return c
+    params, keyring = _grouped_key_set(gks, c, "rotate_sum_grouped")
+    ring, n, batch = c[0].ring, c[0].count, c[0].batch
+    level = ring.L
+    prim = [x.coeffs_primal() for x in c.cs]               # before the hand-over (see keyswitch)
+    if ring.ctx is not keyring.ctx:
+        keyring.ctx.wait_for(ring.ctx)
+    ct = _pack(prim, ring, n, ctx=keyring.ctx)
+    out = DeviceBuffer(n * 2 * level * ring.N)
+    keyring.ctx.rotate_sum_grouped(keyring.L, level, params.n_special, params.group, [[g.prepared_grouped().ptr for g in grp] for grp in groups],
+                                   [[g.galois_element for g in grp] for grp in groups], len(gks[0].key.key), ct.ptr, out.ptr, n)
+    res = _unpack(out, ring, n, 2, batch, primal=True, ctx=keyring.ctx)
+    if ring.ctx is not keyring.ctx:
+        ring.ctx.wait_for(keyring.ctx)
+    return CipherText(c.params, res, c.scale)
+
+
+def matmul_bsgs_fold_grouped(baby_gks, giant_gks, diags, cs, fold_gk_groups, bias=None) -> CipherText:
+    """matmul_bsgs_fold on keys with grouped digits (tfhe_matmul_bsgs_fold_grouped): matmul_bsgs_blocks_grouped without a bias ->
+    rotate_sum_grouped(fold_gk_groups, .) -> + bias, word for word.  Operands (rect_diagonals), usage errors, scale and result as for
+    matmul_bsgs_fold; the keys are Galois keys of ONE GroupedRaised parameter set, at least one of them."""
+    return _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, _fold_groups(fold_gk_groups), grouped="matmul_bsgs_fold_grouped")
+
+
 def _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, fold_groups, grouped=None):
     """matmul_bsgs_blocks (fold_groups None) and matmul_bsgs_fold (a list of lists of Galois keys, possibly empty); grouped: the name of
-    the caller that takes keys with grouped digits (matmul_bsgs_grouped / matmul_bsgs_blocks_grouped), which have no fold"""
+    the caller that takes keys with grouped digits (matmul_bsgs_grouped / matmul_bsgs_blocks_grouped, which have no fold, and
+    matmul_bsgs_fold_grouped)"""
     baby_gks, giant_gks, cs, diags = list(baby_gks), list(giant_gks), list(cs), list(diags)
     if grouped:
-        if not baby_gks + giant_gks:
+        fold_gks = [g for grp in fold_groups or [] for g in grp]
+        if not baby_gks + giant_gks + fold_gks:
             raise UsageError(f"{grouped}: no Galois key at all (GroupedRaised) -- plain products, use .* and +")
         if not cs:
             raise UsageError("matmul_bsgs_blocks: one set of diagonals per input ciphertext, at least one input")
-        gparams, gkeyring = _grouped_key_set(baby_gks + giant_gks, cs[0], grouped)
+        gparams, gkeyring = _grouped_key_set(baby_gks + giant_gks + fold_gks, cs[0], grouped)
     else:
         _refuse_grouped_keys(baby_gks + giant_gks + [g for grp in fold_groups or [] for g in grp], "matmul_bsgs_blocks / matmul_bsgs_fold")
     if len(diags) != len(cs) or not cs:
@@ -2051,10 +2085,15 @@ def _matmul_bsgs_blocks(baby_gks, giant_gks, diags, cs, bias, fold_groups, group
     cts = [packed[id(x)] if id(x) in packed else packed.setdefault(id(x), _pack(p, ring, n, ctx=keyring.ctx)) for x, p in zip(cs, prims)]
     out = DeviceBuffer(n * 2 * sz)
     if grouped:
-        keyring.ctx.matmul_bsgs_grouped(keyring.L, level, gparams.n_special, gparams.group, [g.prepared_grouped().ptr for g in baby_gks],
-                                        [g.galois_element for g in baby_gks], [g.prepared_grouped().ptr for g in giant_gks],
-                                        [g.galois_element for g in giant_gks], len(gks[0].key.key), [d.ptr for d in dgs], [t.ptr for t in cts],
-                                        None if bprim is None else bprim.ptr, out.ptr, n)
+        gkeys = (keyring.L, level, gparams.n_special, gparams.group, [g.prepared_grouped().ptr for g in baby_gks],
+                 [g.galois_element for g in baby_gks], [g.prepared_grouped().ptr for g in giant_gks], [g.galois_element for g in giant_gks],
+                 len(gks[0].key.key), [d.ptr for d in dgs], [t.ptr for t in cts])
+        if fold_groups is None:
+            keyring.ctx.matmul_bsgs_grouped(*gkeys, None if bprim is None else bprim.ptr, out.ptr, n)
+        else:
+            keyring.ctx.matmul_bsgs_fold_grouped(*gkeys, [[g.prepared_grouped().ptr for g in grp] for grp in fold_groups],
+                                                 [[g.galois_element for g in grp] for grp in fold_groups],
+                                                 None if bprim is None else bprim.ptr, out.ptr, n)
         res = _unpack(out, ring, n, 2, batch, primal=True, ctx=keyring.ctx)
         if ring.ctx is not keyring.ctx:
             ring.ctx.wait_for(keyring.ctx)
